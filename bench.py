@@ -8,21 +8,27 @@ on the configuration BASELINE.json quotes its metric on: bicycle-*sized* synthet
 Medium asset (296 MB), 1200x797 (SURVEY.md section 8d "C2"; the real INRIA model is not available offline).
 All inputs are resident in HBM before the timed region.  The camera orbits by 0.25 degrees per frame.
 
-    python bench.py [--gpus N --steps K --warmup W] [--config C2] [--blend exact|fast] [--cpu-baseline auto|off] [--sort-mode both|full|visible]
+    python bench.py [--gpus N --steps K --warmup W] [--config C2] [--blend exact|fast] [--dump-outputs DIR] [--full] [--cpu-baseline auto|off] [--sort-mode both|full|visible]
 (--config C2d: C2 with bicycle-like overdraw, ~18 tiles per visible splat -- a non-headline stress of the composite stage.)
+
+A plain run does what the headline figure needs and nothing else: it builds the scene, uploads the asset, warms up W frames, times exactly K
+frames of the headline mode (visible_in_flight, or --headline) in ONE region, and prints the result line (`ms_per_step` = that region / K).
+--dump-outputs DIR then writes what the last timed step computed on rank 0 (bench_outputs/ is the conventional DIR; last_step_outputs).
+--full adds everything below: every sort mode, five regions per mode (median), the per-stage and per-kernel timing passes, the roofline with
+its rocprofv3 counters and the VALU probe, the copy ceiling, the GPU-internal cross-check, the oracle's end-of-orbit check and the CPU baseline.
 
 Sort modes: `full` = SortPoints as the reference runs it (all N splats keyed and sorted every frame; SH only for visible splats, m_GpuView on
 demand); `reference_shaped` = the same plus gs_renderer_set_view_buffer_mode(every_frame): the reference's whole per-frame work (sort all N,
 CSCalcViewData's colour + 40-byte record for every splat in front of the camera); `visible` = GS_SORT_VISIBLE, cull first and sort the splats
-that are drawn (same frame, same order among the drawn splats: include/gsplat_c.h).  By default all three are measured back to back over the
-SAME frames; `modes` carries all.  The headline (`value`, `ms_per_step`, `config.sort_mode`) is the visible-only mode IF this run's end-of-orbit
+that are drawn (same frame, same order among the drawn splats: include/gsplat_c.h).  With --full all of them are measured back to back over the
+SAME frames; `modes` carries all, and the headline (`value`, `ms_per_step`, `config.sort_mode`) is the visible-only mode IF this run's end-of-orbit
 check holds: at N = 1 the CPU oracle replays EVERY SortPoints of the whole measurement (warm-up + every timed and instrumented region: a stable
 sort of all N per call, sequentially) and, on the last frame, the order the mode drew from must be the visible subsequence of the oracle's order
 buffer, the library's consolidated buffer (gs_renderer_download_order) the oracle's whole buffer, and the frame within the framebuffer bar of the
 oracle's; at N > 1 (no oracle) the consolidated buffer must equal the buffer the full mode built with its own sorts over the same frames and the
 two frames must be the same bits.  Otherwise the headline is the full mode and the line says why.  --headline full|visible pins it.
 
-Counters: at N = 1 the run spawns three short children of itself (the headline mode, the same frames) under `rocprofv3 --pmc FETCH_SIZE`,
+Counters (--full): at N = 1 the run spawns three short children of itself (the headline mode, the same frames) under `rocprofv3 --pmc FETCH_SIZE`,
 `--pmc WRITE_SIZE`, `--pmc SQ_INSTS_VALU` (separate passes), so `roofline.traffic` and `roofline.valu` are measured in THIS run on THIS box
 (--pmc off skips them).
 
@@ -56,6 +62,7 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0     # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
 HBM_ACHIEVABLE_GBS = 6300.0   # the same guide's measured float4-copy rate (79 % of the spec peak)
+STEADY_S = 1.0                # a plain run: seconds of untimed passes over the timed frames before they are timed (steady_state)
 
 
 def parse():
@@ -66,11 +73,13 @@ def parse():
     ap.add_argument("--config", default="C2", choices=["C1", "C2", "C2d", "C3", "C4", "C5"])
     ap.add_argument("--splats", type=int, default=0, help="override the splat count (debugging only; result is labelled)")
     ap.add_argument("--blend", default="exact", choices=["exact", "fast"])
-    ap.add_argument("--cpu-baseline", default="auto", choices=["auto", "off"])
+    ap.add_argument("--cpu-baseline", default=None, choices=["auto", "off"], help="the oracle's end-of-orbit replay + the CPU baseline (default: auto with --full, else off)")
     ap.add_argument("--sort-nth-frame", type=int, default=1)
-    ap.add_argument("--repeats", type=int, default=5, help="the timed region (exactly --steps frames) is run this many times back to back; ms_per_step / value are the MEDIAN region")
+    ap.add_argument("--repeats", type=int, default=None, help="the timed region (exactly --steps frames) is run this many times back to back; ms_per_step / value are the MEDIAN region "
+                                                              "(default: 5 with --full, else 1)")
     ap.add_argument("--broadcast", action="store_true", help="go through gs_comm_create / gs_asset_broadcast even with one rank")
-    ap.add_argument("--sort-mode", default="all", choices=["all", "both", "full", "visible", "reference_shaped", "visible_in_flight"], help="which modes to measure (both = full + visible)")
+    ap.add_argument("--sort-mode", default=None, choices=["all", "both", "full", "visible", "reference_shaped", "visible_in_flight"],
+                    help="which modes to measure (both = full + visible; default: all with --full, else the headline mode alone)")
     ap.add_argument("--headline", default="auto", choices=["auto", "full", "visible", "visible_in_flight", "reference_shaped"],
                     help="which measured mode `value` reports (auto: the fastest of visible_in_flight / visible whose end-of-orbit check holds, else full)")
     ap.add_argument("--in-flight", type=int, default=2, help="renderers (contexts = streams) the visible_in_flight mode deals its frames / views to")
@@ -79,12 +88,26 @@ def parse():
                          "host: the host holds --in-flight renderers on contexts of their own over one asset and deals the frames itself")
     ap.add_argument("--in-flight-targets", type=int, default=1, help="library lanes: sets of targets the host draws into in rotation (1: every frame into the same target, as the "
                                                                          "sequential modes do -- the library double-buffers a target's pixels itself while it has lanes)")
-    ap.add_argument("--pmc", default="auto", choices=["auto", "off"], help="auto: at N = 1 spawn rocprofv3 --pmc children of this script for HBM traffic and VALU instruction counts")
+    ap.add_argument("--pmc", default=None, choices=["auto", "off"], help="auto: at N = 1 spawn rocprofv3 --pmc children of this script for HBM traffic and VALU instruction counts "
+                                                                        "(default: auto with --full, else off)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: every sort mode, the per-stage / per-kernel timing passes, the roofline and its "
+                                                        "counters, the copy ceiling, the GPU-internal cross-check, the oracle's end-of-orbit check and the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the headline mode's last step computed to DIR/<name>.npy "
+                                                                       "(float32 / float64, at most 64 MB in all; larger outputs as a fixed, seeded sample)")
     ap.add_argument("--pmc-child", default="", help="(internal) path of the pickled asset: run the frames of one mode and exit -- what the rocprofv3 children execute")
     ap.add_argument("--child-mode", default="visible", help="(internal) mode of a --pmc-child run")
     ap.add_argument("--child-first", type=int, default=0, help="(internal) first frame of the timed region of a --pmc-child run")
     ap.add_argument("--dry-run", action="store_true", help="no GPU work: the rank / view / reduction logic and the JSON schema only (CPU test of the N > 1 path, gloo)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if args.cpu_baseline is None:
+        args.cpu_baseline = "auto" if args.full else "off"
+    if args.pmc is None:
+        args.pmc = "auto" if args.full else "off"
+    if args.sort_mode is None:
+        args.sort_mode = "all" if args.full else ("visible_in_flight" if args.headline == "auto" else args.headline)
+    return args
 
 
 def stage_bytes(n, P, vis, W, H, asset, passes_pair, mode="full", tie_fix=True, depth_passes=4):
@@ -505,7 +528,7 @@ def main():
     # a device-to-device copy ceiling measured on this GPU BEFORE the timed regions (SURVEY.md section 8d asks for it next to the 8 TB/s
     # spec; boxes differ by up to 8 %): 512 MiB read + 512 MiB written, 10 times
     copy_ceiling = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             src = torch.empty(512 << 20, dtype=torch.uint8, device="cuda")
             dst = torch.empty_like(src)
@@ -522,10 +545,36 @@ def main():
 
     frames_warm = max(args.warmup, 1)
 
+    def steady_state(first):
+        """A plain run's single timed region must not carry the ramp of a first pass over its frames (the freshly reserved pair buffers, the lanes'
+        first overlap, the clocks): the timed frames first .. first+K-1, in order and pipelined as the timed region runs them, cycled untimed for
+        STEADY_S seconds (a pair buffer that overflows here is grown here).  Nothing they compute changes: the order a sequence of sorts leaves
+        depends only on the order of the LAST occurrences of its distinct matrices (a stable sort through the previous order; GS_SORT_VISIBLE keeps
+        exactly that chain), and the timed pass repeats every one of them last."""
+        full_sync()
+        logged = len(sort_log)                               # (these sorts change nothing the oracle's replay would see: not logged)
+        t0 = time.perf_counter()
+        k = 0
+        while True:
+            frame(first + k % args.steps)
+            k += 1
+            if k % 16 == 0:
+                sync_lanes()
+                if time.perf_counter() - t0 >= STEADY_S:
+                    break
+        del sort_log[logged:]
+        for X in active:
+            try:
+                X.r.FrameStats()
+            except GsError as e:
+                if e.code != -6:                             # (-6: the last of these frames overflowed; the buffer has been grown)
+                    raise
+
     def measure(mode, repeats, instrument=True):
         """One mode: warm-up (sizes the pair buffer: an overflowing frame grows it and is re-run), `repeats` un-instrumented regions of
-        exactly K frames, then the same K frames with the per-stage hipEvents, then once more with the Onesweep launches' own timestamps.
+        exactly K frames, then (--full only) the same K frames with the per-stage hipEvents, then once more with the Onesweep launches' own timestamps.
         Afterwards the renderer is left as the last frame left it (the end-of-orbit state the checks read)."""
+        lean = not args.full                                 # a plain run: the warm-up and the timed regions, nothing else
         piped = mode == "visible_in_flight"
         lib_lanes = piped and args.in_flight_impl == "library"
         active[:] = [lane(k) for k in range(max(1, args.in_flight))] if (piped and not lib_lanes) else [lanes[0]]
@@ -543,11 +592,11 @@ def main():
         fi = 0
         first_frame_ms = first_again_ms = None
         for _ in range(frames_warm):
-            if fi == 0:                       # the very first frame (identity order: keys in Morton order, cold buffers), timed on its own
+            if fi == 0 and not lean:          # the very first frame (identity order: keys in Morton order, cold buffers), timed on its own
                 sync_lanes()
                 t_first = time.perf_counter()
             frame(fi)
-            if fi == 0:
+            if fi == 0 and not lean:
                 sync_lanes()
                 first_frame_ms = (time.perf_counter() - t_first) * 1e3
                 # ... and the same frame once more (same matrix: the sort changes nothing, the history does not grow): what is left of the
@@ -569,6 +618,8 @@ def main():
         st = r.FrameStats()
         for X in active:
             X.r.ReservePairs(int(st.tile_pairs * 1.5) + (1 << 20))
+        if lean:
+            steady_state(fi)
         # The un-instrumented region -- exactly K frames between barrier + synchronize -- is run `repeats` times back to back over the same
         # frames; ms_per_step and value are the MEDIAN region's (min / max / every region reported next to them): one 14 ms region alone is a
         # coin-flip inside +-4 % on these boxes.
@@ -579,8 +630,9 @@ def main():
         gc.disable()
         regions = [run_region(fi, gather=True) for _ in range(max(repeats, 1))]
         per_rank = list(per_rank_s)
-        if piped:                                            # frames in flight side by side: per-kernel brackets mean nothing; the sequential visible mode has them
-            run_region(fi); run_region(fi)                   # (the two instrumented passes of the other modes, as plain regions: every mode logs the SAME sequence of sorts)
+        if piped or lean:                                    # frames in flight side by side: per-kernel brackets mean nothing; the sequential visible mode has them
+            if not lean:
+                run_region(fi); run_region(fi)               # (the two instrumented passes of the other modes, as plain regions: every mode logs the SAME sequence of sorts)
             gc.enable()
             for X in active:
                 X.r.FrameStats()
@@ -590,7 +642,7 @@ def main():
             return dict(mode=mode, fi=fi, regions=regions, per_rank=per_rank, elapsed=float(np.median(regions)), elapsed_instr=None, resolve_ms=None, st=last_lane.r.FrameStats(),
                         frame_ms=None, stage=None, stage_k=None, first_frame_ms=first_frame_ms, first_again_ms=first_again_ms, sorts=list(sort_log),
                         history=dict(rows=int(rows), limit=int(limit), consolidations=int(cons)), lane=last_lane, lanes=(max(1, args.in_flight) if lib_lanes else len(active)),
-                        impl=("library" if lib_lanes else "host"))
+                        impl=(("library" if lib_lanes else "host") if piped else None))
         # ---- the same K frames again with the per-stage hipEvents recorded (14 per frame, on the stream each kernel is
         #      launched on).  The events themselves cost ~50 us of a 0.6 ms frame (every record is a barrier + signal packet
         #      between two kernels), so the headline time comes from the regions above and the per-kernel durations from this one.
@@ -629,14 +681,35 @@ def main():
             x["vis_order"] = L.r.DownloadVisibleOrder()
             x["vis_stats"] = L.r.FrameStats()
         x["order"] = L.r.DownloadOrder()
+        if args.dump_outputs and rank == 0:
+            x["outputs"] = last_step_outputs(x)
+
+    def last_step_outputs(x):
+        """--dump-outputs: what the mode's last step handed its caller -- per view the splat target (RGBA16F, as float32) and its composite onto the
+        bench's background (linear RGBA float32), the order the last frame was drawn from and the order buffer (seeded samples), the frame's tile
+        pairs and visible splats.  Read after the timed steps; within DUMP_BYTES (cap_outputs)."""
+        i = x["fi"] + args.steps - 1
+        out = {}
+        for vi, v in enumerate(my_views):
+            X = active[(i * len(my_views) + vi) % len(active)]          # the target frame() drew this view of the last step into
+            t = (X.rt_sets[(i * len(my_views) + vi) % len(X.rt_sets)] if X.rt_sets else X.rts)[vi]
+            sfx = "" if len(my_views) == 1 else f"_view{v}"
+            out["framebuffer" + sfx] = t.Download().view(np.float16).astype(np.float32)
+            out["resolved" + sfx] = t.Resolve(tuple(float(c) for c in bg), want8=False)[0]
+        if "vis_order" in x:
+            out["visible_order"] = seeded_sample(x["vis_order"], DUMP_ORDER_SAMPLE, "visible_order").astype(np.float64)
+        out["order"] = seeded_sample(x["order"], DUMP_ORDER_SAMPLE, "order").astype(np.float64)
+        out["frame_stats"] = np.asarray([x["st"].tile_pairs, x["st"].visible_splats], np.float64)
+        return cap_outputs(out)
 
     modes = {"all": ["full", "reference_shaped", "visible", "visible_in_flight"], "both": ["full", "visible"]}.get(args.sort_mode, [args.sort_mode])
-    if "visible_in_flight" in modes and "visible" not in modes:
+    if args.full and "visible_in_flight" in modes and "visible" not in modes:
         modes.insert(modes.index("visible_in_flight"), "visible")                  # the per-kernel figures come from one frame at a time
     res = {}
     for m in modes:
         res[m] = measure(m, args.repeats if m != "reference_shaped" else min(args.repeats, 3), instrument=(m != "reference_shaped"))
-        end_state(res[m])
+        if args.full or args.dump_outputs or args.cpu_baseline == "auto":
+            end_state(res[m])
     active[:] = [lanes[0]]
     r.SetFramesInFlight(1)
     r.SetViewBufferMode(False)
@@ -645,7 +718,7 @@ def main():
     #      the full mode carried every one of them out as a real stable sort of all N, the visible-only mode recorded them and carried them out on
     #      demand (consolidation: one sort + the chain fix-up) -- two independent code paths that must end in the same order buffer, and in the same frame
     cross = None
-    if "visible" in res and "full" in res:
+    if args.full and "visible" in res and "full" in res:
         V_, F_ = res["visible"], res["full"]
         same_log = same_sorts(V_["sorts"], F_["sorts"])
         gmask = np.zeros(n, bool)
@@ -683,16 +756,51 @@ def main():
         print(f"bench.py: WARNING: the end-of-orbit check FAILED for {failed}; the headline is the {headline} mode", file=sys.stderr, flush=True)
     if headline not in res:
         headline = modes[0]
+    if not args.full and args.headline == "auto":
+        headline_reason = ("a plain run measures the default headline mode alone and checks nothing; --full measures every mode, lets the oracle replay the "
+                           "orbit and reports the fastest visible-only mode that passes")
     R = res[headline]
     # per-kernel durations, stage brackets and counters are taken with ONE frame at a time: with frames in flight side by side a kernel's bracket
     # holds other frames' kernels too
-    K = res["visible"] if headline == "visible_in_flight" else R
+    K = res["visible"] if headline == "visible_in_flight" and "visible" in res else R
     stage, stage_k, st, resolve_ms, frame_ms = K["stage"], K["stage_k"], R["st"], K["resolve_ms"], K["frame_ms"]
     elapsed = R["elapsed"]
     ms_per_step = elapsed / args.steps * 1e3
     msplats = n * args.steps * num_views / elapsed / 1e6
+    ref_msplats = 6_131_954 / 6.8e-3 / 1e6      # 6.8 ms/frame, RTX 3080 Ti, real bicycle scene
+    regions = R["regions"]
+    vsb = lambda x: round(n * args.steps * num_views / x["elapsed"] / 1e6 / num_views / ref_msplats, 3) if args.config == "C2" and not args.splats else None
 
-    if rank == 0:
+    if rank == 0 and args.dump_outputs:
+        write_outputs(args.dump_outputs, R["outputs"])
+
+    if rank == 0 and not args.full:
+        # a plain run: the headline figure and what it was measured on (everything else: --full)
+        out = {
+            "metric": f"Msplats/s rendered (sort+view+composite+resolve), {cfg.label}; ms/frame in ms_per_step",
+            "value": round(msplats, 2), "unit": "Msplats/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 4),
+            "ms_per_step_regions": [round(x / args.steps * 1e3, 4) for x in regions],
+            "ms_per_step_per_rank": [round(x / args.steps * 1e3, 4) for x in R["per_rank"]] if R["per_rank"] else None,
+            "higher_is_better": True, "scaling": "strong" if args.config == "C5" else "weak",
+            "vs_baseline": vsb(R), "dtype": "f32", "data": "synthetic", "full": False,
+            "config": {"workload": cfg.label + (f" [splat count overridden to {n}]" if args.splats else ""),
+                       "sort_mode": headline, "headline_reason": headline_reason,
+                       "frames_in_flight": (R.get("lanes", 1) if headline == "visible_in_flight" else 1),
+                       "frames_in_flight_impl": (R.get("impl") if headline == "visible_in_flight" else None),
+                       "splats": n, "resolution": [W, H], "asset_MB": round(asset_bytes / 1e6, 1), "views": num_views, "views_per_rank": len(my_views),
+                       "blend": args.blend, "sort_nth_frame": args.sort_nth_frame, "tile_pairs_P": int(st.tile_pairs), "tile": f"{st.tile_w}x{st.tile_h}",
+                       "visible_splats": int(st.visible_splats),
+                       "parallelism": (f"view-parallel x{world} (one camera per GPU, asset broadcast once by gs_asset_broadcast = ncclBroadcast per blob)" if world > 1 else "single GPU"),
+                       "rccl_ranks": rccl_ranks, "host_group": ("gloo" if world > 1 else None),
+                       "baseline_note": "vs_baseline = per-view Msplats/s / 901.8 (reference: 6.8 ms/frame on RTX 3080 Ti with the REAL INRIA bicycle, whose overdraw is far higher than this synthetic scene's: context only)"},
+            "modes": {m: {"ms_per_step": round(x["elapsed"] / args.steps * 1e3, 4), "value_Msplats_s": round(n * args.steps * num_views / x["elapsed"] / 1e6, 2)}
+                      for m, x in res.items()},
+            "setup_s": {"scene_build": round(t_build, 1), "asset_broadcast": round(t_bcast, 3)},
+        }
+        print(json.dumps(out), flush=True)
+
+    if rank == 0 and args.full:
         P = int(st.tile_pairs)
         numTiles = st.tiles_x * st.tiles_y
         passes_pair = 1 if numTiles <= 256 else (2 if numTiles <= 65536 else 3)
@@ -832,9 +940,6 @@ def main():
                     "first_frame_again_ms": round(x["first_again_ms"], 3) if x["first_again_ms"] is not None else None,
                     "sort_history": x["history"]}
 
-        ref_msplats = 6_131_954 / 6.8e-3 / 1e6      # 6.8 ms/frame, RTX 3080 Ti, real bicycle scene
-        regions = R["regions"]
-        vsb = lambda x: round(n * args.steps * num_views / x["elapsed"] / 1e6 / num_views / ref_msplats, 3) if args.config == "C2" and not args.splats else None
         out = {
             "metric": f"Msplats/s rendered (sort+view+composite+resolve), {cfg.label}; ms/frame in ms_per_step",
             "value": round(msplats, 2), "unit": "Msplats/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -848,7 +953,7 @@ def main():
             # the same size, so the ratio is context, not a like-for-like comparison (config.baseline_note)
             "vs_baseline": vsb(R),
             "vs_baseline_by_mode": {m: vsb(x) for m, x in res.items()},
-            "dtype": "f32", "data": "synthetic",
+            "dtype": "f32", "data": "synthetic", "full": True,
             "config": {"workload": cfg.label + (f" [splat count overridden to {n}]" if args.splats else ""),
                        "sort_mode": headline, "headline_reason": headline_reason,
                        "frames_in_flight": (R.get("lanes", 1) if headline == "visible_in_flight" else 1),
@@ -921,6 +1026,36 @@ def same_sorts(a, b):
         return out
     a, b = dedup(a), dedup(b)
     return len(a) == len(b) and all(x is y or np.array_equal(x, y) for x, y in zip(a, b))
+
+
+DUMP_BYTES = 63_000_000        # --dump-outputs: at most this much in all (64 MB with the .npy headers and some room)
+DUMP_ORDER_SAMPLE = 1 << 20    # entries kept of an order buffer (millions of splats)
+
+
+def seeded_sample(a, k, name):
+    """A fixed subset of k elements of `a` (flattened), in index order; the positions depend only on the name and the size."""
+    a = np.asarray(a).reshape(-1)
+    if a.size <= k:
+        return a
+    import zlib
+    idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(a.size, k, replace=False))
+    return a[idx]
+
+
+def cap_outputs(arrays):
+    """{name: float32 / float64 array} within DUMP_BYTES: when the whole set is larger, every array becomes the same fraction of its elements
+    (seeded_sample, flattened)."""
+    total = sum(v.nbytes for v in arrays.values())
+    if total <= DUMP_BYTES:
+        return arrays
+    f = DUMP_BYTES / total * 0.99
+    return {k: seeded_sample(v, max(1, int(v.size * f)), k) for k, v in arrays.items()}
+
+
+def write_outputs(out_dir, arrays):
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 def cpu_baseline_and_replay(asset, r, res, cam, n, W, H, blend_mode):

@@ -1,4 +1,4 @@
-"""Kernel durations with frames in flight, from a rocprofv3 --kernel-trace csv of `bench.py --sort-mode visible_in_flight --repeats 1`:
+"""Kernel durations with frames in flight, from a rocprofv3 --kernel-trace csv of `bench.py --full --sort-mode visible_in_flight --repeats 1`:
 per kernel the median duration one frame at a time (the `visible` mode's frames: one queue) and in flight (two queues), the share of the
 in-flight wall time during which 1 / 2 kernels run, and the busy time per queue.
     python scripts/inflight_trace.py <kernel_trace.csv> [fraction of the one-at-a-time part to drop, default 0.4]

@@ -77,3 +77,37 @@ def test_headline_is_gated_on_the_end_of_orbit_check():
     import numpy as np
     a, c = np.arange(16, dtype=np.float32), np.arange(16, dtype=np.float32) + 1
     assert b.same_sorts([a, a, c], [a, c, c]) and not b.same_sorts([a, c], [c, a]) and not b.same_sorts([a, c, a], [a, c])
+
+
+def test_plain_run_defaults_and_full(monkeypatch):
+    """A plain run measures the headline mode alone, in one region, with no oracle replay and no counter children; --full restores the
+    measurement of every mode (five regions each, oracle, counters).  Explicit options win in both."""
+    import sys
+    b = _bench()
+
+    def parse(*argv):
+        monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+        return b.parse()
+    a = parse("--steps", "7", "--warmup", "2")
+    assert (a.full, a.steps, a.warmup, a.repeats, a.cpu_baseline, a.pmc, a.sort_mode, a.dump_outputs) == (False, 7, 2, 1, "off", "off", "visible_in_flight", "")
+    assert parse("--headline", "full").sort_mode == "full"
+    a = parse("--full")
+    assert (a.full, a.repeats, a.cpu_baseline, a.pmc, a.sort_mode) == (True, 5, "auto", "auto", "all")
+    a = parse("--full", "--repeats", "3", "--pmc", "off", "--sort-mode", "both", "--dump-outputs", "d")
+    assert (a.repeats, a.pmc, a.sort_mode, a.dump_outputs) == (3, "off", "both", "d")
+
+
+def test_dumped_outputs_are_capped_by_a_fixed_sample():
+    import numpy as np
+    b = _bench()
+    a = np.arange(1000, dtype=np.float64)
+    s1, s2 = b.seeded_sample(a, 100, "order"), b.seeded_sample(a.copy(), 100, "order")
+    assert s1.size == 100 and np.array_equal(s1, s2) and np.all(np.diff(s1) > 0)            # the same positions every time, in index order
+    assert not np.array_equal(s1, b.seeded_sample(a, 100, "visible_order"))
+    assert np.array_equal(b.seeded_sample(a, 5000, "order"), a)
+    small = {"x": np.ones((4, 4), np.float32)}
+    assert b.cap_outputs(small) is small
+    big = {"img": np.zeros((b.DUMP_BYTES // 4,), np.float32), "order": np.zeros((b.DUMP_BYTES // 16,), np.float64)}
+    capped = b.cap_outputs(big)
+    assert sum(v.nbytes for v in capped.values()) <= b.DUMP_BYTES and set(capped) == set(big)
+    assert all(v.dtype == big[k].dtype for k, v in capped.items())
