@@ -151,13 +151,13 @@ typedef struct gs_stage_times {
      * histogram-scan, copy-back and tile-range kernels that share those stages */
     float onesweep_depth_ms;   /* sum of the depth-sort launches of one frame */
     float onesweep_pairs_ms;   /* sum of the pair-sort launches of one frame */
-    uint32_t onesweep_pair_launches;   /* 1..3, by tile count */
+    uint32_t onesweep_pair_launches;   /* of the last draw, by tile count: 1 (<= 256 tiles), 2 (<= 65,536), 3 (up to 2^24) */
     /* the same launches by their OWN start / stop timestamps (the dispatch's completion signal, as rocprofv3 --kernel-trace reports
      * them): no event packets and no kernel boundaries inside, so <= the bracketed figures above.  0 unless the frames were recorded
      * with gs_renderer_set_kernel_timing(r, 1). */
     float onesweep_depth_kernel_ms;    /* sum over the depth-sort launches */
     float onesweep_pairs_kernel_ms;    /* sum over the pair-sort launches */
-    uint32_t onesweep_depth_launches;  /* of the last frame: 4 (8-bit passes), or 3 (GS_SORT_VISIBLE: 9-bit passes over keys reduced to a window around the last frame's range) */
+    uint32_t onesweep_depth_launches;  /* of the last frame: 4 (8-bit passes), or 0 when the frame made no depth sort (GS_SORT_VISIBLE with no sort recorded on an identity base: drawn in index order) */
 } gs_stage_times;
 
 int32_t gs_abi_version(void);
