@@ -372,7 +372,7 @@ int32_t gs_target_device_ptr(gs_target* t, void** rgba16f_dev, void** resolved_r
 int32_t gs_target_set_profiling(gs_target* t, int32_t enabled);
 int32_t gs_target_resolve_time(gs_target* t, float* mean_ms, int32_t* count);
 
-/* ---- native importer (host code, no GPU needed): GaussianSplatAssetCreator.CreateAsset minus the Unity asset database -- */
+/* ---- native importer (host code; no GPU needed, one optional GPU stage): GaussianSplatAssetCreator.CreateAsset minus the Unity asset database -- */
 /* InputSplatData (GaussianFileReader.cs:17-26) as separate arrays, in the PLY domain after ReorderSHs: */
 typedef struct gs_import_input {
     uint32_t splat_count;
@@ -395,6 +395,18 @@ int32_t gs_import_blob_sizes(uint32_t splat_count, const gs_import_formats* form
  * bounds_min/max (may be NULL) receive the position bounds (GaussianSplatAsset.boundsMin/Max). */
 int32_t gs_import_encode(const gs_import_input* in, const gs_import_formats* formats, void* const blobs[5], const uint64_t sizes[5],
                          float bounds_min[3], float bounds_max[3]);
+/* The one stage of the importer that can run on a GPU: the nearest-mean assignment of the Cluster* SH palette
+ * (GaussianSplatAssetCreator.cs:476-518), n x k x 45 multiply-adds in double, five passes per import.  Host and GPU perform the same
+ * operations in the same order -- dot = dot + (double)x[i][c] * (double)means[j][c] for c = 0..44, product and sum each rounded to double
+ * (no FMA), d_j = |means[j]|^2 - 2 dot, index = 0 if d_0 is NaN, else the smallest j attaining the minimum over the non-NaN d_j -- so the
+ * indices, and with them the asset's bytes, are identical wherever the assignment ran.  There is no host fallback: a HIP failure is
+ * GS_ERR_HIP / GS_ERR_OUT_OF_MEMORY.  The work goes on the context's stream; the means are uploaded once per call and the points pass through
+ * a device buffer of fixed size in batches (GSPLAT_IMPORT_BATCH = points per batch, read at every call, overrides the size). */
+/* nearest-mean assignment of n 45-float vectors to k means; ctx NULL = the host loop, else the context's GPU. Blocks. */
+int32_t gs_import_assign_clusters(gs_context* ctx, const float* x, uint64_t n, const float* means, uint32_t k, uint32_t* index_out);
+/* gs_import_encode with the Cluster* assignment passes on ctx's GPU (ctx NULL: identical to gs_import_encode) */
+int32_t gs_import_encode_on(gs_context* ctx, const gs_import_input* in, const gs_import_formats* formats,
+                            void* const blobs[5], const uint64_t sizes[5], float bounds_min[3], float bounds_max[3]);
 
 /* PLY input (PLYFileReader.cs:25-76 header rules; GaussianFileReader.cs:80-208 attribute mapping + ReorderSHs): binary
  * little-endian, float properties; x y z f_dc_0..2 opacity scale_0..2 rot_0..3 required, f_rest_* optional (0 if absent).

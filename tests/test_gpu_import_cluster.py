@@ -1,0 +1,166 @@
+"""-m gpu: the nearest-mean assignment of the Cluster* SH palette on the GPU (csrc/gs_cluster.hip through
+gs_import_assign_clusters / gs_import_encode_on with a context) against the host loop of the same entry points: the same index
+for every point and the same asset bytes, no tolerance.  The cases aim at where the kernel merges partial results: across
+tiles of 64 means, across the 16 threads that share a point, at the tail of K and of n, and across batches of points."""
+import numpy as np
+import pytest
+
+import cluster_cases as CC
+import oracle_lib as O
+from common import default_camera
+from test_import import _same
+from unitygaussiansplatting_amd import creator, scenes
+from unitygaussiansplatting_amd.renderer import GaussianSplatRenderer, RenderTarget
+
+pytestmark = pytest.mark.gpu
+
+SPECIAL = CC.special_cases()
+TIE_DISTANCES = [1, 2, 3, 4, 8, 16, 32, 64, 128, 256, 512, 1_024, 2_048]
+
+
+def _check(ctx, x, m):
+    want = creator.AssignClusters(x, m)                                 # the host loop
+    got = creator.AssignClusters(x, m, context=ctx)
+    bad = np.flatnonzero(got != want)
+    assert len(bad) == 0, f"{len(bad)} of {len(x)} indices differ, first at {bad[:5]}: gpu {got[bad[:5]]} != host {want[bad[:5]]}"
+    return got
+
+
+@pytest.mark.parametrize("k", [1, 2, 63, 65, 4_096, 4_097])
+@pytest.mark.parametrize("n", [1, 63, 65, 257, 1_037])
+def test_gpu_assignment_equals_host_sizes(gpu_ctx, n, k):
+    x, m = CC.random_case(n, k, 1_000 * n + k)
+    _check(gpu_ctx, x, m)
+    got = _check(gpu_ctx, CC.points_near_means(m, n, n + k), m)        # every part of the table is some point's answer
+    if n >= 257 and k >= 63:
+        assert len(np.unique(got)) > 50
+
+
+def _tied_table(k, seed):
+    """Random means in which, for every distance D of TIE_DISTANCES and for D = k - 1, one mean is repeated D rows after its original."""
+    rng = np.random.default_rng(seed)
+    m = rng.standard_normal((k, CC.DIM)).astype(np.float32)
+    pairs, used = [(0, k - 1)], {0, k - 1}
+    for dist in TIE_DISTANCES:
+        lo = next(r for r in range(1 + 37 * len(pairs), k) if r not in used and r + dist < k and r + dist not in used)
+        pairs.append((lo, lo + dist))
+        used |= {lo, lo + dist}
+    for lo, hi in pairs:
+        m[hi] = m[lo]
+    assert sorted(hi - lo for lo, hi in pairs) == TIE_DISTANCES + [k - 1]
+    return m, pairs
+
+
+@pytest.mark.parametrize("k", [4_097, 4_160])
+def test_gpu_assignment_exact_ties_lower_index_wins(gpu_ctx, k):
+    """A mean and its copy are equally near to every point, bit for bit; the pair sits in one thread, in two threads of a tile, in
+    neighbouring tiles, in far tiles, in the first and the last tile (the K tail).  Points ON the mean and points near it."""
+    m, pairs = _tied_table(k, 5)
+    rng = np.random.default_rng(6)
+    pts, owner = [], []
+    for lo, _ in pairs:
+        pts.append(m[lo][None, :])
+        pts.append(m[lo][None, :] + 0.01 * rng.standard_normal((4, CC.DIM)).astype(np.float32))
+        owner += [lo] * 5
+    x = np.concatenate(pts).astype(np.float32)
+    got = _check(gpu_ctx, x, m)
+    assert np.array_equal(got, np.asarray(owner, np.uint32))           # the original row: the lower index of the tied pair
+    assert np.array_equal(CC.reference_assign(x, m), got)
+
+
+def test_gpu_assignment_all_zero(gpu_ctx):
+    for n, k in ((257, 4_097), (65, 63)):
+        got = _check(gpu_ctx, np.zeros((n, CC.DIM), np.float32), np.zeros((k, CC.DIM), np.float32))
+        assert not got.any()
+
+
+def test_gpu_assignment_largest_table_last_row(gpu_ctx):
+    k, n = 65_536, 300
+    rng = np.random.default_rng(9)
+    m = rng.standard_normal((k, CC.DIM)).astype(np.float32)
+    m[k - 1] = 3.0 * rng.standard_normal(CC.DIM).astype(np.float32)     # far from the rest of the table
+    x = (m[k - 1][None, :] + 0.05 * rng.standard_normal((n, CC.DIM))).astype(np.float32)
+    got = _check(gpu_ctx, x, m)
+    assert (got == k - 1).all()
+
+
+def test_gpu_assignment_magnitudes_denormals_negative_zero(gpu_ctx):
+    rng = np.random.default_rng(10)
+    n, k = 257, 193
+    scale = (10.0 ** rng.uniform(-3, 3, (k, 1))).astype(np.float32)
+    m = (rng.standard_normal((k, CC.DIM)) * scale).astype(np.float32)
+    x = CC.points_near_means(m, n, 11, noise=0.0)
+    x = (x * (1.0 + 0.01 * rng.standard_normal((n, CC.DIM)))).astype(np.float32)
+    got = _check(gpu_ctx, x, m)
+    assert len(np.unique(got)) > 20
+    xs = (x * (10.0 ** rng.uniform(-3, 3, (n, 1)))).astype(np.float32)     # point and mean magnitudes unrelated
+    _check(gpu_ctx, xs, m)
+    # -0.0: columns of negative zeros in points and means (products of either sign of zero; 0.0 + -0.0 inside the sum)
+    xz, mz = x.copy(), m.copy()
+    xz[:, ::3] = -0.0
+    mz[::2, 1::3] = -0.0
+    mz[5] = -0.0
+    mz[9] = 0.0                                                          # d = +0.0 - 2 * (+-0.0): a tie between rows 5 and 9 wherever they are nearest
+    _check(gpu_ctx, xz, mz)
+    _check(gpu_ctx, np.full((65, CC.DIM), -0.0, np.float32), mz)
+    for name in ("denormal_points", "denormal_means", "denormal_both"):
+        _check(gpu_ctx, *SPECIAL[name])
+
+
+@pytest.mark.parametrize("name", sorted(n for n in SPECIAL if not n.startswith("denormal")))
+def test_gpu_assignment_special_values(gpu_ctx, name):
+    x, m = SPECIAL[name]
+    got = _check(gpu_ctx, x, m)
+    assert np.array_equal(got, CC.reference_assign(x, m))
+
+
+def test_gpu_assignment_across_batches(gpu_ctx, monkeypatch):
+    x, m = CC.random_case(1_037, 4_097, 77)
+    x = np.concatenate([x[:500], CC.points_near_means(m, 537, 78)])
+    whole = _check(gpu_ctx, x, m)
+    monkeypatch.setenv("GSPLAT_IMPORT_BATCH", "256")                    # read at every call: 4 full batches + one of 13 points
+    assert np.array_equal(_check(gpu_ctx, x, m), whole)
+    monkeypatch.setenv("GSPLAT_IMPORT_BATCH", "1")
+    assert np.array_equal(creator.AssignClusters(x[:70], m[:130], context=gpu_ctx), creator.AssignClusters(x[:70], m[:130]))
+
+
+def test_gpu_assignment_validates_arguments_with_a_context(gpu_ctx):
+    import ctypes as C
+    from unitygaussiansplatting_amd import _abi, _lib
+    x, m = CC.random_case(4, 3, 1)
+    out = np.zeros(4, np.uint32)
+    lib = _lib.lib()
+    assert lib.gs_import_assign_clusters(gpu_ctx._h, x.ctypes.data, 0, m.ctypes.data, 3, out.ctypes.data) == _abi.GS_ERR_INVALID_ARGUMENT
+    assert lib.gs_import_assign_clusters(gpu_ctx._h, x.ctypes.data, 4, m.ctypes.data, 0, out.ctypes.data) == _abi.GS_ERR_INVALID_ARGUMENT
+    assert lib.gs_import_assign_clusters(gpu_ctx._h, None, 4, m.ctypes.data, 3, out.ctypes.data) == _abi.GS_ERR_INVALID_ARGUMENT
+
+
+def _import_both_ways(ctx, quality, n):
+    raw = scenes.make_splats(n, 200 + n, 3.0)
+    host = creator.CreateAssetFromSplatsNative(raw, quality)
+    gpu = creator.CreateAssetFromSplatsNative(raw, quality, context=ctx)
+    _same(host, gpu)                                                     # all five blobs, the bounds and dataHash
+    return gpu
+
+
+def test_import_on_gpu_same_bytes_very_low_and_renders(gpu_ctx):
+    a = _import_both_ways(gpu_ctx, "VeryLow", 4_500)
+    r = GaussianSplatRenderer(gpu_ctx, a)
+    r.OnEnable()
+    cam = default_camera(W=320, H=200)
+    rt = RenderTarget(gpu_ctx, cam.pixelWidth, cam.pixelHeight)
+    r.SortPoints(cam)
+    r.CalcViewData(cam)
+    rt.Clear()
+    r.Draw(cam, rt)
+    img = rt.Download()
+    got = r.DownloadView()
+    want = O.Oracle(a).calc_view(r.FrameParams(cam))
+    assert np.array_equal(got.view(np.uint32).reshape(-1, 10), want.view(np.uint32).reshape(-1, 10))
+    assert (want["pos"][:, 3] > 0).sum() > 500 and np.asarray(img).any()
+    rt.Dispose()
+    r.OnDisable()
+
+
+def test_import_on_gpu_same_bytes_low(gpu_ctx):
+    _import_both_ways(gpu_ctx, "Low", 17_000)

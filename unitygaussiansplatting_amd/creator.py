@@ -483,9 +483,12 @@ def CreateAssetFromSplats(raw: InputSplatData, quality: str = "Medium", *, forma
 
 
 def CreateAssetFromSplatsNative(raw: InputSplatData, quality: str = "Medium", *, formatPos=None, formatScale=None, formatColor=None,
-                                formatSH=None, name: str = "asset", morton: bool = True, linearize: bool = True) -> GaussianSplatAsset:
+                                formatSH=None, name: str = "asset", morton: bool = True, linearize: bool = True,
+                                context=None) -> GaussianSplatAsset:
     """The same asset through the native importer of libgsplat_hip.so (gs_import_encode, csrc/gs_import.cpp: multi-threaded
-    host C++).  Bit-identical to CreateAssetFromSplats for every format and preset (tests/test_import.py), Cluster* palettes and BC7 included."""
+    host C++).  Bit-identical to CreateAssetFromSplats for every format and preset (tests/test_import.py), Cluster* palettes and BC7 included.
+    context: a renderer.GpuContext -- the nearest-mean assignment passes of the Cluster* formats then run on its GPU (gs_import_encode_on,
+    csrc/gs_cluster.hip); the asset is the same bytes."""
     import ctypes as C
     from . import _lib
     from ._abi import gs_import_formats, gs_import_input
@@ -503,12 +506,29 @@ def CreateAssetFromSplatsNative(raw: InputSplatData, quality: str = "Medium", *,
     blobs = [np.zeros(int(sz), np.uint8) if sz else None for sz in sizes]
     ptrs = (C.c_void_p * 5)(*[b.ctypes.data if b is not None else None for b in blobs])
     bmin, bmax = (C.c_float * 3)(), (C.c_float * 3)()
-    _lib.check(_lib.lib().gs_import_encode(C.byref(inp), C.byref(fmt), ptrs, sizes, bmin, bmax), "gs_import_encode")
+    if context is None:
+        _lib.check(_lib.lib().gs_import_encode(C.byref(inp), C.byref(fmt), ptrs, sizes, bmin, bmax), "gs_import_encode")
+    else:
+        _lib.check(_lib.lib().gs_import_encode_on(context._h, C.byref(inp), C.byref(fmt), ptrs, sizes, bmin, bmax), "gs_import_encode_on")
     a = GaussianSplatAsset(splatCount=n, posFormat=fp, scaleFormat=fs, shFormat=fsh, colorFormat=fc, posData=blobs[0], otherData=blobs[1],
                            colorData=blobs[2], shData=blobs[3], chunkData=blobs[4], boundsMin=tuple(bmin), boundsMax=tuple(bmax), name=name)
     a.dataHash = a.ComputeDataHash()
     a.Validate()
     return a
+
+
+def AssignClusters(x, means, context=None) -> np.ndarray:
+    """Index of the nearest of `means` [K,45] for every row of `x` [N,45] (fp32 in, distances in float64 as ClusterSHs' assign; first
+    minimum) through gs_import_assign_clusters: the native host loop, or with context = a renderer.GpuContext the HIP kernel of
+    csrc/gs_cluster.hip on its GPU.  The two return the same indices for every input, NaN and infinities included."""
+    import ctypes as C
+    from . import _lib
+    x = np.ascontiguousarray(x, f32).reshape(-1, 45)
+    means = np.ascontiguousarray(means, f32).reshape(-1, 45)
+    out = np.zeros(len(x), np.uint32)
+    _lib.check(_lib.lib().gs_import_assign_clusters(context._h if context is not None else None, x.ctypes.data, len(x), means.ctypes.data,
+                                                    len(means), out.ctypes.data), "gs_import_assign_clusters")
+    return out
 
 
 # --------------------------------------------------------------------------------------------------

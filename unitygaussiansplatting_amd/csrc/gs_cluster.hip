@@ -1,0 +1,186 @@
+// gs_cluster.hip -- the importer's one hot loop on the GPU: nearest-mean assignment of the 45-D SH vectors to the K palette
+// entries of the Cluster* SH formats (GaussianSplatAssetCreator.cs:476-518; host form: assign_clusters in gs_import.cpp).
+//
+// The contract is the host loop, operation for operation, so that the two give the same index for every point and an import
+// is the same bytes wherever the assignment ran.  For point i and mean j:
+//     dot = 0.0;  for k = 0..44 in that order: dot = dot + (double)x[i][k] * (double)m[j][k]      (product rounded, then the sum)
+//     d_j = c2[j] - 2.0 * dot          c2[j] = the same sequential sum of m*m, computed once on the host
+// with plain fp64 VALU multiplies and adds: no FMA (the file is compiled without contraction and says so itself below), no
+// reassociation, no MFMA (whose internal summation order is not ours to fix).  IEEE double multiply and add round on gfx950 as
+// on x86, so the distances are the host's bits and ties fall the same way.
+// The index is what the host's scan (best = 0; take j when d_j < bd) gives: 0 if d_0 is NaN, else the smallest j attaining the
+// minimum over the non-NaN d_j.  Partial results -- a thread's running best over the mean tiles, then the 16 threads that share
+// a point -- are merged with "d < bd, or d == bd and j < bj", under which a NaN never wins; the lane that owns mean 0 remembers
+// whether d_0 was NaN.  NaN, +-inf, -0.0 and denormals therefore need no route of their own.
+//
+// Shape: a workgroup of 256 threads holds 64 points (fp64, converted once, in LDS for the whole kernel) and walks the means in
+// tiles of 64 (fp64 in LDS, converted once per tile; the next tile's floats are fetched into registers under the arithmetic).
+// A thread owns 4 points x 4 means = 16 accumulators: per k it reads 2 + 2 double2 from LDS for 16 multiplies + 16 adds,
+// 2 B of LDS per lane-operation, half of what the CU's LDS delivers beside four SIMDs of fp64 VALU.
+#include <stdlib.h>
+
+#include <algorithm>
+
+#include "gs_common.h"
+
+#pragma clang fp contract(off)
+
+namespace gs {
+
+namespace {
+
+constexpr int kDim = 45;                  // floats per SH vector
+constexpr int kTile = 64;                 // points per workgroup = means per tile
+constexpr int kClusterThreads = 256;
+constexpr int kRow = 66;                  // doubles per LDS row [k][0..63]: 64 + 2 of padding -- rows stay 16-byte aligned for the double2 reads and
+                                          // the staging stores of one wave (consecutive k, 528 B apart) spread over the banks
+constexpr int kTileElems = kTile * kDim;  // 2,880 floats of a full tile, contiguous in memory
+constexpr int kPre = (kTileElems + kClusterThreads - 1) / kClusterThreads;   // 12 staged floats per thread
+constexpr uint32_t kNone = 0xFFFFFFFFu;   // "no candidate yet": loses every index tie
+
+// the one merge rule: in-thread over ascending j, across mean tiles and across threads.  A NaN d compares false twice.
+__device__ __forceinline__ void take_better(double d, uint32_t j, double& bd, uint32_t& bj) {
+    if (d < bd || (d == bd && j < bj)) { bd = d; bj = j; }
+}
+
+__global__ __launch_bounds__(kClusterThreads) void assign_clusters_kernel(const float* __restrict__ x, uint32_t n, const float* __restrict__ means,
+                                                                          const double* __restrict__ c2, uint32_t K, uint32_t* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) double xs[kDim * kRow];
+    __shared__ __attribute__((aligned(16))) double ms[kDim * kRow];
+    __shared__ double c2s[kTile];
+    const uint32_t t = threadIdx.x;
+    const uint32_t mg = t & 15, pg = t >> 4;       // this thread: means 2mg, 2mg+1, 32+2mg, 33+2mg of a tile x points 2pg, 2pg+1, 32+2pg, 33+2pg
+    const uint32_t p0 = blockIdx.x * (uint32_t)kTile;
+    const uint32_t np = min((uint32_t)kTile, n - p0);
+    const float* xb = x + (size_t)p0 * kDim;
+    for (uint32_t e = t; e < (uint32_t)kTileElems; e += kClusterThreads) {     // points: fp64 once, [k][point]; rows past n are zero and never stored
+        const uint32_t p = e / kDim, k = e - p * kDim;
+        xs[k * kRow + p] = p < np ? (double)xb[e] : 0.0;
+    }
+
+    float pre[kPre];
+    auto fetch = [&](uint32_t j0) {                                            // the floats of tile j0.. (contiguous), zero past mean K-1
+        const size_t base = (size_t)j0 * kDim, end = (size_t)K * kDim;
+#pragma unroll
+        for (int i = 0; i < kPre; ++i) {
+            const uint32_t e = t + (uint32_t)i * kClusterThreads;
+            pre[i] = (e < (uint32_t)kTileElems && base + e < end) ? means[base + e] : 0.0f;
+        }
+    };
+
+    const double inf = __longlong_as_double(0x7FF0000000000000ll);
+    double bd[4] = { inf, inf, inf, inf };
+    uint32_t bj[4] = { kNone, kNone, kNone, kNone };
+    uint32_t d0nan = 0;                            // bit a: d_0 of point a was NaN (only the thread that owns mean 0 ever sets it: mg == 0, the storing lane)
+    const uint32_t jl[4] = { 2 * mg, 2 * mg + 1, 32 + 2 * mg, 33 + 2 * mg };  // ascending
+
+    fetch(0);
+    for (uint32_t j0 = 0; j0 < K; j0 += kTile) {
+        __syncthreads();                           // the previous tile has been read by every wave
+#pragma unroll
+        for (int i = 0; i < kPre; ++i) {
+            const uint32_t e = t + (uint32_t)i * kClusterThreads;
+            if (e < (uint32_t)kTileElems) { const uint32_t j = e / kDim, k = e - j * kDim; ms[k * kRow + j] = (double)pre[i]; }
+        }
+        if (t < (uint32_t)kTile) c2s[t] = j0 + t < K ? c2[j0 + t] : 0.0;
+        __syncthreads();
+        if (j0 + kTile < K) fetch(j0 + kTile);     // lands under the arithmetic below
+
+        double acc[4][4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) acc[a][b] = 0.0;
+#pragma unroll 5
+        for (int k = 0; k < kDim; ++k) {
+            const double2 x0 = *(const double2*)&xs[k * kRow + 2 * pg], x1 = *(const double2*)&xs[k * kRow + 32 + 2 * pg];
+            const double2 m0 = *(const double2*)&ms[k * kRow + 2 * mg], m1 = *(const double2*)&ms[k * kRow + 32 + 2 * mg];
+            const double xv[4] = { x0.x, x0.y, x1.x, x1.y }, mv[4] = { m0.x, m0.y, m1.x, m1.y };
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int b = 0; b < 4; ++b) acc[a][b] = acc[a][b] + xv[a] * mv[b];       // v_mul_f64, v_add_f64: two roundings
+        }
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const uint32_t j = j0 + jl[b];
+            if (j < K) {                           // the K tail: padding means take no part
+                const double c = c2s[jl[b]];
+#pragma unroll
+                for (int a = 0; a < 4; ++a) {
+                    const double d = c - 2.0 * acc[a][b];
+                    if (j == 0 && d != d) d0nan |= 1u << a;
+                    take_better(d, j, bd[a], bj[a]);
+                }
+            }
+        }
+    }
+
+    // the 16 threads that share a point are 16 consecutive lanes of one wave
+#pragma unroll
+    for (int s = 8; s >= 1; s >>= 1)
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            const double od = __shfl_xor(bd[a], s);
+            const uint32_t oj = __shfl_xor(bj[a], s);
+            take_better(od, oj, bd[a], bj[a]);
+        }
+    if (mg == 0) {
+        const uint32_t pl[4] = { 2 * pg, 2 * pg + 1, 32 + 2 * pg, 33 + 2 * pg };
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+            if (pl[a] < np) out[p0 + pl[a]] = ((d0nan >> a) & 1u) || bj[a] == kNone ? 0u : bj[a];    // d_0 NaN, or every d NaN: the host's scan stays at 0
+    }
+}
+
+struct DeviceBuffers {                             // freed on every path out of assign_clusters_gpu
+    float* means = nullptr; double* c2 = nullptr; float* x = nullptr; uint32_t* out = nullptr;
+    ~DeviceBuffers() { (void)hipFree(means); (void)hipFree(c2); (void)hipFree(x); (void)hipFree(out); }
+};
+
+constexpr uint64_t kPointBudgetBytes = 256ull << 20;        // device memory for one batch of points + their indices
+constexpr uint64_t kMaxBatch = 1ull << 24;                  // 32-bit point offsets inside the kernel
+
+uint64_t batch_points(uint64_t n) {
+    uint64_t b = kPointBudgetBytes / (kDim * 4 + 4);
+    if (const char* e = getenv("GSPLAT_IMPORT_BATCH")) {     // read per call
+        char* end = nullptr;
+        const unsigned long long v = strtoull(e, &end, 10);
+        if (end != e && v > 0) b = v;
+    }
+    return std::max<uint64_t>(1, std::min(std::min(b, kMaxBatch), n));
+}
+
+} // namespace
+
+// gs_import_assign_clusters with a context: the means (+ their squared norms, summed on the host exactly as the host loop sums them) are uploaded
+// once, the points go through one device buffer in batches; everything is enqueued on the context's stream in order and waited for at the end.
+int32_t assign_clusters_gpu(gs_context* ctx, const float* x, uint64_t n, const float* means, uint32_t K, uint32_t* out) {
+    GS_HIP(hipSetDevice(ctx->device));
+    std::vector<double> c2(K);
+    for (uint32_t j = 0; j < K; ++j) {
+        double sq = 0.0;
+        for (int k = 0; k < kDim; ++k) { const double m = means[(size_t)j * kDim + k]; sq += m * m; }
+        c2[j] = sq;
+    }
+    const uint64_t batch = batch_points(n);
+    DeviceBuffers d;
+    GS_HIP(hipMalloc((void**)&d.means, (size_t)K * kDim * 4));
+    GS_HIP(hipMalloc((void**)&d.c2, (size_t)K * 8));
+    GS_HIP(hipMalloc((void**)&d.x, (size_t)batch * kDim * 4));
+    GS_HIP(hipMalloc((void**)&d.out, (size_t)batch * 4));
+    hipStream_t st = ctx->stream;
+    GS_HIP(hipMemcpyAsync(d.means, means, (size_t)K * kDim * 4, hipMemcpyHostToDevice, st));
+    GS_HIP(hipMemcpyAsync(d.c2, c2.data(), (size_t)K * 8, hipMemcpyHostToDevice, st));
+    for (uint64_t i0 = 0; i0 < n; i0 += batch) {
+        const uint32_t nb = (uint32_t)std::min<uint64_t>(batch, n - i0);
+        GS_HIP(hipMemcpyAsync(d.x, x + (size_t)i0 * kDim, (size_t)nb * kDim * 4, hipMemcpyHostToDevice, st));
+        assign_clusters_kernel<<<dim3((nb + kTile - 1) / kTile), dim3(kClusterThreads), 0, st>>>(d.x, nb, d.means, d.c2, K, d.out);
+        GS_HIP(hipGetLastError());
+        GS_HIP(hipMemcpyAsync(out + i0, d.out, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
+    }
+    GS_HIP(hipStreamSynchronize(st));              // (on an error path above, the hipFree calls of ~DeviceBuffers wait for what was enqueued)
+    return GS_OK;
+}
+
+} // namespace gs

@@ -7,6 +7,8 @@
 //   Editor/GaussianSplatAssetCreator.cs :362-429  bounds + Morton reorder, :520-658 chunk bounds / normalisation,
 //                                       :705-758  Encode* / EmitEncodedVector (truncating (uint)(v * (k + 0.5f))),
 //                                       :776-805  other data, :863-932 colour texture (16x16 Morton tiles), :934-1037 SH items
+// The one stage that can also run on a GPU is the nearest-mean assignment of the Cluster* SH palette (gs_cluster.hip, through
+// gs_import_encode_on / gs_import_assign_clusters with a context): the same operations in the same order, the same bytes.
 // Arithmetic is plain IEEE fp32, one rounding per operation (-ffp-contract=off), and the two transcendental steps are
 // written out (exp as Cephes-style range reduction + polynomial, x^(1/8) as three correctly rounded square roots) so that
 // the bytes are a function of this source only: unitygaussiansplatting_amd/creator.py performs the same operations with
@@ -33,6 +35,7 @@
 
 namespace gs {
 int32_t fail(int32_t code, const char* what);
+int32_t assign_clusters_gpu(gs_context* ctx, const float* x, uint64_t n, const float* means, uint32_t K, uint32_t* out);   // gs_cluster.hip
 }
 
 namespace {
@@ -221,7 +224,7 @@ void bc7_encode_mode6(const float px[16][4], uint8_t out[16]) {
 // that the two importers emit the same bytes: stride-sampled seeds and training subset, 4 Lloyd iterations on the subset
 // (assignment by the smallest |c|^2 - 2 x.c in double, first minimum; means = double sums in point order, rounded to fp32),
 // then one assignment pass over all splats.  x: n x 45.  The assignment is the importer's one GEMM-shaped loop (n x K x 45).
-void assign_clusters(const float* x, size_t n, const std::vector<float>& means, uint32_t K, uint32_t* out) {
+void assign_clusters(const float* x, size_t n, const float* means, uint32_t K, uint32_t* out) {
     std::vector<double> mt((size_t)45 * K), c2(K);                            // means transposed: the inner loop runs over clusters
     for (uint32_t j = 0; j < K; ++j) {
         double sq = 0.0;
@@ -244,7 +247,15 @@ void assign_clusters(const float* x, size_t n, const std::vector<float>& means, 
     });
 }
 
-void cluster_shs(const float* x, size_t n, uint32_t K, std::vector<float>& means, std::vector<uint32_t>& index) {
+// ctx == null: the host loop above; else the same assignment on the context's GPU (gs_cluster.hip: the same index for every point, by construction).
+// The mean update stays on the host either way: its summation order is part of the bytes.
+int32_t assign_clusters_on(gs_context* ctx, const float* x, size_t n, const float* means, uint32_t K, uint32_t* out) {
+    if (ctx) return gs::assign_clusters_gpu(ctx, x, n, means, K, out);
+    assign_clusters(x, n, means, K, out);
+    return GS_OK;
+}
+
+int32_t cluster_shs(gs_context* ctx, const float* x, size_t n, uint32_t K, std::vector<float>& means, std::vector<uint32_t>& index) {
     means.resize((size_t)K * 45);
     for (uint32_t j = 0; j < K; ++j) memcpy(&means[(size_t)j * 45], x + (((uint64_t)j * n) / K) * 45, 180);
     const size_t S = 200000;
@@ -258,7 +269,7 @@ void cluster_shs(const float* x, size_t n, uint32_t K, std::vector<float>& means
     }
     std::vector<uint32_t> idx(ns), start(K + 1), sorted(ns);
     for (int it = 0; it < 4; ++it) {
-        assign_clusters(sub, ns, means, K, idx.data());
+        { const int32_t rc = assign_clusters_on(ctx, sub, ns, means.data(), K, idx.data()); if (rc != GS_OK) return rc; }
         std::fill(start.begin(), start.end(), 0u);                           // counting sort: the points of a cluster in point order
         for (size_t i = 0; i < ns; ++i) start[idx[i] + 1]++;
         for (uint32_t j = 0; j < K; ++j) start[j + 1] += start[j];
@@ -274,7 +285,7 @@ void cluster_shs(const float* x, size_t n, uint32_t K, std::vector<float>& means
         });
     }
     index.resize(n);
-    assign_clusters(x, n, means, K, index.data());
+    return assign_clusters_on(ctx, x, n, means.data(), K, index.data());
 }
 
 struct Splat { float pos[3], dc0[3], sh[45], opacity, scale[3], rot[4]; };      // linearised
@@ -302,17 +313,29 @@ int32_t gs_import_blob_sizes(uint32_t splat_count, const gs_import_formats* f, u
     return GS_OK;
 }
 
-static int32_t import_encode_impl(const gs_import_input* in, const gs_import_formats* f, void* const blobs[5], const uint64_t sizes[5],
+static int32_t import_encode_impl(gs_context* ctx, const gs_import_input* in, const gs_import_formats* f, void* const blobs[5], const uint64_t sizes[5],
                                   float bounds_min[3], float bounds_max[3]);
 
-int32_t gs_import_encode(const gs_import_input* in, const gs_import_formats* f, void* const blobs[5], const uint64_t sizes[5],
-                         float bounds_min[3], float bounds_max[3]) {
-    try { return import_encode_impl(in, f, blobs, sizes, bounds_min, bounds_max); }      // nothing may throw across the C boundary
+int32_t gs_import_encode_on(gs_context* ctx, const gs_import_input* in, const gs_import_formats* f, void* const blobs[5], const uint64_t sizes[5],
+                            float bounds_min[3], float bounds_max[3]) {
+    try { return import_encode_impl(ctx, in, f, blobs, sizes, bounds_min, bounds_max); }      // nothing may throw across the C boundary
     catch (const std::bad_alloc&) { return gs::fail(GS_ERR_OUT_OF_MEMORY, "host allocation"); }
     catch (...) { return gs::fail(GS_ERR_INVALID_ARGUMENT, "unexpected failure in the importer"); }
 }
 
-static int32_t import_encode_impl(const gs_import_input* in, const gs_import_formats* f, void* const blobs[5], const uint64_t sizes[5],
+int32_t gs_import_encode(const gs_import_input* in, const gs_import_formats* f, void* const blobs[5], const uint64_t sizes[5],
+                         float bounds_min[3], float bounds_max[3]) {
+    return gs_import_encode_on(nullptr, in, f, blobs, sizes, bounds_min, bounds_max);
+}
+
+int32_t gs_import_assign_clusters(gs_context* ctx, const float* x, uint64_t n, const float* means, uint32_t k, uint32_t* index_out) {
+    if (!x || !means || !index_out || n == 0 || k == 0) return gs::fail(GS_ERR_INVALID_ARGUMENT, "null argument / no points / no means");
+    try { return assign_clusters_on(ctx, x, (size_t)n, means, k, index_out); }
+    catch (const std::bad_alloc&) { return gs::fail(GS_ERR_OUT_OF_MEMORY, "host allocation"); }
+    catch (...) { return gs::fail(GS_ERR_INVALID_ARGUMENT, "unexpected failure in the importer"); }
+}
+
+static int32_t import_encode_impl(gs_context* ctx, const gs_import_input* in, const gs_import_formats* f, void* const blobs[5], const uint64_t sizes[5],
                                   float bounds_min[3], float bounds_max[3]) {
     if (!in || !f || !blobs || !sizes) return gs::fail(GS_ERR_INVALID_ARGUMENT, "null argument");
     uint64_t need[5];
@@ -377,7 +400,8 @@ static int32_t import_encode_impl(const gs_import_input* in, const gs_import_for
     if (clustered) {
         std::vector<float> x((size_t)n * 45);
         parallel_for(n, 1 << 14, [&](size_t a, size_t b) { for (size_t i = a; i < b; ++i) memcpy(&x[i * 45], s[order[i]].sh, 180); });
-        cluster_shs(x.data(), n, sh_clusters(f->sh_format), shMeans, shIndex);
+        const int32_t crc = cluster_shs(ctx, x.data(), n, sh_clusters(f->sh_format), shMeans, shIndex);
+        if (crc != GS_OK) return crc;
     }
     // BC7: the colour texels are gathered as floats first and compressed block by block afterwards
     const bool bc7 = f->color_format == GS_COLOR_BC7;
