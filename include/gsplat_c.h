@@ -297,6 +297,44 @@ int32_t gs_renderer_set_cutouts(gs_renderer* r, const gs_cutout* cutouts, uint32
 /* m_GpuEditDeleted + _SplatBitsValid (GaussianSplatRenderer.cs:497,501; SplatUtilities.compute:204-214): one bit per
  * splat, bit set = deleted (clip.w = 0).  `words` = ceil(N/32) host uint32s, copied; NULL => _SplatBitsValid = 0. */
 int32_t gs_renderer_set_deleted_bits(gs_renderer* r, const uint32_t* words, size_t word_count);
+
+/* ---- selection and deletion: GaussianSplatRenderer.Edit* (GaussianSplatRenderer.cs:705-740,767-840,896-934) ----------
+ * (additions to ABI 9)  The half of the reference's editor that never writes the asset: the selection set, rectangle selection
+ * through a camera, counts and bounds, deletion.  The seven kernels behind it -- CSInitEditData, CSUpdateEditData, CSClearBuffer,
+ * CSInvertSelection, CSSelectAll, CSOrBuffers, CSSelectionUpdate (SplatUtilities.compute:266-423) -- leave in memory, word for word,
+ * what the reference's leave.  The buffers are made at the first edit call (EnsureEditingBuffers, :767-786): `selected` and its
+ * mouse-down copy, ceil(N/32) zeroed words each; the deleted buffer is the one gs_renderer_set_deleted_bits fills -- made (zeroed) by
+ * the first delete, and read as zeros while it does not exist.  Every kernel tests the splats against the renderer's current
+ * gs_renderer_set_cutouts list (IsSplatCut), as the reference's do.
+ * Selection has NO VISUAL EFFECT: the reference's highlight of selected splats (RenderGaussianSplats.shader:63-73,87-101) is not built;
+ * only deletion changes a frame.  Moving, rotating, scaling, exporting and copying splats (CSTranslateSelection .. CSCopySplats) are not
+ * built either: they rewrite the asset's blobs, which are immutable and shared here.
+ * Two literal quirks of the reference are kept: select-all / invert set the bits of the last word beyond N and the counts include them
+ * (N = 33: select all reports 64 selected), and a splat whose pixel position is NaN is inside every rectangle.
+ * The mutating calls are asynchronous on the context's stream like every other call; the info / download calls block.  Selection lives
+ * on the renderer it was made on; with frames in flight the lanes' deleted bits follow a delete by a device-to-device copy on each
+ * lane's own stream (no host synchronisation), so a frame already dealt to a lane keeps the bits of the time it was dealt. */
+typedef struct gs_edit_info {          /* m_GpuEditCountsBounds decoded; 36 bytes */
+    uint32_t selected, deleted, cut;    /* editSelectedSplats, editDeletedSplats, editCutSplats: deleted splats count as neither selected nor cut */
+    float bounds_min[3], bounds_max[3]; /* object space, of the selected splats; raw: +1e38 / -1e38 when nothing is selected */
+} gs_edit_info;
+int32_t gs_renderer_edit_select_all(gs_renderer* r);                /* EditSelectAll :906-915: every bit but the cut splats' */
+int32_t gs_renderer_edit_deselect_all(gs_renderer* r);              /* EditDeselectAll :917-922 */
+int32_t gs_renderer_edit_invert_selection(gs_renderer* r);          /* EditInvertSelection :924-934 */
+int32_t gs_renderer_edit_store_selection(gs_renderer* r);           /* EditStoreSelectionMouseDown :788-792 */
+/* EditUpdateSelection (:811-840): selected = mouse-down copy, then CSSelectionUpdate with p's matrix_object_to_world / matrix_vp / screen_w,h;
+ * selection_rect = _SelectionRect (x_min, y_min, x_max, y_max), pixels, x right, y UP from the bottom edge.  A splat that is not cut, has
+ * clip.w > 0 and whose centre projects inside the rectangle is added to the selection, or with subtract != 0 removed from it. */
+int32_t gs_renderer_edit_update_selection(gs_renderer* r, const gs_frame_params* p, const float selection_rect[4], int32_t subtract);
+int32_t gs_renderer_edit_delete_selected(gs_renderer* r);           /* EditDeleteSelected :896-904: deleted |= selected; selected = 0 */
+/* UpdateEditCountsAndBounds (:705-740): CSInitEditData + CSUpdateEditData; blocks.  All zeros while the renderer has no edit buffers. */
+int32_t gs_renderer_edit_info(gs_renderer* r, gs_edit_info* out);
+/* the selected words from the host (ceil(N/32) of them, copied), e.g. a selection the host computed or saved */
+int32_t gs_renderer_edit_upload_selected_bits(gs_renderer* r, const uint32_t* words, size_t word_count);
+/* ceil(N/32) words each; any may be NULL; a buffer that does not exist reads as zeros; blocks */
+int32_t gs_renderer_edit_download_bits(gs_renderer* r, uint32_t* selected, uint32_t* selected_mouse_down, uint32_t* deleted, size_t word_count);
+int32_t gs_renderer_edit_release(gs_renderer* r);                   /* frees selected + mouse-down; deleted bits stay */
+
 /* m_RenderMode + m_PointDisplaySize (GaussianSplatRenderer.cs:241-242; material choice :126-131).  DebugPoints / DebugPointIndices
  * (GaussianDebugRenderPoints.shader) draw every splat as an opaque screen-space square of `point_display_size` pixels, nearest
  * wins (ZWrite On), colour = saturate(DC colour) or an index code; gs_renderer_draw then neither needs gs_renderer_sort nor

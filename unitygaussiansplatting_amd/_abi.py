@@ -48,6 +48,11 @@ class gs_cutout(C.Structure):
     _fields_ = [("matrix", C.c_float * 16), ("type_and_flags", C.c_uint32)]
 
 
+class gs_edit_info(C.Structure):         # m_GpuEditCountsBounds decoded (gs_renderer_edit_info)
+    _fields_ = [("selected", C.c_uint32), ("deleted", C.c_uint32), ("cut", C.c_uint32),
+                ("bounds_min", C.c_float * 3), ("bounds_max", C.c_float * 3)]
+
+
 class gs_import_input(C.Structure):
     _fields_ = [("splat_count", C.c_uint32), ("pos", C.c_void_p), ("dc0", C.c_void_p), ("sh", C.c_void_p),
                 ("opacity", C.c_void_p), ("scale", C.c_void_p), ("rot", C.c_void_p)]

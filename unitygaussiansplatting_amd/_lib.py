@@ -6,7 +6,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-from ._abi import (gs_asset_desc, gs_cutout, gs_frame_params, gs_frame_stats, gs_import_formats, gs_import_input,
+from ._abi import (gs_asset_desc, gs_cutout, gs_edit_info, gs_frame_params, gs_frame_stats, gs_import_formats, gs_import_input,
                    gs_stage_times)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -54,6 +54,16 @@ SIGNATURES = {
     "gs_renderer_render": (C.c_int32, [_P, C.POINTER(C.c_float), C.POINTER(gs_frame_params), _P, C.c_int32]),
     "gs_renderer_set_cutouts": (C.c_int32, [_P, C.POINTER(gs_cutout), C.c_uint32]),
     "gs_renderer_set_deleted_bits": (C.c_int32, [_P, _P, C.c_size_t]),
+    "gs_renderer_edit_select_all": (C.c_int32, [_P]),
+    "gs_renderer_edit_deselect_all": (C.c_int32, [_P]),
+    "gs_renderer_edit_invert_selection": (C.c_int32, [_P]),
+    "gs_renderer_edit_store_selection": (C.c_int32, [_P]),
+    "gs_renderer_edit_update_selection": (C.c_int32, [_P, C.POINTER(gs_frame_params), C.POINTER(C.c_float), C.c_int32]),
+    "gs_renderer_edit_delete_selected": (C.c_int32, [_P]),
+    "gs_renderer_edit_info": (C.c_int32, [_P, C.POINTER(gs_edit_info)]),
+    "gs_renderer_edit_upload_selected_bits": (C.c_int32, [_P, _P, C.c_size_t]),
+    "gs_renderer_edit_download_bits": (C.c_int32, [_P, _P, _P, _P, C.c_size_t]),
+    "gs_renderer_edit_release": (C.c_int32, [_P]),
     "gs_renderer_set_view_buffer_mode": (C.c_int32, [_P, C.c_int32]),
     "gs_renderer_set_blend_mode": (C.c_int32, [_P, C.c_int32]),
     "gs_renderer_set_render_mode": (C.c_int32, [_P, C.c_int32, C.c_float]),

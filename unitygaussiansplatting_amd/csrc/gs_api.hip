@@ -1,6 +1,7 @@
 // gs_api.hip -- the C-ABI of include/gsplat_c.h: object lifetime, argument validation, stream sequencing.
 // Mirrors what GaussianSplatRenderer.cs / GpuSorting.cs do on Unity's main thread (buffer creation :373-445,
-// dispatch order :108-211,579-639, disposal :527-577); every kernel lives in gs_sort/gs_view/gs_raster.hip.
+// dispatch order :108-211,579-639, disposal :527-577); every kernel lives in gs_sort/gs_view/gs_raster.hip
+// (the edit entry points sit next to their kernels in gs_edit.hip).
 #include <stdarg.h>
 #include <stdlib.h>
 
@@ -409,6 +410,7 @@ int32_t gs_renderer_destroy(gs_renderer* r) {
     if (r->distances) (void)hipFree(r->distances);
     if (r->order) (void)hipFree(r->order);
     if (r->depthControl) (void)hipFree(r->depthControl);
+    edit_free(r);
     if (r->deletedBits) (void)hipFree(r->deletedBits);
     if (r->cutouts) (void)hipFree(r->cutouts);
     if (r->cutoutsHost) (void)hipHostFree(r->cutoutsHost);

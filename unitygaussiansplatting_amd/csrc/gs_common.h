@@ -253,6 +253,13 @@ struct gs_renderer {
     uint32_t cutoutsHostCount = 0;
     hipEvent_t cutoutsCopied = nullptr;
     bool cutoutsCopyPending = false;
+    // selection state of the edit kernels (gs_edit.hip; EnsureEditingBuffers, GaussianSplatRenderer.cs:767-786), made at the first edit call; the deleted
+    // buffer of that function is deletedBits above.  On the owning renderer only: a lane holds nothing but its copy of deletedBits.
+    uint32_t* editSelected = nullptr;       // m_GpuEditSelected: ceil(N/32) words
+    uint32_t* editSelectedMouseDown = nullptr;   // m_GpuEditSelectedMouseDown
+    uint32_t* editCountsBounds = nullptr;   // m_GpuEditCountsBounds: 3 counts + 6 sortable uints
+    hipEvent_t evEditDeleted = nullptr;     // context's stream -> lanes: deletedBits holds a delete's result
+    hipEvent_t evEditCopied = nullptr;      // (on a lane) lane's stream -> owner's: the lane has taken its copy
     float viewW = 0.f, viewH = 0.f, viewNear = 0.f, viewFar = 0.f;   // what the last calc_view was run with
     bool viewValid = false;
     bool viewMaterialised = false;          // the N x 40 B view buffer holds the last calc_view's records (written on demand)
@@ -386,4 +393,6 @@ int32_t enqueue_debug_points(gs_renderer* r, const gs_frame_params* p, gs_target
 int32_t enqueue_debug_boxes(gs_renderer* r, const gs_frame_params* p, gs_target* rt, bool chunks);   // RenderMode.DebugBoxes / DebugChunkBounds
 int32_t enqueue_resolve(gs_target* t, const float bg[4], bool want8);
 int32_t flush_clear(gs_target* t);          // perform a pending gs_target_clear now
+// edit (gs_edit.hip)
+void edit_free(gs_renderer* r);             // the selection buffers and the edit events (not deletedBits)
 } // namespace gs

@@ -9,7 +9,8 @@
 //   GaussianSplatting.hlsl :5-11 InvSquareCentered01, :29-53 CalcMatrixFromRotationScale/CalcCovariance3D,
 //   :56-90 CalcCovariance2D, :113-127,183-194 Morton texel address, :130-179 ShadeSH, :219-229 DecodeRotation,
 //   :261-300 DecodePacked_*, :325-421 LoadUShort/LoadUInt/LoadAndDecodeVector/LoadSplatPos, :428-608 LoadSplatData
-//   SplatUtilities.compute :52-57 FloatToSortableUint, :107-162 DecomposeCovariance, :189-252 CSCalcViewData
+//   SplatUtilities.compute :52-57 FloatToSortableUint, :107-162 DecomposeCovariance, :189-252 CSCalcViewData,
+//   :279-296 CSUpdateEditData's bounds, :400-416 CSSelectionUpdate's hit test (the edit kernels: gs_edit.hip)
 #pragma once
 #include <stdint.h>
 
@@ -648,6 +649,39 @@ GS_HD bool IsSplatCut(const EditView& e, float px, float py, float pz) {
         finalCut = finalCut || !invert;
     }
     return finalCut;
+}
+
+// ---- the edit kernels' per-splat arithmetic (SplatUtilities.compute:266-423; kernels in gs_edit.hip) ----
+// What CSSelectionUpdate reads of a frame: _MatrixObjectToWorld (rows 0..2), UNITY_MATRIX_VP, _VecScreenParams.xy and
+// _SelectionRect = (x_min, y_min, x_max, y_max) in pixels, y up from the bottom edge
+struct EditSelect {
+    float o2w[12];
+    float vp[16];
+    float screenW, screenH;
+    float rect[4];
+};
+
+// CSSelectionUpdate's test of one splat (SplatUtilities.compute:400-416): does the rectangle select it?  World and clip position
+// are CalcViewGeom's expressions, so the clip position has the bits of the view record's pos.  Every comparison is the
+// reference's, literally: a NaN w is not "behind", and a NaN pixel position is outside no edge of the rectangle, so it is a hit.
+GS_HD bool EditSelectionHit(const EditSelect& S, const EditView& E, const V3& pos) {
+    if (IsSplatCut(E, pos.x, pos.y, pos.z)) return false;
+    const float wx = mrow(S.o2w, 0, pos.x, pos.y, pos.z), wy = mrow(S.o2w, 1, pos.x, pos.y, pos.z), wz = mrow(S.o2w, 2, pos.x, pos.y, pos.z);
+    const float cx = mrow(S.vp, 0, wx, wy, wz), cy = mrow(S.vp, 1, wx, wy, wz), cw = mrow(S.vp, 3, wx, wy, wz);
+    if (cw <= 0.0f) return false;                                  // behindCam
+    const float px = ((cx / cw) * 0.5f + 0.5f) * S.screenW;        // (centerClipPos.y *= -1 first, :406)
+    const float py = (((-cy) / cw) * -0.5f + 0.5f) * S.screenH;
+    if (px < S.rect[0] || px > S.rect[2] || py < S.rect[1] || py > S.rect[3]) return false;
+    return true;
+}
+
+// CSUpdateEditData's bounds of one selected splat (SplatUtilities.compute:279-296), as the sortable uints the kernel's
+// InterlockedMin / Max take: min(1e38, p) / max(-1e38, p) per component -- fminf / fmaxf drop a NaN as HLSL's min / max do.
+// FloatToSortableUint is monotonic over every float, so integer min / max of these in any grouping gives the same bits.
+GS_HD void EditSplatBounds(const V3& pos, uint32_t lo[3], uint32_t hi[3]) {
+    lo[0] = FloatToSortableUint(fminf(1.0e38f, pos.x)); hi[0] = FloatToSortableUint(fmaxf(-1.0e38f, pos.x));
+    lo[1] = FloatToSortableUint(fminf(1.0e38f, pos.y)); hi[1] = FloatToSortableUint(fmaxf(-1.0e38f, pos.y));
+    lo[2] = FloatToSortableUint(fminf(1.0e38f, pos.z)); hi[2] = FloatToSortableUint(fmaxf(-1.0e38f, pos.z));
 }
 
 // CSCalcViewData for one splat (SplatUtilities.compute:189-252), in two halves so that a caller which only needs the

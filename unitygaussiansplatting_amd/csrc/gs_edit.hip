@@ -1,0 +1,336 @@
+// gs_edit.hip -- selection and deletion: the edit kernels of SplatUtilities.compute that never write the asset, and the
+// gs_renderer_edit_* entry points over them (GaussianSplatRenderer.Edit*, GaussianSplatRenderer.cs:705-740,767-840,896-934).
+//
+// Restated word for word in what they leave in memory:
+//   CSInitEditData + CSUpdateEditData  SplatUtilities.compute:266-325   counts of selected / deleted / cut splats, bounds of the selection
+//   CSClearBuffer                      :327-334                         (a memset)
+//   CSInvertSelection / CSSelectAll    :336-377                         every bit, cut splats cleared
+//   CSOrBuffers                        :380-389                         deleted |= selected
+//   CSSelectionUpdate                  :391-423                         rectangle selection through a camera, add or subtract
+// Not built: CSTranslateSelection .. CSCopySplats (they rewrite the pos / other blobs, which this library shares between contexts, lanes
+// and replicas) and the highlight of selected splats in the fragment stage (RenderGaussianSplats.shader:63-73,87-101: it replaces a splat's
+// opacity by -1, which here would go through PrepareSplat's cull and footprint bound and the blend's alpha window).  Selection therefore
+// has NO VISUAL EFFECT: only deletion changes a frame, through the deleted bits calc_view already reads.
+//
+// Shape (wave64; not the reference's, which runs one thread per WORD with a 32-iteration position loop, neighbouring threads reading
+// positions 32 records apart): one thread per SPLAT, 256-thread workgroups aligned to the 256-splat chunk so that the chunk header is
+// workgroup-uniform.  The per-splat predicate (cut / hit) becomes a word through __ballot; a wave owns exactly two consecutive words, one
+// lane per word does a plain read-modify-write -- no other wave touches that word, so the reference's per-splat InterlockedOr / And is not
+// needed and the result is identical.  No word index >= ceil(N/32) is ever stored.  Counts are popcounts of the words, bounds reduce per
+// wave with __shfl_xor and across the four waves in LDS: at most nine global atomics per workgroup.
+//
+// Two literal quirks of the reference, kept:
+//   - CSSelectAll / CSInvertSelection set the bits of the last word beyond N, and CSUpdateEditData counts them: N = 33, select all ->
+//     selected = 64.  The words and the counts are the parity surface, so they are the reference's.
+//   - a splat whose pixel position is NaN is inside every rectangle (all four comparisons are false).
+// One difference: the bounds are reduced as sortable uints at every level (a total order, so any grouping gives the same bits); a
+// component that is +0 for one selected splat and -0 for another reports -0, where the reference leaves it to the GPU's min().
+#include <new>
+
+#include "gs_common.h"
+
+namespace gs {
+
+constexpr uint32_t kSortableMinInit = __builtin_bit_cast(uint32_t, 1.0e38f) ^ 0x80000000u;   // FloatToSortableUint(1.0e38)
+constexpr uint32_t kSortableMaxInit = ~__builtin_bit_cast(uint32_t, -1.0e38f);              // FloatToSortableUint(-1.0e38)
+
+// the word of a 64-bit ballot this lane's splat belongs to
+__device__ __forceinline__ uint32_t ballot_word(unsigned long long b, uint32_t lane) { return (uint32_t)(b >> (lane & 32u)); }
+
+// CSSelectAll (invert = 0) / CSInvertSelection (invert = 1)
+__global__ __launch_bounds__(256) void edit_select_all_kernel(gsm::AssetView a, gsm::EditView e, uint32_t* __restrict__ sel, uint32_t nWords, uint32_t invert) {
+    const uint32_t idx = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u;
+    bool cut = false;
+    if (idx < a.n) {
+        const gsm::V3 pos = gsm::LoadSplatPosChunk(a, idx, blockIdx.x);
+        cut = gsm::IsSplatCut(e, pos.x, pos.y, pos.z);
+    }
+    const uint32_t cutw = ballot_word(__ballot(cut), lane);
+    const uint32_t w = idx >> 5;
+    if ((lane & 31u) == 0u && w < nWords) {
+        uint32_t v = invert ? ~sel[w] : ~0u;
+        v &= ~cutw;                                                // do not select splats that are cut
+        sel[w] = v;
+    }
+}
+
+// Graphics.CopyBuffer(mouse-down copy -> selected) + CSSelectionUpdate in one pass: every word is written once
+__global__ __launch_bounds__(256) void edit_selection_update_kernel(gsm::AssetView a, gsm::EditView e, gsm::EditSelect S, const uint32_t* __restrict__ mouseDown,
+                                                                    uint32_t* __restrict__ sel, uint32_t nWords, uint32_t add) {
+    const uint32_t idx = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u;
+    bool hit = false;
+    if (idx < a.n) hit = gsm::EditSelectionHit(S, e, gsm::LoadSplatPosChunk(a, idx, blockIdx.x));
+    const uint32_t hitw = ballot_word(__ballot(hit), lane);
+    const uint32_t w = idx >> 5;
+    if ((lane & 31u) == 0u && w < nWords) {
+        const uint32_t v = mouseDown[w];
+        sel[w] = add ? (v | hitw) : (v & ~hitw);
+    }
+}
+
+// CSOrBuffers (deleted |= selected) + CSClearBuffer (selected = 0): EditDeleteSelected
+__global__ __launch_bounds__(256) void edit_delete_kernel(uint32_t* __restrict__ deleted, uint32_t* __restrict__ sel, uint32_t nWords) {
+    const uint32_t w = blockIdx.x * 256u + threadIdx.x;
+    if (w >= nWords) return;
+    deleted[w] |= sel[w];
+    sel[w] = 0u;
+}
+
+// CSInitEditData
+__global__ void edit_init_data_kernel(uint32_t* __restrict__ out) {
+    const uint32_t t = threadIdx.x;
+    if (t < 9u) out[t] = t < 3u ? 0u : (t < 6u ? kSortableMinInit : kSortableMaxInit);
+}
+
+// CSUpdateEditData
+__global__ __launch_bounds__(256) void edit_update_data_kernel(gsm::AssetView a, gsm::EditView e, const uint32_t* __restrict__ sel, uint32_t nWords,
+                                                               uint32_t* __restrict__ out) {
+    __shared__ uint32_t s_part[4][9];
+    const uint32_t idx = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const bool inside = idx < a.n;
+    gsm::V3 pos = { 0.0f, 0.0f, 0.0f };
+    bool cut = false;
+    if (inside) {
+        pos = gsm::LoadSplatPosChunk(a, idx, blockIdx.x);
+        cut = gsm::IsSplatCut(e, pos.x, pos.y, pos.z);
+    }
+    const uint32_t cutw = ballot_word(__ballot(cut), lane);
+    const uint32_t w = idx >> 5;
+    uint32_t valSel = 0u, valDel = 0u;
+    if (w < nWords) {                                              // (the 32 lanes of a word read the same address)
+        valSel = sel[w];
+        if (e.deletedBits) valDel = e.deletedBits[w];
+    }
+    valSel &= ~valDel;                                             // don't count deleted splats as selected
+    valSel &= ~cutw;                                               // don't count cut splats as selected
+    const uint32_t valCut = cutw & ~valDel;                        // don't count deleted splats as cut
+    // counts: the popcounts of the wave's two words (held by lanes 0 and 32), bits beyond N included as in the reference
+    uint32_t v[9];
+    v[0] = (uint32_t)(__popc((uint32_t)__builtin_amdgcn_readlane((int)valSel, 0)) + __popc((uint32_t)__builtin_amdgcn_readlane((int)valSel, 32)));
+    v[1] = (uint32_t)(__popc((uint32_t)__builtin_amdgcn_readlane((int)valDel, 0)) + __popc((uint32_t)__builtin_amdgcn_readlane((int)valDel, 32)));
+    v[2] = (uint32_t)(__popc((uint32_t)__builtin_amdgcn_readlane((int)valCut, 0)) + __popc((uint32_t)__builtin_amdgcn_readlane((int)valCut, 32)));
+    // bounds of the selected splats (the reference's loop stops at N: a bit beyond it has no position); a wave that selected nothing
+    // -- most waves under a rectangle selection -- skips the reduction
+    v[3] = v[4] = v[5] = kSortableMinInit;
+    v[6] = v[7] = v[8] = kSortableMaxInit;
+    const bool mine = inside && ((valSel >> (idx & 31u)) & 1u);
+    if (__ballot(mine) != 0ull) {
+        if (mine) gsm::EditSplatBounds(pos, v + 3, v + 6);
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) {
+#pragma unroll
+            for (int k = 3; k < 6; ++k) v[k] = min(v[k], (uint32_t)__shfl_xor((int)v[k], m));
+#pragma unroll
+            for (int k = 6; k < 9; ++k) v[k] = max(v[k], (uint32_t)__shfl_xor((int)v[k], m));
+        }
+    }
+    if (lane == 0u) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) s_part[wave][k] = v[k];
+    }
+    __syncthreads();
+    const uint32_t t = threadIdx.x;
+    if (t < 9u) {
+        const uint32_t p0 = s_part[0][t], p1 = s_part[1][t], p2 = s_part[2][t], p3 = s_part[3][t];
+        if (t < 3u) {
+            const uint32_t sum = p0 + p1 + p2 + p3;
+            if (sum) atomicAdd(out + t, sum);
+        } else if (t < 6u) {
+            const uint32_t lo = min(min(p0, p1), min(p2, p3));
+            if (lo != kSortableMinInit) atomicMin(out + t, lo);    // (the workgroup selected nothing: what the buffer was initialised with)
+        } else {
+            const uint32_t hi = max(max(p0, p1), max(p2, p3));
+            if (hi != kSortableMaxInit) atomicMax(out + t, hi);
+        }
+    }
+}
+
+static inline size_t edit_words(const gs_renderer* r) { return ((size_t)r->n + 31) / 32; }
+
+static gsm::EditView edit_view(const gs_renderer* r) {
+    gsm::EditView e;
+    e.deletedBits = r->deletedBits; e.cutouts = r->cutouts; e.cutoutCount = r->cutoutCount;
+    return e;
+}
+
+// EnsureEditingBuffers (GaussianSplatRenderer.cs:767-786) without the deleted buffer, which is made when a delete first needs it
+static int32_t edit_ensure(gs_renderer* r) {
+    if (r->laneOf) return fail(GS_ERR_INVALID_ARGUMENT, "a lane holds no selection: edit its owner");
+    GS_HIP(hipSetDevice(r->ctx->device));
+    if (r->editSelected) return GS_OK;
+    const size_t bytes = edit_words(r) * 4;
+    uint32_t *sel = nullptr, *md = nullptr, *cb = nullptr;
+    hipError_t e = hipMalloc((void**)&sel, bytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&md, bytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&cb, 9 * 4);
+    if (e == hipSuccess) e = hipMemsetAsync(sel, 0, bytes, r->ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(md, 0, bytes, r->ctx->stream);
+    if (e != hipSuccess) {
+        if (sel) (void)hipFree(sel);
+        if (md) (void)hipFree(md);
+        if (cb) (void)hipFree(cb);
+        return fail_hip(e, "allocate edit buffers", __FILE__, __LINE__);
+    }
+    r->editSelected = sel; r->editSelectedMouseDown = md; r->editCountsBounds = cb;
+    return GS_OK;
+}
+
+void edit_free(gs_renderer* r) {
+    if (r->editSelected) (void)hipFree(r->editSelected);
+    if (r->editSelectedMouseDown) (void)hipFree(r->editSelectedMouseDown);
+    if (r->editCountsBounds) (void)hipFree(r->editCountsBounds);
+    r->editSelected = r->editSelectedMouseDown = r->editCountsBounds = nullptr;
+    if (r->evEditDeleted) { (void)hipEventDestroy(r->evEditDeleted); r->evEditDeleted = nullptr; }
+    if (r->evEditCopied) { (void)hipEventDestroy(r->evEditCopied); r->evEditCopied = nullptr; }
+}
+
+static inline uint32_t splat_grid(const gs_renderer* r) { return (r->n + 255u) / 256u; }
+static inline uint32_t word_grid(const gs_renderer* r) { return (uint32_t)((edit_words(r) + 255) / 256); }
+
+// The lanes' copies of the deleted bits follow a delete: a device-to-device copy on each lane's OWN stream, behind an event on the
+// context's stream -- no host synchronisation, and a frame already dealt to a lane keeps the bits of the time it was dealt (its calc_view is
+// ahead of the copy on that stream).  The context's stream then waits for the copies, so that whatever writes or frees the owner's buffer
+// next (another delete, gs_renderer_set_deleted_bits) comes after they have read it.
+static int32_t edit_deleted_to_lanes(gs_renderer* r) {
+    if (r->lanes.empty()) return GS_OK;
+    const size_t bytes = edit_words(r) * 4;
+    if (!r->evEditDeleted) GS_HIP(hipEventCreateWithFlags(&r->evEditDeleted, hipEventDisableTiming));
+    GS_HIP(hipEventRecord(r->evEditDeleted, r->ctx->stream));
+    for (gs_renderer* L : r->lanes) {
+        if (!L->deletedBits) GS_HIP(hipMalloc((void**)&L->deletedBits, bytes));
+        if (!L->evEditCopied) GS_HIP(hipEventCreateWithFlags(&L->evEditCopied, hipEventDisableTiming));
+        GS_HIP(hipStreamWaitEvent(L->ctx->stream, r->evEditDeleted, 0));
+        GS_HIP(hipMemcpyAsync(L->deletedBits, r->deletedBits, bytes, hipMemcpyDeviceToDevice, L->ctx->stream));
+        GS_HIP(hipEventRecord(L->evEditCopied, L->ctx->stream));
+        GS_HIP(hipStreamWaitEvent(r->ctx->stream, L->evEditCopied, 0));
+    }
+    return GS_OK;
+}
+
+} // namespace gs
+
+using namespace gs;
+
+extern "C" {
+
+int32_t gs_renderer_edit_select_all(gs_renderer* r) {
+    if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
+    GS_TRY(edit_ensure(r));
+    hipLaunchKernelGGL(edit_select_all_kernel, dim3(splat_grid(r)), dim3(256), 0, r->ctx->stream, r->asset->view, edit_view(r), r->editSelected,
+                       (uint32_t)edit_words(r), 0u);
+    GS_HIP(hipGetLastError());
+    return GS_OK;
+}
+
+int32_t gs_renderer_edit_invert_selection(gs_renderer* r) {
+    if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
+    GS_TRY(edit_ensure(r));
+    hipLaunchKernelGGL(edit_select_all_kernel, dim3(splat_grid(r)), dim3(256), 0, r->ctx->stream, r->asset->view, edit_view(r), r->editSelected,
+                       (uint32_t)edit_words(r), 1u);
+    GS_HIP(hipGetLastError());
+    return GS_OK;
+}
+
+int32_t gs_renderer_edit_deselect_all(gs_renderer* r) {
+    if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
+    GS_TRY(edit_ensure(r));
+    GS_HIP(hipMemsetAsync(r->editSelected, 0, edit_words(r) * 4, r->ctx->stream));          // CSClearBuffer
+    return GS_OK;
+}
+
+int32_t gs_renderer_edit_store_selection(gs_renderer* r) {
+    if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
+    GS_TRY(edit_ensure(r));
+    GS_HIP(hipMemcpyAsync(r->editSelectedMouseDown, r->editSelected, edit_words(r) * 4, hipMemcpyDeviceToDevice, r->ctx->stream));
+    return GS_OK;
+}
+
+int32_t gs_renderer_edit_update_selection(gs_renderer* r, const gs_frame_params* p, const float selection_rect[4], int32_t subtract) {
+    if (!r || !p || !selection_rect) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
+    GS_TRY(edit_ensure(r));
+    gsm::EditSelect S;
+    memcpy(S.o2w, p->matrix_object_to_world, sizeof(S.o2w));
+    memcpy(S.vp, p->matrix_vp, sizeof(S.vp));
+    S.screenW = p->screen_w; S.screenH = p->screen_h;
+    memcpy(S.rect, selection_rect, sizeof(S.rect));
+    hipLaunchKernelGGL(edit_selection_update_kernel, dim3(splat_grid(r)), dim3(256), 0, r->ctx->stream, r->asset->view, edit_view(r), S,
+                       (const uint32_t*)r->editSelectedMouseDown, r->editSelected, (uint32_t)edit_words(r), subtract ? 0u : 1u);
+    GS_HIP(hipGetLastError());
+    return GS_OK;
+}
+
+int32_t gs_renderer_edit_delete_selected(gs_renderer* r) {
+    if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
+    GS_TRY(edit_ensure(r));
+    const size_t bytes = edit_words(r) * 4;
+    if (!r->deletedBits) {
+        uint32_t* d = nullptr;
+        GS_HIP(hipMalloc((void**)&d, bytes));
+        const hipError_t e = hipMemsetAsync(d, 0, bytes, r->ctx->stream);
+        if (e != hipSuccess) { (void)hipFree(d); return fail_hip(e, "clear deleted bits", __FILE__, __LINE__); }
+        r->deletedBits = d;
+    }
+    hipLaunchKernelGGL(edit_delete_kernel, dim3(word_grid(r)), dim3(256), 0, r->ctx->stream, r->deletedBits, r->editSelected, (uint32_t)edit_words(r));
+    GS_HIP(hipGetLastError());
+    return edit_deleted_to_lanes(r);
+}
+
+int32_t gs_renderer_edit_info(gs_renderer* r, gs_edit_info* out) {
+    if (!r || !out) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
+    memset(out, 0, sizeof(*out));
+    if (!r->editSelected) return GS_OK;                            // UpdateEditCountsAndBounds without edit buffers (:707-715)
+    GS_HIP(hipSetDevice(r->ctx->device));
+    hipLaunchKernelGGL(edit_init_data_kernel, dim3(1), dim3(64), 0, r->ctx->stream, r->editCountsBounds);
+    hipLaunchKernelGGL(edit_update_data_kernel, dim3(splat_grid(r)), dim3(256), 0, r->ctx->stream, r->asset->view, edit_view(r),
+                       (const uint32_t*)r->editSelected, (uint32_t)edit_words(r), r->editCountsBounds);
+    GS_HIP(hipGetLastError());
+    uint32_t res[9];
+    GS_HIP(hipMemcpyAsync(res, r->editCountsBounds, sizeof(res), hipMemcpyDeviceToHost, r->ctx->stream));
+    GS_HIP(hipStreamSynchronize(r->ctx->stream));
+    out->selected = res[0]; out->deleted = res[1]; out->cut = res[2];
+    for (int k = 0; k < 3; ++k) {                                  // SortableUintToFloat (:699-703)
+        const uint32_t lo = res[3 + k], hi = res[6 + k];
+        out->bounds_min[k] = gsm::u2f(lo ^ (((lo >> 31) - 1u) | 0x80000000u));
+        out->bounds_max[k] = gsm::u2f(hi ^ (((hi >> 31) - 1u) | 0x80000000u));
+    }
+    return GS_OK;
+}
+
+int32_t gs_renderer_edit_upload_selected_bits(gs_renderer* r, const uint32_t* words, size_t word_count) {
+    if (!r || !words) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
+    if (word_count != edit_words(r)) return fail(GS_ERR_INVALID_ARGUMENT, "selected bits: word_count must be ceil(splat_count / 32)");
+    GS_TRY(edit_ensure(r));
+    GS_HIP(hipMemcpyAsync(r->editSelected, words, word_count * 4, hipMemcpyHostToDevice, r->ctx->stream));
+    GS_HIP(hipStreamSynchronize(r->ctx->stream));                  // `words` is only read during the call
+    return GS_OK;
+}
+
+int32_t gs_renderer_edit_download_bits(gs_renderer* r, uint32_t* selected, uint32_t* selected_mouse_down, uint32_t* deleted, size_t word_count) {
+    if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
+    if (word_count != edit_words(r)) return fail(GS_ERR_INVALID_ARGUMENT, "edit bits: word_count must be ceil(splat_count / 32)");
+    GS_HIP(hipSetDevice(r->ctx->device));
+    const size_t bytes = word_count * 4;
+    uint32_t* const dst[3] = { selected, selected_mouse_down, deleted };
+    const uint32_t* const src[3] = { r->editSelected, r->editSelectedMouseDown, r->deletedBits };
+    for (int k = 0; k < 3; ++k) {
+        if (!dst[k]) continue;
+        if (src[k]) GS_HIP(hipMemcpyAsync(dst[k], src[k], bytes, hipMemcpyDeviceToHost, r->ctx->stream));
+        else memset(dst[k], 0, bytes);                             // a buffer that does not exist reads as zeros
+    }
+    GS_HIP(hipStreamSynchronize(r->ctx->stream));
+    return GS_OK;
+}
+
+int32_t gs_renderer_edit_release(gs_renderer* r) {
+    if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
+    if (!r->editSelected) return GS_OK;
+    GS_HIP(hipSetDevice(r->ctx->device));
+    GS_HIP(hipStreamSynchronize(r->ctx->stream));
+    if (r->editSelected) (void)hipFree(r->editSelected);
+    if (r->editSelectedMouseDown) (void)hipFree(r->editSelectedMouseDown);
+    if (r->editCountsBounds) (void)hipFree(r->editCountsBounds);
+    r->editSelected = r->editSelectedMouseDown = r->editCountsBounds = nullptr;
+    return GS_OK;
+}
+
+} // extern "C"

@@ -88,6 +88,19 @@ namespace GaussianSplatting.Runtime
         public unsafe struct Cutout { public fixed float matrix[16]; public uint typeAndFlags; }
         [DllImport(Lib)] public static extern int gs_renderer_set_cutouts(IntPtr renderer, Cutout[] cutouts, uint count);
         [DllImport(Lib)] public static extern int gs_renderer_set_deleted_bits(IntPtr renderer, uint[] words, UIntPtr wordCount);
+        // selection and deletion (GaussianSplatRenderer.Edit*, GaussianSplatRenderer.cs:705-740,767-840,896-934); selection has no visual effect
+        [StructLayout(LayoutKind.Sequential)]
+        public unsafe struct EditInfo { public uint selected, deleted, cut; public fixed float boundsMin[3]; public fixed float boundsMax[3]; }
+        [DllImport(Lib)] public static extern int gs_renderer_edit_select_all(IntPtr renderer);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_deselect_all(IntPtr renderer);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_invert_selection(IntPtr renderer);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_store_selection(IntPtr renderer);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_update_selection(IntPtr renderer, ref FrameParams p, float[] selectionRect4, int subtract);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_delete_selected(IntPtr renderer);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_info(IntPtr renderer, out EditInfo info);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_upload_selected_bits(IntPtr renderer, uint[] words, UIntPtr wordCount);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_download_bits(IntPtr renderer, uint[] selected, uint[] selectedMouseDown, uint[] deleted, UIntPtr wordCount);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_release(IntPtr renderer);
         [DllImport(Lib)] public static extern int gs_renderer_set_view_buffer_mode(IntPtr renderer, int everyFrame);
         [DllImport(Lib)] public static extern int gs_renderer_set_blend_mode(IntPtr renderer, int mode);
         [DllImport(Lib)] public static extern int gs_renderer_set_tile_shape(IntPtr renderer, uint tileW, uint tileH);

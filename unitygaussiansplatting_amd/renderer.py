@@ -18,8 +18,8 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from ._abi import (GS_ERR_PAIR_OVERFLOW, GS_SORT_FULL, GS_SORT_VISIBLE, VIEW_DTYPE, gs_frame_params, gs_frame_stats, gs_stage_times,
-                   make_asset_desc)
+from ._abi import (GS_ERR_PAIR_OVERFLOW, GS_SORT_FULL, GS_SORT_VISIBLE, VIEW_DTYPE, gs_edit_info, gs_frame_params, gs_frame_stats,
+                   gs_stage_times, make_asset_desc)
 from ._lib import GsError, check
 from .asset import GaussianSplatAsset, kCurrentVersion
 from .camera import Camera, Transform, frame_params, sort_matrix
@@ -55,6 +55,30 @@ class RenderMode(enum.IntEnum):          # GaussianSplatRenderer.RenderMode (:21
 class SortMode(enum.IntEnum):            # gs_sort_mode: what SortPoints sorts (no counterpart in the reference, whose sort precedes its cull)
     Full = GS_SORT_FULL                  # all N splats, every SortPoints, like GaussianSplatRenderer.SortPoints (:612-639)
     Visible = GS_SORT_VISIBLE            # cull first: only the splats CalcViewData found visible, inside Draw
+
+
+class Bounds:
+    """UnityEngine.Bounds as UpdateEditCountsAndBounds uses it (GaussianSplatRenderer.cs:735-739): center + extents, float32."""
+
+    def __init__(self):
+        self.center = np.zeros(3, np.float32)
+        self.extents = np.zeros(3, np.float32)
+
+    def SetMinMax(self, mn, mx) -> None:
+        mn, mx = np.asarray(mn, np.float32), np.asarray(mx, np.float32)
+        with np.errstate(over="ignore", invalid="ignore"):
+            self.extents = ((mx - mn) * np.float32(0.5)).astype(np.float32)
+            self.center = (mn + self.extents).astype(np.float32)
+
+    @property
+    def min(self) -> np.ndarray:
+        with np.errstate(over="ignore", invalid="ignore"):
+            return (self.center - self.extents).astype(np.float32)
+
+    @property
+    def max(self) -> np.ndarray:
+        with np.errstate(over="ignore", invalid="ignore"):
+            return (self.center + self.extents).astype(np.float32)
 
 
 class GpuContext:
@@ -199,7 +223,8 @@ class GpuSorting:
 
 
 class GaussianSplatRenderer:
-    """GaussianSplatRenderer component (GaussianSplatRenderer.cs:214-680), render path only."""
+    """GaussianSplatRenderer component (GaussianSplatRenderer.cs:214-680): the render path, and of the editing half (:705-934) selection and
+    deletion -- Edit* below.  Selected splats are not highlighted: selection has no visual effect, only deletion changes a frame."""
 
     def __init__(self, ctx: GpuContext, asset: Optional[GaussianSplatAsset] = None, transform: Optional[Transform] = None):
         self.ctx = ctx
@@ -228,6 +253,13 @@ class GaussianSplatRenderer:
         self.m_PrevAsset = None
         self.m_PrevHash = None
         self.m_Registered = False
+        # edit state (:273-277, 705-740)
+        self.m_GpuEditSelected = False            # the native renderer's edit buffers exist (EnsureEditingBuffers)
+        self.editSelectedSplats = 0
+        self.editDeletedSplats = 0
+        self.editCutSplats = 0
+        self.editModified = False
+        self.editSelectedBounds = Bounds()
         ctx._adopt(self)
 
     def Dispose(self) -> None:
@@ -284,6 +316,10 @@ class GaussianSplatRenderer:
     def DisposeResourcesForAsset(self) -> None:     # :527-565
         l = _lib.lib()
         if self._r_h:
+            if self.m_GpuEditSelected:
+                l.gs_renderer_edit_release(self._r_h)   # DisposeBuffer(ref m_GpuEditSelected) ..., :547-553
+            self.m_GpuEditSelected = False
+            self.editModified = False
             l.gs_renderer_destroy(self._r_h)
             self._r_h = C.c_void_p()
         if self._asset_h:
@@ -353,12 +389,97 @@ class GaussianSplatRenderer:
 
     def SetDeletedBits(self, bits: Optional[np.ndarray]) -> None:
         """The m_GpuEditDeleted buffer (:269,779): one bit per splat, ceil(N/32) uint32 words; None = no edit buffers
-        (_SplatBitsValid = 0).  The editing tools that fill it in the reference (EditDeleteSelected ...) are out of scope."""
+        (_SplatBitsValid = 0).  EditDeleteSelected fills it on the GPU; this call overwrites it from the host."""
         if bits is None:
             check(_lib.lib().gs_renderer_set_deleted_bits(self._r_h, None, 0), "gs_renderer_set_deleted_bits")
             return
         w = np.ascontiguousarray(bits, np.uint32)
         check(_lib.lib().gs_renderer_set_deleted_bits(self._r_h, w.ctypes.data, len(w)), "gs_renderer_set_deleted_bits")
+
+    # -- editing: selection and deletion (:705-740, 767-840, 896-934) --------------------------------------------
+    def UpdateEditCountsAndBounds(self) -> None:    # :705-740
+        if not self.m_GpuEditSelected:
+            self.editSelectedSplats = self.editDeletedSplats = self.editCutSplats = 0
+            self.editModified = False
+            self.editSelectedBounds = Bounds()
+            return
+        self.UpdateCutoutsBuffer()                  # SetAssetDataOnCS, :507
+        info = gs_edit_info()
+        check(_lib.lib().gs_renderer_edit_info(self._r_h, C.byref(info)), "gs_renderer_edit_info")
+        self.editSelectedSplats, self.editDeletedSplats, self.editCutSplats = info.selected, info.deleted, info.cut
+        bounds = Bounds()
+        bounds.SetMinMax(np.array(info.bounds_min[:], np.float32), np.array(info.bounds_max[:], np.float32))
+        e = bounds.extents
+        with np.errstate(over="ignore", invalid="ignore"):
+            sqr = np.float32(np.float32(e[0] * e[0] + e[1] * e[1]) + e[2] * e[2])
+        if float(sqr) < 0.01:
+            bounds.extents = np.full(3, 0.1, np.float32)
+        self.editSelectedBounds = bounds
+
+    def EnsureEditingBuffers(self) -> bool:         # :767-786 (the native renderer makes the buffers at the edit call that follows)
+        if not self.HasValidAsset or not self.HasValidRenderSetup:
+            return False
+        self.m_GpuEditSelected = True
+        return True
+
+    def EditStoreSelectionMouseDown(self) -> None:  # :788-792
+        if not self.EnsureEditingBuffers():
+            return
+        check(_lib.lib().gs_renderer_edit_store_selection(self._r_h), "gs_renderer_edit_store_selection")
+
+    def EditUpdateSelection(self, rectMin, rectMax, cam: Camera, subtract: bool) -> None:     # :811-840
+        """rectMin / rectMax: the corners of the drag in pixels, x right and y up from the bottom edge, as the reference's tool hands them in
+        (rectMin = its top-left corner: the smaller x, the larger y)."""
+        if not self.EnsureEditingBuffers():
+            return
+        self.UpdateCutoutsBuffer()
+        p = self.FrameParams(cam)
+        rect = np.array([rectMin[0], rectMax[1], rectMax[0], rectMin[1]], np.float32)       # :835
+        check(_lib.lib().gs_renderer_edit_update_selection(self._r_h, C.byref(p), _fptr(rect), int(bool(subtract))), "gs_renderer_edit_update_selection")
+        self.UpdateEditCountsAndBounds()
+
+    def EditDeleteSelected(self) -> None:           # :896-904
+        if not self.EnsureEditingBuffers():
+            return
+        check(_lib.lib().gs_renderer_edit_delete_selected(self._r_h), "gs_renderer_edit_delete_selected")     # UnionGraphicsBuffers + EditDeselectAll
+        self.UpdateEditCountsAndBounds()
+        if self.editDeletedSplats != 0:
+            self.editModified = True
+
+    def EditSelectAll(self) -> None:                # :906-915
+        if not self.EnsureEditingBuffers():
+            return
+        self.UpdateCutoutsBuffer()
+        check(_lib.lib().gs_renderer_edit_select_all(self._r_h), "gs_renderer_edit_select_all")
+        self.UpdateEditCountsAndBounds()
+
+    def EditDeselectAll(self) -> None:              # :917-922
+        if not self.EnsureEditingBuffers():
+            return
+        check(_lib.lib().gs_renderer_edit_deselect_all(self._r_h), "gs_renderer_edit_deselect_all")
+        self.UpdateEditCountsAndBounds()
+
+    def EditInvertSelection(self) -> None:          # :924-934
+        if not self.EnsureEditingBuffers():
+            return
+        self.UpdateCutoutsBuffer()
+        check(_lib.lib().gs_renderer_edit_invert_selection(self._r_h), "gs_renderer_edit_invert_selection")
+        self.UpdateEditCountsAndBounds()
+
+    def DownloadEditBits(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(selected, selected at mouse-down, deleted): ceil(N/32) uint32 words each; a buffer that does not exist reads as zeros.  Blocks."""
+        n = (self.m_SplatCount + 31) // 32
+        out = [np.zeros(n, np.uint32) for _ in range(3)]
+        check(_lib.lib().gs_renderer_edit_download_bits(self._r_h, out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data, n), "gs_renderer_edit_download_bits")
+        return out[0], out[1], out[2]
+
+    def UploadSelectedBits(self, bits: np.ndarray) -> None:
+        """The selection from the host: ceil(N/32) uint32 words."""
+        if not self.EnsureEditingBuffers():
+            return
+        w = np.ascontiguousarray(bits, np.uint32)
+        check(_lib.lib().gs_renderer_edit_upload_selected_bits(self._r_h, w.ctypes.data, len(w)), "gs_renderer_edit_upload_selected_bits")
+        self.UpdateEditCountsAndBounds()
 
     def CalcViewData(self, cam: Camera) -> None:    # :579-610
         self.UpdateCutoutsBuffer()                  # SetAssetDataOnCS, :507
