@@ -31,7 +31,7 @@ int32_t fail_hip(hipError_t e, const char* what, const char* file, int line) {
 }
 
 void prof_record(gs_renderer* r, int k, hipStream_t st) {
-    if (!r->profiling || !r->ev) return;
+    if (!r->profiling || r->ev.empty()) return;
     const int idx = r->profCur * kEvPerFrame + k;
     if (hipEventRecord(r->ev[idx], st ? st : r->ctx->stream) == hipSuccess) r->evValid[idx] = 1;
 }
@@ -46,10 +46,10 @@ int32_t mark_order_use(gs_renderer* r) {
     return GS_OK;
 }
 void prof_end_frame(gs_renderer* r) {
-    if (!r->profiling || !r->ev) return;
+    if (!r->profiling || r->ev.empty()) return;
     r->profCompleted++;
     r->profCur = (r->profCur + 1) % r->profCapacity;
-    memset(r->evValid + (size_t)r->profCur * kEvPerFrame, 0, kEvPerFrame);
+    memset(r->evValid.data() + (size_t)r->profCur * kEvPerFrame, 0, kEvPerFrame);
 }
 
 } // namespace gs
@@ -219,8 +219,9 @@ int32_t gs_asset_create(gs_context* ctx, const gs_asset_desc* d, gs_asset** out)
         if (!src[k] || have[k] == 0) { a->blobs[k] = nullptr; a->sizes[k] = 0; continue; }
         if (a->owned) {
             // +16 B: the 2-byte-aligned dword stitching of LoadUInt may touch the dword after the last record
-            hipError_t e = hipMalloc(&a->blobs[k], have[k] + 16);
-            if (e == hipSuccess) e = hipMemsetAsync((uint8_t*)a->blobs[k] + have[k], 0, 16, ctx->stream);
+            hipError_t e = a->ownedBlobs[k].alloc(have[k] + 16);
+            a->blobs[k] = a->ownedBlobs[k];
+            if (e == hipSuccess) e = hipMemsetAsync(a->ownedBlobs[k] + have[k], 0, 16, ctx->stream);
             if (e == hipSuccess) e = hipMemcpyAsync(a->blobs[k], src[k], have[k], hipMemcpyHostToDevice, ctx->stream);
             if (e != hipSuccess) { gs_asset_destroy(a); return fail_hip(e, "asset upload", __FILE__, __LINE__); }
         } else {
@@ -239,7 +240,6 @@ int32_t gs_asset_create(gs_context* ctx, const gs_asset_desc* d, gs_asset** out)
 int32_t gs_asset_destroy(gs_asset* a) {
     if (!a) return GS_OK;
     (void)hipSetDevice(a->ctx->device);
-    if (a->owned) for (int k = 0; k < 5; ++k) if (a->blobs[k]) (void)hipFree(a->blobs[k]);
     delete a;
     return GS_OK;
 }
@@ -323,8 +323,8 @@ int32_t gs_renderer_set_frames_in_flight(gs_renderer* r, int32_t frames) {
         if (rc == GS_OK) rc = gs_renderer_create(c, r->asset, &L);
         if (rc == GS_OK) {
             L->laneOf = r;
-            hipError_t e = hipEventCreateWithFlags(&L->evTargetFree, hipEventDisableTiming);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&L->evBlendDone, hipEventDisableTiming);
+            hipError_t e = L->evTargetFree.create(hipEventDisableTiming);
+            if (e == hipSuccess) e = L->evBlendDone.create(hipEventDisableTiming);
             if (e != hipSuccess) rc = fail_hip(e, "create lane events", __FILE__, __LINE__);
         }
         // the owner's settings as they are now; later changes are forwarded by the setters themselves
@@ -334,7 +334,7 @@ int32_t gs_renderer_set_frames_in_flight(gs_renderer* r, int32_t frames) {
             L->visHistLimit = r->visHistLimit;
             if (r->pairCapacity > L->pairCapacity) rc = gs_renderer_reserve_pairs(L, r->pairCapacity);
         }
-        if (rc == GS_OK && r->cutoutCount) rc = gs_renderer_set_cutouts(L, (const gs_cutout*)r->cutoutsHost, r->cutoutCount);
+        if (rc == GS_OK && r->cutoutCount) rc = gs_renderer_set_cutouts(L, (const gs_cutout*)r->cutoutsHost.get(), r->cutoutCount);
         if (rc == GS_OK && r->deletedBits) {
             const size_t words = ((size_t)r->n + 31) / 32;
             uint32_t* h = new (std::nothrow) uint32_t[words];
@@ -365,6 +365,23 @@ int32_t gs_renderer_frames_in_flight(const gs_renderer* r, int32_t* frames, int3
     return GS_OK;
 }
 
+static int32_t renderer_init(gs_renderer* r) {
+    gs_context* ctx = r->ctx;
+    GS_HIP(r->view.alloc((size_t)r->n * sizeof(gsm::ViewData) + 64));
+    GS_HIP(r->keyBySplat.alloc(((size_t)r->n + 16) * 4));
+    GS_HIP(r->distances.alloc(((size_t)r->n + 16) * 4));
+    GS_HIP(r->order.alloc(((size_t)r->n + 16) * 4));
+    GS_HIP(r->depthControl.alloc(2 * sizeof(SortControl)));
+    GS_HIP(hipMemsetAsync(r->depthControl, 0, 2 * sizeof(SortControl), ctx->stream));
+    GS_HIP(r->evOrderFree.create(hipEventDisableTiming));
+    GS_HIP(r->evSortDone.create(hipEventDisableTiming));
+    GS_TRY(sort_state_create(ctx, r->depthSort, r->n, true));   // (small partitions: the visible-only sort)
+    GS_TRY(renderer_alloc_raster(r));
+    GS_TRY(enqueue_set_indices(ctx, r->order, r->n));
+    GS_HIP(hipMemsetAsync(r->view, 0, (size_t)r->n * sizeof(gsm::ViewData), ctx->stream));
+    return mark_order_use(r);                                    // the first sort (second queue) waits for these initialisations
+}
+
 int32_t gs_renderer_create(gs_context* ctx, gs_asset* asset, gs_renderer** out) {
     if (!ctx || !asset || !out) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
     *out = nullptr;
@@ -375,21 +392,7 @@ int32_t gs_renderer_create(gs_context* ctx, gs_asset* asset, gs_renderer** out) 
     gs_renderer* r = new (std::nothrow) gs_renderer();
     if (!r) return fail(GS_ERR_OUT_OF_MEMORY, "host allocation");
     r->ctx = ctx; r->asset = asset; r->n = asset->view.n;
-    int32_t rc = GS_OK;
-    auto chk = [&](hipError_t e, const char* what) { if (rc == GS_OK && e != hipSuccess) rc = fail_hip(e, what, __FILE__, __LINE__); };
-    chk(hipMalloc((void**)&r->view, (size_t)r->n * sizeof(gsm::ViewData) + 64), "alloc view");
-    chk(hipMalloc((void**)&r->keyBySplat, ((size_t)r->n + 16) * 4), "alloc sort keys");
-    chk(hipMalloc((void**)&r->distances, ((size_t)r->n + 16) * 4), "alloc distances");
-    chk(hipMalloc((void**)&r->order, ((size_t)r->n + 16) * 4), "alloc order");
-    chk(hipMalloc((void**)&r->depthControl, 2 * sizeof(SortControl)), "alloc sort control");
-    if (rc == GS_OK) chk(hipMemsetAsync(r->depthControl, 0, 2 * sizeof(SortControl), ctx->stream), "clear sort control");
-    chk(hipEventCreateWithFlags(&r->evOrderFree, hipEventDisableTiming), "create event");
-    chk(hipEventCreateWithFlags(&r->evSortDone, hipEventDisableTiming), "create event");
-    if (rc == GS_OK) rc = sort_state_create(ctx, r->depthSort, r->n, true);        // (small partitions: the visible-only sort)
-    if (rc == GS_OK) rc = renderer_alloc_raster(r);
-    if (rc == GS_OK) rc = enqueue_set_indices(ctx, r->order, r->n);
-    if (rc == GS_OK) chk(hipMemsetAsync(r->view, 0, (size_t)r->n * sizeof(gsm::ViewData), ctx->stream), "clear view");
-    if (rc == GS_OK) rc = mark_order_use(r);                    // the first sort (second queue) waits for these initialisations
+    const int32_t rc = renderer_init(r);
     if (rc != GS_OK) { gs_renderer_destroy(r); return rc; }
     *out = r;
     return GS_OK;
@@ -401,25 +404,7 @@ int32_t gs_renderer_destroy(gs_renderer* r) {
     (void)hipSetDevice(r->ctx->device);
     (void)hipStreamSynchronize(r->ctx->aux);
     (void)hipStreamSynchronize(r->ctx->stream);
-    if (r->evTargetFree) (void)hipEventDestroy(r->evTargetFree);
-    if (r->evBlendDone) (void)hipEventDestroy(r->evBlendDone);
-    if (r->evOrderFree) (void)hipEventDestroy(r->evOrderFree);
-    if (r->evSortDone) (void)hipEventDestroy(r->evSortDone);
-    if (r->view) (void)hipFree(r->view);
-    if (r->keyBySplat) (void)hipFree(r->keyBySplat);
-    if (r->distances) (void)hipFree(r->distances);
-    if (r->order) (void)hipFree(r->order);
-    if (r->depthControl) (void)hipFree(r->depthControl);
-    edit_free(r);
-    if (r->deletedBits) (void)hipFree(r->deletedBits);
-    if (r->cutouts) (void)hipFree(r->cutouts);
-    if (r->cutoutsHost) (void)hipHostFree(r->cutoutsHost);
-    if (r->cutoutsCopied) (void)hipEventDestroy(r->cutoutsCopied);
-    sort_state_destroy(r->depthSort);
-    renderer_free_raster(r);
-    vis_free(r);
-    if (r->ev) { for (int k = 0; k < r->profCapacity * kEvPerFrame; ++k) (void)hipEventDestroy(r->ev[k]); delete[] r->ev; delete[] r->evValid; }
-    delete r;
+    delete r;                                                    // (its handles release the buffers and events: nothing is in flight any more)
     return GS_OK;
 }
 
@@ -554,7 +539,7 @@ int32_t gs_renderer_calc_view(gs_renderer* r, const gs_frame_params* p) {
 // therefore noticed within the pipeline depth, not only when the caller polls gs_renderer_frame_stats.
 static int32_t maybe_grow_pairs(gs_renderer* r) {
     if (!r->frameInFlight) return GS_OK;
-    const unsigned long long seen = *(volatile unsigned long long*)&r->hostReport->pairCount;
+    const unsigned long long seen = *(volatile unsigned long long*)&r->hostReport.get()->pairCount;
     // at the 2^30 ceiling there is nothing to grow: the draw goes ahead truncated (gs_renderer_frame_stats reports the frame), so
     // that a later frame that fits renders normally and rewrites the report
     if (seen > r->pairCapacity) {
@@ -598,16 +583,11 @@ int32_t gs_renderer_set_cutouts(gs_renderer* r, const gs_cutout* cutouts, uint32
     GS_TRY(bind_device(r->ctx));
     if (count) {
         if (!r->cutouts) {                                   // all three resources or none
-            uint32_t* dev = nullptr; uint8_t* host = nullptr; hipEvent_t ev = nullptr;
-            hipError_t e = hipMalloc((void**)&dev, (size_t)GS_MAX_CUTOUTS * sizeof(gs_cutout));
-            if (e == hipSuccess) e = hipHostMalloc((void**)&host, (size_t)GS_MAX_CUTOUTS * sizeof(gs_cutout), hipHostMallocDefault);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-            if (e != hipSuccess) {
-                if (dev) (void)hipFree(dev);
-                if (host) (void)hipHostFree(host);
-                return fail_hip(e, "allocate cutout buffers", __FILE__, __LINE__);
-            }
-            r->cutouts = dev; r->cutoutsHost = host; r->cutoutsCopied = ev;
+            DevBuf<uint32_t> dev; PinnedBuf<uint8_t> host; Event ev;
+            GS_HIP(dev.alloc((size_t)GS_MAX_CUTOUTS * sizeof(gs_cutout)));
+            GS_HIP(host.alloc((size_t)GS_MAX_CUTOUTS * sizeof(gs_cutout), hipHostMallocDefault));
+            GS_HIP(ev.create(hipEventDisableTiming));
+            r->cutouts = std::move(dev); r->cutoutsHost = std::move(host); r->cutoutsCopied = std::move(ev);
             r->cutoutsHostCount = 0;
         }
         // the C# re-uploads the buffer every CalcViewData (UpdateCutoutsBuffer); here an unchanged set costs nothing.
@@ -633,12 +613,12 @@ int32_t gs_renderer_set_deleted_bits(gs_renderer* r, const uint32_t* words, size
     GS_TRY(bind_device(r->ctx));
     const size_t need = ((size_t)r->n + 31) / 32;
     if (!words) {                                           // _SplatBitsValid = 0
-        if (r->deletedBits) { GS_HIP(hipStreamSynchronize(r->ctx->stream)); (void)hipFree(r->deletedBits); r->deletedBits = nullptr; }
+        if (r->deletedBits) { GS_HIP(hipStreamSynchronize(r->ctx->stream)); r->deletedBits.reset(); }
         for (gs_renderer* L : r->lanes) GS_TRY(gs_renderer_set_deleted_bits(L, nullptr, 0));
         return GS_OK;
     }
     if (word_count != need) return fail(GS_ERR_INVALID_ARGUMENT, "deleted bits: word_count must be ceil(splat_count / 32)");
-    if (!r->deletedBits) GS_HIP(hipMalloc((void**)&r->deletedBits, need * 4));
+    if (!r->deletedBits) GS_HIP(r->deletedBits.alloc(need * 4));
     // an edit-time operation (EditDeleteSelected): stream-ordered copy, then block so `words` is only read during the call
     GS_HIP(hipMemcpyAsync(r->deletedBits, words, need * 4, hipMemcpyHostToDevice, r->ctx->stream));
     GS_HIP(hipStreamSynchronize(r->ctx->stream));
@@ -693,23 +673,13 @@ int32_t gs_renderer_set_profiling(gs_renderer* r, int32_t frames) {
     GS_TRY(bind_device(r->ctx));
     if (frames > r->profCapacity) {
         GS_HIP(hipStreamSynchronize(r->ctx->stream));
-        const size_t cnt = (size_t)frames * kEvPerFrame;
-        hipEvent_t* ev = new (std::nothrow) hipEvent_t[cnt]();            // value-initialised: null handles
-        uint8_t* valid = new (std::nothrow) uint8_t[cnt]();
-        hipError_t e = (ev && valid) ? hipSuccess : hipErrorOutOfMemory;
-        size_t made = 0;
-        for (; e == hipSuccess && made < cnt; ++made) e = hipEventCreate(&ev[made]);
-        if (e != hipSuccess) {                                            // the renderer keeps its previous ring
-            for (size_t k = 0; ev && k < made; ++k) if (ev[k]) (void)hipEventDestroy(ev[k]);
-            delete[] ev; delete[] valid;
-            return fail_hip(e, "create profiling events", __FILE__, __LINE__);
-        }
-        if (r->ev) { for (int k = 0; k < r->profCapacity * kEvPerFrame; ++k) (void)hipEventDestroy(r->ev[k]); delete[] r->ev; delete[] r->evValid; }
-        r->ev = ev; r->evValid = valid; r->profCapacity = frames;
+        std::vector<Event> ev((size_t)frames * kEvPerFrame);
+        for (Event& e : ev) GS_HIP(e.create(hipEventDefault));           // on failure the renderer keeps its previous ring
+        r->ev = std::move(ev); r->profCapacity = frames;
     }
     r->profiling = frames > 0;
     r->profCur = 0; r->profCompleted = 0;
-    if (r->evValid) memset(r->evValid, 0, (size_t)r->profCapacity * kEvPerFrame);
+    r->evValid.assign(r->ev.size(), 0);
     return GS_OK;
 }
 
@@ -729,16 +699,12 @@ int32_t gs_renderer_reserve_pairs(gs_renderer* r, uint64_t cap) {
     GS_TRY(bind_device(r->ctx));
     GS_HIP(hipStreamSynchronize(r->ctx->stream));
     // new buffers first; the renderer only changes once every allocation has succeeded
-    uint32_t *nk = nullptr, *nv = nullptr;
+    DevBuf<uint32_t> nk, nv;
     SortState ns;
-    hipError_t e = hipMalloc((void**)&nk, ((size_t)cap + 16) * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&nv, ((size_t)cap + 16) * 4);
-    int32_t rc = e == hipSuccess ? sort_state_create(r->ctx, ns, (uint32_t)cap) : fail_hip(e, "grow pair buffers", __FILE__, __LINE__);
-    if (rc != GS_OK) { if (nk) (void)hipFree(nk); if (nv) (void)hipFree(nv); sort_state_destroy(ns); return rc; }
-    if (r->pairKeys) (void)hipFree(r->pairKeys);
-    if (r->pairVals) (void)hipFree(r->pairVals);
-    sort_state_destroy(r->pairSort);
-    r->pairKeys = nk; r->pairVals = nv; r->pairSort = ns; r->pairCapacity = cap;
+    GS_HIP(nk.alloc(((size_t)cap + 16) * 4));
+    GS_HIP(nv.alloc(((size_t)cap + 16) * 4));
+    GS_TRY(sort_state_create(r->ctx, ns, (uint32_t)cap));
+    r->pairKeys = std::move(nk); r->pairVals = std::move(nv); r->pairSort = std::move(ns); r->pairCapacity = cap;
     // a lane that had to grow: its siblings draw the same scene (a frame repeated after GS_ERR_PAIR_OVERFLOW goes to the next lane)
     if (r->laneOf)
         for (gs_renderer* S : r->laneOf->lanes)
@@ -754,7 +720,7 @@ int32_t gs_renderer_poll_pairs(gs_renderer* r, uint64_t* tile_pairs, uint64_t* p
         r->truncPairs = r->truncCapacity = 0;
         return GS_OK;
     }
-    *tile_pairs = r->hostReport ? (uint64_t)*(volatile unsigned long long*)&r->hostReport->pairCount : 0u;
+    *tile_pairs = r->hostReport ? (uint64_t)*(volatile unsigned long long*)&r->hostReport.get()->pairCount : 0u;
     *pair_capacity = r->pairCapacity;
     return GS_OK;
 }
@@ -893,17 +859,18 @@ int32_t gs_renderer_frame_stats(gs_renderer* r, gs_frame_stats* out) {
     out->pair_capacity = r->pairCapacity;
     out->tiles_x = r->lastTilesX; out->tiles_y = r->lastTilesY;
     out->tile_w = r->lastTileWL ? 1u << r->lastTileWL : 0u; out->tile_h = r->lastTileHL ? 1u << r->lastTileHL : 0u;      // 0 x 0: nothing drawn yet
+    const FrameReport* rep = r->hostReport;
     if (r->frameInFlight) {
-        out->tile_pairs = r->hostReport->pairCount;
-        out->visible_splats = r->hostReport->visible;
-        out->sort_error = depthErr | r->hostReport->pairSortError | (r->hostReport->binError & 2u);
+        out->tile_pairs = rep->pairCount;
+        out->visible_splats = rep->visible;
+        out->sort_error = depthErr | rep->pairSortError | (rep->binError & 2u);
         if (r->visDrawn) {
             uint32_t visErr = 0;
             GS_HIP(hipMemcpy(&visErr, &vis_control(r)->error, 4, hipMemcpyDeviceToHost));
             out->sort_error |= visErr;
             out->sort_mode = GS_SORT_VISIBLE;
-            out->tie_long_runs = r->hostReport->tieLongRuns;
-            out->tie_longest_run = r->hostReport->tieLongest;
+            out->tie_long_runs = rep->tieLongRuns;
+            out->tie_longest_run = rep->tieLongest;
         }
     } else out->sort_error = depthErr;
     if (out->sort_error) return fail(GS_ERR_SORT_TIMEOUT, "a bounded look-back spin expired");
@@ -921,7 +888,7 @@ int32_t gs_renderer_frame_times(gs_renderer* r, float* out_ms, int32_t capacity,
     if (!r || !out_ms || !count || capacity < 0) return fail(GS_ERR_INVALID_ARGUMENT, "bad argument");
     *count = 0;
     r = lane_cur(r);                                             // (with lanes: the ring of the lane that drew last -- every lane times its own frames)
-    if (!r->ev) return fail(GS_ERR_INVALID_ARGUMENT, "profiling was never enabled");
+    if (r->ev.empty()) return fail(GS_ERR_INVALID_ARGUMENT, "profiling was never enabled");
     GS_TRY(bind_device(r->ctx));
     GS_HIP(hipStreamSynchronize(r->ctx->aux));
     GS_HIP(hipStreamSynchronize(r->ctx->stream));
@@ -944,7 +911,7 @@ int32_t gs_renderer_stage_times(gs_renderer* r, gs_stage_times* out) {
     if (!r || !out) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
     memset(out, 0, sizeof(*out));
     r = lane_cur(r);
-    if (!r->ev) return fail(GS_ERR_INVALID_ARGUMENT, "profiling was never enabled");
+    if (r->ev.empty()) return fail(GS_ERR_INVALID_ARGUMENT, "profiling was never enabled");
     GS_TRY(bind_device(r->ctx));
     GS_HIP(hipStreamSynchronize(r->ctx->aux));
     GS_HIP(hipStreamSynchronize(r->ctx->stream));
@@ -975,7 +942,7 @@ int32_t gs_renderer_stage_times(gs_renderer* r, gs_stage_times* out) {
     out->total_ms = out->calc_distances_ms + out->sort_ms + out->calc_view_ms + out->bin_ms + out->pair_sort_ms + out->blend_ms;
     out->frames = (uint32_t)(r->profCompleted < r->profCapacity ? r->profCompleted : r->profCapacity);
     r->profCur = 0; r->profCompleted = 0;
-    memset(r->evValid, 0, (size_t)r->profCapacity * kEvPerFrame);
+    r->evValid.assign(r->evValid.size(), 0);
     return GS_OK;
 }
 
@@ -988,7 +955,7 @@ int32_t gs_target_create(gs_context* ctx, uint32_t w, uint32_t h, gs_target** ou
     gs_target* t = new (std::nothrow) gs_target();
     if (!t) return fail(GS_ERR_OUT_OF_MEMORY, "host allocation");
     t->ctx = ctx; t->width = w; t->height = h;
-    hipError_t e = hipMalloc((void**)&t->rgba16f, (size_t)w * h * 8);
+    hipError_t e = t->rgba16f.alloc((size_t)w * h * 8);
     if (e == hipSuccess) e = hipMemsetAsync(t->rgba16f, 0, (size_t)w * h * 8, ctx->stream);
     if (e != hipSuccess) { delete t; return fail_hip(e, "alloc target", __FILE__, __LINE__); }
     *out = t;
@@ -999,15 +966,6 @@ int32_t gs_target_destroy(gs_target* t) {
     if (!t) return GS_OK;
     (void)hipSetDevice(t->ctx->device);
     (void)hipStreamSynchronize(t->ctx->stream);        // (a lane's blend into the target is joined into this stream by its draw)
-    if (t->rgba16f) (void)hipFree(t->rgba16f);
-    if (t->rgba16fAlt) (void)hipFree(t->rgba16fAlt);
-    if (t->evLastUseAlt) (void)hipEventDestroy(t->evLastUseAlt);
-    if (t->resolved) (void)hipFree(t->resolved);
-    if (t->resolved8) (void)hipFree(t->resolved8);
-    if (t->sceneDepthOwned) (void)hipFree(t->sceneDepthOwned);
-    if (t->zbuf) (void)hipFree(t->zbuf);
-    if (t->rev) { for (int k = 0; k < 2 * gs_target::kResolveRing; ++k) if (t->rev[k]) (void)hipEventDestroy(t->rev[k]); delete[] t->rev; }
-    if (t->evLastUse) (void)hipEventDestroy(t->evLastUse);
     delete t;
     return GS_OK;
 }
@@ -1020,7 +978,7 @@ int32_t gs_target_clear(gs_target* t) {
     if (!t->ctx->children.empty() && !t->exposed) {
         if (!t->rgba16fAlt) {
             GS_TRY(bind_device(t->ctx));
-            GS_HIP(hipMalloc((void**)&t->rgba16fAlt, (size_t)t->width * t->height * 8));
+            GS_HIP(t->rgba16fAlt.alloc((size_t)t->width * t->height * 8));
         }
         std::swap(t->rgba16f, t->rgba16fAlt);
         std::swap(t->evLastUse, t->evLastUseAlt);
@@ -1035,7 +993,7 @@ int32_t gs_target_set_scene_depth(gs_target* t, const float* depth, int32_t memo
     if (!depth) { t->sceneDepth = nullptr; return GS_OK; }      // a buffer we own stays allocated for the next host upload
     if (memory_kind == 1) { t->sceneDepth = depth; return GS_OK; }
     const size_t bytes = (size_t)t->width * t->height * sizeof(float);
-    if (!t->sceneDepthOwned) GS_HIP(hipMalloc((void**)&t->sceneDepthOwned, bytes));
+    if (!t->sceneDepthOwned) GS_HIP(t->sceneDepthOwned.alloc(bytes));
     GS_HIP(hipMemcpyAsync(t->sceneDepthOwned, depth, bytes, hipMemcpyHostToDevice, t->ctx->stream));
     GS_HIP(hipStreamSynchronize(t->ctx->stream));               // `depth` is only read during the call
     t->sceneDepth = t->sceneDepthOwned;
@@ -1053,9 +1011,9 @@ int32_t gs_target_resolve(gs_target* t, const float bg[4], float* out32, uint8_t
     GS_TRY(bind_device(t->ctx));
     GS_TRY(flush_clear(t));
     const int slot = t->revCount % gs_target::kResolveRing;
-    if (t->profiling && t->rev) GS_HIP(hipEventRecord(t->rev[2 * slot], t->ctx->stream));
+    if (t->profiling && !t->rev.empty()) GS_HIP(hipEventRecord(t->rev[2 * slot], t->ctx->stream));
     GS_TRY(enqueue_resolve(t, bg, out8 != nullptr));
-    if (t->profiling && t->rev) { GS_HIP(hipEventRecord(t->rev[2 * slot + 1], t->ctx->stream)); t->revCount++; }
+    if (t->profiling && !t->rev.empty()) { GS_HIP(hipEventRecord(t->rev[2 * slot + 1], t->ctx->stream)); t->revCount++; }
     const size_t px = (size_t)t->width * t->height;
     if (out32) GS_HIP(hipMemcpyAsync(out32, t->resolved, px * 16, hipMemcpyDeviceToHost, t->ctx->stream));
     if (out8) GS_HIP(hipMemcpyAsync(out8, t->resolved8, px * 4, hipMemcpyDeviceToHost, t->ctx->stream));
@@ -1066,13 +1024,10 @@ int32_t gs_target_resolve(gs_target* t, const float bg[4], float* out32, uint8_t
 int32_t gs_target_set_profiling(gs_target* t, int32_t enabled) {
     if (!t) return fail(GS_ERR_INVALID_ARGUMENT, "target is null");
     GS_TRY(bind_device(t->ctx));
-    if (enabled && !t->rev) {
-        const int cnt = 2 * gs_target::kResolveRing;
-        hipEvent_t* ev = new (std::nothrow) hipEvent_t[cnt]();
-        if (!ev) return fail(GS_ERR_OUT_OF_MEMORY, "host allocation");
-        for (int k = 0; k < cnt; ++k)
-            if (hipEventCreate(&ev[k]) != hipSuccess) { for (int j = 0; j < k; ++j) (void)hipEventDestroy(ev[j]); delete[] ev; return fail(GS_ERR_HIP, "hipEventCreate"); }
-        t->rev = ev;
+    if (enabled && t->rev.empty()) {
+        std::vector<Event> ev(2 * gs_target::kResolveRing);
+        for (Event& e : ev) GS_HIP(e.create(hipEventDefault));
+        t->rev = std::move(ev);
     }
     t->profiling = enabled != 0;
     t->revCount = 0;
@@ -1083,7 +1038,7 @@ int32_t gs_target_resolve_time(gs_target* t, float* mean_ms, int32_t* count) {
     if (!t || !mean_ms) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
     *mean_ms = 0.f;
     if (count) *count = 0;
-    if (!t->rev) return fail(GS_ERR_INVALID_ARGUMENT, "profiling was never enabled on this target");
+    if (t->rev.empty()) return fail(GS_ERR_INVALID_ARGUMENT, "profiling was never enabled on this target");
     GS_TRY(bind_device(t->ctx));
     GS_HIP(hipStreamSynchronize(t->ctx->stream));
     const int n = t->revCount < gs_target::kResolveRing ? t->revCount : gs_target::kResolveRing;
@@ -1113,7 +1068,7 @@ int32_t gs_sorter_create(gs_context* ctx, uint32_t max_count, gs_sorter** out) {
     if (!s) return fail(GS_ERR_OUT_OF_MEMORY, "host allocation");
     s->ctx = ctx;
     int32_t rc = sort_state_create(ctx, s->st, max_count, true);     // (every pass shape available: small counts sort in 4,096-key partitions)
-    if (rc == GS_OK && hipMalloc((void**)&s->control, sizeof(SortControl)) != hipSuccess) rc = fail(GS_ERR_OUT_OF_MEMORY, "alloc sort control");
+    if (rc == GS_OK && s->control.alloc(sizeof(SortControl)) != hipSuccess) rc = fail(GS_ERR_OUT_OF_MEMORY, "alloc sort control");
     if (rc != GS_OK) { gs_sorter_destroy(s); return rc; }
     *out = s;
     return GS_OK;
@@ -1123,10 +1078,6 @@ int32_t gs_sorter_destroy(gs_sorter* s) {
     if (!s) return GS_OK;
     (void)hipSetDevice(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);
-    sort_state_destroy(s->st);
-    if (s->control) (void)hipFree(s->control);
-    if (s->tmpKeys) (void)hipFree(s->tmpKeys);
-    if (s->tmpVals) (void)hipFree(s->tmpVals);
     delete s;
     return GS_OK;
 }
@@ -1150,8 +1101,10 @@ int32_t gs_sorter_sort_host(gs_sorter* s, uint32_t* keys, uint32_t* values, uint
     if (count == 0) return GS_OK;
     GS_TRY(bind_device(s->ctx));
     if (!s->tmpKeys) {
-        GS_HIP(hipMalloc((void**)&s->tmpKeys, (size_t)(s->st.maxCount + 16) * 4));
-        GS_HIP(hipMalloc((void**)&s->tmpVals, (size_t)(s->st.maxCount + 16) * 4));
+        DevBuf<uint32_t> k, v;                                   // both or neither
+        GS_HIP(k.alloc((size_t)(s->st.maxCount + 16) * 4));
+        GS_HIP(v.alloc((size_t)(s->st.maxCount + 16) * 4));
+        s->tmpKeys = std::move(k); s->tmpVals = std::move(v);
     }
     hipStream_t st = s->ctx->stream;
     GS_HIP(hipMemcpyAsync(s->tmpKeys, keys, (size_t)count * 4, hipMemcpyHostToDevice, st));
@@ -1160,7 +1113,7 @@ int32_t gs_sorter_sort_host(gs_sorter* s, uint32_t* keys, uint32_t* values, uint
     GS_HIP(hipMemcpyAsync(keys, s->tmpKeys, (size_t)count * 4, hipMemcpyDeviceToHost, st));
     GS_HIP(hipMemcpyAsync(values, s->tmpVals, (size_t)count * 4, hipMemcpyDeviceToHost, st));
     uint32_t err = 0;
-    GS_HIP(hipMemcpyAsync(&err, &s->control->error, 4, hipMemcpyDeviceToHost, st));
+    GS_HIP(hipMemcpyAsync(&err, &s->control.get()->error, 4, hipMemcpyDeviceToHost, st));
     GS_HIP(hipStreamSynchronize(st));
     if (err) return fail(GS_ERR_SORT_TIMEOUT, "a bounded look-back spin expired");
     return GS_OK;

@@ -133,11 +133,6 @@ __global__ __launch_bounds__(kClusterThreads) void assign_clusters_kernel(const 
     }
 }
 
-struct DeviceBuffers {                             // freed on every path out of assign_clusters_gpu
-    float* means = nullptr; double* c2 = nullptr; float* x = nullptr; uint32_t* out = nullptr;
-    ~DeviceBuffers() { (void)hipFree(means); (void)hipFree(c2); (void)hipFree(x); (void)hipFree(out); }
-};
-
 constexpr uint64_t kPointBudgetBytes = 256ull << 20;        // device memory for one batch of points + their indices
 constexpr uint64_t kMaxBatch = 1ull << 24;                  // 32-bit point offsets inside the kernel
 
@@ -164,22 +159,22 @@ int32_t assign_clusters_gpu(gs_context* ctx, const float* x, uint64_t n, const f
         c2[j] = sq;
     }
     const uint64_t batch = batch_points(n);
-    DeviceBuffers d;
-    GS_HIP(hipMalloc((void**)&d.means, (size_t)K * kDim * 4));
-    GS_HIP(hipMalloc((void**)&d.c2, (size_t)K * 8));
-    GS_HIP(hipMalloc((void**)&d.x, (size_t)batch * kDim * 4));
-    GS_HIP(hipMalloc((void**)&d.out, (size_t)batch * 4));
+    DevBuf<float> dMeans, dX; DevBuf<double> dC2; DevBuf<uint32_t> dOut;      // freed on every path out
+    GS_HIP(dMeans.alloc((size_t)K * kDim * 4));
+    GS_HIP(dC2.alloc((size_t)K * 8));
+    GS_HIP(dX.alloc((size_t)batch * kDim * 4));
+    GS_HIP(dOut.alloc((size_t)batch * 4));
     hipStream_t st = ctx->stream;
-    GS_HIP(hipMemcpyAsync(d.means, means, (size_t)K * kDim * 4, hipMemcpyHostToDevice, st));
-    GS_HIP(hipMemcpyAsync(d.c2, c2.data(), (size_t)K * 8, hipMemcpyHostToDevice, st));
+    GS_HIP(hipMemcpyAsync(dMeans, means, (size_t)K * kDim * 4, hipMemcpyHostToDevice, st));
+    GS_HIP(hipMemcpyAsync(dC2, c2.data(), (size_t)K * 8, hipMemcpyHostToDevice, st));
     for (uint64_t i0 = 0; i0 < n; i0 += batch) {
         const uint32_t nb = (uint32_t)std::min<uint64_t>(batch, n - i0);
-        GS_HIP(hipMemcpyAsync(d.x, x + (size_t)i0 * kDim, (size_t)nb * kDim * 4, hipMemcpyHostToDevice, st));
-        assign_clusters_kernel<<<dim3((nb + kTile - 1) / kTile), dim3(kClusterThreads), 0, st>>>(d.x, nb, d.means, d.c2, K, d.out);
+        GS_HIP(hipMemcpyAsync(dX, x + (size_t)i0 * kDim, (size_t)nb * kDim * 4, hipMemcpyHostToDevice, st));
+        assign_clusters_kernel<<<dim3((nb + kTile - 1) / kTile), dim3(kClusterThreads), 0, st>>>(dX, nb, dMeans, dC2, K, dOut);
         GS_HIP(hipGetLastError());
-        GS_HIP(hipMemcpyAsync(out + i0, d.out, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
+        GS_HIP(hipMemcpyAsync(out + i0, dOut, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
     }
-    GS_HIP(hipStreamSynchronize(st));              // (on an error path above, the hipFree calls of ~DeviceBuffers wait for what was enqueued)
+    GS_HIP(hipStreamSynchronize(st));              // (on an error path above, the hipFree calls of the buffers' handles wait for what was enqueued)
     return GS_OK;
 }
 

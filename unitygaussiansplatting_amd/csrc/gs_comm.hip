@@ -94,8 +94,9 @@ int32_t receive_alloc(gs_context* ctx, const uint64_t h[kHeaderWords], gs_asset*
     for (int k = 0; k < 5; ++k) {
         a->sizes[k] = h[7 + k];
         if (!a->sizes[k]) continue;
-        hipError_t e = hipMalloc(&a->blobs[k], a->sizes[k] + 16);           // + the decoders' tail pad, as gs_asset_create
-        if (e == hipSuccess) e = hipMemsetAsync((uint8_t*)a->blobs[k] + a->sizes[k], 0, 16, ctx->stream);
+        hipError_t e = a->ownedBlobs[k].alloc(a->sizes[k] + 16);            // + the decoders' tail pad, as gs_asset_create
+        a->blobs[k] = a->ownedBlobs[k];
+        if (e == hipSuccess) e = hipMemsetAsync(a->ownedBlobs[k] + a->sizes[k], 0, 16, ctx->stream);
         if (e != hipSuccess) { gs_asset_destroy(a); return gs::fail_hip(e, "asset replica: allocate blob", __FILE__, __LINE__); }
     }
     *out = a;
@@ -116,7 +117,7 @@ struct gs_comm {
     gs_context* ctx = nullptr;
     ncclComm_t comm = nullptr;
     int nranks = 1, rank = 0;
-    uint64_t* headerDev = nullptr;          // 16 x u64 scratch for the asset header
+    gs::DevBuf<uint64_t> headerDev;         // 16 x u64 scratch for the asset header
 };
 
 using namespace gs;
@@ -145,7 +146,7 @@ int32_t gs_comm_create(gs_context* ctx, int32_t nranks, int32_t rank, const uint
     memcpy(uid.internal, id, GS_COMM_ID_BYTES);
     ncclResult_t e = rccl().CommInitRank(&c->comm, nranks, uid, rank);          // collective: returns once every rank has joined
     if (e != ncclSuccess) { delete c; return fail_nccl(e, "ncclCommInitRank"); }
-    if (hipMalloc((void**)&c->headerDev, 16 * sizeof(uint64_t)) != hipSuccess) { (void)rccl().CommDestroy(c->comm); delete c; return fail(GS_ERR_OUT_OF_MEMORY, "comm scratch"); }
+    if (c->headerDev.alloc(16 * sizeof(uint64_t)) != hipSuccess) { (void)rccl().CommDestroy(c->comm); delete c; return fail(GS_ERR_OUT_OF_MEMORY, "comm scratch"); }
     *out = c;
     return GS_OK;
 }
@@ -155,7 +156,6 @@ int32_t gs_comm_destroy(gs_comm* c) {
     (void)hipSetDevice(c->ctx->device);
     (void)hipStreamSynchronize(c->ctx->stream);
     if (c->comm && rccl().ok) (void)rccl().CommDestroy(c->comm);
-    if (c->headerDev) (void)hipFree(c->headerDev);
     delete c;
     return GS_OK;
 }

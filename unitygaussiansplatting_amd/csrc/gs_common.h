@@ -5,10 +5,12 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <utility>
 #include <vector>
 
 #include "../../include/gsplat_c.h"
 #include "gs_device_math.h"
+#include "gs_handles.h"
 
 // Issue priority of the frame's latency-bound kernels (the sort passes, the key / binning / fix-up kernels, resolve): with frames in flight they share their SIMDs
 // with another frame's blend, whose heaviest tiles raise their own priority (gs_raster.hip); a chain kernel's few instructions between two waits then queue behind
@@ -77,11 +79,11 @@ __host__ __device__ inline size_t vis_alloc_bytes(uint32_t n) { return vis_mask_
 
 // Onesweep look-back state for one sort (shared by all passes: every pass uses a fresh epoch)
 struct SortState {
-    uint32_t* altKeys = nullptr;
-    uint32_t* altVals = nullptr;
-    uint32_t* status = nullptr;             // maxParts x 256 words {epoch:18 | count:14}: a partition's digit counts
-    unsigned long long* groupAgg = nullptr; // 4 passes x maxGroups x 256 words {members:24 | sum:40}, zeroed per sort
-    unsigned long long* groupIncl = nullptr;// maxGroups x 256 words {epoch:32 | inclusive prefix:32} through the end of a group
+    DevBuf<uint32_t> altKeys;
+    DevBuf<uint32_t> altVals;
+    DevBuf<uint32_t> status;                // maxParts x 256 words {epoch:18 | count:14}: a partition's digit counts
+    DevBuf<unsigned long long> groupAgg;    // 4 passes x maxGroups x 256 words {members:24 | sum:40}, zeroed per sort
+    DevBuf<unsigned long long> groupIncl;   // maxGroups x 256 words {epoch:32 | inclusive prefix:32} through the end of a group
     uint32_t maxGroups = 0;
     uint32_t maxCount = 0;
     uint32_t maxParts = 0;
@@ -181,7 +183,8 @@ bool gs_shared_gpu(const gs_context* ctx);      // may another kernel that waits
 struct gs_asset {
     gs_context* ctx = nullptr;
     gsm::AssetView view{};
-    void* blobs[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    void* blobs[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // the owned allocations below, or the host's (borrowed)
+    gs::DevBuf<uint8_t> ownedBlobs[5];
     uint64_t sizes[5] = {0, 0, 0, 0, 0};
     bool owned = true;
 };
@@ -189,27 +192,27 @@ struct gs_asset {
 struct gs_sorter {
     gs_context* ctx = nullptr;
     gs::SortState st;
-    gs::SortControl* control = nullptr;     // device
-    uint32_t* tmpKeys = nullptr;            // for sort_host
-    uint32_t* tmpVals = nullptr;
+    gs::DevBuf<gs::SortControl> control;    // device
+    gs::DevBuf<uint32_t> tmpKeys;           // for sort_host
+    gs::DevBuf<uint32_t> tmpVals;
 };
 
 struct gs_target {
     gs_context* ctx = nullptr;
     uint32_t width = 0, height = 0;
-    uint16_t* rgba16f = nullptr;            // W*H*4 halfs
+    gs::DevBuf<uint16_t> rgba16f;           // W*H*4 halfs
     bool clearPending = false;              // gs_target_clear was called and nothing has touched the target since: the next
                                             // draw writes every pixel itself (no 8 B/px memset); any other reader clears first
     // optional depth attachment (the camera's depth buffer the reference draws the splats against, GaussianSplatRenderer.cs:195):
     // W*H view depths of the opaque scene; a fragment survives iff the splat's clip.w <= depth
     const float* sceneDepth = nullptr;      // device
-    float* sceneDepthOwned = nullptr;       // the copy made of a host buffer (sceneDepth points at it), or null
-    unsigned long long* zbuf = nullptr;     // W*H x u64 {view depth bits, ~splat index}: the depth buffer of the debug point modes (all ones = empty)
-    float* resolved = nullptr;              // W*H*4 floats, lazily allocated
-    uint8_t* resolved8 = nullptr;
+    gs::DevBuf<float> sceneDepthOwned;      // the copy made of a host buffer (sceneDepth points at it), or null
+    gs::DevBuf<unsigned long long> zbuf;    // W*H x u64 {view depth bits, ~splat index}: the depth buffer of the debug point modes (all ones = empty)
+    gs::DevBuf<float> resolved;             // W*H*4 floats, lazily allocated
+    gs::DevBuf<uint8_t> resolved8;
     // optional timing of gs_target_resolve: a ring of event pairs on the context's stream
     static constexpr int kResolveRing = 64;
-    hipEvent_t* rev = nullptr;              // 2 x kResolveRing events, or null (profiling off)
+    std::vector<gs::Event> rev;             // 2 x kResolveRing events, or empty (profiling off)
     bool profiling = false;
     int revCount = 0;                       // resolves recorded since the last read (may exceed the ring: the oldest are overwritten)
     // Lanes (gs_renderer_set_frames_in_flight) draw into the target from streams of their own: a lane's blend waits for the target's LAST USE -- the resolve
@@ -218,10 +221,10 @@ struct gs_target {
     // A host that draws every frame into the SAME target would still queue every blend behind the previous frame's composite (which reads the pixels the blend is
     // about to overwrite).  So while the context has lanes the target holds TWO pixel buffers and gs_target_clear -- after which nothing of the old content can be
     // seen -- moves on to the other one: frame k + 1 is blended into one buffer while frame k's is being resolved from the other.  rgba16f is the current one.
-    hipEvent_t evLastUse = nullptr;         // of the current buffer (swapped with evLastUseAlt by the flip)
+    gs::Event evLastUse;                    // of the current buffer (swapped with evLastUseAlt by the flip)
     bool lastUseValid = false;
-    uint16_t* rgba16fAlt = nullptr;         // the other buffer, allocated at the first flip
-    hipEvent_t evLastUseAlt = nullptr;
+    gs::DevBuf<uint16_t> rgba16fAlt;        // the other buffer, allocated at the first flip
+    gs::Event evLastUseAlt;
     bool lastUseValidAlt = false;
     bool exposed = false;                   // gs_target_device_ptr handed the memory out: the host's own work on the context's stream may touch it (and the pointer stays put)
 };
@@ -231,58 +234,58 @@ struct gs_renderer {
     gs_asset* asset = nullptr;
     uint32_t n = 0;
     // reference buffers (GaussianSplatRenderer.cs:407,431-432)
-    gsm::ViewData* view = nullptr;          // m_GpuView
-    uint32_t* keyBySplat = nullptr;         // N x u32: the frame's sort key of every splat, in splat-index order
-    uint32_t* distances = nullptr;          // m_GpuSortDistances
-    uint32_t* order = nullptr;              // m_GpuSortKeys (_OrderBuffer)
+    gs::DevBuf<gsm::ViewData> view;         // m_GpuView
+    gs::DevBuf<uint32_t> keyBySplat;        // N x u32: the frame's sort key of every splat, in splat-index order
+    gs::DevBuf<uint32_t> distances;         // m_GpuSortDistances
+    gs::DevBuf<uint32_t> order;             // m_GpuSortKeys (_OrderBuffer)
     gs::SortState depthSort;
-    gs::SortControl* depthControl = nullptr;   // two blocks, used alternately: each sort zeroes the other one for the next
+    gs::DevBuf<gs::SortControl> depthControl;  // two blocks, used alternately: each sort zeroes the other one for the next
     int depthControlIdx = 0;                   // the block the last / current sort uses
     // compositor buffers
-    gs::SplatRec* recs = nullptr;           // N x 32 B, indexed by splat (written by calc_view)
-    gsm::BoxRec* boxRecs = nullptr;         // N x 64 B, debug box modes only (allocated on first use)
-    uint32_t* chunkOrder = nullptr;         // identity order of the chunks (DebugChunkBounds draws them in index order)
-    float* recW = nullptr;                  // N x 4 B: clip.w of the visible splats, filled by the draw only when the target has a depth attachment
-    uint2* rects = nullptr;                 // N x 8 B: x = x0 | y0 << 16, y = (x1 + 1) | (y1 + 1) << 16, pixels (0 = culled): gsm::PackPixelRect
-    unsigned long long* visMask = nullptr;  // ceil(N/64) x 8 B: bit s = splat s reaches at least one tile (written by calc_view); + ceil(N/64) B per-wave flags (wave_flags_of)
+    gs::DevBuf<gs::SplatRec> recs;          // N x 32 B, indexed by splat (written by calc_view)
+    gs::DevBuf<gsm::BoxRec> boxRecs;        // N x 64 B, debug box modes only (allocated on first use)
+    gs::DevBuf<uint32_t> chunkOrder;        // identity order of the chunks (DebugChunkBounds draws them in index order)
+    gs::DevBuf<float> recW;                 // N x 4 B: clip.w of the visible splats, filled by the draw only when the target has a depth attachment
+    gs::DevBuf<uint2> rects;                // N x 8 B: x = x0 | y0 << 16, y = (x1 + 1) | (y1 + 1) << 16, pixels (0 = culled): gsm::PackPixelRect
+    gs::DevBuf<unsigned long long> visMask; // ceil(N/64) x 8 B: bit s = splat s reaches at least one tile (written by calc_view); + ceil(N/64) B per-wave flags (wave_flags_of)
     // edit state read by calc_view (m_GpuEditDeleted / m_GpuEditCutouts, GaussianSplatRenderer.cs:266,269)
-    uint32_t* deletedBits = nullptr;        // ceil(N/32) words, or null (_SplatBitsValid = 0)
-    uint32_t* cutouts = nullptr;            // GS_MAX_CUTOUTS x 17 dwords
+    gs::DevBuf<uint32_t> deletedBits;       // ceil(N/32) words, or null (_SplatBitsValid = 0)
+    gs::DevBuf<uint32_t> cutouts;           // GS_MAX_CUTOUTS x 17 dwords
     uint32_t cutoutCount = 0;
-    uint8_t* cutoutsHost = nullptr;         // pinned shadow of the last uploaded set
+    gs::PinnedBuf<uint8_t> cutoutsHost;     // pinned shadow of the last uploaded set
     uint32_t cutoutsHostCount = 0;
-    hipEvent_t cutoutsCopied = nullptr;
+    gs::Event cutoutsCopied;
     bool cutoutsCopyPending = false;
     // selection state of the edit kernels (gs_edit.hip; EnsureEditingBuffers, GaussianSplatRenderer.cs:767-786), made at the first edit call; the deleted
     // buffer of that function is deletedBits above.  On the owning renderer only: a lane holds nothing but its copy of deletedBits.
-    uint32_t* editSelected = nullptr;       // m_GpuEditSelected: ceil(N/32) words
-    uint32_t* editSelectedMouseDown = nullptr;   // m_GpuEditSelectedMouseDown
-    uint32_t* editCountsBounds = nullptr;   // m_GpuEditCountsBounds: 3 counts + 6 sortable uints
-    hipEvent_t evEditDeleted = nullptr;     // context's stream -> lanes: deletedBits holds a delete's result
-    hipEvent_t evEditCopied = nullptr;      // (on a lane) lane's stream -> owner's: the lane has taken its copy
+    gs::DevBuf<uint32_t> editSelected;      // m_GpuEditSelected: ceil(N/32) words
+    gs::DevBuf<uint32_t> editSelectedMouseDown;  // m_GpuEditSelectedMouseDown
+    gs::DevBuf<uint32_t> editCountsBounds;  // m_GpuEditCountsBounds: 3 counts + 6 sortable uints
+    gs::Event evEditDeleted;                // context's stream -> lanes: deletedBits holds a delete's result
+    gs::Event evEditCopied;                 // (on a lane) lane's stream -> owner's: the lane has taken its copy
     float viewW = 0.f, viewH = 0.f, viewNear = 0.f, viewFar = 0.f;   // what the last calc_view was run with
     bool viewValid = false;
     bool viewMaterialised = false;          // the N x 40 B view buffer holds the last calc_view's records (written on demand)
     bool alwaysWriteView = false;           // gs_renderer_set_view_buffer_mode(1): write it every frame like the reference
     gs_frame_params lastParams;             // of the last gs_renderer_calc_view (for the on-demand FULL launch)
-    uint32_t* pairKeys = nullptr;           // tile ids
-    uint32_t* pairVals = nullptr;           // sorted positions
+    gs::DevBuf<uint32_t> pairKeys;          // tile ids
+    gs::DevBuf<uint32_t> pairVals;          // sorted positions
     gs::SortState pairSort;
     uint64_t pairCapacity = 0;
     // per-frame zero arena: [BinControl | SortControl(pair) | binStatus | tileStart | tileEnd]
-    uint8_t* frameArena = nullptr;          // two copies, used alternately: each draw zeroes the other one for the next
+    gs::DevBuf<uint8_t> frameArena;         // two copies, used alternately: each draw zeroes the other one for the next
     int arenaIdx = 0;
     size_t frameArenaBytes = 0;             // of one copy
     size_t offBinStatus = 0, offBinGroupAgg = 0, offBinGroupBase = 0, offTileStart = 0, offTileEnd = 0, offPairControl = 0;
     uint32_t arenaTiles = 0;                // tiles the arena was sized for
-    uint32_t* tileCost = nullptr;           // 2 x arenaTiles x u32: batches each tile walked -- a draw writes copy costIdx and reads (for scheduling) the other
+    gs::DevBuf<uint32_t> tileCost;          // 2 x arenaTiles x u32: batches each tile walked -- a draw writes copy costIdx and reads (for scheduling) the other
     int costIdx = 0;
     uint32_t costTiles[2] = {0, 0};         // tile count of the draw that wrote each copy (0 = none): a schedule can be made from it for the same count only
     uint32_t costShape[2] = {0, 0};         // ... and the same tile shape (log2 w | log2 h << 8)
     uint32_t tileOverrideWL = 0, tileOverrideHL = 0;   // gs_renderer_set_tile_shape: log2 tile width / height, 0 = automatic
     uint32_t lastTileWL = 0, lastTileHL = 0;           // of the last draw (0 x 0: nothing drawn yet)
     bool adaptTall = false;                            // automatic shape: 32x32 instead of 32x16 (large splats; adapt_tile_shape)
-    uint32_t* tileOrderBuf = nullptr;       // arenaTiles x u32: the blend's tile schedule of the draw in flight
+    gs::DevBuf<uint32_t> tileOrderBuf;      // arenaTiles x u32: the blend's tile schedule of the draw in flight
     uint32_t binParts = 0;
     int blendMode = 0;
     int renderMode = 0;                     // gs_render_mode (GaussianSplatRenderer.RenderMode, :126-131)
@@ -290,14 +293,13 @@ struct gs_renderer {
     // profiling: a ring of per-frame hipEvent sets (slot advances at the end of gs_renderer_draw)
     bool profiling = false;
     bool kernelTiming = false;              // gs_renderer_set_kernel_timing: Onesweep launches carry their own start / stop events
-    hipEvent_t* ev = nullptr;               // profCapacity x kEvPerFrame
-    uint8_t* evValid = nullptr;
+    std::vector<gs::Event> ev;              // profCapacity x kEvPerFrame
+    std::vector<uint8_t> evValid;
     int profCapacity = 0, profCur = 0, profCompleted = 0;
     // host copy of last frame's control (pinned), read lazily
-    gs::FrameReport* hostReport = nullptr;  // pinned + mapped: written by the last small kernel of a draw (no copy launch)
-    gs::FrameReport* hostReportDev = nullptr;   // its device-side address
-    hipEvent_t evSortDone = nullptr;        // aux -> main join (timing disabled)
-    hipEvent_t evOrderFree = nullptr;       // main -> aux fork: the last operation of the main queue that reads or writes order[]
+    gs::PinnedBuf<gs::FrameReport> hostReport; // pinned + mapped: written by the last small kernel of a draw (no copy launch) through hostReport.device()
+    gs::Event evSortDone;                   // aux -> main join (timing disabled)
+    gs::Event evOrderFree;                  // main -> aux fork: the last operation of the main queue that reads or writes order[]
     bool distancesStale = false;      // the last depth pass skipped the sorted-key write: gs_renderer_download_distances gathers them
     bool sortPending = false;               // a sort on ctx->aux has not been joined into ctx->stream yet
     uint32_t lastTilesX = 0, lastTilesY = 0, lastPairPasses = 0, lastDepthPasses = 4;
@@ -312,21 +314,21 @@ struct gs_renderer {
     // the reference's buffer NOW = order[] stably sorted by visHist, oldest first
     bool visBaseIdentity = true;            // order[] is CSSetIndices' identity (rank[s] = s: no rank array needed)
     bool visRankValid = false;              // visBaseRank holds the inverse of order[]
-    uint32_t* visBaseRank = nullptr;        // N x u32, allocated when first needed
+    gs::DevBuf<uint32_t> visBaseRank;       // N x u32, allocated when first needed
     bool visOrderValid = false;             // visIdx holds the sorted visible order of the last calc_view under the current history
     bool visDrawn = false;                  // the draw in flight was binned from visIdx
     float visHist[gs::kVisHistory][4];      // sort-matrix rows (m[8..11]) since the base, most recent first, no row twice
     int visHistDepth = 0;
     int visHistLimit = gs::kVisHistory;     // rows kept before the base is consolidated (gs_renderer_set_sort_history_limit; GSPLAT_VIS_HISTORY)
     unsigned long long visConsolidations = 0;
-    uint32_t* visKeys = nullptr;            // N x u32 each, allocated on first use: compacted (key, splat index) of the visible splats, sorted in place
-    uint32_t* visIdx = nullptr;
-    uint32_t* visRectX = nullptr;           // N x u32 each: the pixel rectangle (rects[visIdx[i]].x / .y) by SORTED position (vis_offsets_kernel's gather)
-    uint32_t* visRectY = nullptr;
-    uint32_t* visPairOffset = nullptr;      // N x u32: first (tile, splat) pair slot of every sorted position (vis_offsets_kernel)
-    uint32_t* visChunkStart = nullptr;      // per chunk of 1024 pair slots: the sorted position its first slot belongs to; sized by the pair capacity
+    gs::DevBuf<uint32_t> visKeys;           // N x u32 each, allocated on first use: compacted (key, splat index) of the visible splats, sorted in place
+    gs::DevBuf<uint32_t> visIdx;
+    gs::DevBuf<uint32_t> visRectX;          // N x u32 each: the pixel rectangle (rects[visIdx[i]].x / .y) by SORTED position (vis_offsets_kernel's gather)
+    gs::DevBuf<uint32_t> visRectY;
+    gs::DevBuf<uint32_t> visPairOffset;     // N x u32: first (tile, splat) pair slot of every sorted position (vis_offsets_kernel)
+    gs::DevBuf<uint32_t> visChunkStart;     // per chunk of 1024 pair slots: the sorted position its first slot belongs to; sized by the pair capacity
     uint32_t visChunkCap = 0;
-    gs::VisControl* visControl = nullptr;   // two blocks, used alternately
+    gs::DevBuf<gs::VisControl> visControl;  // two blocks, used alternately
     int visControlIdx = 0;
     // ---- frames in flight inside the library (gs_renderer_set_frames_in_flight; gs_api.hip) ----
     // lanes: renderers on contexts (= streams) of their own over this renderer's asset, owned by it; while GS_SORT_VISIBLE draws splats every gs_renderer_calc_view
@@ -334,8 +336,8 @@ struct gs_renderer {
     std::vector<gs_renderer*> lanes;
     int laneCur = -1;                       // the lane of the frame in progress (-1: none yet)
     gs_renderer* laneOf = nullptr;          // a lane's owner
-    hipEvent_t evTargetFree = nullptr;      // a lane drawing into its owner's target: target's stream -> lane (before the blend) ...
-    hipEvent_t evBlendDone = nullptr;       // ... and lane -> target's stream (after it)
+    gs::Event evTargetFree;                 // a lane drawing into its owner's target: target's stream -> lane (before the blend) ...
+    gs::Event evBlendDone;                  // ... and lane -> target's stream (after it)
 };
 
 namespace gs {
@@ -346,7 +348,6 @@ int32_t mark_order_use(gs_renderer* r);     // the main queue has just been give
 void prof_end_frame(gs_renderer* r);
 // sort entry points (gs_sort.hip)
 int32_t sort_state_create(gs_context* ctx, SortState& st, uint32_t maxCount, bool smallPartitions = false);
-void sort_state_destroy(SortState& st);
 // keys of all splats in index order (CSCalcDistances' arithmetic) + the four digit histograms; the gather through the
 // previous order is done by the first sort pass (enqueue_sort_passes with gatherKeys)
 int32_t enqueue_sort_keys(gs_context* ctx, hipStream_t st, const gsm::AssetView& a, const float* matSort, uint32_t* keyBySplat,
@@ -369,7 +370,6 @@ int32_t enqueue_set_indices(gs_context* ctx, uint32_t* order, uint32_t n);
 // visible-only depth sort (gs_vissort.hip)
 inline bool vis_active(const gs_renderer* r) { return r->sortMode == GS_SORT_VISIBLE; }
 int32_t vis_alloc(gs_renderer* r);                                   // visKeys / visIdx / visControl, on first use
-void vis_free(gs_renderer* r);
 int32_t vis_push_matrix(gs_renderer* r, const float* matrixSort);    // gs_renderer_sort in visible mode: history bookkeeping (+ a consolidation when the history is full)
 // order[] := the reference's whole order buffer now (one full sort of the base by the most recent row + the chain fix-up over N); the history shrinks
 // to that row.  Also what hands the buffer to GS_SORT_FULL / gs_renderer_download_order.  (gs_api.hip)
@@ -385,7 +385,6 @@ ViewOutputs view_outputs(gs_renderer* r);
 void flatten_params(const gs_frame_params* p, gsm::FrameConsts& c);
 // raster (gs_raster.hip)
 int32_t renderer_alloc_raster(gs_renderer* r);
-void renderer_free_raster(gs_renderer* r);
 int32_t enqueue_draw(gs_renderer* r, const gs_frame_params* p, gs_target* rt);
 void auto_tile_shape(uint32_t width, uint32_t height, uint32_t& wl, uint32_t& hl);                       // the automatic tile shape for a target size
 void pick_tile_shape(const gs_renderer* r, uint32_t width, uint32_t height, uint32_t& wl, uint32_t& hl);  // ... or the renderer's override
@@ -394,5 +393,5 @@ int32_t enqueue_debug_boxes(gs_renderer* r, const gs_frame_params* p, gs_target*
 int32_t enqueue_resolve(gs_target* t, const float bg[4], bool want8);
 int32_t flush_clear(gs_target* t);          // perform a pending gs_target_clear now
 // edit (gs_edit.hip)
-void edit_free(gs_renderer* r);             // the selection buffers and the edit events (not deletedBits)
+void edit_free(gs_renderer* r);             // the selection buffers (not deletedBits, not the edit events)
 } // namespace gs

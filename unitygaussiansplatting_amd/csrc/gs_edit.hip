@@ -159,29 +159,18 @@ static int32_t edit_ensure(gs_renderer* r) {
     GS_HIP(hipSetDevice(r->ctx->device));
     if (r->editSelected) return GS_OK;
     const size_t bytes = edit_words(r) * 4;
-    uint32_t *sel = nullptr, *md = nullptr, *cb = nullptr;
-    hipError_t e = hipMalloc((void**)&sel, bytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&md, bytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&cb, 9 * 4);
-    if (e == hipSuccess) e = hipMemsetAsync(sel, 0, bytes, r->ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(md, 0, bytes, r->ctx->stream);
-    if (e != hipSuccess) {
-        if (sel) (void)hipFree(sel);
-        if (md) (void)hipFree(md);
-        if (cb) (void)hipFree(cb);
-        return fail_hip(e, "allocate edit buffers", __FILE__, __LINE__);
-    }
-    r->editSelected = sel; r->editSelectedMouseDown = md; r->editCountsBounds = cb;
+    DevBuf<uint32_t> sel, md, cb;
+    GS_HIP(sel.alloc(bytes));
+    GS_HIP(md.alloc(bytes));
+    GS_HIP(cb.alloc(9 * 4));
+    GS_HIP(hipMemsetAsync(sel, 0, bytes, r->ctx->stream));
+    GS_HIP(hipMemsetAsync(md, 0, bytes, r->ctx->stream));
+    r->editSelected = std::move(sel); r->editSelectedMouseDown = std::move(md); r->editCountsBounds = std::move(cb);
     return GS_OK;
 }
 
 void edit_free(gs_renderer* r) {
-    if (r->editSelected) (void)hipFree(r->editSelected);
-    if (r->editSelectedMouseDown) (void)hipFree(r->editSelectedMouseDown);
-    if (r->editCountsBounds) (void)hipFree(r->editCountsBounds);
-    r->editSelected = r->editSelectedMouseDown = r->editCountsBounds = nullptr;
-    if (r->evEditDeleted) { (void)hipEventDestroy(r->evEditDeleted); r->evEditDeleted = nullptr; }
-    if (r->evEditCopied) { (void)hipEventDestroy(r->evEditCopied); r->evEditCopied = nullptr; }
+    r->editSelected.reset(); r->editSelectedMouseDown.reset(); r->editCountsBounds.reset();
 }
 
 static inline uint32_t splat_grid(const gs_renderer* r) { return (r->n + 255u) / 256u; }
@@ -194,11 +183,11 @@ static inline uint32_t word_grid(const gs_renderer* r) { return (uint32_t)((edit
 static int32_t edit_deleted_to_lanes(gs_renderer* r) {
     if (r->lanes.empty()) return GS_OK;
     const size_t bytes = edit_words(r) * 4;
-    if (!r->evEditDeleted) GS_HIP(hipEventCreateWithFlags(&r->evEditDeleted, hipEventDisableTiming));
+    if (!r->evEditDeleted) GS_HIP(r->evEditDeleted.create(hipEventDisableTiming));
     GS_HIP(hipEventRecord(r->evEditDeleted, r->ctx->stream));
     for (gs_renderer* L : r->lanes) {
-        if (!L->deletedBits) GS_HIP(hipMalloc((void**)&L->deletedBits, bytes));
-        if (!L->evEditCopied) GS_HIP(hipEventCreateWithFlags(&L->evEditCopied, hipEventDisableTiming));
+        if (!L->deletedBits) GS_HIP(L->deletedBits.alloc(bytes));
+        if (!L->evEditCopied) GS_HIP(L->evEditCopied.create(hipEventDisableTiming));
         GS_HIP(hipStreamWaitEvent(L->ctx->stream, r->evEditDeleted, 0));
         GS_HIP(hipMemcpyAsync(L->deletedBits, r->deletedBits, bytes, hipMemcpyDeviceToDevice, L->ctx->stream));
         GS_HIP(hipEventRecord(L->evEditCopied, L->ctx->stream));
@@ -264,11 +253,10 @@ int32_t gs_renderer_edit_delete_selected(gs_renderer* r) {
     GS_TRY(edit_ensure(r));
     const size_t bytes = edit_words(r) * 4;
     if (!r->deletedBits) {
-        uint32_t* d = nullptr;
-        GS_HIP(hipMalloc((void**)&d, bytes));
-        const hipError_t e = hipMemsetAsync(d, 0, bytes, r->ctx->stream);
-        if (e != hipSuccess) { (void)hipFree(d); return fail_hip(e, "clear deleted bits", __FILE__, __LINE__); }
-        r->deletedBits = d;
+        DevBuf<uint32_t> d;
+        GS_HIP(d.alloc(bytes));
+        GS_HIP(hipMemsetAsync(d, 0, bytes, r->ctx->stream));
+        r->deletedBits = std::move(d);
     }
     hipLaunchKernelGGL(edit_delete_kernel, dim3(word_grid(r)), dim3(256), 0, r->ctx->stream, r->deletedBits, r->editSelected, (uint32_t)edit_words(r));
     GS_HIP(hipGetLastError());
@@ -326,10 +314,7 @@ int32_t gs_renderer_edit_release(gs_renderer* r) {
     if (!r->editSelected) return GS_OK;
     GS_HIP(hipSetDevice(r->ctx->device));
     GS_HIP(hipStreamSynchronize(r->ctx->stream));
-    if (r->editSelected) (void)hipFree(r->editSelected);
-    if (r->editSelectedMouseDown) (void)hipFree(r->editSelectedMouseDown);
-    if (r->editCountsBounds) (void)hipFree(r->editCountsBounds);
-    r->editSelected = r->editSelectedMouseDown = r->editCountsBounds = nullptr;
+    edit_free(r);
     return GS_OK;
 }
 

@@ -1346,29 +1346,29 @@ inline size_t align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
 
 int32_t ensure_arena(gs_renderer* r, uint32_t numTiles) {
     if (r->frameArena && numTiles <= r->arenaTiles) return GS_OK;
-    if (r->frameArena) { GS_HIP(hipStreamSynchronize(r->ctx->stream)); (void)hipFree(r->frameArena); r->frameArena = nullptr; }
-    size_t off = 0;
-    off = align_up(sizeof(BinControl), 256);
-    r->offPairControl = off; off += align_up(sizeof(SortControl), 256);
+    if (r->frameArena) GS_HIP(hipStreamSynchronize(r->ctx->stream));
+    // the new arena, scheduling hints and schedule first: on a failure the renderer keeps the three it has (and what describes them), for the tile count they were made for
+    const size_t offPairControl = align_up(sizeof(BinControl), 256);
     // (GS_SORT_VISIBLE draws reuse the two arrays: one word per 256 positions = 8 binParts, one per 64 of those)
-    r->offBinStatus = off;   off += align_up((size_t)(8u * r->binParts + 1u) * 8, 256);
-    r->offBinGroupAgg = off; off += align_up((size_t)((8u * r->binParts + 64u) / 64u + 1u) * 8, 256);
-    r->offBinGroupBase = off; off += align_up((size_t)((r->binParts + 63) / 64) * 8, 256);
-    r->offTileStart = off;   off += align_up((size_t)numTiles * 4, 256);
-    r->offTileEnd = off;     off += align_up((size_t)numTiles * 4, 256);
-    off = align_up(off, 256);
-    r->frameArenaBytes = off;
-    r->arenaTiles = numTiles;
-    GS_HIP(hipMalloc((void**)&r->frameArena, 2 * off));
-    GS_HIP(hipMemsetAsync(r->frameArena, 0, 2 * off, r->ctx->stream));
-    r->arenaIdx = 0;
+    const size_t offBinStatus = offPairControl + align_up(sizeof(SortControl), 256);
+    const size_t offBinGroupAgg = offBinStatus + align_up((size_t)(8u * r->binParts + 1u) * 8, 256);
+    const size_t offBinGroupBase = offBinGroupAgg + align_up((size_t)((8u * r->binParts + 64u) / 64u + 1u) * 8, 256);
+    const size_t offTileStart = offBinGroupBase + align_up((size_t)((r->binParts + 63) / 64) * 8, 256);
+    const size_t offTileEnd = offTileStart + align_up((size_t)numTiles * 4, 256);
+    const size_t bytes = offTileEnd + align_up((size_t)numTiles * 4, 256);
+    DevBuf<uint8_t> arena; DevBuf<uint32_t> cost, order;
+    GS_HIP(arena.alloc(2 * bytes));
+    GS_HIP(hipMemsetAsync(arena, 0, 2 * bytes, r->ctx->stream));
     // persist across frames (not part of the zeroed arena): the scheduling hints and the schedule itself, two copies each
-    if (r->tileCost) (void)hipFree(r->tileCost);
-    if (r->tileOrderBuf) (void)hipFree(r->tileOrderBuf);
-    r->tileCost = nullptr; r->tileOrderBuf = nullptr;
-    GS_HIP(hipMalloc((void**)&r->tileCost, (size_t)2 * numTiles * 4));
-    GS_HIP(hipMemsetAsync(r->tileCost, 0, (size_t)2 * numTiles * 4, r->ctx->stream));
-    GS_HIP(hipMalloc((void**)&r->tileOrderBuf, (size_t)numTiles * 4));
+    GS_HIP(cost.alloc((size_t)2 * numTiles * 4));
+    GS_HIP(hipMemsetAsync(cost, 0, (size_t)2 * numTiles * 4, r->ctx->stream));
+    GS_HIP(order.alloc((size_t)numTiles * 4));
+    r->frameArena = std::move(arena); r->tileCost = std::move(cost); r->tileOrderBuf = std::move(order);
+    r->offPairControl = offPairControl; r->offBinStatus = offBinStatus; r->offBinGroupAgg = offBinGroupAgg; r->offBinGroupBase = offBinGroupBase;
+    r->offTileStart = offTileStart; r->offTileEnd = offTileEnd;
+    r->frameArenaBytes = bytes;
+    r->arenaTiles = numTiles;
+    r->arenaIdx = 0;
     r->costIdx = 0; r->costTiles[0] = r->costTiles[1] = 0;
     return GS_OK;
 }
@@ -1380,11 +1380,11 @@ ViewOutputs view_outputs(gs_renderer* r) { return ViewOutputs{ r->view, r->recs,
 int32_t renderer_alloc_raster(gs_renderer* r) {
     gs_context* ctx = r->ctx;
     r->binParts = div_up(r->n, kBinPart);
-    GS_HIP(hipMalloc((void**)&r->recs, (size_t)r->n * sizeof(SplatRec) + 64));
-    GS_HIP(hipMalloc((void**)&r->recW, (size_t)r->n * sizeof(float) + 64));
-    GS_HIP(hipMalloc((void**)&r->rects, (size_t)r->n * sizeof(uint2) + 64));
+    GS_HIP(r->recs.alloc((size_t)r->n * sizeof(SplatRec) + 64));
+    GS_HIP(r->recW.alloc((size_t)r->n * sizeof(float) + 64));
+    GS_HIP(r->rects.alloc((size_t)r->n * sizeof(uint2) + 64));
     GS_HIP(hipMemsetAsync(r->rects, 0, (size_t)r->n * sizeof(uint2), ctx->stream));
-    GS_HIP(hipMalloc((void**)&r->visMask, vis_alloc_bytes(r->n)));
+    GS_HIP(r->visMask.alloc(vis_alloc_bytes(r->n)));
     GS_HIP(hipMemsetAsync(r->visMask, 0, vis_alloc_bytes(r->n), ctx->stream));
     if (r->pairCapacity == 0) {
         unsigned long long cap = (unsigned long long)r->n * 8ull;
@@ -1392,32 +1392,12 @@ int32_t renderer_alloc_raster(gs_renderer* r) {
         if (cap > kSortMaxCount) cap = kSortMaxCount;           // 32-bit byte offsets inside the sort kernels
         r->pairCapacity = cap;
     }
-    GS_HIP(hipMalloc((void**)&r->pairKeys, ((size_t)r->pairCapacity + 16) * 4));
-    GS_HIP(hipMalloc((void**)&r->pairVals, ((size_t)r->pairCapacity + 16) * 4));
+    GS_HIP(r->pairKeys.alloc(((size_t)r->pairCapacity + 16) * 4));
+    GS_HIP(r->pairVals.alloc(((size_t)r->pairCapacity + 16) * 4));
     GS_TRY(sort_state_create(ctx, r->pairSort, (uint32_t)r->pairCapacity));
-    GS_HIP(hipHostMalloc((void**)&r->hostReport, sizeof(FrameReport), hipHostMallocMapped));
+    GS_HIP(r->hostReport.alloc(sizeof(FrameReport), hipHostMallocMapped));
     memset(r->hostReport, 0, sizeof(FrameReport));
-    GS_HIP(hipHostGetDevicePointer((void**)&r->hostReportDev, r->hostReport, 0));
     return GS_OK;
-}
-
-void renderer_free_raster(gs_renderer* r) {
-    if (r->recs) (void)hipFree(r->recs);
-    if (r->rects) (void)hipFree(r->rects);
-    if (r->recW) (void)hipFree(r->recW);
-    if (r->boxRecs) (void)hipFree(r->boxRecs);
-    if (r->chunkOrder) (void)hipFree(r->chunkOrder);
-    r->recW = nullptr; r->boxRecs = nullptr; r->chunkOrder = nullptr;
-    if (r->visMask) (void)hipFree(r->visMask);
-    if (r->pairKeys) (void)hipFree(r->pairKeys);
-    if (r->pairVals) (void)hipFree(r->pairVals);
-    sort_state_destroy(r->pairSort);
-    if (r->frameArena) (void)hipFree(r->frameArena);
-    if (r->tileCost) (void)hipFree(r->tileCost);
-    if (r->tileOrderBuf) (void)hipFree(r->tileOrderBuf);
-    r->tileCost = nullptr; r->tileOrderBuf = nullptr;
-    if (r->hostReport) (void)hipHostFree(r->hostReport);
-    r->recs = nullptr; r->rects = nullptr; r->visMask = nullptr; r->pairKeys = r->pairVals = nullptr; r->frameArena = nullptr; r->hostReport = nullptr; r->hostReportDev = nullptr;
 }
 
 namespace {
@@ -1479,13 +1459,15 @@ int32_t bin_and_sort(gs_renderer* r, const gs_frame_params* p, gs_target* rt, co
         // GS_SORT_VISIBLE: offsets + output-partitioned emission (see vis_offsets_kernel)
         const uint32_t capChunks = div_up(cap, kEmitChunk) + 1u;
         if (r->visChunkCap < capChunks) {
-            if (r->visChunkStart) { GS_HIP(hipStreamSynchronize(st)); (void)hipFree(r->visChunkStart); r->visChunkStart = nullptr; r->visChunkCap = 0; }
-            GS_HIP(hipMalloc((void**)&r->visChunkStart, (size_t)capChunks * 4));
+            if (r->visChunkStart) GS_HIP(hipStreamSynchronize(st));
+            DevBuf<uint32_t> chunkStart;
+            GS_HIP(chunkStart.alloc((size_t)capChunks * 4));
+            r->visChunkStart = std::move(chunkStart);
             r->visChunkCap = capChunks;
         }
         // (blockSum lives in the arena's bin-status words, groupSum -- zeroed, accumulated with atomics -- in its bin-group words: ensure_arena sizes both)
         // (the host only knows the bound N: the grids follow the visible count of the last draw that reported, + 1/8, and stride)
-        const uint32_t lastVis = (r->hostReport && r->frameInFlight) ? *(volatile uint32_t*)&r->hostReport->visible : 0u;
+        const uint32_t lastVis = (r->hostReport && r->frameInFlight) ? *(volatile uint32_t*)&r->hostReport.get()->visible : 0u;
         const uint32_t gridFor = lastVis ? min(count, lastVis + lastVis / 8u + 4096u) : count;
         // (8 workgroups per CU = every wave slot; 2 .. 64 per CU measured within 1 us of each other at C2, r05 call 11: the gather is at the
         // memory system's random-sector rate whatever is in flight)
@@ -1509,7 +1491,7 @@ int32_t bin_and_sort(gs_renderer* r, const gs_frame_params* p, gs_target* rt, co
     GS_TRY(mark_order_use(r));                                  // the next frame's depth sort may overwrite order[] from here on
     prof_record(r, 4);
     // the host only knows the capacity; the pair count of the last finished frame (pinned report) picks the sort's pass shape
-    const unsigned long long lastPairs = r->hostReport ? *(volatile unsigned long long*)&r->hostReport->pairCount : 0ull;
+    const unsigned long long lastPairs = r->hostReport ? *(volatile unsigned long long*)&r->hostReport.get()->pairCount : 0ull;
     const uint32_t expectPairs = (uint32_t)(lastPairs < (unsigned long long)cap ? lastPairs : (unsigned long long)cap);
     GS_TRY(enqueue_sort_passes(ctx, st, r->pairSort, pairCtl, r->pairKeys, r->pairVals, cap, &binCtl->pairCountClamped, passes, 255u, r, 12, bits, nullptr, false,
                                expectPairs ? expectPairs : 1u));
@@ -1521,7 +1503,7 @@ int32_t bin_and_sort(gs_renderer* r, const gs_frame_params* p, gs_target* rt, co
     // list lengths) only when there is no cost history for this tile grid (first draw, another target size) or the caller asks
     if (!schedInBin)
         hipLaunchKernelGGL(tile_order_kernel, dim3(1), dim3(1024), 0, st, o.tileStart, o.tileEnd, o.costRead, numTiles, rc.tilesX, o.tileOrder, binCtl, &pairCtl->error,
-                           r->hostReportDev, shapeKey);
+                           r->hostReport.device(), shapeKey);
     prof_record(r, 5);
     o.dstIsZero = rt->clearPending ? 1 : 0;                      // this draw writes every pixel of the target: the clear is folded in
     rt->clearPending = false;
@@ -1577,7 +1559,7 @@ static int32_t reserve_for_smaller_tile(gs_renderer* r, uint32_t twl, uint32_t t
     if (!r->frameInFlight || !r->hostReport || !r->lastTileWL) return GS_OK;
     const uint32_t lastArea = r->lastTileWL + r->lastTileHL, area = twl + thl;      // log2 areas
     if (area >= lastArea) return GS_OK;
-    const unsigned long long seen = *(volatile unsigned long long*)&r->hostReport->pairCount;
+    const unsigned long long seen = *(volatile unsigned long long*)&r->hostReport.get()->pairCount;
     unsigned long long want = (seen << (lastArea - area));
     want += want / 4u;
     if (want > kSortMaxCount) want = kSortMaxCount;
@@ -1627,11 +1609,11 @@ int32_t enqueue_draw(gs_renderer* r, const gs_frame_params* p, gs_target* rt) {
     if (rt->sceneDepth) {
         gsm::FrameConsts fc;
         flatten_params(p, fc);
-        hipLaunchKernelGGL(splat_depth_kernel, dim3(div_up(r->n, 256)), dim3(256), 0, st, r->asset->view, fc, (const uint32_t*)r->visMask, r->recW);
+        hipLaunchKernelGGL(splat_depth_kernel, dim3(div_up(r->n, 256)), dim3(256), 0, st, r->asset->view, fc, (const uint32_t*)r->visMask.get(), r->recW);
     }
 #define GS_LAUNCH_BLEND_S(M, D, WL, HL) hipLaunchKernelGGL((blend_kernel<M, D, WL, HL>), dim3(numTiles), dim3(64u << (WL + HL - 6)), 0, st, r->pairVals, tileStart, tileEnd, \
                                              tileOrder, ds.costWrite, r->recs, rt->rgba16f, rc, dstIsZero, r->recW, rt->sceneDepth, \
-                                             ds.binCtl, ds.pairSortError, r->hostReportDev)
+                                             ds.binCtl, ds.pairSortError, r->hostReport.device())
 #define GS_LAUNCH_BLEND(M, D) do { if (twl == 4u) GS_LAUNCH_BLEND_S(M, D, 4, 4); else if (thl == 4u) GS_LAUNCH_BLEND_S(M, D, 5, 4); else GS_LAUNCH_BLEND_S(M, D, 5, 5); } while (0)
     if (rt->sceneDepth) { if (r->blendMode == 0) GS_LAUNCH_BLEND(0, true); else GS_LAUNCH_BLEND(1, true); }
     else { if (r->blendMode == 0) GS_LAUNCH_BLEND(0, false); else GS_LAUNCH_BLEND(1, false); }
@@ -1657,9 +1639,9 @@ int32_t enqueue_debug_boxes(gs_renderer* r, const gs_frame_params* p, gs_target*
     const uint32_t count = chunks ? a.chunkCount : r->n;
     if (chunks && count == 0) return GS_OK;                      // m_GpuChunksValid == false: instanceCount = 0 (GaussianSplatRenderer.cs:161-162)
     if (chunks && (uint64_t)count * 256u < (uint64_t)r->n) return fail(GS_ERR_INVALID_ASSET, "chunk blob smaller than the splat count");
-    if (!r->boxRecs) GS_HIP(hipMalloc((void**)&r->boxRecs, (size_t)r->n * sizeof(gsm::BoxRec) + 64));
+    if (!r->boxRecs) GS_HIP(r->boxRecs.alloc((size_t)r->n * sizeof(gsm::BoxRec) + 64));
     if (chunks && !r->chunkOrder) {
-        GS_HIP(hipMalloc((void**)&r->chunkOrder, ((size_t)count + 16) * 4));
+        GS_HIP(r->chunkOrder.alloc(((size_t)count + 16) * 4));
         GS_TRY(enqueue_set_indices(ctx, r->chunkOrder, count));
     }
     if (!chunks) GS_TRY(join_sort(r));
@@ -1702,7 +1684,7 @@ int32_t enqueue_debug_points(gs_renderer* r, const gs_frame_params* p, gs_target
     GS_TRY(flush_clear(rt));                                    // the squares only touch the pixels they cover
     const uint32_t numPix = rt->width * rt->height;
     if (!rt->zbuf) {
-        GS_HIP(hipMalloc((void**)&rt->zbuf, (size_t)numPix * 8));
+        GS_HIP(rt->zbuf.alloc((size_t)numPix * 8));
         GS_HIP(hipMemsetAsync(rt->zbuf, 0xff, (size_t)numPix * 8, st));      // afterwards the resolve kernel resets what it consumes
     }
     gsm::FrameConsts c;
@@ -1730,7 +1712,7 @@ int32_t flush_clear(gs_target* t) {
 
 int32_t target_touched(gs_target* t, hipStream_t st) {
     if (t->ctx->children.empty()) { t->lastUseValid = false; return GS_OK; }      // no lanes: the context's stream orders everything by itself
-    if (!t->evLastUse) GS_HIP(hipEventCreateWithFlags(&t->evLastUse, hipEventDisableTiming));
+    if (!t->evLastUse) GS_HIP(t->evLastUse.create(hipEventDisableTiming));
     GS_HIP(hipEventRecord(t->evLastUse, st));
     t->lastUseValid = true;
     return GS_OK;
@@ -1739,8 +1721,10 @@ int32_t target_touched(gs_target* t, hipStream_t st) {
 int32_t enqueue_resolve(gs_target* t, const float bg[4], bool want8) {
     const uint32_t numPix = t->width * t->height;
     if (!t->resolved) {
-        GS_HIP(hipMalloc((void**)&t->resolved, (size_t)numPix * 16));
-        GS_HIP(hipMalloc((void**)&t->resolved8, (size_t)numPix * 4));
+        DevBuf<float> f32; DevBuf<uint8_t> u8;                   // both or neither
+        GS_HIP(f32.alloc((size_t)numPix * 16));
+        GS_HIP(u8.alloc((size_t)numPix * 4));
+        t->resolved = std::move(f32); t->resolved8 = std::move(u8);
     }
     hipLaunchKernelGGL(resolve_kernel, dim3(div_up(numPix, 256)), dim3(256), 0, t->ctx->stream, t->rgba16f, numPix, bg[0], bg[1], bg[2], bg[3],
                        t->resolved, want8 ? t->resolved8 : (uint8_t*)nullptr);      // the sRGB 8-bit image (3 powf per pixel) only when asked for

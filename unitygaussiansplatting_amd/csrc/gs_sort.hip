@@ -552,29 +552,22 @@ inline uint32_t div_up(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 } // namespace
 
 
-int32_t sort_state_create(gs_context* ctx, SortState& st, uint32_t maxCount, bool smallPartitions) {
+int32_t sort_state_create(gs_context* ctx, SortState& out, uint32_t maxCount, bool smallPartitions) {
     if (maxCount > kSortMaxCount) return fail(GS_ERR_INVALID_ARGUMENT, "sort capacity above 2^30 keys");
+    SortState st;                                // `out` changes only once every allocation has succeeded
     st.maxCount = maxCount;
     st.partMin = smallPartitions ? (uint32_t)PART_MIN : (uint32_t)PART_A;       // the smallest partition a pass of this sort may use: sizes the status / group words
     st.maxParts = div_up(maxCount > 0 ? maxCount : 1, st.partMin);
-    GS_HIP(hipMalloc((void**)&st.altKeys, ((size_t)maxCount + 16) * 4));
-    GS_HIP(hipMalloc((void**)&st.altVals, ((size_t)maxCount + 16) * 4));
-    GS_HIP(hipMalloc((void**)&st.status, (size_t)st.maxParts * RADIX * 4));
+    GS_HIP(st.altKeys.alloc(((size_t)maxCount + 16) * 4));
+    GS_HIP(st.altVals.alloc(((size_t)maxCount + 16) * 4));
+    GS_HIP(st.status.alloc((size_t)st.maxParts * RADIX * 4));
     GS_HIP(hipMemsetAsync(st.status, 0, (size_t)st.maxParts * RADIX * 4, ctx->stream));
     st.maxGroups = div_up(st.maxParts, (uint32_t)GROUP);
-    GS_HIP(hipMalloc((void**)&st.groupAgg, (size_t)4 * st.maxGroups * RADIX * 8));
-    GS_HIP(hipMalloc((void**)&st.groupIncl, (size_t)st.maxGroups * RADIX * 8));
+    GS_HIP(st.groupAgg.alloc((size_t)4 * st.maxGroups * RADIX * 8));
+    GS_HIP(st.groupIncl.alloc((size_t)st.maxGroups * RADIX * 8));
     GS_HIP(hipMemsetAsync(st.groupIncl, 0, (size_t)st.maxGroups * RADIX * 8, ctx->stream));
+    out = std::move(st);
     return GS_OK;
-}
-
-void sort_state_destroy(SortState& st) {
-    if (st.altKeys) (void)hipFree(st.altKeys);
-    if (st.altVals) (void)hipFree(st.altVals);
-    if (st.status) (void)hipFree(st.status);
-    if (st.groupAgg) (void)hipFree(st.groupAgg);
-    if (st.groupIncl) (void)hipFree(st.groupIncl);
-    st = SortState();
 }
 
 namespace { __global__ __launch_bounds__(256) void gather_keys_kernel(const uint32_t* __restrict__ keyBySplat, const uint32_t* __restrict__ order, uint32_t* __restrict__ out, uint32_t n) {
@@ -671,14 +664,14 @@ int32_t enqueue_sort_passes(gs_context* ctx, hipStream_t stream, SortState& st, 
         // pass).  The timestamped launches cost ~6 us each themselves, which is why this is a mode of its own and not part of the
         // stage brackets (with it on, sort_ms / pair_sort_ms read ~25 us high).
         hipEvent_t evStart = nullptr, evStop = nullptr;
-        if (profR && profR->profiling && profR->kernelTiming && profR->ev && evFirst >= 0) {
+        if (profR && profR->profiling && profR->kernelTiming && !profR->ev.empty() && evFirst >= 0) {
             const int kb = profR->profCur * kEvPerFrame + (evFirst == 10 ? 14 : 22) + 2 * p;
             evStart = profR->ev[kb]; evStop = profR->ev[kb + 1];
             profR->evValid[kb] = profR->evValid[kb + 1] = 1;
         }
 #define GS_LAUNCH_ONESWEEP_K(B, G, KIN, K) \
         hipExtLaunchKernelGGL((onesweep_kernel<B, G, K>), dim3(grid), dim3(THREADS), 0, stream, evStart, evStop, 0, (const uint32_t*)(KIN), (const uint32_t*)vs, kdst, vd, \
-                              (const uint32_t*)hist, st.status, agg, st.groupIncl, (uint32_t*)control->tickets[p], &control->error, nUpper, nPtr, shift, epoch, mask, histCopies, gs_shared_gpu(ctx) ? 0u : ((gatherKeys ? 1u : 0u) | 2u))
+                              (const uint32_t*)hist, st.status.get(), agg, st.groupIncl.get(), (uint32_t*)control->tickets[p], &control->error, nUpper, nPtr, shift, epoch, mask, histCopies, gs_shared_gpu(ctx) ? 0u : ((gatherKeys ? 1u : 0u) | 2u))
 #define GS_LAUNCH_ONESWEEP(B, G, KIN) do { if (shapeB) GS_LAUNCH_ONESWEEP_K(B, G, KIN, KPT_B); else GS_LAUNCH_ONESWEEP_K(B, G, KIN, KPT_A); } while (0)
         if (p == 0 && gatherKeys) GS_LAUNCH_ONESWEEP(8, true, gatherKeys);
         else if (shapeC) GS_LAUNCH_ONESWEEP_K(8, false, ks, KPT_C);

@@ -472,40 +472,15 @@ __global__ __launch_bounds__(256) void invert_order_kernel(const uint32_t* __res
 
 int32_t vis_alloc(gs_renderer* r) {
     if (r->visKeys) return GS_OK;
-    uint32_t *k = nullptr, *v = nullptr, *x = nullptr, *y = nullptr, *po = nullptr; VisControl* c = nullptr;
-    hipError_t e = hipMalloc((void**)&k, ((size_t)r->n + 16) * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&v, ((size_t)r->n + 16) * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&x, ((size_t)r->n + 16) * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&y, ((size_t)r->n + 16) * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&po, ((size_t)r->n + 16) * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&c, 2 * sizeof(VisControl));
-    if (e == hipSuccess) e = hipMemsetAsync(c, 0, 2 * sizeof(VisControl), r->ctx->stream);
-    if (e != hipSuccess) {
-        if (k) (void)hipFree(k);
-        if (v) (void)hipFree(v);
-        if (x) (void)hipFree(x);
-        if (y) (void)hipFree(y);
-        if (po) (void)hipFree(po);
-        if (c) (void)hipFree(c);
-        return fail_hip(e, "allocate the visible-sort buffers", __FILE__, __LINE__);
-    }
-    r->visKeys = k; r->visIdx = v; r->visRectX = x; r->visRectY = y; r->visPairOffset = po; r->visControl = c; r->visControlIdx = 0;
+    DevBuf<uint32_t> k, v, x, y, po; DevBuf<VisControl> c;
+    for (DevBuf<uint32_t>* b : {&k, &v, &x, &y, &po}) GS_HIP(b->alloc(((size_t)r->n + 16) * 4));
+    GS_HIP(c.alloc(2 * sizeof(VisControl)));
+    GS_HIP(hipMemsetAsync(c, 0, 2 * sizeof(VisControl), r->ctx->stream));
+    r->visKeys = std::move(k); r->visIdx = std::move(v); r->visRectX = std::move(x); r->visRectY = std::move(y); r->visPairOffset = std::move(po);
+    r->visControl = std::move(c); r->visControlIdx = 0;
     static const int envLimit = [] { const char* s = getenv("GSPLAT_VIS_HISTORY"); const int v = s ? atoi(s) : 0; return (v >= 2 && v <= kVisHistory) ? v : 0; }();
     if (envLimit && r->visHistLimit == kVisHistory) r->visHistLimit = envLimit;
     return GS_OK;
-}
-
-void vis_free(gs_renderer* r) {
-    if (r->visKeys) (void)hipFree(r->visKeys);
-    if (r->visIdx) (void)hipFree(r->visIdx);
-    if (r->visRectX) (void)hipFree(r->visRectX);
-    if (r->visRectY) (void)hipFree(r->visRectY);
-    if (r->visPairOffset) (void)hipFree(r->visPairOffset);
-    if (r->visChunkStart) (void)hipFree(r->visChunkStart);
-    if (r->visControl) (void)hipFree(r->visControl);
-    if (r->visBaseRank) (void)hipFree(r->visBaseRank);
-    r->visKeys = r->visIdx = r->visRectX = r->visRectY = r->visPairOffset = r->visChunkStart = r->visBaseRank = nullptr; r->visControl = nullptr; r->visChunkCap = 0;
-    r->visRankValid = false;
 }
 
 // The sorts made since the base, as a list of DISTINCT rows, most recent first.  Sorting by a matrix that is already the head changes
@@ -556,7 +531,7 @@ int32_t enqueue_visible_sort(gs_renderer* r) {
     const uint32_t n = r->n;
     const uint32_t words = div_up(n, 64u);
     if (!r->visBaseIdentity && !r->visRankValid) {               // the base is a real order buffer: its inverse ends the tie chain
-        if (!r->visBaseRank) GS_HIP(hipMalloc((void**)&r->visBaseRank, ((size_t)n + 16) * 4));
+        if (!r->visBaseRank) GS_HIP(r->visBaseRank.alloc(((size_t)n + 16) * 4));
         GS_TRY(join_sort(r));
         hipLaunchKernelGGL(invert_order_kernel, dim3(max(1u, min(div_up(n, 256u), (uint32_t)ctx->cuCount * 8u))), dim3(256), 0, st, (const uint32_t*)r->order, r->visBaseRank, n);
         GS_HIP(hipGetLastError());
@@ -593,7 +568,7 @@ int32_t enqueue_visible_sort(gs_renderer* r) {
     prof_record(r, 1, st);
     if (sorted) {
         // the pass shape follows the visible count of the last draw that reported (the host only knows the bound N)
-        const uint32_t lastVisible = (r->hostReport && r->frameInFlight) ? *(volatile uint32_t*)&r->hostReport->visible : 0u;
+        const uint32_t lastVisible = (r->hostReport && r->frameInFlight) ? *(volatile uint32_t*)&r->hostReport.get()->visible : 0u;
         // the fix-up reads the sorted keys.  Not needed while ties are already in the base order: one matrix on the identity (a stable sort of
         // the index-ordered compaction), or ranks as keys (no ties at all)
         const bool needFix = byMatrix && (r->visHistDepth > 1 || !r->visBaseIdentity);
