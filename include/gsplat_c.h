@@ -307,8 +307,8 @@ int32_t gs_renderer_set_deleted_bits(gs_renderer* r, const uint32_t* words, size
  * the first delete, and read as zeros while it does not exist.  Every kernel tests the splats against the renderer's current
  * gs_renderer_set_cutouts list (IsSplatCut), as the reference's do.
  * Selection has NO VISUAL EFFECT: the reference's highlight of selected splats (RenderGaussianSplats.shader:63-73,87-101) is not built;
- * only deletion changes a frame.  Moving, rotating, scaling, exporting and copying splats (CSTranslateSelection .. CSCopySplats) are not
- * built either: they rewrite the asset's blobs, which are immutable and shared here.
+ * only deletion changes a frame.  Moving, rotating, scaling and copying splats (CSTranslateSelection .. CSCopySplats) are not
+ * built either: they rewrite the asset's blobs, which are immutable and shared here.  Exporting only reads them: see below.
  * Two literal quirks of the reference are kept: select-all / invert set the bits of the last word beyond N and the counts include them
  * (N = 33: select all reports 64 selected), and a splat whose pixel position is NaN is inside every rectangle.
  * The mutating calls are asynchronous on the context's stream like every other call; the info / download calls block.  Selection lives
@@ -334,6 +334,32 @@ int32_t gs_renderer_edit_upload_selected_bits(gs_renderer* r, const uint32_t* wo
 /* ceil(N/32) words each; any may be NULL; a buffer that does not exist reads as zeros; blocks */
 int32_t gs_renderer_edit_download_bits(gs_renderer* r, uint32_t* selected, uint32_t* selected_mouse_down, uint32_t* deleted, size_t word_count);
 int32_t gs_renderer_edit_release(gs_renderer* r);                   /* frees selected + mouse-down; deleted bits stay */
+
+/* ---- export: EditExportData (GaussianSplatRenderer.cs:936-958), CSExportData (SplatUtilities.compute:523-673) and the editor's
+ * ExportPlyFile (GaussianSplatRendererEditor.cs:394-445)  (additions to ABI 9) ----
+ * A record is the reference's ExportSplatData = InputSplatData = one PLY vertex: 62 floats -- pos, nor, f_dc, 45 f_rest (15 R, 15 G, 15 B),
+ * opacity (logit), scale (log), rot (w x y z) -- decoded from the asset in whatever formats it has.  log() is LogDet, the project's fixed
+ * member of HLSL's family, so the bytes are the same on every machine.  With bake_transform != 0 the record is
+ * moved into world space as the reference does: position by the matrix, rotation by `rotation` (x y z w) after the axis flips of a
+ * negative `scale`, scale by |scale|, SH rotated by the matrix' rotation.  The calls read the renderer's current deleted bits (none = all
+ * zero) and gs_renderer_set_cutouts list, run on the context's stream and BLOCK until the output is complete.  Output that goes to the
+ * host is produced in batches of whole 256-splat chunks through a fixed device buffer and two pinned buffers, never N x 248 bytes at once
+ * (GSPLAT_EXPORT_BATCH = splats per batch, read at every call). */
+#define GS_EXPORT_RECORD_BYTES 248
+typedef struct gs_export_params {
+    float matrix_object_to_world[16];   /* transform.localToWorldMatrix, row-major */
+    float rotation[4];                  /* transform.localRotation x y z w */
+    float scale[3];                     /* transform.localScale */
+    uint32_t bake_transform;            /* _ExportTransformFlags */
+} gs_export_params;
+/* EditExportData: all N records in index order, nor = 1 for cut splats (deleted ones are written like any other: the editor skips them).
+ * out: host memory (memory_kind 0) or device memory (1, 8-byte aligned: GS_ERR_INVALID_ARGUMENT otherwise) of at least N x 248 bytes. */
+int32_t gs_renderer_edit_export_data(gs_renderer* r, const gs_export_params* p, void* out, size_t bytes, int32_t memory_kind);
+/* the records of the alive splats only (not deleted, not cut), index order, nor = 0; *alive = their number; out (host memory,
+ * capacity_records records) may be NULL to get the count alone. */
+int32_t gs_renderer_edit_export_alive(gs_renderer* r, const gs_export_params* p, void* out, size_t capacity_records, uint32_t* alive);
+/* ExportPlyFile: the reference's header + the alive records.  On an error the partially written file is removed. */
+int32_t gs_renderer_edit_export_ply(gs_renderer* r, const gs_export_params* p, const char* path, uint32_t* alive);
 
 /* m_RenderMode + m_PointDisplaySize (GaussianSplatRenderer.cs:241-242; material choice :126-131).  DebugPoints / DebugPointIndices
  * (GaussianDebugRenderPoints.shader) draw every splat as an opaque screen-space square of `point_display_size` pixels, nearest

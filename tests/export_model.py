@@ -1,0 +1,233 @@
+"""The yardstick of the export (helper, not a test): a numpy restatement of CSExportData (SplatUtilities.compute:523-673), RotateSH
+(SphericalHarmonics.hlsl:24-210) and the editor's ExportPlyFile (GaussianSplatRendererEditor.cs:394-445), written from the reference's text, on
+top of a decoded [N, 59] array -- LoadSplatData of every splat as Oracle.decode_all() / ref_lib.Ref.decode_all() lay it out: pos 3, rot 4 (xyzw),
+scale 3, opacity, col 3, sh 15 x 3.
+
+Every operation is one float32 operation in the reference's order; the three places where HLSL leaves a family of results take the member the
+project fixes: log = creator.LogDet, the band matrices of the SH rotation by the recurrence gs_device_math.h documents (coefficients formed in float64 and
+rounded once, terms added left to right; this file is written from that description and the paper, not from the C++), length = sqrt((x x + y y) + z z).
+mul(_MatrixObjectToWorld, float4(pos, 1)) is the fmaf chain of calc_view's world position (creator.fma32 is an exact fmaf).
+With dtype = float64 the SH rotation runs in double precision: what tests/test_export_model.py holds to the defining property of a rotation."""
+from __future__ import annotations
+
+import numpy as np
+
+import edit_model as EM
+from unitygaussiansplatting_amd import creator
+from unitygaussiansplatting_amd.creator import LogDet, fma32
+
+f32 = np.float32
+def sh_rot_matrix(o2w, dtype=f32):
+    """CalcSHRotMatrix (SplatUtilities.compute:588-609): the rows of the 3x3 part, each divided by its length"""
+    m = np.asarray(o2w, dtype).reshape(4, 4)[:3, :3].astype(dtype)
+    out = np.zeros((3, 3), dtype)
+    for r in range(3):
+        x, y, z = m[r]
+        inv = dtype(1.0) / np.sqrt((x * x + y * y) + z * z)
+        out[r] = (x * inv, y * inv, z * inv)
+    return out
+
+
+def _band_terms(l: int, m: int, n: int):
+    """[(coefficient in float64, i, a)]: entry (m, n) of band l is the sum of coefficient * P_i(a, n), in this order.  The Ivanic-Ruedenberg
+    recurrence for real spherical harmonics (J. Phys. Chem. 100 (1996) 6342 and its errata), written from the paper's table of U, V, W and
+    their weights u, v, w; the Kronecker deltas of the table are the case distinctions below."""
+    d = np.float64((l + n) * (l - n) if abs(n) < l else 2 * l * (2 * l - 1))
+    am = abs(m)
+    u = np.sqrt(np.float64((l + m) * (l - m)) / d)
+    v = np.sqrt(np.float64((l + am - 1) * (l + am)) / d) * 0.5
+    w = -(np.sqrt(np.float64((l - am - 1) * (l - am)) / d) * 0.5)
+    r2 = np.sqrt(np.float64(2.0))
+    terms = [(u, 0, m)]
+    if m == 0:
+        terms += [(-(v * r2), 1, 1), (-(v * r2), -1, -1)]
+    elif m > 0:
+        terms += [(v * r2, 1, 0)] if m == 1 else [(v, 1, m - 1), (-v, -1, 1 - m)]
+        terms += [(w, 1, m + 1), (w, -1, -m - 1)]
+    else:
+        terms += [(v * r2, -1, 0)] if m == -1 else [(v, 1, m + 1), (v, -1, -m - 1)]
+        terms += [(w, 1, m - 1), (-w, -1, 1 - m)]
+    return terms
+
+
+def _next_band(r1: dict, prev: dict, l: int, dtype) -> dict:
+    """band l from band l - 1 (dicts keyed by (row, column) in -l .. l); every product and sum rounds once in `dtype`, left to right"""
+    def P(i, a, n):
+        if n == l:
+            return r1[i, 1] * prev[a, l - 1] - r1[i, -1] * prev[a, 1 - l]
+        if n == -l:
+            return r1[i, 1] * prev[a, 1 - l] + r1[i, -1] * prev[a, l - 1]
+        return r1[i, 0] * prev[a, n]
+
+    out = {}
+    for m in range(-l, l + 1):
+        for n in range(-l, l + 1):
+            acc = None
+            for c64, i, a in _band_terms(l, m, n):
+                c = dtype(c64)                                     # the coefficient: formed in float64, rounded once
+                if c == 0:
+                    continue                                       # (the only terms that would step outside band l - 1)
+                t = c * P(i, a, n)
+                acc = t if acc is None else acc + t
+            out[m, n] = dtype(0.0) if acc is None else acc
+            assert type(out[m, n]) is dtype
+    return out
+
+
+def sh_bands(o2w, dtype=f32):
+    """(sh1 [3,3], sh2 [5,5], sh3 [7,7]) of the dispatch's matrix: band 1 = the normalised matrix in the order y, z, x with the signs of
+    ShadeSH's basis (-y, z, -x) (SphericalHarmonics.hlsl:76-83), bands 2 and 3 by the recurrence"""
+    m = sh_rot_matrix(o2w, dtype)
+    axis, sign = (1, 2, 0), (1, -1, 1)
+    r1 = {(i - 1, j - 1): dtype(sign[i] * sign[j]) * m[axis[i], axis[j]] for i in range(3) for j in range(3)}
+    with np.errstate(all="ignore"):
+        r2 = _next_band(r1, r1, 2, dtype)
+        r3 = _next_band(r1, r2, 3, dtype)
+    as_array = lambda d, l: np.array([[d[a, b] for b in range(-l, l + 1)] for a in range(-l, l + 1)], dtype)
+    return as_array(r1, 1), as_array(r2, 2), as_array(r3, 3)
+
+
+def rotate_sh(sh, bands, dtype=f32):
+    """RotateSH on [N, 15, 3] coefficients (band 0, the colour, passes through): Dot3 / Dot5 / Dot7 (:11-22), sums left to right"""
+    sh = np.asarray(sh, dtype)
+    out = np.empty_like(sh)
+    with np.errstate(all="ignore"):
+        for first, mat in zip((0, 3, 8), bands):
+            n = len(mat)
+            for k in range(n):
+                acc = (sh[:, first, :] * mat[k][0]).astype(dtype)
+                for j in range(1, n):
+                    acc = (acc + (sh[:, first + j, :] * mat[k][j]).astype(dtype)).astype(dtype)
+                out[:, first + k, :] = acc
+    return out
+
+
+def quat_mul(a, b):
+    """QuatMul (GaussianSplatting.hlsl:19-22), xyzw, a: one quaternion, b: [N, 4]"""
+    ax, ay, az, aw = (f32(v) for v in a)
+    bx, by, bz, bw = (b[:, k].astype(f32) for k in range(4))
+    x = (aw * bx + (ax * bw + ay * bz)) - az * by
+    y = (aw * by + (ay * bw + az * bx)) - ax * bz
+    z = (aw * bz + (az * bw + ax * by)) - ay * bx
+    w = (aw * bw + -(ax * bx + ay * by)) - az * bz
+    return np.stack([x, y, z, w], axis=1).astype(f32)
+
+
+def mul_point(o2w, pos):
+    """rows 0..2 of mul(M, float4(pos, 1)) as calc_view forms them: fmaf(m2, z, fmaf(m1, y, fmaf(m0, x, m3)))"""
+    m = np.asarray(o2w, f32).reshape(4, 4)
+    x, y, z = pos[:, 0], pos[:, 1], pos[:, 2]
+    return np.stack([fma32(m[r, 2], z, fma32(m[r, 1], y, fma32(m[r, 0], x, m[r, 3]))) for r in range(3)], axis=1)
+
+
+def export_records(dec, cut, transform=None):
+    """CSExportData over a decoded [N, 59] array: [N, 62] float32.  cut: bool per splat (IsSplatCut of the OBJECT-space position).
+    transform: None (_ExportTransformFlags = 0) or (matrix_object_to_world 4x4, rotation xyzw, scale xyz)."""
+    dec = np.ascontiguousarray(dec, f32)
+    n = len(dec)
+    pos, rot, scale, opacity, col = dec[:, 0:3], dec[:, 3:7].copy(), dec[:, 7:10], dec[:, 10], dec[:, 11:14]
+    sh = dec[:, 14:59].reshape(n, 15, 3)
+    with np.errstate(all="ignore"):
+        if transform is not None:
+            o2w, q, s = transform
+            s = np.asarray(s, f32)
+            pos = mul_point(o2w, pos)
+            if s[0] < 0:
+                rot[:, [1, 2]] = -rot[:, [1, 2]]
+            if s[1] < 0:
+                rot[:, [0, 2]] = -rot[:, [0, 2]]
+            if s[2] < 0:
+                rot[:, [0, 1]] = -rot[:, [0, 1]]
+            rot = quat_mul(np.asarray(q, f32), rot)
+            scale = (scale * np.abs(s)).astype(f32)
+            sh = rotate_sh(sh, sh_bands(o2w, f32), f32)
+        out = np.zeros((n, 62), f32)
+        out[:, 0:3] = pos
+        out[:, 3:6] = np.where(np.asarray(cut, bool), f32(1.0), f32(0.0))[:, None]
+        out[:, 6:9] = (col - f32(0.5)) / f32(0.2820948)                       # ColorToSH0
+        out[:, 9:54] = sh.transpose(0, 2, 1).reshape(n, 45)                   # 15 R, 15 G, 15 B
+        out[:, 54] = LogDet((opacity / np.maximum(f32(1.0) - opacity, f32(1.0e-6))).astype(f32))      # InvSigmoid
+        out[:, 55:58] = LogDet(scale)
+        out[:, 58] = rot[:, 3]
+        out[:, 59:62] = rot[:, 0:3]                                           # rot.wxyz
+    return out
+
+
+def transform_of(tr):
+    """(matrix, rotation, scale) of a camera.Transform as GaussianSplatRenderer.ExportParams hands them over"""
+    return np.asarray(tr.localToWorldMatrix, f32), np.asarray(tr.rotation, f32), np.asarray(tr.scale, f32)
+
+
+class ExportModel:
+    """The export of one asset under an edit state: EM.EditModel supplies the cut flags and the deleted words"""
+
+    def __init__(self, asset, decoded=None):
+        self.edit = EM.EditModel(asset)
+        self.n = self.edit.n
+        self.dec = self.edit.orc.decode_all() if decoded is None else np.ascontiguousarray(decoded, f32)
+
+    def deleted(self) -> np.ndarray:
+        return EM.unpack_bits(self.edit.bits()[2], self.n)        # the bits beyond N do not exist for the export
+
+    def alive(self) -> np.ndarray:
+        return ~self.deleted() & ~self.edit.cut
+
+    def export_data(self, tr=None, bake=False) -> np.ndarray:
+        return export_records(self.dec, self.edit.cut, transform_of(tr) if bake else None)
+
+    def export_alive(self, tr=None, bake=False) -> np.ndarray:
+        rows = self.export_data(tr, bake)[self.alive()]
+        assert not rows[:, 3:6].any()
+        return rows
+
+    def splats(self, tr=None, bake=False) -> creator.InputSplatData:
+        """the alive records as the columns creator.WritePLY takes"""
+        return columns(self.export_alive(tr, bake))
+
+
+def columns(rows) -> creator.InputSplatData:
+    rows = np.ascontiguousarray(rows, f32)
+    n = len(rows)
+    return creator.InputSplatData(pos=rows[:, 0:3].copy(), dc0=rows[:, 6:9].copy(), sh=rows[:, 9:54].reshape(n, 3, 15).transpose(0, 2, 1).copy(),
+                                  opacity=rows[:, 54].copy(), scale=rows[:, 55:58].copy(), rot=rows[:, 58:62].copy())
+
+
+# ---- shared cases of the CPU premises and the GPU tests ---------------------------------------------------------------------------------
+PATTERNS = ("nothing deleted", "everything deleted", "everything cut", "half deleted under cutouts", "one chunk deleted", "only the last alive")
+
+
+def pattern(name: str, n: int):
+    """(deleted words or None, cutout list or None) of a pattern for n splats"""
+    from unitygaussiansplatting_amd import camera
+    from unitygaussiansplatting_amd.cutout import GaussianCutout, Type
+    nw = (n + 31) // 32
+    if name == "nothing deleted":
+        return None, None                                          # and no deleted buffer
+    if name == "everything deleted":
+        return EM.pack_bits(np.ones(n, bool), nw), None
+    if name == "everything cut":                                   # every splat is outside a far, tiny ellipsoid that is not inverted
+        return None, [GaussianCutout(Type.Ellipsoid, False, camera.Transform(position=(100.0, 100.0, 100.0), scale=(0.01, 0.01, 0.01)))]
+    if name == "half deleted under cutouts":                       # an ellipsoid plus an inverted box (EM.cutout_lists: the box comes first)
+        return EM.pack_bits(np.random.default_rng(77).random(n) < 0.5, nw), EM.cutout_lists()["ellipsoid+inverted box"]
+    if name == "one chunk deleted":                                # exactly the second whole chunk (the first if there is only one)
+        first = 256 if n >= 512 else 0
+        flags = np.zeros(n, bool)
+        flags[first:first + 256] = True
+        return EM.pack_bits(flags, nw), None
+    if name == "only the last alive":
+        flags = np.ones(n, bool)
+        flags[n - 1] = False
+        return EM.pack_bits(flags, nw), None
+    raise KeyError(name)
+
+
+def apply_pattern(model: "ExportModel", name: str, renderer_matrix) -> None:
+    words, cuts = pattern(name, model.n)
+    model.edit.set_deleted_bits(words)
+    model.edit.set_cutouts(cuts, renderer_matrix)
+
+
+# alive splats the patterns leave in small_asset(20000, 5, quality): pinned by tests/test_export_model.py
+ALIVE_20000 = {"nothing deleted": 20000, "everything deleted": 0, "everything cut": 0, "one chunk deleted": 19744, "only the last alive": 1}
+ALIVE_HALF_20000 = {"VeryLow": 2327, "Low": 2327, "Medium": 2327, "High": 2328, "VeryHigh": 2328}      # "half deleted under cutouts" (10,088 deleted, 15,183 cut)
+BAKE_TRANSFORM = dict(position=(0.3, -0.2, 0.5), rotation=(0.18257419, 0.36514837, 0.54772256, 0.73029674), scale=(-1.25, 0.75, 1.5))

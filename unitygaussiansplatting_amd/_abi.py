@@ -53,6 +53,14 @@ class gs_edit_info(C.Structure):         # m_GpuEditCountsBounds decoded (gs_ren
                 ("bounds_min", C.c_float * 3), ("bounds_max", C.c_float * 3)]
 
 
+GS_EXPORT_RECORD_BYTES = 248
+
+
+class gs_export_params(C.Structure):     # what CSExportData reads of its dispatch (gs_renderer_edit_export_*)
+    _fields_ = [("matrix_object_to_world", C.c_float * 16), ("rotation", C.c_float * 4), ("scale", C.c_float * 3),
+                ("bake_transform", C.c_uint32)]
+
+
 class gs_import_input(C.Structure):
     _fields_ = [("splat_count", C.c_uint32), ("pos", C.c_void_p), ("dc0", C.c_void_p), ("sh", C.c_void_p),
                 ("opacity", C.c_void_p), ("scale", C.c_void_p), ("rot", C.c_void_p)]

@@ -148,6 +148,72 @@ def ExpDet(x):
     return (p * scale).astype(f32)
 
 
+def fma32(a, b, c):
+    """fmaf(a, b, c) on float32 arrays, exactly: the product of two fp32 values is exact in fp64; its sum with c is rounded TO ODD in fp64
+    (TwoSum gives the rounding error; an inexact sum takes the neighbour with an odd last bit), after which the rounding to fp32 is the
+    rounding of the exact value (53 >= 2 * 24 + 2 bits).  Non-finite values pass through ordinary fp64 arithmetic."""
+    p = np.asarray(a, f32).astype(np.float64) * np.asarray(b, f32).astype(np.float64)
+    c = np.asarray(c, f32).astype(np.float64)
+    with np.errstate(all="ignore"):
+        s = p + c
+        bb = s - p
+        err = (p - (s - bb)) + (c - bb)
+        fix = np.isfinite(s) & (err != 0.0) & ((s.view(np.int64) & 1) == 0)
+        towards = np.where(err > 0.0, np.inf, -np.inf)
+        s = np.where(fix, np.nextafter(s, towards), s)
+        return s.astype(f32)
+
+
+LOGDET_REL = 1.1 * 2.0 ** -24        # LogDet's error bound: |LogDet(x) - ln x| <= LOGDET_REL |ln x| + LOGDET_ABS
+LOGDET_ABS = 1.2e-7
+
+
+def LogDet(x):
+    """ln(x) from fp32 operations only, one rounding each: the twin of ExpDet, and bit for bit gsm::LogDetFull (csrc/gs_device_math.h) on
+    the GPU and in the host build.  HLSL's log -- what CSExportData calls -- is a family of results; this is the member the project fixes.
+    Special inputs give the IEEE results: -inf for +-0, NaN for a negative or NaN input, +inf for +inf.  A denormal input is scaled by 2^23
+    (exact) first.
+
+    Construction: x = 2^e m with m in (0.7071.., 1.41421356]; t = (m - 1) / (m + 1), |t| <= 0.171573; ln m = 2 atanh t = 2 t (1 + t^2/3 +
+    t^4/5 + t^6/7 + ...), truncated after t^6/7 and evaluated by Horner in t^2 with fmaf; result = fmaf(e, C, 2 t p), C = fl32(ln 2).
+
+    Error bound, against the exact logarithm of the fp32 argument, with u = 2^-24:
+      truncation   2 |t| t^8 / (9 (1 - t^2)) <= 2.95e-8
+      rounding     m - 1 is exact (Sterbenz); m + 1 and the division round once each, so t carries <= 2 u relative, t^2 <= 5 u; p lies in
+                   [1, 1.01) and carries <= 1.1 u (its last fmaf's u plus the <= 0.07 u the inner terms pass on); (2 t) p then <= 4.1 u
+                   relative of |ln m| <= 0.34658: <= 8.5e-8
+      constant     |C - ln 2| = 1.905e-9 times |e| <= (|ln x| / ln 2 + 0.5): <= 2.75e-9 |ln x| + 1e-9  (0.05 u |ln x|)
+      last fmaf    one rounding of the result: <= u |ln x| (1 + o(1))
+    Sum: |LogDet(x) - ln x| <= 1.1 * 2^-24 |ln x| + 1.2e-7  (LOGDET_REL, LOGDET_ABS), for every positive finite x, denormals included."""
+    x = np.asarray(x, f32)
+    shape = x.shape
+    x = np.ascontiguousarray(x).reshape(-1)
+    u = x.view(np.uint32).copy()
+    out = np.empty(len(u), f32)
+    neg_or_nan = u > np.uint32(0x7f800000)
+    zero = (u << np.uint32(1)) == 0
+    pinf = u == np.uint32(0x7f800000)
+    with np.errstate(all="ignore"):
+        den = (u < np.uint32(0x00800000)) & ~zero
+        xs = np.where(den, x * f32(8388608.0), x).astype(f32)
+        us = xs.view(np.uint32)
+        e = (np.where(den, f32(-150.0), f32(-127.0)) + (us >> np.uint32(23)).astype(np.int32).astype(f32)).astype(f32)
+        m = ((us & np.uint32(0x7fffff)) | np.uint32(0x3f800000)).view(f32)
+        big = m > f32(1.41421356)
+        m = np.where(big, m * f32(0.5), m).astype(f32)
+        e = np.where(big, e + f32(1.0), e).astype(f32)
+        t = ((m - f32(1.0)) / (m + f32(1.0))).astype(f32)
+        t2 = (t * t).astype(f32)
+        p = fma32(t2, f32(1.0) / f32(7.0), f32(0.2))
+        p = fma32(t2, p, f32(1.0) / f32(3.0))
+        p = fma32(t2, p, f32(1.0))
+        out[:] = fma32(e, f32(0.69314718), ((f32(2.0) * t) * p).astype(f32))
+    out[neg_or_nan] = np.array([0x7fc00000], np.uint32).view(f32)[0]
+    out[zero] = -np.inf
+    out[pinf] = np.inf
+    return out.reshape(shape)
+
+
 def Sigmoid(v):                      # GaussianUtils.cs:9-12
     v = np.asarray(v, f32)
     return (f32(1) / (f32(1) + ExpDet(-v))).astype(f32)

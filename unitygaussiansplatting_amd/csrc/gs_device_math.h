@@ -996,9 +996,8 @@ GS_HD float DecideAlpha(float alphaNative, float y, float a, bool& live) {
 
 // ln(x) for a positive normal x from fp32 operations only (bit manipulation, one division, explicit fmaf): the same bits
 // on the host and on the device, unlike logf().  |error| < 1e-6 (atanh series of the mantissa reduced to [0.707, 1.414)).
-GS_HD float LogDet(float x) {
-    const uint32_t u = f2u(x);
-    float e = (float)((int)(u >> 23) - 127);
+GS_HD float LogDetCore(uint32_t u, int ebias) {                 // u: the bits of a positive normal float; ebias: -127 (or -150 for a denormal scaled by 2^23)
+    float e = (float)((int)(u >> 23) + ebias);
     float m = u2f((u & 0x7fffffu) | 0x3f800000u);
     if (m > 1.41421356f) { m *= 0.5f; e += 1.0f; }
     const float t = (m - 1.0f) / (m + 1.0f);
@@ -1006,6 +1005,7 @@ GS_HD float LogDet(float x) {
     const float p = fmaf(t2, fmaf(t2, fmaf(t2, 1.0f / 7.0f, 0.2f), 1.0f / 3.0f), 1.0f);
     return fmaf(e, 0.69314718f, (2.0f * t) * p);
 }
+GS_HD float LogDet(float x) { return LogDetCore(f2u(x), -127); }
 
 // Can the splat put a live fragment on a pixel centre of the square block of pixel centres [bc - half, bc + half]^2 ?
 // A fragment is live iff |q1| <= 2, |q2| <= 2 and exp(-(q1^2+q2^2)) a >= 1/255, q_k = u_k . (p - c)  (frag, :79-106).
@@ -1066,6 +1066,181 @@ GS_HD bool PrepareSplat(const ViewData& v, float W, float H, float nearClip, flo
     if (x0 > x1 || y0 > y1) return true;         // drawn by the reference, but every fragment is below 1/255
     fp.x0 = x0; fp.x1 = x1; fp.y0 = y0; fp.y1 = y1;
     return true;
+}
+
+// ---- export: CSExportData (SplatUtilities.compute:523-673; kernels in gs_export.hip) ---------------------------------------------
+// LogDet over every float: the IEEE results for the special inputs (-inf for +-0, NaN for a negative or NaN input, +inf for +inf), a
+// denormal input scaled by 2^23 first (exact), LogDet's construction otherwise -- so a positive normal x gives LogDet(x)'s bits.  HLSL's
+// log is a family of results (an approximation per vendor); this is the member the project fixes: fp32 operations only, one rounding each,
+// so the GPU, the host build and the numpy twin (creator.LogDet, which states and derives the error bound) agree bit for bit.
+GS_HD float LogDetFull(float x) {
+    const uint32_t u = f2u(x);
+    if (u >= 0x7f800000u) {                                        // +inf, NaN, or the sign bit set
+        if ((u << 1) == 0u) return u2f(0xff800000u);               // -0
+        if (u == 0x7f800000u) return x;
+        return u2f(0x7fc00000u);
+    }
+    if (u == 0u) return u2f(0xff800000u);
+    if (u < 0x00800000u) return LogDetCore(f2u(x * 8388608.0f), -150);
+    return LogDetCore(u, -127);
+}
+
+// LoadSplatData (GaussianSplatting.hlsl:428-608), every field: the one consumer of the full decode is the export
+struct SplatFull { V3 pos; V4 rot; V3 scale; float opacity; V3 col; V3 sh[15]; };
+GS_HD void LoadSplatDataFull(const AssetView& a, uint32_t idx, uint32_t ci, const V3& pos, SplatFull& s) {
+    s.pos = pos;                                                   // LoadSplatPosChunk(a, idx, ci), loaded by the caller for its cut test
+    uint32_t otherStride = 4 + vecStride(a.scaleFmt);
+    if (a.shFmt > 3) otherStride += 2;
+    const uint64_t otherAddr = (uint64_t)idx * otherStride;
+    s.rot = DecodeRotation(LoadUInt(a.other, otherAddr));
+    s.scale = LoadVec(a.other, otherAddr + 4, a.scaleFmt);
+    V4 col = LoadColorTexel(a, idx);
+    uint32_t shIndex = idx;
+    if (a.shFmt > 3) shIndex = LoadUShort(a.other, otherAddr + otherStride - 2);      // Cluster*: the palette index first, the gather second
+    const uint8_t* sp = a.sh + (uint64_t)shIndex * shStrideOf(a.shFmt);
+#pragma unroll
+    for (int k = 0; k < 15; ++k) s.sh[k] = LoadSH(sp, a.shFmt, k + 1);
+    if (ci < a.chunkCount) {
+        const ChunkRaw ck = LoadChunk(a.chunk, ci);
+        s.scale.x = lerpf(f16tof32(ck.w[10]), f16tof32(ck.w[10] >> 16), s.scale.x);
+        s.scale.y = lerpf(f16tof32(ck.w[11]), f16tof32(ck.w[11] >> 16), s.scale.y);
+        s.scale.z = lerpf(f16tof32(ck.w[12]), f16tof32(ck.w[12] >> 16), s.scale.z);
+        s.scale.x *= s.scale.x; s.scale.y *= s.scale.y; s.scale.z *= s.scale.z;
+        s.scale.x *= s.scale.x; s.scale.y *= s.scale.y; s.scale.z *= s.scale.z;
+        s.scale.x *= s.scale.x; s.scale.y *= s.scale.y; s.scale.z *= s.scale.z;
+        col.x = lerpf(f16tof32(ck.w[0]), f16tof32(ck.w[0] >> 16), col.x);
+        col.y = lerpf(f16tof32(ck.w[1]), f16tof32(ck.w[1] >> 16), col.y);
+        col.z = lerpf(f16tof32(ck.w[2]), f16tof32(ck.w[2] >> 16), col.z);
+        col.w = lerpf(f16tof32(ck.w[3]), f16tof32(ck.w[3] >> 16), col.w);
+        col.w = InvSquareCentered01(col.w);
+        if (a.shFmt > 0 && a.shFmt <= 3) {
+            const V3 lo = { f16tof32(ck.w[13]), f16tof32(ck.w[14]), f16tof32(ck.w[15]) };
+            const V3 hi = { f16tof32(ck.w[13] >> 16), f16tof32(ck.w[14] >> 16), f16tof32(ck.w[15] >> 16) };
+#pragma unroll
+            for (int k = 0; k < 15; ++k) s.sh[k] = { lerpf(lo.x, hi.x, s.sh[k].x), lerpf(lo.y, hi.y, s.sh[k].y), lerpf(lo.z, hi.z, s.sh[k].z) };
+        }
+    }
+    s.opacity = col.w;
+    s.col = { col.x, col.y, col.z };
+}
+
+// The band matrices of RotateSH (SphericalHarmonics.hlsl:24-210) for the matrix of CalcSHRotMatrix (SplatUtilities.compute:588-609).  The
+// reference rebuilds them in every thread; they depend on the dispatch's matrix only, so the host builds them once per call with this
+// function and the kernel receives the 83 floats by value.
+// Formulation (the project's own; the reference unrolls the same recurrence into 74 closed expressions): the Ivanic-Ruedenberg recurrence
+// for real spherical harmonics (J. Phys. Chem. 100 (1996) 6342, with the 1998 errata).  With R the band-1 matrix (rows / columns m, n = -1, 0, 1)
+// and M the matrix of band l - 1, entry (m, n) of band l, m, n = -l .. l, is a sum of at most five terms c * P_i(a, n):
+//     P_i(a, n) = R(i, 0) M(a, n)                                  for |n| < l
+//               = R(i, 1) M(a, l - 1) - R(i, -1) M(a, -l + 1)      for n = l
+//               = R(i, 1) M(a, -l + 1) + R(i, -1) M(a, l - 1)      for n = -l
+//     d = (l + n)(l - n) for |n| < l, else 2l (2l - 1);  u = sqrt((l + m)(l - m) / d);  v = sqrt((l + |m| - 1)(l + |m|) / d) / 2;
+//     w = -sqrt((l - |m| - 1)(l - |m|) / d) / 2
+//     m = 0:  u P_0(0), -v sqrt2 P_1(1), -v sqrt2 P_-1(-1)
+//     m > 0:  u P_0(m), v sqrt(1 + [m = 1]) P_1(m - 1), -v [m != 1] P_-1(-m + 1), w P_1(m + 1), w P_-1(-m - 1)
+//     m < 0:  u P_0(m), v [m != -1] P_1(m + 1), v sqrt(1 + [m = -1]) P_-1(-m - 1), w P_1(m - 1), -w P_-1(-m + 1)
+// Operation order (what makes the bits a function of this text): every coefficient c is formed in fp64 -- the ratio, its square root, the
+// factor 1/2, the factor sqrt2 where it applies, the sign -- and rounded to fp32 once; a term whose fp32 coefficient is zero is skipped;
+// P_i is one fp32 product, or two products and their sum / difference; the terms are c * P, added left to right in the order listed.
+// The band-1 matrix carries the signs of ShadeSH's basis (-y, z, -x), as the reference's does (SphericalHarmonics.hlsl:76-83); length() is
+// sqrt((x x + y y) + z z).  Choices of one member of a family, as with LogDet.
+struct SHRot { float sh1[3][3]; float sh2[5][5]; float sh3[7][7]; };
+GS_HD float SHRotP(const float (*r1)[3], const float* prev, int l, int i, int a, int n) {
+    const int w = 2 * l - 1, c = l - 1;                             // prev: (2l - 1) x (2l - 1), index = value + l - 1
+    const float* row = prev + (a + c) * w;
+    if (n == l) return r1[i + 1][2] * row[2 * c] - r1[i + 1][0] * row[0];
+    if (n == -l) return r1[i + 1][2] * row[0] + r1[i + 1][0] * row[2 * c];
+    return r1[i + 1][1] * row[n + c];
+}
+struct SHRotSum {                                                  // the running sum of one entry
+    const float (*r1)[3]; const float* prev; int l, n; float acc; bool any;
+    GS_HD void add(double c64, int i, int a) {
+        const float c = (float)c64;
+        if (c == 0.0f) return;                                     // (also what keeps P_i(a, n) inside band l - 1: |a| = l only ever meets c = 0)
+        const float t = c * SHRotP(r1, prev, l, i, a, n);
+        acc = any ? acc + t : t;
+        any = true;
+    }
+};
+GS_HD void SHRotBand(const float (*r1)[3], const float* prev, int l, float* out) {
+    const double sqrt2 = sqrt(2.0);
+    for (int m = -l; m <= l; ++m)
+        for (int n = -l; n <= l; ++n) {
+            const int am = m < 0 ? -m : m, an = n < 0 ? -n : n;
+            const double d = an < l ? (double)((l + n) * (l - n)) : (double)(2 * l * (2 * l - 1));
+            const double u = sqrt((double)((l + m) * (l - m)) / d);
+            const double v = sqrt((double)((l + am - 1) * (l + am)) / d) * 0.5;
+            const double w = -(sqrt((double)((l - am - 1) * (l - am)) / d) * 0.5);
+            SHRotSum s = { r1, prev, l, n, 0.0f, false };
+            s.add(u, 0, m);
+            if (m == 0) { s.add(-(v * sqrt2), 1, 1); s.add(-(v * sqrt2), -1, -1); }
+            else if (m > 0) { s.add(m == 1 ? v * sqrt2 : v, 1, m - 1); if (m != 1) s.add(-v, -1, -m + 1); s.add(w, 1, m + 1); s.add(w, -1, -m - 1); }
+            else { if (m != -1) s.add(v, 1, m + 1); s.add(m == -1 ? v * sqrt2 : v, -1, -m - 1); s.add(w, 1, m - 1); s.add(-w, -1, -m + 1); }
+            out[(m + l) * (2 * l + 1) + (n + l)] = s.any ? s.acc : 0.0f;
+        }
+}
+GS_HD void CalcSHRot(const float* o2w, SHRot& R) {                 // o2w: _MatrixObjectToWorld, rows of 4
+    float m[3][3];
+    for (int r = 0; r < 3; ++r) {
+        const float x = o2w[r * 4], y = o2w[r * 4 + 1], z = o2w[r * 4 + 2];
+        const float inv = 1.0f / sqrtf((x * x + y * y) + z * z);
+        m[r][0] = x * inv; m[r][1] = y * inv; m[r][2] = z * inv;
+    }
+    // band 1: rows / columns in the order y, z, x of the real harmonics, with the basis' signs
+    R.sh1[0][0] = m[1][1]; R.sh1[0][1] = -m[1][2]; R.sh1[0][2] = m[1][0];
+    R.sh1[1][0] = -m[2][1]; R.sh1[1][1] = m[2][2]; R.sh1[1][2] = -m[2][0];
+    R.sh1[2][0] = m[0][1]; R.sh1[2][1] = -m[0][2]; R.sh1[2][2] = m[0][0];
+    SHRotBand(R.sh1, &R.sh1[0][0], 2, &R.sh2[0][0]);
+    SHRotBand(R.sh1, &R.sh2[0][0], 3, &R.sh3[0][0]);
+}
+
+// what CSExportData reads of its dispatch: _ExportTransformFlags, _MatrixObjectToWorld (rows 0..2), _ExportTransformRotation (xyzw),
+// _ExportTransformScale, and the band matrices of the matrix
+struct ExportXform { uint32_t bake; float o2w[12]; float rot[4]; float scale[3]; SHRot sh; };
+
+// Dot3 / Dot5 / Dot7 of RotateSH (SphericalHarmonics.hlsl:11-22) for one output coefficient: products and sums one by one, left to right
+GS_HD V3 SHDotRow(const V3* v, const float* f, int n) {
+    V3 r = { v[0].x * f[0], v[0].y * f[0], v[0].z * f[0] };
+    for (int k = 1; k < n; ++k) { r.x = r.x + v[k].x * f[k]; r.y = r.y + v[k].y * f[k]; r.z = r.z + v[k].z * f[k]; }
+    return r;
+}
+
+// The body of CSExportData (SplatUtilities.compute:616-673) for one splat: rec = the 62 floats of ExportSplatData = InputSplatData
+// (pos, nor, dc0, 15 R + 15 G + 15 B SH coefficients, opacity, scale, rot wxyz).  pos = LoadSplatPosChunk(a, idx, ci) and cut = IsSplatCut(pos)
+// come from the caller, which needs them before it decides whether the splat is exported at all.
+GS_HD void ExportSplat(const AssetView& a, const ExportXform& X, uint32_t idx, uint32_t ci, const V3& pos, bool cut, float* rec) {
+    SplatFull s;
+    LoadSplatDataFull(a, idx, ci, pos, s);
+    if (X.bake != 0u) {
+        s.pos = { mrow(X.o2w, 0, pos.x, pos.y, pos.z), mrow(X.o2w, 1, pos.x, pos.y, pos.z), mrow(X.o2w, 2, pos.x, pos.y, pos.z) };
+        // (this only handles axis flips from scale, not any arbitrary scaling: the reference's note)
+        if (X.scale[0] < 0.0f) { s.rot.y = -s.rot.y; s.rot.z = -s.rot.z; }
+        if (X.scale[1] < 0.0f) { s.rot.x = -s.rot.x; s.rot.z = -s.rot.z; }
+        if (X.scale[2] < 0.0f) { s.rot.x = -s.rot.x; s.rot.y = -s.rot.y; }
+        const V4 qa = { X.rot[0], X.rot[1], X.rot[2], X.rot[3] }, qb = s.rot;          // QuatMul(a, b), GaussianSplatting.hlsl:19-22
+        s.rot.x = (qa.w * qb.x + (qa.x * qb.w + qa.y * qb.z)) - qa.z * qb.y;
+        s.rot.y = (qa.w * qb.y + (qa.y * qb.w + qa.z * qb.x)) - qa.x * qb.z;
+        s.rot.z = (qa.w * qb.z + (qa.z * qb.w + qa.x * qb.y)) - qa.y * qb.x;
+        s.rot.w = (qa.w * qb.w + -(qa.x * qb.x + qa.y * qb.y)) - qa.z * qb.z;
+        s.scale.x *= fabsf(X.scale[0]); s.scale.y *= fabsf(X.scale[1]); s.scale.z *= fabsf(X.scale[2]);
+        V3 out[15];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) out[k] = SHDotRow(s.sh, X.sh.sh1[k], 3);
+#pragma unroll
+        for (int k = 0; k < 5; ++k) out[3 + k] = SHDotRow(s.sh + 3, X.sh.sh2[k], 5);
+#pragma unroll
+        for (int k = 0; k < 7; ++k) out[8 + k] = SHDotRow(s.sh + 8, X.sh.sh3[k], 7);
+#pragma unroll
+        for (int k = 0; k < 15; ++k) s.sh[k] = out[k];
+    }
+    const float nor = cut ? 1.0f : 0.0f;                           // mark as skipped for export
+    rec[0] = s.pos.x; rec[1] = s.pos.y; rec[2] = s.pos.z;
+    rec[3] = nor; rec[4] = nor; rec[5] = nor;
+    rec[6] = (s.col.x - 0.5f) / 0.2820948f; rec[7] = (s.col.y - 0.5f) / 0.2820948f; rec[8] = (s.col.z - 0.5f) / 0.2820948f;      // ColorToSH0
+#pragma unroll
+    for (int k = 0; k < 15; ++k) { rec[9 + k] = s.sh[k].x; rec[24 + k] = s.sh[k].y; rec[39 + k] = s.sh[k].z; }
+    rec[54] = LogDetFull(s.opacity / fmaxf(1.0f - s.opacity, 1.0e-6f));                 // InvSigmoid
+    rec[55] = LogDetFull(s.scale.x); rec[56] = LogDetFull(s.scale.y); rec[57] = LogDetFull(s.scale.z);
+    rec[58] = s.rot.w; rec[59] = s.rot.x; rec[60] = s.rot.y; rec[61] = s.rot.z;
 }
 
 } // namespace gsm

@@ -7,8 +7,8 @@
 //   CSInvertSelection / CSSelectAll    :336-377                         every bit, cut splats cleared
 //   CSOrBuffers                        :380-389                         deleted |= selected
 //   CSSelectionUpdate                  :391-423                         rectangle selection through a camera, add or subtract
-// Not built: CSTranslateSelection .. CSCopySplats (they rewrite the pos / other blobs, which this library shares between contexts, lanes
-// and replicas) and the highlight of selected splats in the fragment stage (RenderGaussianSplats.shader:63-73,87-101: it replaces a splat's
+// Not built: CSTranslateSelection .. CSScaleSelection and CSCopySplats (they rewrite the pos / other blobs, which this library shares between contexts,
+// lanes and replicas; CSExportData only reads them: gs_export.hip) and the highlight of selected splats in the fragment stage (RenderGaussianSplats.shader:63-73,87-101: it replaces a splat's
 // opacity by -1, which here would go through PrepareSplat's cull and footprint bound and the blend's alpha window).  Selection therefore
 // has NO VISUAL EFFECT: only deletion changes a frame, through the deleted bits calc_view already reads.
 //

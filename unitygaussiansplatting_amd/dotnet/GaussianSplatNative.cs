@@ -101,6 +101,13 @@ namespace GaussianSplatting.Runtime
         [DllImport(Lib)] public static extern int gs_renderer_edit_upload_selected_bits(IntPtr renderer, uint[] words, UIntPtr wordCount);
         [DllImport(Lib)] public static extern int gs_renderer_edit_download_bits(IntPtr renderer, uint[] selected, uint[] selectedMouseDown, uint[] deleted, UIntPtr wordCount);
         [DllImport(Lib)] public static extern int gs_renderer_edit_release(IntPtr renderer);
+        // export (EditExportData, GaussianSplatRenderer.cs:936-958; ExportPlyFile, GaussianSplatRendererEditor.cs:394-445): records of 62 floats = InputSplatData
+        public const int ExportRecordBytes = 248;
+        [StructLayout(LayoutKind.Sequential)]
+        public unsafe struct ExportParams { public fixed float matrixObjectToWorld[16]; public fixed float rotation[4]; public fixed float scale[3]; public uint bakeTransform; }
+        [DllImport(Lib)] public static extern int gs_renderer_edit_export_data(IntPtr renderer, ref ExportParams p, IntPtr dst, UIntPtr bytes, int memoryKind);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_export_alive(IntPtr renderer, ref ExportParams p, IntPtr dst, UIntPtr capacityRecords, out uint alive);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_export_ply(IntPtr renderer, ref ExportParams p, [MarshalAs(UnmanagedType.LPStr)] string path, out uint alive);
         [DllImport(Lib)] public static extern int gs_renderer_set_view_buffer_mode(IntPtr renderer, int everyFrame);
         [DllImport(Lib)] public static extern int gs_renderer_set_blend_mode(IntPtr renderer, int mode);
         [DllImport(Lib)] public static extern int gs_renderer_set_tile_shape(IntPtr renderer, uint tileW, uint tileH);

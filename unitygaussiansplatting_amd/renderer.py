@@ -18,7 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from ._abi import (GS_ERR_PAIR_OVERFLOW, GS_SORT_FULL, GS_SORT_VISIBLE, VIEW_DTYPE, gs_edit_info, gs_frame_params, gs_frame_stats,
+from ._abi import (GS_ERR_PAIR_OVERFLOW, GS_SORT_FULL, GS_SORT_VISIBLE, VIEW_DTYPE, gs_edit_info, gs_export_params, gs_frame_params, gs_frame_stats,
                    gs_stage_times, make_asset_desc)
 from ._lib import GsError, check
 from .asset import GaussianSplatAsset, kCurrentVersion
@@ -480,6 +480,44 @@ class GaussianSplatRenderer:
         w = np.ascontiguousarray(bits, np.uint32)
         check(_lib.lib().gs_renderer_edit_upload_selected_bits(self._r_h, w.ctypes.data, len(w)), "gs_renderer_edit_upload_selected_bits")
         self.UpdateEditCountsAndBounds()
+
+    # -- editing: export (:936-958; GaussianSplatRendererEditor.cs:394-445) ------------------------------------------
+    def ExportParams(self, bakeTransform: bool) -> gs_export_params:
+        """What EditExportData hands CSExportData: transform.localRotation, localScale and localToWorldMatrix, and the bake flag."""
+        p = gs_export_params()
+        tr = self.transform
+        p.matrix_object_to_world[0:16] = [float(v) for v in np.asarray(tr.localToWorldMatrix, np.float32).reshape(-1)]
+        p.rotation[0:4] = [float(np.float32(v)) for v in tr.rotation]
+        p.scale[0:3] = [float(np.float32(v)) for v in tr.scale]
+        p.bake_transform = 1 if bakeTransform else 0
+        return p
+
+    def EditExportData(self, bakeTransform: bool = False) -> np.ndarray:      # :936-958
+        """All N records of CSExportData, [N, 62] float32 (creator.PLY_ATTRS), nor = 1 for the cut splats.  Blocks."""
+        self.UpdateCutoutsBuffer()                  # SetAssetDataOnCS, :507
+        out = np.zeros((self.m_SplatCount, 62), np.float32)
+        p = self.ExportParams(bakeTransform)
+        check(_lib.lib().gs_renderer_edit_export_data(self._r_h, C.byref(p), out.ctypes.data, out.nbytes, 0), "gs_renderer_edit_export_data")
+        return out
+
+    def ExportAlive(self, bakeTransform: bool = False) -> np.ndarray:
+        """The records of the splats that are neither deleted nor cut, in index order: [alive, 62] float32.  Blocks."""
+        self.UpdateCutoutsBuffer()
+        p = self.ExportParams(bakeTransform)
+        alive = C.c_uint32(0)
+        check(_lib.lib().gs_renderer_edit_export_alive(self._r_h, C.byref(p), None, 0, C.byref(alive)), "gs_renderer_edit_export_alive")
+        out = np.zeros((alive.value, 62), np.float32)
+        if alive.value:
+            check(_lib.lib().gs_renderer_edit_export_alive(self._r_h, C.byref(p), out.ctypes.data, alive.value, C.byref(alive)), "gs_renderer_edit_export_alive")
+        return out
+
+    def ExportPlyFile(self, path: str, bakeTransform: bool = False) -> int:   # GaussianSplatRendererEditor.cs:394-445
+        """Writes the alive splats as a PLY file the importer reads back; returns their number.  Blocks."""
+        self.UpdateCutoutsBuffer()
+        p = self.ExportParams(bakeTransform)
+        alive = C.c_uint32(0)
+        check(_lib.lib().gs_renderer_edit_export_ply(self._r_h, C.byref(p), os.fsencode(path), C.byref(alive)), "gs_renderer_edit_export_ply")
+        return int(alive.value)
 
     def CalcViewData(self, cam: Camera) -> None:    # :579-610
         self.UpdateCutoutsBuffer()                  # SetAssetDataOnCS, :507
