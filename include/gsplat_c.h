@@ -307,8 +307,8 @@ int32_t gs_renderer_set_deleted_bits(gs_renderer* r, const uint32_t* words, size
  * the first delete, and read as zeros while it does not exist.  Every kernel tests the splats against the renderer's current
  * gs_renderer_set_cutouts list (IsSplatCut), as the reference's do.
  * Selection has NO VISUAL EFFECT: the reference's highlight of selected splats (RenderGaussianSplats.shader:63-73,87-101) is not built;
- * only deletion changes a frame.  Moving, rotating, scaling and copying splats (CSTranslateSelection .. CSCopySplats) are not
- * built either: they rewrite the asset's blobs, which are immutable and shared here.  Exporting only reads them: see below.
+ * only deletion and the transforms below change a frame.  Copying splats and changing their number (CSCopySplats, EditSetSplatCount) are
+ * not built either: they need a writable colour texture and SH blob and a change of N.  Exporting only reads the blobs: see below.
  * Two literal quirks of the reference are kept: select-all / invert set the bits of the last word beyond N and the counts include them
  * (N = 33: select all reports 64 selected), and a splat whose pixel position is NaN is inside every rectangle.
  * The mutating calls are asynchronous on the context's stream like every other call; the info / download calls block.  Selection lives
@@ -333,7 +333,32 @@ int32_t gs_renderer_edit_info(gs_renderer* r, gs_edit_info* out);
 int32_t gs_renderer_edit_upload_selected_bits(gs_renderer* r, const uint32_t* words, size_t word_count);
 /* ceil(N/32) words each; any may be NULL; a buffer that does not exist reads as zeros; blocks */
 int32_t gs_renderer_edit_download_bits(gs_renderer* r, uint32_t* selected, uint32_t* selected_mouse_down, uint32_t* deleted, size_t word_count);
-int32_t gs_renderer_edit_release(gs_renderer* r);                   /* frees selected + mouse-down; deleted bits stay */
+int32_t gs_renderer_edit_release(gs_renderer* r);                   /* frees selected + mouse-down (bits, pos, other); deleted bits and moved splats stay */
+
+/* ---- moving the selection: EditTranslateSelection / EditRotateSelection / EditScaleSelection (GaussianSplatRenderer.cs:794-809,842-894;
+ * CSTranslateSelection, CSRotateSelection, CSScaleSelection, SplatUtilities.compute:425-521)  (additions to ABI 9) ----
+ * The three kernels rewrite positions and rotation words.  An asset's blobs stay immutable and shared: the first transform that can write
+ * gives THIS renderer a private device copy of the pos and / or other blob (copy-on-write), which every later call on the renderer and its
+ * lanes reads -- frames, sorts, selection, bounds, export.  The asset, its replicas and other renderers over it never see an edit; a renderer
+ * that is never transformed allocates nothing.  The reference's format gates are kept literally: positions are written only in a chunk-less
+ * asset with GS_VECTOR_FLOAT32 positions, rotation words only in a chunk-less asset with fp32 scales and fp32 SH; where no gate passes a call
+ * returns GS_OK and changes nothing.  Rotate reads pos and other from their mouse-down copies, scale reads pos from its copy, both write
+ * the current blobs; translate reads and writes the current positions.  Rotate without both store calls (scale: without the pos one) is
+ * GS_ERR_INVALID_ARGUMENT.  SHs are not rotated and splat scales not scaled (the reference's own TODOs).  Arithmetic: DESIGN.md section 4.7;
+ * one deviation -- the fields of a re-encoded rotation word are clamped to their ranges, which only matters for a delta quaternion that is
+ * not of unit length.  Asynchronous on the context's stream and ordered against sorts, GS_SORT_VISIBLE's history (the order buffer as the
+ * reference holds it at the call becomes the new base) and frames in flight (a frame already dealt to a lane finishes with the old
+ * positions).  Until the next calc_view the frame is drawn from the old view records, as in the reference, and a view download that would
+ * have to materialise them fails with GS_ERR_INVALID_ARGUMENT.  Matrices are row-major, quaternions x y z w. */
+int32_t gs_renderer_edit_store_pos_mouse_down(gs_renderer* r);     /* EditStorePosMouseDown   :794-801 */
+int32_t gs_renderer_edit_store_other_mouse_down(gs_renderer* r);   /* EditStoreOtherMouseDown :802-809 */
+int32_t gs_renderer_edit_translate_selection(gs_renderer* r, const float delta[3]);                       /* :842-854 */
+int32_t gs_renderer_edit_rotate_selection(gs_renderer* r, const float center[3], const float local_to_world[16],
+                                          const float world_to_local[16], const float rotation_xyzw[4]);   /* :856-874 */
+int32_t gs_renderer_edit_scale_selection(gs_renderer* r, const float center[3], const float local_to_world[16],
+                                         const float world_to_local[16], const float scale[3]);            /* :877-894 */
+/* the renderer's CURRENT pos / other blobs (the private copy if there is one, else the asset's); either may be NULL; blocks */
+int32_t gs_renderer_edit_download_pos_other(gs_renderer* r, void* pos, size_t pos_bytes, void* other, size_t other_bytes);
 
 /* ---- export: EditExportData (GaussianSplatRenderer.cs:936-958), CSExportData (SplatUtilities.compute:523-673) and the editor's
  * ExportPlyFile (GaussianSplatRendererEditor.cs:394-445)  (additions to ABI 9) ----

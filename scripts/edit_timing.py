@@ -5,6 +5,9 @@ splats, Medium = chunked Norm11 positions), next to the bytes each kernel must m
 
 Timed with events on the context's stream (a torch stream handed to gs_context_create), one pair around every call: the median of --runs calls
 after --warmup calls, and the mean of a back-to-back batch of update_selection calls between one pair (launch gaps included, host latency not).
+The three calls a drag of a move / rotate / scale tool repeats -- gs_renderer_edit_translate_selection, _rotate_selection, _scale_selection -- are
+timed the same way on the same splats as an fp32, chunk-less asset (VeryHigh: the only kind the reference's kernels write), with the rectangle's
+selection and with everything selected; the first call, which makes the renderer's private copy of the blobs, is recorded on its own.
 A record, not a gate: nothing is asserted about the times.
 
     timeout 900 python scripts/edit_timing.py [--config C2] [--splats N] [--out profiles/edit_timing.json]"""
@@ -41,7 +44,6 @@ def main() -> int:
     cfg = scenes.CONFIGS[args.config]
     raw = scenes.make_config_splats(cfg, args.splats)
     asset = creator.CreateAssetFromSplatsNative(raw, cfg.quality, name=cfg.key)
-    del raw
     n = asset.splatCount
     words = (n + 31) // 32
 
@@ -93,6 +95,46 @@ def main() -> int:
     bytes_info = pos_bytes + chunk_bytes + words * 4                # selected words in (no deleted buffer in this run); 36 bytes out
     med_u, med_i = statistics.median(t_update), statistics.median(t_info)
     name, cus, _ = ctx.DeviceInfo()
+    r.DisposeResourcesForAsset()
+
+    # ---- the transforms, on the same splats as an fp32, chunk-less asset -----------------------------------------------------------------------
+    import numpy as np
+    asset32 = creator.CreateAssetFromSplatsNative(raw, "VeryHigh", name=cfg.key + "_fp32")
+    del raw
+    r = GaussianSplatRenderer(ctx, asset32)
+    r.CreateResourcesForAsset()
+    tool = camera.Transform(position=(0.2, -0.1, 0.3), rotation=(0.1, 0.2, 0.05, 0.9695), scale=(1.25, 0.75, -1.5))
+    fp = lambda v: np.ascontiguousarray(v, np.float32).reshape(-1)
+    arrs = {"delta": fp((0.01, -0.02, 0.005)), "centre": fp((0.3, -0.2, 0.1)), "l2w": fp(tool.localToWorldMatrix), "w2l": fp(tool.worldToLocalMatrix),
+            "quat": fp((0.18257419, 0.36514837, 0.54772256, 0.73029674)), "scale": fp((1.01, 0.99, 1.0))}
+    ptr = {k: v.ctypes.data_as(C.POINTER(C.c_float)) for k, v in arrs.items()}
+
+    def translate():
+        _lib.check(lib.gs_renderer_edit_translate_selection(r._r_h, ptr["delta"]), "gs_renderer_edit_translate_selection")
+
+    def rotate():
+        _lib.check(lib.gs_renderer_edit_rotate_selection(r._r_h, ptr["centre"], ptr["l2w"], ptr["w2l"], ptr["quat"]), "gs_renderer_edit_rotate_selection")
+
+    def scale():
+        _lib.check(lib.gs_renderer_edit_scale_selection(r._r_h, ptr["centre"], ptr["l2w"], ptr["w2l"], ptr["scale"]), "gs_renderer_edit_scale_selection")
+
+    r.EditDeselectAll(); r.EditStoreSelectionMouseDown()
+    _lib.check(lib.gs_renderer_edit_update_selection(r._r_h, C.byref(P), rect, 0), "gs_renderer_edit_update_selection")
+    r.EditStorePosMouseDown(); r.EditStoreOtherMouseDown()
+    t_first = {"translate (copies pos)": timed(translate, 1)[0], "rotate (copies other)": timed(rotate, 1)[0]}
+    transforms = {}
+    for label in ("the rectangle's selection", "everything selected"):
+        if label == "everything selected":
+            r.EditSelectAll()
+        edit_info()
+        sel_n = int(info.selected)
+        for fn in (translate, rotate, scale):
+            timed(fn, args.warmup)
+            t = timed(fn, args.runs)
+            # a selected splat: 12 B of pos in and out (rotate and scale read the mouse-down copy), rotate 4 B of other in and out; every splat: its selection bit
+            per = 24 + (8 if fn is rotate else 0)
+            transforms.setdefault(fn.__name__, {})[label] = {"selected": sel_n, "median_ms": statistics.median(t), "min_ms": min(t), "max_ms": max(t),
+                                                              "bytes_to_move": min(sel_n, n) * per + words * 4}
     out = {
         "device": name, "cus": cus, "config": cfg.key, "label": cfg.label + (f" [--splats {args.splats}]" if args.splats else ""),
         "splats": n, "words": words, "pos_format": str(asset.posFormat), "runs": args.runs, "warmup": args.warmup,
@@ -103,6 +145,8 @@ def main() -> int:
                       "gb_per_s_at_median": bytes_info / (med_i * 1e-3) / 1e9,
                       "median_ms_nothing_selected": statistics.median(t_info_none), "median_ms_everything_selected": statistics.median(t_info_all),
                       "note": "two kernels + a 36-byte device-to-host copy + the stream synchronise inside the call; median_ms is with the rectangle's selection"},
+        "transforms": {"asset": "the same splats, VeryHigh (fp32 positions, scales and SH, no chunks)", "first_call_ms": t_first, "calls": transforms,
+                       "note": "bytes_to_move counts whole records of the selected splats; the hardware moves the 64- / 128-byte lines they lie in"},
         "timing": "events on the context's stream around every call; thresholds: none (a record)",
     }
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -64,6 +64,12 @@ SIGNATURES = {
     "gs_renderer_edit_upload_selected_bits": (C.c_int32, [_P, _P, C.c_size_t]),
     "gs_renderer_edit_download_bits": (C.c_int32, [_P, _P, _P, _P, C.c_size_t]),
     "gs_renderer_edit_release": (C.c_int32, [_P]),
+    "gs_renderer_edit_store_pos_mouse_down": (C.c_int32, [_P]),
+    "gs_renderer_edit_store_other_mouse_down": (C.c_int32, [_P]),
+    "gs_renderer_edit_translate_selection": (C.c_int32, [_P, C.POINTER(C.c_float)]),
+    "gs_renderer_edit_rotate_selection": (C.c_int32, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "gs_renderer_edit_scale_selection": (C.c_int32, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "gs_renderer_edit_download_pos_other": (C.c_int32, [_P, _P, C.c_size_t, _P, C.c_size_t]),
     "gs_renderer_edit_export_data": (C.c_int32, [_P, C.POINTER(gs_export_params), _P, C.c_size_t, C.c_int32]),
     "gs_renderer_edit_export_alive": (C.c_int32, [_P, C.POINTER(gs_export_params), _P, C.c_size_t, C.POINTER(C.c_uint32)]),
     "gs_renderer_edit_export_ply": (C.c_int32, [_P, C.POINTER(gs_export_params), C.c_char_p, C.POINTER(C.c_uint32)]),

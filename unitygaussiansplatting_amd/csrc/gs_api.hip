@@ -284,7 +284,7 @@ static void lanes_destroy(gs_renderer* r) {
 
 // The lanes take over the owner's order: its buffer as the reference holds it now (the recorded sorts carried out) becomes every lane's base, the
 // owner's remaining history (its head row at most) theirs.  Rare: when lanes are made, when the mode is switched to GS_SORT_VISIBLE, after reset / upload.
-static int32_t lanes_resync(gs_renderer* r) {
+extern "C++" int32_t gs::lanes_resync(gs_renderer* r) {
     if (r->lanes.empty()) return GS_OK;
     GS_TRY(bind_device(r->ctx));
     if (r->sortMode != GS_SORT_VISIBLE) return GS_OK;            // GS_SORT_FULL runs on the owner alone: the lanes idle until the mode comes back (and are resynchronised then)
@@ -421,7 +421,7 @@ static int32_t materialise_distances(gs_renderer* r) {
 static int32_t enqueue_full_sort(gs_renderer* r, const float m[16], bool consolidating);
 
 // order[] is about to stop being what the visible-only mode calls its base (reset, upload, a sort in GS_SORT_FULL)
-static void vis_base_changed(gs_renderer* r, bool identity) {
+extern "C++" void gs::vis_base_changed(gs_renderer* r, bool identity) {
     r->visBaseIdentity = identity; r->visRankValid = false; r->visHistDepth = 0; r->visOrderValid = false;
 }
 
@@ -499,7 +499,7 @@ static int32_t enqueue_full_sort(gs_renderer* r, const float m[16], bool consoli
     SortControl* control = r->depthControl + r->depthControlIdx;
     // CSCalcDistances: keys of all splats in index order (+ the digit histograms); the gather through the previous order
     // (_SplatSortKeys, SplatUtilities.compute:76) is the first Onesweep pass's key load
-    GS_TRY(enqueue_sort_keys(ctx, st, r->asset->view, m, r->keyBySplat, control, r->depthControl + (r->depthControlIdx ^ 1), r->n, r->depthSort));
+    GS_TRY(enqueue_sort_keys(ctx, st, asset_view(r), m, r->keyBySplat, control, r->depthControl + (r->depthControlIdx ^ 1), r->n, r->depthSort));
     if (profR) gs::prof_record(r, 1, st);
     // (skipLastKeys: the last depth pass writes only the order -- nothing on the frame's path reads the sorted keys; materialise_distances)
     GS_TRY(enqueue_sort_passes(ctx, st, r->depthSort, control, r->distances, r->order, r->n, nullptr, 4, 255u, profR, 10, 8, r->keyBySplat, !consolidating));
@@ -524,8 +524,9 @@ int32_t gs_renderer_calc_view(gs_renderer* r, const gs_frame_params* p) {
     rec_ev(r, 7);
     gsm::EditView e;
     e.deletedBits = r->deletedBits; e.cutouts = r->cutouts; e.cutoutCount = r->cutoutCount;
-    GS_TRY(enqueue_calc_view(r->ctx, r->asset->view, p, e, view_outputs(r), r->alwaysWriteView));
+    GS_TRY(enqueue_calc_view(r->ctx, asset_view(r), p, e, view_outputs(r), r->alwaysWriteView));
     r->viewMaterialised = r->alwaysWriteView;
+    r->movedSinceView = false;
     r->visOrderValid = false;                                    // the visible set may have changed
     r->lastParams = *p;
     r->viewW = p->screen_w; r->viewH = p->screen_h; r->viewNear = p->near_clip; r->viewFar = p->far_clip; r->viewValid = true;
@@ -823,12 +824,14 @@ int32_t gs_renderer_download_view(gs_renderer* r, void* out, size_t bytes) {
     if (!r || !out || bytes > (size_t)r->n * sizeof(gsm::ViewData)) return fail(GS_ERR_INVALID_ARGUMENT, "bad argument");
     r = lane_cur(r);
     if (r->viewValid && !r->viewMaterialised) {
+        // ... unless the splats have been moved since (gs_edit.hip): lastParams would give records of the NEW positions, which is not what m_GpuView holds
+        if (r->movedSinceView) return fail(GS_ERR_INVALID_ARGUMENT, "calc_view has not run since the splats were moved");
         // m_GpuView is materialised on demand: the per-frame launch skips it (nothing in this renderer reads it); re-run the
         // frame's launch as the reference's full kernel.  rec/rect/visibility are rewritten with identical values.
         GS_TRY(bind_device(r->ctx));
         gsm::EditView e;
         e.deletedBits = r->deletedBits; e.cutouts = r->cutouts; e.cutoutCount = r->cutoutCount;
-        GS_TRY(enqueue_calc_view(r->ctx, r->asset->view, &r->lastParams, e, view_outputs(r), true));
+        GS_TRY(enqueue_calc_view(r->ctx, asset_view(r), &r->lastParams, e, view_outputs(r), true));
         r->viewMaterialised = true;
     }
     return download(r->ctx, out, r->view, bytes);

@@ -263,6 +263,17 @@ struct gs_renderer {
     gs::DevBuf<uint32_t> editCountsBounds;  // m_GpuEditCountsBounds: 3 counts + 6 sortable uints
     gs::Event evEditDeleted;                // context's stream -> lanes: deletedBits holds a delete's result
     gs::Event evEditCopied;                 // (on a lane) lane's stream -> owner's: the lane has taken its copy
+    // The renderer's own, writable copy of the two blobs the transform kernels write (CSTranslateSelection / CSRotateSelection / CSScaleSelection): made by
+    // the first transform whose format gate can pass, null until then (gs::asset_view).  The asset itself -- shared between contexts, lanes and replicas --
+    // is never written; lanes read their owner's copies in place.
+    gs::DevBuf<uint8_t> privPos;            // m_GpuPosData of this renderer
+    gs::DevBuf<uint8_t> privOther;          // m_GpuOtherData
+    gs::DevBuf<uint8_t> editPosMouseDown;   // m_GpuEditPosMouseDown: made only when the position gate can pass
+    gs::DevBuf<uint8_t> editOtherMouseDown; // m_GpuEditOtherMouseDown: ... the rotation gate
+    bool editPosStored = false, editOtherStored = false;   // EditStorePosMouseDown / EditStoreOtherMouseDown have run since the last release
+    gs::Event evEditMoved;                  // context's stream -> lanes: a transform's kernel is behind this
+    gs::Event evEditLaneIdle;               // (on a lane) lane's stream -> owner's: the frames dealt so far have read the old positions
+    bool movedSinceView = false;            // the splats were moved after the last calc_view: lastParams no longer reproduce the view buffer
     float viewW = 0.f, viewH = 0.f, viewNear = 0.f, viewFar = 0.f;   // what the last calc_view was run with
     bool viewValid = false;
     bool viewMaterialised = false;          // the N x 40 B view buffer holds the last calc_view's records (written on demand)
@@ -393,5 +404,17 @@ int32_t enqueue_debug_boxes(gs_renderer* r, const gs_frame_params* p, gs_target*
 int32_t enqueue_resolve(gs_target* t, const float bg[4], bool want8);
 int32_t flush_clear(gs_target* t);          // perform a pending gs_target_clear now
 // edit (gs_edit.hip)
-void edit_free(gs_renderer* r);             // the selection buffers (not deletedBits, not the edit events)
+void edit_free(gs_renderer* r);             // the selection buffers and the mouse-down copies (not deletedBits, not the private blobs, not the edit events)
+// gs_api.hip: order[] stops being the visible-only mode's base / the lanes take over the owner's order
+void vis_base_changed(gs_renderer* r, bool identity);
+int32_t lanes_resync(gs_renderer* r);
+// The asset as THIS renderer sees it: the asset's view with pos / other replaced by the renderer's private copies where they exist.  A lane sees what its
+// owner sees.  Every launch that reads the blobs takes its view from here.
+inline gsm::AssetView asset_view(const gs_renderer* r) {
+    const gs_renderer* o = r->laneOf ? r->laneOf : r;
+    gsm::AssetView v = r->asset->view;
+    if (o->privPos) v.pos = o->privPos;
+    if (o->privOther) v.other = o->privOther;
+    return v;
+}
 } // namespace gs

@@ -10,7 +10,9 @@
 //   :56-90 CalcCovariance2D, :113-127,183-194 Morton texel address, :130-179 ShadeSH, :219-229 DecodeRotation,
 //   :261-300 DecodePacked_*, :325-421 LoadUShort/LoadUInt/LoadAndDecodeVector/LoadSplatPos, :428-608 LoadSplatData
 //   SplatUtilities.compute :52-57 FloatToSortableUint, :107-162 DecomposeCovariance, :189-252 CSCalcViewData,
-//   :279-296 CSUpdateEditData's bounds, :400-416 CSSelectionUpdate's hit test (the edit kernels: gs_edit.hip)
+//   :279-296 CSUpdateEditData's bounds, :400-416 CSSelectionUpdate's hit test, :425-521 CSTranslateSelection / CSRotateSelection /
+//   CSScaleSelection with GaussianSplatting.hlsl :13-22 QuatRotateVector / QuatMul, :230-259 PackSmallest3Rotation, :301-304
+//   EncodeQuatToNorm10 (the edit kernels: gs_edit.hip)
 #pragma once
 #include <stdint.h>
 
@@ -306,6 +308,54 @@ GS_HD V4 DecodeRotation(uint32_t enc) {
     if (idx == 1) q = { qx, qw, qy, qz };
     if (idx == 2) q = { qx, qy, qw, qz };
     return q;
+}
+
+// QuatMul(a, b) (GaussianSplatting.hlsl:19-22): every product and sum on its own, in the order of the reference's text
+GS_HD V4 QuatMul(const V4& qa, const V4& qb) {
+    V4 r;
+    r.x = (qa.w * qb.x + (qa.x * qb.w + qa.y * qb.z)) - qa.z * qb.y;
+    r.y = (qa.w * qb.y + (qa.y * qb.w + qa.z * qb.x)) - qa.x * qb.z;
+    r.z = (qa.w * qb.z + (qa.z * qb.w + qa.x * qb.y)) - qa.y * qb.x;
+    r.w = (qa.w * qb.w + -(qa.x * qb.x + qa.y * qb.y)) - qa.z * qb.z;
+    return r;
+}
+
+// QuatRotateVector(v, r) (GaussianSplatting.hlsl:13-17): t = 2 cross(r.xyz, v); v + r.w t + cross(r.xyz, t)
+GS_HD V3 QuatRotateVector(const V3& v, const V4& r) {
+    const float tx = 2.0f * (r.y * v.z - r.z * v.y), ty = 2.0f * (r.z * v.x - r.x * v.z), tz = 2.0f * (r.x * v.y - r.y * v.x);
+    const float cx = r.y * tz - r.z * ty, cy = r.z * tx - r.x * tz, cz = r.x * ty - r.y * tx;
+    return { (v.x + r.w * tx) + cx, (v.y + r.w * ty) + cy, (v.z + r.w * tz) + cz };
+}
+
+// PackSmallest3Rotation (GaussianSplatting.hlsl:230-259): the strict > chain (the first of equal magnitudes wins; a NaN never does), the
+// swizzles, q.w >= 0 ? 1 : -1 (so -0 counts as positive and a NaN as negative), (three * sqrt(2.0)) * 0.5 + 0.5 as three fp32 operations
+// with sqrt(2.0) the fp32 square root (the halving is exact, so a fused last step gives the same bits), index / 3.0 as a division.
+GS_HD V4 PackSmallest3Rotation(V4 q) {
+    const float ax = fabsf(q.x), ay = fabsf(q.y), az = fabsf(q.z), aw = fabsf(q.w);
+    int index = 0;
+    float maxV = ax;
+    if (ay > maxV) { index = 1; maxV = ay; }
+    if (az > maxV) { index = 2; maxV = az; }
+    if (aw > maxV) { index = 3; maxV = aw; }
+    if (index == 0) q = { q.y, q.z, q.w, q.x };
+    if (index == 1) q = { q.x, q.z, q.w, q.y };
+    if (index == 2) q = { q.x, q.y, q.w, q.z };
+    const float s = (q.w >= 0.0f) ? 1.0f : -1.0f, SQRT2 = 1.41421356237f;
+    V4 r;
+    r.x = ((q.x * s) * SQRT2) * 0.5f + 0.5f;
+    r.y = ((q.y * s) * SQRT2) * 0.5f + 0.5f;
+    r.z = ((q.z * s) * SQRT2) * 0.5f + 0.5f;
+    r.w = (float)index / 3.0f;
+    return r;
+}
+
+// EncodeQuatToNorm10 (GaussianSplatting.hlsl:301-304): truncating conversions of v * 1023.5 / v.w * 3.5.  One deviation: every field is
+// clamped to its range first (a NaN becomes 0) -- a delta quaternion that is not of unit length takes `three` out of [0, 1], where the
+// reference's conversion is undefined or spills into the next field; for every value inside the range the result is the reference's.
+GS_HD uint32_t EncodeNormField(float v, float scale, float hi) { return (uint32_t)fminf(fmaxf(v * scale, 0.0f), hi); }
+GS_HD uint32_t EncodeQuatToNorm10(const V4& v) {
+    return EncodeNormField(v.x, 1023.5f, 1023.0f) | (EncodeNormField(v.y, 1023.5f, 1023.0f) << 10) | (EncodeNormField(v.z, 1023.5f, 1023.0f) << 20) |
+           (EncodeNormField(v.w, 3.5f, 3.0f) << 30);
 }
 
 // SH coefficient k (1..15) of the splat whose SH record starts at `sp`, before chunk de-normalisation
@@ -682,6 +732,31 @@ GS_HD void EditSplatBounds(const V3& pos, uint32_t lo[3], uint32_t hi[3]) {
     lo[0] = FloatToSortableUint(fminf(1.0e38f, pos.x)); hi[0] = FloatToSortableUint(fmaxf(-1.0e38f, pos.x));
     lo[1] = FloatToSortableUint(fminf(1.0e38f, pos.y)); hi[1] = FloatToSortableUint(fmaxf(-1.0e38f, pos.y));
     lo[2] = FloatToSortableUint(fminf(1.0e38f, pos.z)); hi[2] = FloatToSortableUint(fmaxf(-1.0e38f, pos.z));
+}
+
+// CSTranslateSelection / CSRotateSelection / CSScaleSelection for one selected splat (SplatUtilities.compute:425-521).  What the three
+// read of their dispatch: _SelectionCenter, _MatrixObjectToWorld and _MatrixWorldToObject (rows 0..2), and _SelectionDelta (xyz; translate,
+// scale) or _SelectionDeltaRot (xyzw; rotate).  mul(M, float4(p, 1)) is mrow's fmaf chain, as everywhere; every other operation rounds once,
+// in the order of the reference's text.  SHs are not rotated and a splat's own scale is not scaled: the reference's @TODOs, kept.
+struct EditXform { float center[3]; float o2w[12]; float w2o[12]; float delta[4]; };
+GS_HD V3 EditTranslatePos(const EditXform& X, const V3& pos) { return { pos.x + X.delta[0], pos.y + X.delta[1], pos.z + X.delta[2] }; }
+GS_HD V3 EditRotatePos(const EditXform& X, const V3& mouseDown) {
+    V3 p = { mouseDown.x - X.center[0], mouseDown.y - X.center[1], mouseDown.z - X.center[2] };
+    p = { mrow(X.o2w, 0, p.x, p.y, p.z), mrow(X.o2w, 1, p.x, p.y, p.z), mrow(X.o2w, 2, p.x, p.y, p.z) };
+    p = QuatRotateVector(p, { X.delta[0], X.delta[1], X.delta[2], X.delta[3] });
+    p = { mrow(X.w2o, 0, p.x, p.y, p.z), mrow(X.w2o, 1, p.x, p.y, p.z), mrow(X.w2o, 2, p.x, p.y, p.z) };
+    return { p.x + X.center[0], p.y + X.center[1], p.z + X.center[2] };
+}
+GS_HD V3 EditScalePos(const EditXform& X, const V3& mouseDown) {
+    V3 p = { mouseDown.x - X.center[0], mouseDown.y - X.center[1], mouseDown.z - X.center[2] };
+    p = { mrow(X.o2w, 0, p.x, p.y, p.z), mrow(X.o2w, 1, p.x, p.y, p.z), mrow(X.o2w, 2, p.x, p.y, p.z) };
+    p = { p.x * X.delta[0], p.y * X.delta[1], p.z * X.delta[2] };
+    p = { mrow(X.w2o, 0, p.x, p.y, p.z), mrow(X.w2o, 1, p.x, p.y, p.z), mrow(X.w2o, 2, p.x, p.y, p.z) };
+    return { p.x + X.center[0], p.y + X.center[1], p.z + X.center[2] };
+}
+// the rotation word of a rotated splat: decode the mouse-down word, QuatMul(rot, delta) ("@TODO: correct rotation": the reference's), encode
+GS_HD uint32_t EditRotateWord(const EditXform& X, uint32_t mouseDown) {
+    return EncodeQuatToNorm10(PackSmallest3Rotation(QuatMul(DecodeRotation(mouseDown), { X.delta[0], X.delta[1], X.delta[2], X.delta[3] })));
 }
 
 // CSCalcViewData for one splat (SplatUtilities.compute:189-252), in two halves so that a caller which only needs the
@@ -1216,11 +1291,7 @@ GS_HD void ExportSplat(const AssetView& a, const ExportXform& X, uint32_t idx, u
         if (X.scale[0] < 0.0f) { s.rot.y = -s.rot.y; s.rot.z = -s.rot.z; }
         if (X.scale[1] < 0.0f) { s.rot.x = -s.rot.x; s.rot.z = -s.rot.z; }
         if (X.scale[2] < 0.0f) { s.rot.x = -s.rot.x; s.rot.y = -s.rot.y; }
-        const V4 qa = { X.rot[0], X.rot[1], X.rot[2], X.rot[3] }, qb = s.rot;          // QuatMul(a, b), GaussianSplatting.hlsl:19-22
-        s.rot.x = (qa.w * qb.x + (qa.x * qb.w + qa.y * qb.z)) - qa.z * qb.y;
-        s.rot.y = (qa.w * qb.y + (qa.y * qb.w + qa.z * qb.x)) - qa.x * qb.z;
-        s.rot.z = (qa.w * qb.z + (qa.z * qb.w + qa.x * qb.y)) - qa.y * qb.x;
-        s.rot.w = (qa.w * qb.w + -(qa.x * qb.x + qa.y * qb.y)) - qa.z * qb.z;
+        s.rot = QuatMul({ X.rot[0], X.rot[1], X.rot[2], X.rot[3] }, s.rot);
         s.scale.x *= fabsf(X.scale[0]); s.scale.y *= fabsf(X.scale[1]); s.scale.z *= fabsf(X.scale[2]);
         V3 out[15];
 #pragma unroll

@@ -7,10 +7,14 @@
 //   CSInvertSelection / CSSelectAll    :336-377                         every bit, cut splats cleared
 //   CSOrBuffers                        :380-389                         deleted |= selected
 //   CSSelectionUpdate                  :391-423                         rectangle selection through a camera, add or subtract
-// Not built: CSTranslateSelection .. CSScaleSelection and CSCopySplats (they rewrite the pos / other blobs, which this library shares between contexts,
-// lanes and replicas; CSExportData only reads them: gs_export.hip) and the highlight of selected splats in the fragment stage (RenderGaussianSplats.shader:63-73,87-101: it replaces a splat's
+//   CSTranslateSelection / CSRotateSelection / CSScaleSelection  :425-521  the selected splats' positions (and rotation words) rewritten
+// The last three are the only kernels that write splat data.  The asset's blobs are shared between contexts, lanes and replicas and stay
+// immutable: the first transform whose format gate can pass gives the renderer a private copy of the pos and / or other blob (copy-on-write,
+// gs::asset_view), and from then on every kernel of this renderer and of its lanes reads that copy.  CSExportData only reads: gs_export.hip.
+// Not built: CSCopySplats / EditSetSplatCount (they need a writable colour texture and SH blob and a change of N) and the highlight of
+// selected splats in the fragment stage (RenderGaussianSplats.shader:63-73,87-101: it replaces a splat's
 // opacity by -1, which here would go through PrepareSplat's cull and footprint bound and the blend's alpha window).  Selection therefore
-// has NO VISUAL EFFECT: only deletion changes a frame, through the deleted bits calc_view already reads.
+// has NO VISUAL EFFECT: only deletion and the transforms change a frame.
 //
 // Shape (wave64; not the reference's, which runs one thread per WORD with a 32-iteration position loop, neighbouring threads reading
 // positions 32 records apart): one thread per SPLAT, 256-thread workgroups aligned to the 256-splat chunk so that the chunk header is
@@ -145,6 +149,32 @@ __global__ __launch_bounds__(256) void edit_update_data_kernel(gsm::AssetView a,
     }
 }
 
+// CSTranslateSelection (OP 0), CSRotateSelection (1), CSScaleSelection (2).  The shape of the kernels above: one thread per splat, a wave owns two
+// selection words; a lane reads ITS word (32 lanes, one address) and no record at an index >= N is read or written, whatever the tail bits of the
+// last word say.  A wave whose two words are zero -- most waves under a rectangle selection -- leaves before it touches pos / other.  Only selected
+// lanes load and store, and of a 16-byte other record only the rotation word is rewritten.  pos / other: the renderer's private blobs (null = that
+// gate failed); posMD / otherMD: the mouse-down copies rotate and scale read.
+enum { kEditTranslate = 0, kEditRotate = 1, kEditScale = 2 };
+template <int OP>
+__global__ __launch_bounds__(256) void edit_transform_kernel(uint8_t* __restrict__ pos, uint8_t* __restrict__ other, const uint8_t* __restrict__ posMD,
+                                                             const uint8_t* __restrict__ otherMD, const uint32_t* __restrict__ sel, uint32_t n, gsm::EditXform X) {
+    const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t word = idx < n ? sel[idx >> 5] : 0u;            // idx < n: the word exists
+    if (__ballot(word != 0u) == 0ull) return;
+    if (!((word >> (idx & 31u)) & 1u)) return;                     // (word = 0 beyond N)
+    if (pos) {
+        float* dst = (float*)(pos + (size_t)idx * 12u);
+        const float* src = OP == kEditTranslate ? dst : (const float*)(posMD + (size_t)idx * 12u);
+        const gsm::V3 p = { src[0], src[1], src[2] };
+        const gsm::V3 q = OP == kEditTranslate ? gsm::EditTranslatePos(X, p) : (OP == kEditRotate ? gsm::EditRotatePos(X, p) : gsm::EditScalePos(X, p));
+        dst[0] = q.x; dst[1] = q.y; dst[2] = q.z;
+    }
+    if (OP == kEditRotate && other) {
+        const uint32_t enc = *(const uint32_t*)(otherMD + (size_t)idx * 16u);
+        *(uint32_t*)(other + (size_t)idx * 16u) = gsm::EditRotateWord(X, enc);
+    }
+}
+
 static inline size_t edit_words(const gs_renderer* r) { return ((size_t)r->n + 31) / 32; }
 
 static gsm::EditView edit_view(const gs_renderer* r) {
@@ -171,6 +201,8 @@ static int32_t edit_ensure(gs_renderer* r) {
 
 void edit_free(gs_renderer* r) {
     r->editSelected.reset(); r->editSelectedMouseDown.reset(); r->editCountsBounds.reset();
+    r->editPosMouseDown.reset(); r->editOtherMouseDown.reset();
+    r->editPosStored = r->editOtherStored = false;
 }
 
 static inline uint32_t splat_grid(const gs_renderer* r) { return (r->n + 255u) / 256u; }
@@ -196,6 +228,95 @@ static int32_t edit_deleted_to_lanes(gs_renderer* r) {
     return GS_OK;
 }
 
+// ---- the transforms ---------------------------------------------------------------------------------------------------------------------
+// The reference's format gates, literally (SplatUtilities.compute:445,469,483): positions are written only in a chunk-less asset with fp32
+// positions, rotation words only in a chunk-less asset with fp32 scales and fp32 SH (so an other record is 4 + 12 bytes).
+static inline bool edit_pos_gate(const gs_renderer* r) { const gsm::AssetView& a = r->asset->view; return a.chunkCount == 0 && a.posFmt == 0; }
+static inline bool edit_rot_gate(const gs_renderer* r) { const gsm::AssetView& a = r->asset->view; return a.chunkCount == 0 && a.scaleFmt == 0 && a.shFmt == 0; }
+// what a transform may touch of blob k (0 pos, 1 other): whole records only
+static inline size_t edit_blob_bytes(const gs_renderer* r, int k) { return (size_t)r->n * (k == 0 ? 12u : 16u); }
+
+// the renderer's current pos (k = 0) / other (1) blob, wherever it lives
+static inline const uint8_t* edit_current_blob(const gs_renderer* r, int k) {
+    const gsm::AssetView a = asset_view(r);
+    return k == 0 ? a.pos : a.other;
+}
+
+// copy-on-write: the private copy of blob k, made on the context's stream the first time a transform is about to write it.  Padded like an
+// owned upload of the asset (the dword stitching of LoadUInt may touch the dword after the last record).
+static int32_t edit_make_private(gs_renderer* r, int k) {
+    DevBuf<uint8_t>& priv = k == 0 ? r->privPos : r->privOther;
+    if (priv) return GS_OK;
+    const size_t bytes = (size_t)r->asset->sizes[k];
+    DevBuf<uint8_t> b;
+    GS_HIP(b.alloc(bytes + 16));
+    GS_HIP(hipMemsetAsync(b + bytes, 0, 16, r->ctx->stream));
+    GS_HIP(hipMemcpyAsync(b, r->asset->blobs[k], bytes, hipMemcpyDeviceToDevice, r->ctx->stream));
+    priv = std::move(b);
+    return GS_OK;
+}
+
+// EditStorePosMouseDown / EditStoreOtherMouseDown: the copy is only made where a kernel can read it (the blob's gate)
+static int32_t edit_store_mouse_down(gs_renderer* r, int k) {
+    if (r->laneOf) return fail(GS_ERR_INVALID_ARGUMENT, "a lane holds no edit state: edit its owner");
+    GS_HIP(hipSetDevice(r->ctx->device));
+    if (k == 0 ? edit_pos_gate(r) : edit_rot_gate(r)) {
+        DevBuf<uint8_t>& md = k == 0 ? r->editPosMouseDown : r->editOtherMouseDown;
+        if (!md) GS_HIP(md.alloc(edit_blob_bytes(r, k)));
+        GS_HIP(hipMemcpyAsync(md, edit_current_blob(r, k), edit_blob_bytes(r, k), hipMemcpyDeviceToDevice, r->ctx->stream));
+    }
+    (k == 0 ? r->editPosStored : r->editOtherStored) = true;
+    return GS_OK;
+}
+
+// One transform on the context's stream, ordered against everything else that reads the positions:
+//   - a sort still running on the second queue is joined first, and the next one waits for the kernel (CSCalcDistances reads positions);
+//   - GS_SORT_VISIBLE: the recorded sorts are sorts of the OLD positions, so they are carried out first (order[] = the reference's buffer now), and that
+//     order is the new base with an empty history -- from here on the reference, too, stably sorts that buffer by keys of the new positions;
+//   - lanes read the owner's private blobs in place: the context's stream waits for what each lane has been dealt (those frames finish with the old
+//     positions), the kernel runs, and every lane's stream waits for it.  Events only; edit_deleted_to_lanes turned round.
+static int32_t edit_transform(gs_renderer* r, int op, const gsm::EditXform& X) {
+    const bool doPos = edit_pos_gate(r), doRot = op == kEditRotate && edit_rot_gate(r);
+    if (!doPos && !doRot) return GS_OK;                            // neither gate: the reference's kernel writes nothing
+    GS_TRY(join_sort(r));
+    if (vis_active(r)) GS_TRY(vis_consolidate(r));
+    for (gs_renderer* L : r->lanes) {
+        if (!L->evEditLaneIdle) GS_HIP(L->evEditLaneIdle.create(hipEventDisableTiming));
+        GS_HIP(hipEventRecord(L->evEditLaneIdle, L->ctx->stream));
+        GS_HIP(hipStreamWaitEvent(r->ctx->stream, L->evEditLaneIdle, 0));
+    }
+    if (doPos) GS_TRY(edit_make_private(r, 0));
+    if (doRot) GS_TRY(edit_make_private(r, 1));
+    uint8_t* pos = doPos ? r->privPos.get() : nullptr;
+    uint8_t* other = doRot ? r->privOther.get() : nullptr;
+    const uint8_t* posMD = r->editPosMouseDown, * otherMD = r->editOtherMouseDown;
+    const uint32_t* sel = r->editSelected;
+    const dim3 grid(splat_grid(r)), block(256);
+    if (op == kEditTranslate) hipLaunchKernelGGL(edit_transform_kernel<kEditTranslate>, grid, block, 0, r->ctx->stream, pos, other, posMD, otherMD, sel, r->n, X);
+    else if (op == kEditRotate) hipLaunchKernelGGL(edit_transform_kernel<kEditRotate>, grid, block, 0, r->ctx->stream, pos, other, posMD, otherMD, sel, r->n, X);
+    else hipLaunchKernelGGL(edit_transform_kernel<kEditScale>, grid, block, 0, r->ctx->stream, pos, other, posMD, otherMD, sel, r->n, X);
+    GS_HIP(hipGetLastError());
+    GS_TRY(mark_order_use(r));
+    r->movedSinceView = true;
+    for (gs_renderer* L : r->lanes) L->movedSinceView = true;
+    if (vis_active(r)) {
+        vis_base_changed(r, r->visBaseIdentity);                   // (still CSSetIndices' identity if nothing had been sorted yet)
+        GS_TRY(lanes_resync(r));
+    }
+    if (!r->lanes.empty()) {
+        if (!r->evEditMoved) GS_HIP(r->evEditMoved.create(hipEventDisableTiming));
+        GS_HIP(hipEventRecord(r->evEditMoved, r->ctx->stream));
+        for (gs_renderer* L : r->lanes) GS_HIP(hipStreamWaitEvent(L->ctx->stream, r->evEditMoved, 0));
+    }
+    return GS_OK;
+}
+
+static void edit_xform_matrices(gsm::EditXform& X, const float center[3], const float o2w[16], const float w2o[16]) {
+    memcpy(X.center, center, sizeof(X.center));
+    memcpy(X.o2w, o2w, sizeof(X.o2w));
+    memcpy(X.w2o, w2o, sizeof(X.w2o));
+}
+
 } // namespace gs
 
 using namespace gs;
@@ -205,7 +326,7 @@ extern "C" {
 int32_t gs_renderer_edit_select_all(gs_renderer* r) {
     if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
     GS_TRY(edit_ensure(r));
-    hipLaunchKernelGGL(edit_select_all_kernel, dim3(splat_grid(r)), dim3(256), 0, r->ctx->stream, r->asset->view, edit_view(r), r->editSelected,
+    hipLaunchKernelGGL(edit_select_all_kernel, dim3(splat_grid(r)), dim3(256), 0, r->ctx->stream, asset_view(r), edit_view(r), r->editSelected,
                        (uint32_t)edit_words(r), 0u);
     GS_HIP(hipGetLastError());
     return GS_OK;
@@ -214,7 +335,7 @@ int32_t gs_renderer_edit_select_all(gs_renderer* r) {
 int32_t gs_renderer_edit_invert_selection(gs_renderer* r) {
     if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
     GS_TRY(edit_ensure(r));
-    hipLaunchKernelGGL(edit_select_all_kernel, dim3(splat_grid(r)), dim3(256), 0, r->ctx->stream, r->asset->view, edit_view(r), r->editSelected,
+    hipLaunchKernelGGL(edit_select_all_kernel, dim3(splat_grid(r)), dim3(256), 0, r->ctx->stream, asset_view(r), edit_view(r), r->editSelected,
                        (uint32_t)edit_words(r), 1u);
     GS_HIP(hipGetLastError());
     return GS_OK;
@@ -242,7 +363,7 @@ int32_t gs_renderer_edit_update_selection(gs_renderer* r, const gs_frame_params*
     memcpy(S.vp, p->matrix_vp, sizeof(S.vp));
     S.screenW = p->screen_w; S.screenH = p->screen_h;
     memcpy(S.rect, selection_rect, sizeof(S.rect));
-    hipLaunchKernelGGL(edit_selection_update_kernel, dim3(splat_grid(r)), dim3(256), 0, r->ctx->stream, r->asset->view, edit_view(r), S,
+    hipLaunchKernelGGL(edit_selection_update_kernel, dim3(splat_grid(r)), dim3(256), 0, r->ctx->stream, asset_view(r), edit_view(r), S,
                        (const uint32_t*)r->editSelectedMouseDown, r->editSelected, (uint32_t)edit_words(r), subtract ? 0u : 1u);
     GS_HIP(hipGetLastError());
     return GS_OK;
@@ -269,7 +390,7 @@ int32_t gs_renderer_edit_info(gs_renderer* r, gs_edit_info* out) {
     if (!r->editSelected) return GS_OK;                            // UpdateEditCountsAndBounds without edit buffers (:707-715)
     GS_HIP(hipSetDevice(r->ctx->device));
     hipLaunchKernelGGL(edit_init_data_kernel, dim3(1), dim3(64), 0, r->ctx->stream, r->editCountsBounds);
-    hipLaunchKernelGGL(edit_update_data_kernel, dim3(splat_grid(r)), dim3(256), 0, r->ctx->stream, r->asset->view, edit_view(r),
+    hipLaunchKernelGGL(edit_update_data_kernel, dim3(splat_grid(r)), dim3(256), 0, r->ctx->stream, asset_view(r), edit_view(r),
                        (const uint32_t*)r->editSelected, (uint32_t)edit_words(r), r->editCountsBounds);
     GS_HIP(hipGetLastError());
     uint32_t res[9];
@@ -309,9 +430,63 @@ int32_t gs_renderer_edit_download_bits(gs_renderer* r, uint32_t* selected, uint3
     return GS_OK;
 }
 
+int32_t gs_renderer_edit_store_pos_mouse_down(gs_renderer* r) {
+    if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
+    return edit_store_mouse_down(r, 0);
+}
+
+int32_t gs_renderer_edit_store_other_mouse_down(gs_renderer* r) {
+    if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
+    return edit_store_mouse_down(r, 1);
+}
+
+int32_t gs_renderer_edit_translate_selection(gs_renderer* r, const float delta[3]) {
+    if (!r || !delta) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
+    GS_TRY(edit_ensure(r));
+    gsm::EditXform X;
+    memset(&X, 0, sizeof(X));
+    memcpy(X.delta, delta, 3 * sizeof(float));
+    return edit_transform(r, kEditTranslate, X);
+}
+
+int32_t gs_renderer_edit_rotate_selection(gs_renderer* r, const float center[3], const float local_to_world[16], const float world_to_local[16],
+                                          const float rotation_xyzw[4]) {
+    if (!r || !center || !local_to_world || !world_to_local || !rotation_xyzw) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
+    GS_TRY(edit_ensure(r));
+    if (!r->editPosStored || !r->editOtherStored)                  // "should have captured initial state" (:859)
+        return fail(GS_ERR_INVALID_ARGUMENT, "rotate: the mouse-down copies of pos and other have not been stored");
+    gsm::EditXform X;
+    memset(&X, 0, sizeof(X));
+    edit_xform_matrices(X, center, local_to_world, world_to_local);
+    memcpy(X.delta, rotation_xyzw, 4 * sizeof(float));
+    return edit_transform(r, kEditRotate, X);
+}
+
+int32_t gs_renderer_edit_scale_selection(gs_renderer* r, const float center[3], const float local_to_world[16], const float world_to_local[16],
+                                         const float scale[3]) {
+    if (!r || !center || !local_to_world || !world_to_local || !scale) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
+    GS_TRY(edit_ensure(r));
+    if (!r->editPosStored) return fail(GS_ERR_INVALID_ARGUMENT, "scale: the mouse-down copy of pos has not been stored");      // :880
+    gsm::EditXform X;
+    memset(&X, 0, sizeof(X));
+    edit_xform_matrices(X, center, local_to_world, world_to_local);
+    memcpy(X.delta, scale, 3 * sizeof(float));
+    return edit_transform(r, kEditScale, X);
+}
+
+int32_t gs_renderer_edit_download_pos_other(gs_renderer* r, void* pos, size_t pos_bytes, void* other, size_t other_bytes) {
+    if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
+    if ((pos && pos_bytes > r->asset->sizes[0]) || (other && other_bytes > r->asset->sizes[1])) return fail(GS_ERR_INVALID_ARGUMENT, "more bytes asked for than the blob holds");
+    GS_HIP(hipSetDevice(r->ctx->device));
+    if (pos && pos_bytes) GS_HIP(hipMemcpyAsync(pos, edit_current_blob(r, 0), pos_bytes, hipMemcpyDeviceToHost, r->ctx->stream));
+    if (other && other_bytes) GS_HIP(hipMemcpyAsync(other, edit_current_blob(r, 1), other_bytes, hipMemcpyDeviceToHost, r->ctx->stream));
+    GS_HIP(hipStreamSynchronize(r->ctx->stream));
+    return GS_OK;
+}
+
 int32_t gs_renderer_edit_release(gs_renderer* r) {
     if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
-    if (!r->editSelected) return GS_OK;
+    if (!r->editSelected && !r->editPosStored && !r->editOtherStored) return GS_OK;
     GS_HIP(hipSetDevice(r->ctx->device));
     GS_HIP(hipStreamSynchronize(r->ctx->stream));
     edit_free(r);

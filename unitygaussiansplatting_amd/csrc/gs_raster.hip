@@ -1609,7 +1609,7 @@ int32_t enqueue_draw(gs_renderer* r, const gs_frame_params* p, gs_target* rt) {
     if (rt->sceneDepth) {
         gsm::FrameConsts fc;
         flatten_params(p, fc);
-        hipLaunchKernelGGL(splat_depth_kernel, dim3(div_up(r->n, 256)), dim3(256), 0, st, r->asset->view, fc, (const uint32_t*)r->visMask.get(), r->recW);
+        hipLaunchKernelGGL(splat_depth_kernel, dim3(div_up(r->n, 256)), dim3(256), 0, st, asset_view(r), fc, (const uint32_t*)r->visMask.get(), r->recW);
     }
 #define GS_LAUNCH_BLEND_S(M, D, WL, HL) hipLaunchKernelGGL((blend_kernel<M, D, WL, HL>), dim3(numTiles), dim3(64u << (WL + HL - 6)), 0, st, r->pairVals, tileStart, tileEnd, \
                                              tileOrder, ds.costWrite, r->recs, rt->rgba16f, rc, dstIsZero, r->recW, rt->sceneDepth, \
@@ -1635,7 +1635,7 @@ int32_t enqueue_draw(gs_renderer* r, const gs_frame_params* p, gs_target* rt) {
 int32_t enqueue_debug_boxes(gs_renderer* r, const gs_frame_params* p, gs_target* rt, bool chunks) {
     gs_context* ctx = r->ctx;
     hipStream_t st = ctx->stream;
-    const gsm::AssetView& a = r->asset->view;
+    const gsm::AssetView a = asset_view(r);
     const uint32_t count = chunks ? a.chunkCount : r->n;
     if (chunks && count == 0) return GS_OK;                      // m_GpuChunksValid == false: instanceCount = 0 (GaussianSplatRenderer.cs:161-162)
     if (chunks && (uint64_t)count * 256u < (uint64_t)r->n) return fail(GS_ERR_INVALID_ASSET, "chunk blob smaller than the splat count");
@@ -1690,10 +1690,10 @@ int32_t enqueue_debug_points(gs_renderer* r, const gs_frame_params* p, gs_target
     gsm::FrameConsts c;
     flatten_params(p, c);
     prof_record(r, 3);
-    hipLaunchKernelGGL(debug_points_kernel, dim3(div_up(r->n, 256)), dim3(256), 0, st, r->asset->view, c, 0.5f * r->pointDisplaySize, rt->width, rt->height,
+    hipLaunchKernelGGL(debug_points_kernel, dim3(div_up(r->n, 256)), dim3(256), 0, st, asset_view(r), c, 0.5f * r->pointDisplaySize, rt->width, rt->height,
                        rt->sceneDepth, rt->zbuf);
     prof_record(r, 5);
-    hipLaunchKernelGGL(debug_points_resolve_kernel, dim3(div_up(numPix, 256)), dim3(256), 0, st, r->asset->view, numPix, r->renderMode == GS_RENDER_DEBUG_POINT_INDICES ? 1 : 0,
+    hipLaunchKernelGGL(debug_points_resolve_kernel, dim3(div_up(numPix, 256)), dim3(256), 0, st, asset_view(r), numPix, r->renderMode == GS_RENDER_DEBUG_POINT_INDICES ? 1 : 0,
                        rt->zbuf, rt->rgba16f);
     prof_record(r, 6);
     GS_HIP(hipGetLastError());

@@ -517,7 +517,7 @@ int32_t enqueue_tie_fix_full(gs_renderer* r, const uint32_t* keys, uint32_t* idx
     tie_history(r, H);
     const uint32_t n = r->n;
     const uint32_t tgrid = max(1u, min(div_up(n, (uint32_t)TIE_SEG), (uint32_t)r->ctx->cuCount * 8u));
-    hipLaunchKernelGGL(tie_fix_kernel<TB_POSITION>, dim3(tgrid), dim3(TIE_THREADS), 0, r->ctx->stream, r->asset->view, H, keys, idx, (const uint32_t*)nullptr, n,
+    hipLaunchKernelGGL(tie_fix_kernel<TB_POSITION>, dim3(tgrid), dim3(TIE_THREADS), 0, r->ctx->stream, asset_view(r), H, keys, idx, (const uint32_t*)nullptr, n,
                        (VisControl*)nullptr, (const uint32_t*)nullptr, r->depthSort.altKeys, r->depthSort.altVals);      // (the sort's ping-pong buffers are free again: per-splat scratch)
     GS_HIP(hipGetLastError());
     return GS_OK;
@@ -527,7 +527,7 @@ int32_t enqueue_visible_sort(gs_renderer* r) {
     gs_context* ctx = r->ctx;
     hipStream_t st = ctx->stream;
     GS_TRY(vis_alloc(r));
-    const gsm::AssetView& a = r->asset->view;
+    const gsm::AssetView a = asset_view(r);
     const uint32_t n = r->n;
     const uint32_t words = div_up(n, 64u);
     if (!r->visBaseIdentity && !r->visRankValid) {               // the base is a real order buffer: its inverse ends the tie chain

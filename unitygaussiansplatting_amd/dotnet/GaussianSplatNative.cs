@@ -101,6 +101,13 @@ namespace GaussianSplatting.Runtime
         [DllImport(Lib)] public static extern int gs_renderer_edit_upload_selected_bits(IntPtr renderer, uint[] words, UIntPtr wordCount);
         [DllImport(Lib)] public static extern int gs_renderer_edit_download_bits(IntPtr renderer, uint[] selected, uint[] selectedMouseDown, uint[] deleted, UIntPtr wordCount);
         [DllImport(Lib)] public static extern int gs_renderer_edit_release(IntPtr renderer);
+        // moving the selection (copy-on-write of the renderer's pos / other blobs); matrices row-major, quaternion x y z w
+        [DllImport(Lib)] public static extern int gs_renderer_edit_store_pos_mouse_down(IntPtr renderer);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_store_other_mouse_down(IntPtr renderer);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_translate_selection(IntPtr renderer, float[] delta3);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_rotate_selection(IntPtr renderer, float[] center3, float[] localToWorld16, float[] worldToLocal16, float[] rotationXyzw4);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_scale_selection(IntPtr renderer, float[] center3, float[] localToWorld16, float[] worldToLocal16, float[] scale3);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_download_pos_other(IntPtr renderer, IntPtr pos, UIntPtr posBytes, IntPtr other, UIntPtr otherBytes);
         // export (EditExportData, GaussianSplatRenderer.cs:936-958; ExportPlyFile, GaussianSplatRendererEditor.cs:394-445): records of 62 floats = InputSplatData
         public const int ExportRecordBytes = 248;
         [StructLayout(LayoutKind.Sequential)]

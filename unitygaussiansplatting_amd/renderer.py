@@ -223,8 +223,9 @@ class GpuSorting:
 
 
 class GaussianSplatRenderer:
-    """GaussianSplatRenderer component (GaussianSplatRenderer.cs:214-680): the render path, and of the editing half (:705-934) selection and
-    deletion -- Edit* below.  Selected splats are not highlighted: selection has no visual effect, only deletion changes a frame."""
+    """GaussianSplatRenderer component (GaussianSplatRenderer.cs:214-680): the render path, and of the editing half (:705-934) selection,
+    deletion and moving / rotating / scaling the selection -- Edit* below.  Selected splats are not highlighted: selection has no visual
+    effect, only deletion and the transforms change a frame."""
 
     def __init__(self, ctx: GpuContext, asset: Optional[GaussianSplatAsset] = None, transform: Optional[Transform] = None):
         self.ctx = ctx
@@ -255,6 +256,8 @@ class GaussianSplatRenderer:
         self.m_Registered = False
         # edit state (:273-277, 705-740)
         self.m_GpuEditSelected = False            # the native renderer's edit buffers exist (EnsureEditingBuffers)
+        self.m_GpuEditPosMouseDown = False        # EditStorePosMouseDown / EditStoreOtherMouseDown have run (:794-809)
+        self.m_GpuEditOtherMouseDown = False
         self.editSelectedSplats = 0
         self.editDeletedSplats = 0
         self.editCutSplats = 0
@@ -316,9 +319,9 @@ class GaussianSplatRenderer:
     def DisposeResourcesForAsset(self) -> None:     # :527-565
         l = _lib.lib()
         if self._r_h:
-            if self.m_GpuEditSelected:
+            if self.m_GpuEditSelected or self.m_GpuEditPosMouseDown or self.m_GpuEditOtherMouseDown:
                 l.gs_renderer_edit_release(self._r_h)   # DisposeBuffer(ref m_GpuEditSelected) ..., :547-553
-            self.m_GpuEditSelected = False
+            self.m_GpuEditSelected = self.m_GpuEditPosMouseDown = self.m_GpuEditOtherMouseDown = False
             self.editModified = False
             l.gs_renderer_destroy(self._r_h)
             self._r_h = C.c_void_p()
@@ -480,6 +483,57 @@ class GaussianSplatRenderer:
         w = np.ascontiguousarray(bits, np.uint32)
         check(_lib.lib().gs_renderer_edit_upload_selected_bits(self._r_h, w.ctypes.data, len(w)), "gs_renderer_edit_upload_selected_bits")
         self.UpdateEditCountsAndBounds()
+
+    # -- editing: moving the selection (:794-809, 842-894) -----------------------------------------------------------
+    def EditStorePosMouseDown(self) -> None:        # :794-801
+        check(_lib.lib().gs_renderer_edit_store_pos_mouse_down(self._r_h), "gs_renderer_edit_store_pos_mouse_down")
+        self.m_GpuEditPosMouseDown = True
+
+    def EditStoreOtherMouseDown(self) -> None:      # :802-809
+        check(_lib.lib().gs_renderer_edit_store_other_mouse_down(self._r_h), "gs_renderer_edit_store_other_mouse_down")
+        self.m_GpuEditOtherMouseDown = True
+
+    def EditTranslateSelection(self, localSpacePosDelta) -> None:      # :842-854
+        if not self.EnsureEditingBuffers():
+            return
+        d = np.ascontiguousarray(localSpacePosDelta, np.float32).reshape(3)
+        check(_lib.lib().gs_renderer_edit_translate_selection(self._r_h, _fptr(d)), "gs_renderer_edit_translate_selection")
+        self.UpdateEditCountsAndBounds()
+        self.editModified = True
+
+    def EditRotateSelection(self, localSpaceCenter, localToWorld, worldToLocal, rotation) -> None:      # :856-874
+        """localToWorld / worldToLocal: 4x4 matrices as camera.Transform hands them out; rotation: a quaternion x y z w"""
+        if not self.EnsureEditingBuffers():
+            return
+        if not self.m_GpuEditPosMouseDown or not self.m_GpuEditOtherMouseDown:
+            return                                  # should have captured initial state
+        c = np.ascontiguousarray(localSpaceCenter, np.float32).reshape(3)
+        l2w = np.ascontiguousarray(localToWorld, np.float32).reshape(16)
+        w2l = np.ascontiguousarray(worldToLocal, np.float32).reshape(16)
+        q = np.ascontiguousarray(rotation, np.float32).reshape(4)
+        check(_lib.lib().gs_renderer_edit_rotate_selection(self._r_h, _fptr(c), _fptr(l2w), _fptr(w2l), _fptr(q)), "gs_renderer_edit_rotate_selection")
+        self.UpdateEditCountsAndBounds()
+        self.editModified = True
+
+    def EditScaleSelection(self, localSpaceCenter, localToWorld, worldToLocal, scale) -> None:      # :877-894
+        if not self.EnsureEditingBuffers():
+            return
+        if not self.m_GpuEditPosMouseDown:
+            return                                  # should have captured initial state
+        c = np.ascontiguousarray(localSpaceCenter, np.float32).reshape(3)
+        l2w = np.ascontiguousarray(localToWorld, np.float32).reshape(16)
+        w2l = np.ascontiguousarray(worldToLocal, np.float32).reshape(16)
+        v = np.ascontiguousarray(scale, np.float32).reshape(3)
+        check(_lib.lib().gs_renderer_edit_scale_selection(self._r_h, _fptr(c), _fptr(l2w), _fptr(w2l), _fptr(v)), "gs_renderer_edit_scale_selection")
+        self.UpdateEditCountsAndBounds()
+        self.editModified = True
+
+    def DownloadPosOther(self) -> Tuple[np.ndarray, np.ndarray]:
+        """The renderer's current pos / other blobs as bytes (its private copies once it has been transformed, else the asset's).  Blocks."""
+        a = self.m_Asset
+        pos, other = np.zeros(len(a.posData), np.uint8), np.zeros(len(a.otherData), np.uint8)
+        check(_lib.lib().gs_renderer_edit_download_pos_other(self._r_h, pos.ctypes.data, pos.nbytes, other.ctypes.data, other.nbytes), "gs_renderer_edit_download_pos_other")
+        return pos, other
 
     # -- editing: export (:936-958; GaussianSplatRendererEditor.cs:394-445) ------------------------------------------
     def ExportParams(self, bakeTransform: bool) -> gs_export_params:
