@@ -307,8 +307,7 @@ int32_t gs_renderer_set_deleted_bits(gs_renderer* r, const uint32_t* words, size
  * the first delete, and read as zeros while it does not exist.  Every kernel tests the splats against the renderer's current
  * gs_renderer_set_cutouts list (IsSplatCut), as the reference's do.
  * Selection has NO VISUAL EFFECT: the reference's highlight of selected splats (RenderGaussianSplats.shader:63-73,87-101) is not built;
- * only deletion and the transforms below change a frame.  Copying splats and changing their number (CSCopySplats, EditSetSplatCount) are
- * not built either: they need a writable colour texture and SH blob and a change of N.  Exporting only reads the blobs: see below.
+ * only deletion, the transforms and the merge below change a frame.  Exporting only reads the blobs: see below.
  * Two literal quirks of the reference are kept: select-all / invert set the bits of the last word beyond N and the counts include them
  * (N = 33: select all reports 64 selected), and a splat whose pixel position is NaN is inside every rectangle.
  * The mutating calls are asynchronous on the context's stream like every other call; the info / download calls block.  Selection lives
@@ -385,6 +384,42 @@ int32_t gs_renderer_edit_export_data(gs_renderer* r, const gs_export_params* p, 
 int32_t gs_renderer_edit_export_alive(gs_renderer* r, const gs_export_params* p, void* out, size_t capacity_records, uint32_t* alive);
 /* ExportPlyFile: the reference's header + the alive records.  On an error the partially written file is removed. */
 int32_t gs_renderer_edit_export_ply(gs_renderer* r, const gs_export_params* p, const char* path, uint32_t* alive);
+
+/* ---- merge: EditSetSplatCount / EditCopySplatsInto / EditCopySplats (GaussianSplatRenderer.cs:960-1075), CSCopySplats
+ * (SplatUtilities.compute:675-758); the editor's MergeSplatObjects (GaussianSplatRendererEditor.cs:213-235) is host code over the two
+ * (additions to ABI 9) ----
+ * The kernel decodes source splats of any format, applies the copy transform (position by the matrix, rotation by `rotation` after the axis
+ * flips of a negative `scale`, scale by |scale|, SH rotated by the matrix' rotation: the export's bake) and writes records in the fixed
+ * VeryHigh layout: pos 12 B, other 16 B (Norm10 rotation word + fp32 scale), an fp32 RGBA texel at the Morton position of the destination
+ * index, a 192-byte SH record whose last 12 bytes are not written.  The library takes matrix, rotation and scale as given
+ * (_CopyTransformMatrix / Rotation / Scale); it does not derive them.  Kept literally: the kernel bounds-checks src_start + i and reads ITS
+ * deleted bit but loads splat i (both callers of the reference pass src_start = 0); cut splats are copied like any other; a deleted source bit
+ * is OR-ed into the destination's word and never cleared.  count is clamped at either renderer's end.
+ * The destination must be chunk-less with GS_VECTOR_FLOAT32 pos / scale, fp32 SH and GS_COLOR_FLOAT32X4 colour (the reference tests only
+ * chunkData != null, which its importer makes equivalent), else GS_ERR_INVALID_ARGUMENT with nothing changed.  The asset stays immutable:
+ * the destination's four blobs become private to the renderer on its first copy (copy-on-write), all four at once on a resize.
+ * gs_renderer_edit_set_splat_count: new zero-filled blobs, deleted and selection buffers of new_count splats, the old splats copied into
+ * them (p == NULL: the exact identity), and every per-N buffer replaced: afterwards the renderer is in the state of a freshly created one of
+ * new_count splats over those blobs with the same deleted bits -- identity order, no valid view, an empty sort history, no mouse-down copies --
+ * and its settings (blend / render / sort mode, tile shape, history limit, cutouts, profiling, reserved pairs, frames in flight) kept.  It
+ * synchronises the context and its lanes and BLOCKS.  A count outside [1, 2^30], a lane handle or a failed gate: GS_ERR_INVALID_ARGUMENT;
+ * new_count == the current count: GS_OK, nothing done.  Everything new is allocated before anything old is released: on
+ * GS_ERR_OUT_OF_MEMORY the renderer is unchanged (but for lanes that could not be made again).
+ * gs_renderer_edit_copy_splats_into: asynchronous on the destination's stream, ordered like a transform (sorts, GS_SORT_VISIBLE's history,
+ * frames in flight) and, where the two renderers live on different contexts of one GPU, against the source's stream by events in both
+ * directions.  src == dst, a lane handle or renderers on different GPUs: GS_ERR_INVALID_ARGUMENT. */
+typedef struct gs_copy_params {
+    float matrix[16];                   /* _CopyTransformMatrix = dst.worldToLocal x src.localToWorld, row-major */
+    float rotation[4];                  /* _CopyTransformRotation x y z w (Matrix4x4.rotation of it) */
+    float scale[3];                     /* _CopyTransformScale (Matrix4x4.lossyScale of it) */
+} gs_copy_params;
+int32_t gs_renderer_splat_count(const gs_renderer* r, uint32_t* out);           /* m_SplatCount: the asset's until a resize */
+int32_t gs_renderer_edit_set_splat_count(gs_renderer* r, uint32_t new_count, const gs_copy_params* p);          /* :960-1031 */
+int32_t gs_renderer_edit_copy_splats_into(gs_renderer* src, gs_renderer* dst, const gs_copy_params* p,
+                                          uint32_t src_start, uint32_t dst_start, uint32_t count);               /* :1033-1075 */
+/* the renderer's CURRENT four blobs (private copies where they exist, else the asset's); any pointer may be NULL; blocks */
+int32_t gs_renderer_edit_download_splat_data(gs_renderer* r, void* pos, size_t pos_bytes, void* other, size_t other_bytes,
+                                             void* color, size_t color_bytes, void* sh, size_t sh_bytes);
 
 /* m_RenderMode + m_PointDisplaySize (GaussianSplatRenderer.cs:241-242; material choice :126-131).  DebugPoints / DebugPointIndices
  * (GaussianDebugRenderPoints.shader) draw every splat as an opaque screen-space square of `point_display_size` pixels, nearest

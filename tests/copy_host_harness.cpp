@@ -1,0 +1,81 @@
+// Test-only: the merge's per-splat arithmetic (csrc/gs_device_math.h: CopySplat over LoadSplatDataFull, the shared bake of the export, CalcSHRot,
+// PackSmallest3Rotation, EncodeQuatToNorm10) compiled for the HOST, so that tests/test_copy_model.py can hold it to tests/copy_model.py bit for bit
+// on a box without a GPU.  Never part of the shipped library.  With -DCOPY_HARNESS_MAIN it is a stand-alone program (its own main) that copies a
+// small all-fp32 asset it makes itself and checks the identity's known answer: the form a sanitizer build runs.
+#include "../include/gsplat_c.h"
+#include "../unitygaussiansplatting_amd/csrc/gs_device_math.h"
+
+extern "C" {
+uint32_t ch_sizes(uint32_t which) { return which == 0 ? (uint32_t)sizeof(gs_copy_params) : (which == 1 ? (uint32_t)sizeof(gsm::CopyXform) : (uint32_t)sizeof(gsm::CopyRec)); }
+
+// the records of the splats [first, first + n) of the asset: pos n x 3 floats, other n x 4 words, texel n x 4 floats, sh n x 45 floats.  p == NULL: the exact identity.
+void ch_copy(const gs_asset_desc* d, const gs_copy_params* p, uint32_t first, uint32_t n, float* pos, uint32_t* other, float* texel, float* sh) {
+    gsm::AssetView a;
+    a.pos = (const uint8_t*)d->pos_data; a.other = (const uint8_t*)d->other_data; a.color = (const uint8_t*)d->color_data;
+    a.sh = (const uint8_t*)d->sh_data; a.chunk = (const uint8_t*)d->chunk_data;
+    a.n = d->splat_count; a.posFmt = d->pos_format; a.scaleFmt = d->scale_format; a.colorFmt = d->color_format; a.shFmt = d->sh_format;
+    a.chunkCount = (d->chunk_data && d->chunk_size) ? (uint32_t)(d->chunk_size / 64) : 0;
+    static const gs_copy_params kIdentity = { { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 }, { 0, 0, 0, 1 }, { 1, 1, 1 } };
+    if (!p) p = &kIdentity;
+    gsm::CopyXform X;
+    memcpy(X.m, p->matrix, sizeof(X.m));
+    memcpy(X.rot, p->rotation, sizeof(X.rot));
+    memcpy(X.scale, p->scale, sizeof(X.scale));
+    gsm::CalcSHRot(p->matrix, X.sh);
+    for (uint32_t k = 0; k < n; ++k) {
+        const uint32_t i = first + k;
+        gsm::CopyRec r;
+        gsm::CopySplat(a, X, i, i >> 8, r);                        // (the kernel passes the workgroup's chunk)
+        pos[k * 3] = r.pos.x; pos[k * 3 + 1] = r.pos.y; pos[k * 3 + 2] = r.pos.z;
+        other[k * 4] = r.rot; other[k * 4 + 1] = gsm::f2u(r.scale.x); other[k * 4 + 2] = gsm::f2u(r.scale.y); other[k * 4 + 3] = gsm::f2u(r.scale.z);
+        texel[k * 4] = r.color.x; texel[k * 4 + 1] = r.color.y; texel[k * 4 + 2] = r.color.z; texel[k * 4 + 3] = r.color.w;
+        for (int c = 0; c < 15; ++c) { sh[k * 45 + 3 * c] = r.sh[c].x; sh[k * 45 + 3 * c + 1] = r.sh[c].y; sh[k * 45 + 3 * c + 2] = r.sh[c].z; }
+    }
+}
+}
+
+#ifdef COPY_HARNESS_MAIN
+#include <cstdio>
+#include <vector>
+int main() {
+    const uint32_t n = 300;
+    const size_t texels = (size_t)2048 * 16;
+    std::vector<float> pos(n * 3), color(texels * 4, 0.0f), sh(n * 48, 0.0f);
+    std::vector<uint32_t> other(n * 4 + 4, 0u);
+    uint32_t seed = 12345u;
+    auto rnd = [&]() { seed = seed * 1664525u + 1013904223u; return (float)(seed >> 8) * (1.0f / 16777216.0f) + 0.25f; };      // [0.25, 1.25): no zero, no NaN
+    for (uint32_t i = 0; i < n; ++i) {
+        for (int c = 0; c < 3; ++c) pos[i * 3 + c] = rnd();
+        other[i * 4] = gsm::EncodeQuatToNorm10(gsm::PackSmallest3Rotation({ 0.1f, 0.2f, 0.3f, 0.9f }));
+        for (int c = 0; c < 3; ++c) other[i * 4 + 1 + c] = gsm::f2u(rnd());
+        uint32_t px, py;
+        gsm::SplatIndexToPixelIndex(i, px, py);
+        for (int c = 0; c < 4; ++c) color[((size_t)py * 2048 + px) * 4 + c] = rnd();
+        for (int c = 0; c < 45; ++c) sh[i * 48 + c] = rnd();
+    }
+    gs_asset_desc d;
+    memset(&d, 0, sizeof(d));
+    d.splat_count = n;
+    d.pos_data = pos.data(); d.pos_size = pos.size() * 4;
+    d.other_data = other.data(); d.other_size = (uint64_t)n * 16;
+    d.color_data = color.data(); d.color_size = color.size() * 4;
+    d.sh_data = sh.data(); d.sh_size = sh.size() * 4;
+    std::vector<float> oPos(n * 3), oTex(n * 4), oSh(n * 45);
+    std::vector<uint32_t> oOther(n * 4);
+    ch_copy(&d, nullptr, 0, n, oPos.data(), oOther.data(), oTex.data(), oSh.data());
+    int bad = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        bad += memcmp(&oPos[i * 3], &pos[i * 3], 12) != 0;
+        bad += memcmp(&oOther[i * 4 + 1], &other[i * 4 + 1], 12) != 0;
+        bad += memcmp(&oSh[i * 45], &sh[i * 48], 180) != 0;
+        uint32_t px, py;
+        gsm::SplatIndexToPixelIndex(i, px, py);
+        bad += memcmp(&oTex[i * 4], &color[((size_t)py * 2048 + px) * 4], 16) != 0;
+    }
+    // a mirrored, non-uniform transform: only that it runs clean; the bits are test_copy_model.py's business
+    const gs_copy_params p = { { 0.f, -1.5f, 0.f, 0.3f, -0.75f, 0.f, 0.f, -0.2f, 0.f, 0.f, 2.f, 0.5f, 0.f, 0.f, 0.f, 1.f }, { 0.f, 0.f, 0.70710678f, 0.70710678f }, { -0.75f, 1.5f, 2.f } };
+    ch_copy(&d, &p, 5, n - 5, oPos.data(), oOther.data(), oTex.data(), oSh.data());
+    printf(bad ? "copy harness: %d mismatches\n" : "copy harness ok\n", bad);
+    return bad != 0;
+}
+#endif

@@ -61,6 +61,10 @@ class gs_export_params(C.Structure):     # what CSExportData reads of its dispat
                 ("bake_transform", C.c_uint32)]
 
 
+class gs_copy_params(C.Structure):       # what CSCopySplats reads of its dispatch (gs_renderer_edit_set_splat_count / _copy_splats_into)
+    _fields_ = [("matrix", C.c_float * 16), ("rotation", C.c_float * 4), ("scale", C.c_float * 3)]
+
+
 class gs_import_input(C.Structure):
     _fields_ = [("splat_count", C.c_uint32), ("pos", C.c_void_p), ("dc0", C.c_void_p), ("sh", C.c_void_p),
                 ("opacity", C.c_void_p), ("scale", C.c_void_p), ("rot", C.c_void_p)]

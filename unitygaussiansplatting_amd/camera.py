@@ -71,6 +71,38 @@ def look_rotation(forward: Sequence[float], up: Sequence[float]) -> np.ndarray:
     return np.stack([x, y, z], axis=1)
 
 
+def mat3_to_quat(R: np.ndarray) -> np.ndarray:
+    """The unit quaternion (xyzw, w >= 0 where it is the largest component) of a rotation matrix, float64: the branch on the largest of
+    w, x, y, z, so that no branch divides by a small number."""
+    R = np.asarray(R, np.float64)
+    t = [R[0, 0] + R[1, 1] + R[2, 2], R[0, 0] - R[1, 1] - R[2, 2], R[1, 1] - R[0, 0] - R[2, 2], R[2, 2] - R[0, 0] - R[1, 1]]
+    k = int(np.argmax(t))
+    r = math.sqrt(max(0.0, 1.0 + t[k])) * 2.0          # 4 x the largest component
+    if k == 0:
+        q = ((R[2, 1] - R[1, 2]) / r, (R[0, 2] - R[2, 0]) / r, (R[1, 0] - R[0, 1]) / r, 0.25 * r)
+    elif k == 1:
+        q = (0.25 * r, (R[0, 1] + R[1, 0]) / r, (R[0, 2] + R[2, 0]) / r, (R[2, 1] - R[1, 2]) / r)
+    elif k == 2:
+        q = ((R[0, 1] + R[1, 0]) / r, 0.25 * r, (R[1, 2] + R[2, 1]) / r, (R[0, 2] - R[2, 0]) / r)
+    else:
+        q = ((R[0, 2] + R[2, 0]) / r, (R[1, 2] + R[2, 1]) / r, 0.25 * r, (R[1, 0] - R[0, 1]) / r)
+    q = np.asarray(q, np.float64)
+    return q / np.linalg.norm(q)
+
+
+def matrix_rotation_scale(m: np.ndarray):
+    """(rotation xyzw, scale xyz) of a 4x4 matrix, float32: what EditCopySplats obtains from Unity as Matrix4x4.rotation and Matrix4x4.lossyScale
+    (GaussianSplatRenderer.cs:1053-1054).  scale = the lengths of the columns of the 3x3 part, the x component negated when the determinant is
+    negative (a mirrored matrix); rotation = the quaternion of the matrix whose columns are those of the 3x3 part divided by that scale.  Host
+    code, evaluated in float64 and rounded once; the library takes the three values as given."""
+    M = np.asarray(m, np.float64)[:3, :3]
+    s = np.linalg.norm(M, axis=0)
+    if np.linalg.det(M) < 0.0:
+        s[0] = -s[0]
+    q = mat3_to_quat(M / s[None, :])
+    return q.astype(f32), s.astype(f32)
+
+
 @dataclass
 class Camera:
     """Perspective camera.  `LookAt` builds the pose; Unity's camera-space looks down -Z in worldToCameraMatrix.

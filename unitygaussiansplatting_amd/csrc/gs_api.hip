@@ -320,7 +320,7 @@ int32_t gs_renderer_set_frames_in_flight(gs_renderer* r, int32_t frames) {
             c->internalLane = true;
             if (c->counted) { g_liveContexts[c->device % kMaxTrackedDevices].fetch_sub(1, std::memory_order_relaxed); c->counted = false; }
         }
-        if (rc == GS_OK) rc = gs_renderer_create(c, r->asset, &L);
+        if (rc == GS_OK) rc = renderer_create_n(c, r->asset, r->n, &L);      // (N is the owner's: a resize may have changed it)
         if (rc == GS_OK) {
             L->laneOf = r;
             hipError_t e = L->evTargetFree.create(hipEventDisableTiming);
@@ -382,20 +382,25 @@ static int32_t renderer_init(gs_renderer* r) {
     return mark_order_use(r);                                    // the first sort (second queue) waits for these initialisations
 }
 
+// n: the asset's, or the owner's for a lane of a resized renderer, or the new count of a resize
+extern "C++" int32_t gs::renderer_create_n(gs_context* ctx, gs_asset* asset, uint32_t n, gs_renderer** out) {
+    GS_TRY(bind_device(ctx));
+    gs_renderer* r = new (std::nothrow) gs_renderer();
+    if (!r) return fail(GS_ERR_OUT_OF_MEMORY, "host allocation");
+    r->ctx = ctx; r->asset = asset; r->n = n;
+    const int32_t rc = renderer_init(r);
+    if (rc != GS_OK) { gs_renderer_destroy(r); return rc; }
+    *out = r;
+    return GS_OK;
+}
+
 int32_t gs_renderer_create(gs_context* ctx, gs_asset* asset, gs_renderer** out) {
     if (!ctx || !asset || !out) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
     *out = nullptr;
     // the asset's blobs are immutable: renderers of OTHER contexts on the same GPU may read them too (several frames / views in flight on
     // several streams, one copy of the asset); the caller keeps the asset alive, as for any renderer
     if (asset->ctx != ctx && asset->ctx->device != ctx->device) return fail(GS_ERR_INVALID_ARGUMENT, "asset lives on another GPU (gs_asset_replicate / gs_asset_broadcast)");
-    GS_TRY(bind_device(ctx));
-    gs_renderer* r = new (std::nothrow) gs_renderer();
-    if (!r) return fail(GS_ERR_OUT_OF_MEMORY, "host allocation");
-    r->ctx = ctx; r->asset = asset; r->n = asset->view.n;
-    const int32_t rc = renderer_init(r);
-    if (rc != GS_OK) { gs_renderer_destroy(r); return rc; }
-    *out = r;
-    return GS_OK;
+    return renderer_create_n(ctx, asset, asset->view.n, out);
 }
 
 int32_t gs_renderer_destroy(gs_renderer* r) {

@@ -229,6 +229,9 @@ struct gs_target {
     bool exposed = false;                   // gs_target_device_ptr handed the memory out: the host's own work on the context's stream may touch it (and the pointer stays put)
 };
 
+// gs_renderer_edit_set_splat_count (gs_copy.hip) builds a second gs_renderer of the new N and std::swap()s the two WHOLE structs.  So: no member may
+// point into the struct itself, and a member that is a SETTING (something a host set and expects to keep) must be carried over in resize_build() there
+// -- and, where lanes follow it, in gs_renderer_set_frames_in_flight (gs_api.hip) -- or a resize silently resets it.
 struct gs_renderer {
     gs_context* ctx = nullptr;
     gs_asset* asset = nullptr;
@@ -268,6 +271,12 @@ struct gs_renderer {
     // is never written; lanes read their owner's copies in place.
     gs::DevBuf<uint8_t> privPos;            // m_GpuPosData of this renderer
     gs::DevBuf<uint8_t> privOther;          // m_GpuOtherData
+    // ... and of the two the merge writes as well (CSCopySplats; gs_copy.hip): made by the first copy INTO this renderer, or -- all four -- by a resize
+    gs::DevBuf<uint8_t> privColor;          // m_GpuColorData: 2048 x CalcTextureSize(N).h texels of four fp32
+    gs::DevBuf<uint8_t> privSH;             // m_GpuSHData
+    uint64_t privBytes[4] = {0, 0, 0, 0};   // bytes of each private blob (pos, other, color, sh) while it exists: gs::blob_bytes
+    gs::Event evCopySrcReady;               // (on the destination of a copy) source's stream -> this context's: the source's pending edits are done
+    gs::Event evCopyDone;                   // ... and this context's stream -> the source's: the copy kernel has read the source
     gs::DevBuf<uint8_t> editPosMouseDown;   // m_GpuEditPosMouseDown: made only when the position gate can pass
     gs::DevBuf<uint8_t> editOtherMouseDown; // m_GpuEditOtherMouseDown: ... the rotation gate
     bool editPosStored = false, editOtherStored = false;   // EditStorePosMouseDown / EditStoreOtherMouseDown have run since the last release
@@ -405,16 +414,37 @@ int32_t enqueue_resolve(gs_target* t, const float bg[4], bool want8);
 int32_t flush_clear(gs_target* t);          // perform a pending gs_target_clear now
 // edit (gs_edit.hip)
 void edit_free(gs_renderer* r);             // the selection buffers and the mouse-down copies (not deletedBits, not the private blobs, not the edit events)
+int32_t edit_ensure(gs_renderer* r);        // EnsureEditingBuffers: the zeroed selection buffers, made once
+int32_t edit_make_private(gs_renderer* r, int k);   // copy-on-write of blob k (0 pos, 1 other, 2 color, 3 sh) on the context's stream
+int32_t edit_deleted_to_lanes(gs_renderer* r);      // the lanes' copies of the deleted bits follow the owner's, by events
+// what brackets a kernel that rewrites positions (the transforms, the merge): ordering against sorts, GS_SORT_VISIBLE's history and the lanes
+int32_t edit_before_move(gs_renderer* r);
+int32_t edit_after_move(gs_renderer* r);
+// gs_api.hip: a renderer of n splats over `asset` (n != the asset's: a lane of a resized renderer, or the new state of a resize itself)
+int32_t renderer_create_n(gs_context* ctx, gs_asset* asset, uint32_t n, gs_renderer** out);
 // gs_api.hip: order[] stops being the visible-only mode's base / the lanes take over the owner's order
 void vis_base_changed(gs_renderer* r, bool identity);
 int32_t lanes_resync(gs_renderer* r);
-// The asset as THIS renderer sees it: the asset's view with pos / other replaced by the renderer's private copies where they exist.  A lane sees what its
-// owner sees.  Every launch that reads the blobs takes its view from here.
+// The asset as THIS renderer sees it: the asset's view with the blobs replaced by the renderer's private copies where they exist and N the renderer's
+// (a resize changes it).  A lane sees what its owner sees.  Every launch that reads the blobs takes its view from here.
 inline gsm::AssetView asset_view(const gs_renderer* r) {
     const gs_renderer* o = r->laneOf ? r->laneOf : r;
     gsm::AssetView v = r->asset->view;
     if (o->privPos) v.pos = o->privPos;
     if (o->privOther) v.other = o->privOther;
+    if (o->privColor) v.color = o->privColor;
+    if (o->privSH) v.sh = o->privSH;
+    v.n = o->n;
     return v;
+}
+// bytes of blob k (0 pos, 1 other, 2 color, 3 sh) as this renderer sees it
+inline uint64_t blob_bytes(const gs_renderer* r, int k) {
+    const gs_renderer* o = r->laneOf ? r->laneOf : r;
+    const bool priv = k == 0 ? (bool)o->privPos : (k == 1 ? (bool)o->privOther : (k == 2 ? (bool)o->privColor : (bool)o->privSH));
+    return priv ? o->privBytes[k] : r->asset->sizes[k];
+}
+inline const uint8_t* blob_ptr(const gs_renderer* r, int k) {
+    const gsm::AssetView a = asset_view(r);
+    return k == 0 ? a.pos : (k == 1 ? a.other : (k == 2 ? a.color : a.sh));
 }
 } // namespace gs

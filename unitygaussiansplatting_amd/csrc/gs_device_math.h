@@ -1279,30 +1279,35 @@ GS_HD V3 SHDotRow(const V3* v, const float* f, int n) {
     return r;
 }
 
+// The transform CSExportData bakes (SplatUtilities.compute:627-643) and CSCopySplats applies (:699-712), the same text in both: position through the
+// matrix (m: rows 0..2), the axis flips of a negative scale, QuatMul(rot, .), scale *= |scale|, RotateSH with the band matrices of the matrix.
+GS_HD void BakeSplatTransform(SplatFull& s, const float* m, const float* rot, const float* scale, const SHRot& sh) {
+    const V3 pos = s.pos;
+    s.pos = { mrow(m, 0, pos.x, pos.y, pos.z), mrow(m, 1, pos.x, pos.y, pos.z), mrow(m, 2, pos.x, pos.y, pos.z) };
+    // (this only handles axis flips from scale, not any arbitrary scaling: the reference's note)
+    if (scale[0] < 0.0f) { s.rot.y = -s.rot.y; s.rot.z = -s.rot.z; }
+    if (scale[1] < 0.0f) { s.rot.x = -s.rot.x; s.rot.z = -s.rot.z; }
+    if (scale[2] < 0.0f) { s.rot.x = -s.rot.x; s.rot.y = -s.rot.y; }
+    s.rot = QuatMul({ rot[0], rot[1], rot[2], rot[3] }, s.rot);
+    s.scale.x *= fabsf(scale[0]); s.scale.y *= fabsf(scale[1]); s.scale.z *= fabsf(scale[2]);
+    V3 out[15];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out[k] = SHDotRow(s.sh, sh.sh1[k], 3);
+#pragma unroll
+    for (int k = 0; k < 5; ++k) out[3 + k] = SHDotRow(s.sh + 3, sh.sh2[k], 5);
+#pragma unroll
+    for (int k = 0; k < 7; ++k) out[8 + k] = SHDotRow(s.sh + 8, sh.sh3[k], 7);
+#pragma unroll
+    for (int k = 0; k < 15; ++k) s.sh[k] = out[k];
+}
+
 // The body of CSExportData (SplatUtilities.compute:616-673) for one splat: rec = the 62 floats of ExportSplatData = InputSplatData
 // (pos, nor, dc0, 15 R + 15 G + 15 B SH coefficients, opacity, scale, rot wxyz).  pos = LoadSplatPosChunk(a, idx, ci) and cut = IsSplatCut(pos)
 // come from the caller, which needs them before it decides whether the splat is exported at all.
 GS_HD void ExportSplat(const AssetView& a, const ExportXform& X, uint32_t idx, uint32_t ci, const V3& pos, bool cut, float* rec) {
     SplatFull s;
     LoadSplatDataFull(a, idx, ci, pos, s);
-    if (X.bake != 0u) {
-        s.pos = { mrow(X.o2w, 0, pos.x, pos.y, pos.z), mrow(X.o2w, 1, pos.x, pos.y, pos.z), mrow(X.o2w, 2, pos.x, pos.y, pos.z) };
-        // (this only handles axis flips from scale, not any arbitrary scaling: the reference's note)
-        if (X.scale[0] < 0.0f) { s.rot.y = -s.rot.y; s.rot.z = -s.rot.z; }
-        if (X.scale[1] < 0.0f) { s.rot.x = -s.rot.x; s.rot.z = -s.rot.z; }
-        if (X.scale[2] < 0.0f) { s.rot.x = -s.rot.x; s.rot.y = -s.rot.y; }
-        s.rot = QuatMul({ X.rot[0], X.rot[1], X.rot[2], X.rot[3] }, s.rot);
-        s.scale.x *= fabsf(X.scale[0]); s.scale.y *= fabsf(X.scale[1]); s.scale.z *= fabsf(X.scale[2]);
-        V3 out[15];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) out[k] = SHDotRow(s.sh, X.sh.sh1[k], 3);
-#pragma unroll
-        for (int k = 0; k < 5; ++k) out[3 + k] = SHDotRow(s.sh + 3, X.sh.sh2[k], 5);
-#pragma unroll
-        for (int k = 0; k < 7; ++k) out[8 + k] = SHDotRow(s.sh + 8, X.sh.sh3[k], 7);
-#pragma unroll
-        for (int k = 0; k < 15; ++k) s.sh[k] = out[k];
-    }
+    if (X.bake != 0u) BakeSplatTransform(s, X.o2w, X.rot, X.scale, X.sh);
     const float nor = cut ? 1.0f : 0.0f;                           // mark as skipped for export
     rec[0] = s.pos.x; rec[1] = s.pos.y; rec[2] = s.pos.z;
     rec[3] = nor; rec[4] = nor; rec[5] = nor;
@@ -1312,6 +1317,27 @@ GS_HD void ExportSplat(const AssetView& a, const ExportXform& X, uint32_t idx, u
     rec[54] = LogDetFull(s.opacity / fmaxf(1.0f - s.opacity, 1.0e-6f));                 // InvSigmoid
     rec[55] = LogDetFull(s.scale.x); rec[56] = LogDetFull(s.scale.y); rec[57] = LogDetFull(s.scale.z);
     rec[58] = s.rot.w; rec[59] = s.rot.x; rec[60] = s.rot.y; rec[61] = s.rot.z;
+}
+
+// ---- merge: CSCopySplats (SplatUtilities.compute:675-758; kernel in gs_copy.hip) ----------------------------------------------------
+// what the kernel reads of its dispatch: _CopyTransformMatrix (rows 0..2), _CopyTransformRotation (xyzw), _CopyTransformScale, and the band
+// matrices of the matrix (gsm::CalcSHRot, built once per call on the host)
+struct CopyXform { float m[12]; float rot[4]; float scale[3]; SHRot sh; };
+// one destination record in the reference's fixed layout (:714-747): pos 12 B; other 16 B = { rotation word, scale.xyz }; the colour texel
+// (col.rgb, opacity); 15 x 3 fp32 SH coefficients (the 12 bytes that round an SH record up to 192 are not written)
+struct CopyRec { V3 pos; uint32_t rot; V3 scale; V4 color; V3 sh[15]; };
+// The body of CSCopySplats for the splat the kernel LOADS: LoadSplatData(idx) (:697) -- the thread index, not srcIdx; the two callers of the
+// reference pass _CopySrcStartIndex = 0, where they agree -- transformed like a baked export and re-encoded.  No IsSplatCut: cut splats are copied.
+GS_HD void CopySplat(const AssetView& a, const CopyXform& X, uint32_t idx, uint32_t ci, CopyRec& o) {
+    SplatFull s;
+    LoadSplatDataFull(a, idx, ci, LoadSplatPosChunk(a, idx, ci), s);
+    BakeSplatTransform(s, X.m, X.rot, X.scale, X.sh);
+    o.pos = s.pos;
+    o.rot = EncodeQuatToNorm10(PackSmallest3Rotation(s.rot));
+    o.scale = s.scale;
+    o.color = { s.col.x, s.col.y, s.col.z, s.opacity };
+#pragma unroll
+    for (int k = 0; k < 15; ++k) o.sh[k] = s.sh[k];
 }
 
 } // namespace gsm

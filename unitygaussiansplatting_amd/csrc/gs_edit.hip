@@ -11,7 +11,7 @@
 // The last three are the only kernels that write splat data.  The asset's blobs are shared between contexts, lanes and replicas and stay
 // immutable: the first transform whose format gate can pass gives the renderer a private copy of the pos and / or other blob (copy-on-write,
 // gs::asset_view), and from then on every kernel of this renderer and of its lanes reads that copy.  CSExportData only reads: gs_export.hip.
-// Not built: CSCopySplats / EditSetSplatCount (they need a writable colour texture and SH blob and a change of N) and the highlight of
+// CSCopySplats / EditSetSplatCount / EditCopySplatsInto -- the merge -- are gs_copy.hip.  Not built: the highlight of
 // selected splats in the fragment stage (RenderGaussianSplats.shader:63-73,87-101: it replaces a splat's
 // opacity by -1, which here would go through PrepareSplat's cull and footprint bound and the blend's alpha window).  Selection therefore
 // has NO VISUAL EFFECT: only deletion and the transforms change a frame.
@@ -184,7 +184,7 @@ static gsm::EditView edit_view(const gs_renderer* r) {
 }
 
 // EnsureEditingBuffers (GaussianSplatRenderer.cs:767-786) without the deleted buffer, which is made when a delete first needs it
-static int32_t edit_ensure(gs_renderer* r) {
+int32_t edit_ensure(gs_renderer* r) {
     if (r->laneOf) return fail(GS_ERR_INVALID_ARGUMENT, "a lane holds no selection: edit its owner");
     GS_HIP(hipSetDevice(r->ctx->device));
     if (r->editSelected) return GS_OK;
@@ -212,7 +212,7 @@ static inline uint32_t word_grid(const gs_renderer* r) { return (uint32_t)((edit
 // context's stream -- no host synchronisation, and a frame already dealt to a lane keeps the bits of the time it was dealt (its calc_view is
 // ahead of the copy on that stream).  The context's stream then waits for the copies, so that whatever writes or frees the owner's buffer
 // next (another delete, gs_renderer_set_deleted_bits) comes after they have read it.
-static int32_t edit_deleted_to_lanes(gs_renderer* r) {
+int32_t edit_deleted_to_lanes(gs_renderer* r) {
     if (r->lanes.empty()) return GS_OK;
     const size_t bytes = edit_words(r) * 4;
     if (!r->evEditDeleted) GS_HIP(r->evEditDeleted.create(hipEventDisableTiming));
@@ -237,22 +237,20 @@ static inline bool edit_rot_gate(const gs_renderer* r) { const gsm::AssetView& a
 static inline size_t edit_blob_bytes(const gs_renderer* r, int k) { return (size_t)r->n * (k == 0 ? 12u : 16u); }
 
 // the renderer's current pos (k = 0) / other (1) blob, wherever it lives
-static inline const uint8_t* edit_current_blob(const gs_renderer* r, int k) {
-    const gsm::AssetView a = asset_view(r);
-    return k == 0 ? a.pos : a.other;
-}
+static inline const uint8_t* edit_current_blob(const gs_renderer* r, int k) { return blob_ptr(r, k); }
 
-// copy-on-write: the private copy of blob k, made on the context's stream the first time a transform is about to write it.  Padded like an
-// owned upload of the asset (the dword stitching of LoadUInt may touch the dword after the last record).
-static int32_t edit_make_private(gs_renderer* r, int k) {
-    DevBuf<uint8_t>& priv = k == 0 ? r->privPos : r->privOther;
+// copy-on-write: the private copy of blob k (0 pos, 1 other, 2 color, 3 sh), made on the context's stream the first time a transform or a copy
+// is about to write it.  Padded like an owned upload of the asset (the dword stitching of LoadUInt may touch the dword after the last record).
+int32_t edit_make_private(gs_renderer* r, int k) {
+    DevBuf<uint8_t>& priv = k == 0 ? r->privPos : (k == 1 ? r->privOther : (k == 2 ? r->privColor : r->privSH));
     if (priv) return GS_OK;
-    const size_t bytes = (size_t)r->asset->sizes[k];
+    const size_t bytes = (size_t)blob_bytes(r, k);
     DevBuf<uint8_t> b;
     GS_HIP(b.alloc(bytes + 16));
     GS_HIP(hipMemsetAsync(b + bytes, 0, 16, r->ctx->stream));
-    GS_HIP(hipMemcpyAsync(b, r->asset->blobs[k], bytes, hipMemcpyDeviceToDevice, r->ctx->stream));
+    GS_HIP(hipMemcpyAsync(b, blob_ptr(r, k), bytes, hipMemcpyDeviceToDevice, r->ctx->stream));
     priv = std::move(b);
+    r->privBytes[k] = bytes;
     return GS_OK;
 }
 
@@ -269,15 +267,8 @@ static int32_t edit_store_mouse_down(gs_renderer* r, int k) {
     return GS_OK;
 }
 
-// One transform on the context's stream, ordered against everything else that reads the positions:
-//   - a sort still running on the second queue is joined first, and the next one waits for the kernel (CSCalcDistances reads positions);
-//   - GS_SORT_VISIBLE: the recorded sorts are sorts of the OLD positions, so they are carried out first (order[] = the reference's buffer now), and that
-//     order is the new base with an empty history -- from here on the reference, too, stably sorts that buffer by keys of the new positions;
-//   - lanes read the owner's private blobs in place: the context's stream waits for what each lane has been dealt (those frames finish with the old
-//     positions), the kernel runs, and every lane's stream waits for it.  Events only; edit_deleted_to_lanes turned round.
-static int32_t edit_transform(gs_renderer* r, int op, const gsm::EditXform& X) {
-    const bool doPos = edit_pos_gate(r), doRot = op == kEditRotate && edit_rot_gate(r);
-    if (!doPos && !doRot) return GS_OK;                            // neither gate: the reference's kernel writes nothing
+// the first half of the ordering described below: before the kernel that moves splats is enqueued
+int32_t edit_before_move(gs_renderer* r) {
     GS_TRY(join_sort(r));
     if (vis_active(r)) GS_TRY(vis_consolidate(r));
     for (gs_renderer* L : r->lanes) {
@@ -285,17 +276,11 @@ static int32_t edit_transform(gs_renderer* r, int op, const gsm::EditXform& X) {
         GS_HIP(hipEventRecord(L->evEditLaneIdle, L->ctx->stream));
         GS_HIP(hipStreamWaitEvent(r->ctx->stream, L->evEditLaneIdle, 0));
     }
-    if (doPos) GS_TRY(edit_make_private(r, 0));
-    if (doRot) GS_TRY(edit_make_private(r, 1));
-    uint8_t* pos = doPos ? r->privPos.get() : nullptr;
-    uint8_t* other = doRot ? r->privOther.get() : nullptr;
-    const uint8_t* posMD = r->editPosMouseDown, * otherMD = r->editOtherMouseDown;
-    const uint32_t* sel = r->editSelected;
-    const dim3 grid(splat_grid(r)), block(256);
-    if (op == kEditTranslate) hipLaunchKernelGGL(edit_transform_kernel<kEditTranslate>, grid, block, 0, r->ctx->stream, pos, other, posMD, otherMD, sel, r->n, X);
-    else if (op == kEditRotate) hipLaunchKernelGGL(edit_transform_kernel<kEditRotate>, grid, block, 0, r->ctx->stream, pos, other, posMD, otherMD, sel, r->n, X);
-    else hipLaunchKernelGGL(edit_transform_kernel<kEditScale>, grid, block, 0, r->ctx->stream, pos, other, posMD, otherMD, sel, r->n, X);
-    GS_HIP(hipGetLastError());
+    return GS_OK;
+}
+
+// ... and the second: right after it
+int32_t edit_after_move(gs_renderer* r) {
     GS_TRY(mark_order_use(r));
     r->movedSinceView = true;
     for (gs_renderer* L : r->lanes) L->movedSinceView = true;
@@ -309,6 +294,30 @@ static int32_t edit_transform(gs_renderer* r, int op, const gsm::EditXform& X) {
         for (gs_renderer* L : r->lanes) GS_HIP(hipStreamWaitEvent(L->ctx->stream, r->evEditMoved, 0));
     }
     return GS_OK;
+}
+
+// One transform on the context's stream, ordered against everything else that reads the positions:
+//   - a sort still running on the second queue is joined first, and the next one waits for the kernel (CSCalcDistances reads positions);
+//   - GS_SORT_VISIBLE: the recorded sorts are sorts of the OLD positions, so they are carried out first (order[] = the reference's buffer now), and that
+//     order is the new base with an empty history -- from here on the reference, too, stably sorts that buffer by keys of the new positions;
+//   - lanes read the owner's private blobs in place: the context's stream waits for what each lane has been dealt (those frames finish with the old
+//     positions), the kernel runs, and every lane's stream waits for it.  Events only; edit_deleted_to_lanes turned round.
+static int32_t edit_transform(gs_renderer* r, int op, const gsm::EditXform& X) {
+    const bool doPos = edit_pos_gate(r), doRot = op == kEditRotate && edit_rot_gate(r);
+    if (!doPos && !doRot) return GS_OK;                            // neither gate: the reference's kernel writes nothing
+    GS_TRY(edit_before_move(r));
+    if (doPos) GS_TRY(edit_make_private(r, 0));
+    if (doRot) GS_TRY(edit_make_private(r, 1));
+    uint8_t* pos = doPos ? r->privPos.get() : nullptr;
+    uint8_t* other = doRot ? r->privOther.get() : nullptr;
+    const uint8_t* posMD = r->editPosMouseDown, * otherMD = r->editOtherMouseDown;
+    const uint32_t* sel = r->editSelected;
+    const dim3 grid(splat_grid(r)), block(256);
+    if (op == kEditTranslate) hipLaunchKernelGGL(edit_transform_kernel<kEditTranslate>, grid, block, 0, r->ctx->stream, pos, other, posMD, otherMD, sel, r->n, X);
+    else if (op == kEditRotate) hipLaunchKernelGGL(edit_transform_kernel<kEditRotate>, grid, block, 0, r->ctx->stream, pos, other, posMD, otherMD, sel, r->n, X);
+    else hipLaunchKernelGGL(edit_transform_kernel<kEditScale>, grid, block, 0, r->ctx->stream, pos, other, posMD, otherMD, sel, r->n, X);
+    GS_HIP(hipGetLastError());
+    return edit_after_move(r);
 }
 
 static void edit_xform_matrices(gsm::EditXform& X, const float center[3], const float o2w[16], const float w2o[16]) {
@@ -476,7 +485,7 @@ int32_t gs_renderer_edit_scale_selection(gs_renderer* r, const float center[3], 
 
 int32_t gs_renderer_edit_download_pos_other(gs_renderer* r, void* pos, size_t pos_bytes, void* other, size_t other_bytes) {
     if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
-    if ((pos && pos_bytes > r->asset->sizes[0]) || (other && other_bytes > r->asset->sizes[1])) return fail(GS_ERR_INVALID_ARGUMENT, "more bytes asked for than the blob holds");
+    if ((pos && pos_bytes > blob_bytes(r, 0)) || (other && other_bytes > blob_bytes(r, 1))) return fail(GS_ERR_INVALID_ARGUMENT, "more bytes asked for than the blob holds");
     GS_HIP(hipSetDevice(r->ctx->device));
     if (pos && pos_bytes) GS_HIP(hipMemcpyAsync(pos, edit_current_blob(r, 0), pos_bytes, hipMemcpyDeviceToHost, r->ctx->stream));
     if (other && other_bytes) GS_HIP(hipMemcpyAsync(other, edit_current_blob(r, 1), other_bytes, hipMemcpyDeviceToHost, r->ctx->stream));

@@ -115,6 +115,13 @@ namespace GaussianSplatting.Runtime
         [DllImport(Lib)] public static extern int gs_renderer_edit_export_data(IntPtr renderer, ref ExportParams p, IntPtr dst, UIntPtr bytes, int memoryKind);
         [DllImport(Lib)] public static extern int gs_renderer_edit_export_alive(IntPtr renderer, ref ExportParams p, IntPtr dst, UIntPtr capacityRecords, out uint alive);
         [DllImport(Lib)] public static extern int gs_renderer_edit_export_ply(IntPtr renderer, ref ExportParams p, [MarshalAs(UnmanagedType.LPStr)] string path, out uint alive);
+        // merge (EditSetSplatCount / EditCopySplatsInto, GaussianSplatRenderer.cs:960-1075; MergeSplatObjects, GaussianSplatRendererEditor.cs:213-235)
+        [StructLayout(LayoutKind.Sequential)]
+        public unsafe struct CopyParams { public fixed float matrix[16]; public fixed float rotation[4]; public fixed float scale[3]; }
+        [DllImport(Lib)] public static extern int gs_renderer_splat_count(IntPtr renderer, out uint count);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_set_splat_count(IntPtr renderer, uint newCount, IntPtr copyParamsOrZero);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_copy_splats_into(IntPtr src, IntPtr dst, ref CopyParams p, uint srcStart, uint dstStart, uint count);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_download_splat_data(IntPtr renderer, IntPtr pos, UIntPtr posBytes, IntPtr other, UIntPtr otherBytes, IntPtr color, UIntPtr colorBytes, IntPtr sh, UIntPtr shBytes);
         [DllImport(Lib)] public static extern int gs_renderer_set_view_buffer_mode(IntPtr renderer, int everyFrame);
         [DllImport(Lib)] public static extern int gs_renderer_set_blend_mode(IntPtr renderer, int mode);
         [DllImport(Lib)] public static extern int gs_renderer_set_tile_shape(IntPtr renderer, uint tileW, uint tileH);

@@ -18,11 +18,11 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from ._abi import (GS_ERR_PAIR_OVERFLOW, GS_SORT_FULL, GS_SORT_VISIBLE, VIEW_DTYPE, gs_edit_info, gs_export_params, gs_frame_params, gs_frame_stats,
+from ._abi import (GS_ERR_PAIR_OVERFLOW, GS_SORT_FULL, GS_SORT_VISIBLE, VIEW_DTYPE, gs_copy_params, gs_edit_info, gs_export_params, gs_frame_params, gs_frame_stats,
                    gs_stage_times, make_asset_desc)
 from ._lib import GsError, check
-from .asset import GaussianSplatAsset, kCurrentVersion
-from .camera import Camera, Transform, frame_params, sort_matrix
+from .asset import CalcTextureSize, GaussianSplatAsset, kCurrentVersion, kMaxSplats
+from .camera import Camera, Transform, frame_params, mat_mul, matrix_rotation_scale, sort_matrix
 from .cutout import GaussianCutout, shader_data_array
 
 
@@ -223,9 +223,9 @@ class GpuSorting:
 
 
 class GaussianSplatRenderer:
-    """GaussianSplatRenderer component (GaussianSplatRenderer.cs:214-680): the render path, and of the editing half (:705-934) selection,
-    deletion and moving / rotating / scaling the selection -- Edit* below.  Selected splats are not highlighted: selection has no visual
-    effect, only deletion and the transforms change a frame."""
+    """GaussianSplatRenderer component (GaussianSplatRenderer.cs:214-680): the render path, and of the editing half (:705-1075) selection,
+    deletion, moving / rotating / scaling the selection, export and the merge (EditSetSplatCount / EditCopySplatsInto) -- Edit* below.  Selected
+    splats are not highlighted: selection has no visual effect, only deletion, the transforms and the merge change a frame."""
 
     def __init__(self, ctx: GpuContext, asset: Optional[GaussianSplatAsset] = None, transform: Optional[Transform] = None):
         self.ctx = ctx
@@ -251,6 +251,7 @@ class GaussianSplatRenderer:
         self._r_h = C.c_void_p()
         self._keep: list = []
         self.m_SplatCount = 0
+        self.m_Resized = False                    # EditSetSplatCount has replaced the four blobs by private ones of the VeryHigh layout
         self.m_PrevAsset = None
         self.m_PrevHash = None
         self.m_Registered = False
@@ -311,7 +312,7 @@ class GaussianSplatRenderer:
         self.m_Asset = other.m_Asset
         self._asset_h, self._asset_borrowed = other._asset_h, True
         check(_lib.lib().gs_renderer_create(self.ctx._h, self._asset_h, C.byref(self._r_h)), "gs_renderer_create")
-        self.m_SplatCount = other.m_SplatCount
+        self.m_SplatCount = self._native_splat_count()          # the asset's: a resize of `other` is private to it
         self.m_PrevAsset, self.m_PrevHash = other.m_PrevAsset, other.m_PrevHash
         if self.sortMode != SortMode.Full:
             check(_lib.lib().gs_renderer_set_sort_mode(self._r_h, int(self.sortMode)), "gs_renderer_set_sort_mode")
@@ -331,6 +332,7 @@ class GaussianSplatRenderer:
             self._asset_h = C.c_void_p()
             self._asset_borrowed = False
         self.m_SplatCount = 0
+        self.m_Resized = False
 
     def OnEnable(self) -> None:                     # :475-485
         self.m_FrameCounter = 0
@@ -528,12 +530,76 @@ class GaussianSplatRenderer:
         self.UpdateEditCountsAndBounds()
         self.editModified = True
 
+    def _blob_sizes(self) -> Tuple[int, int, int, int]:
+        """bytes of the renderer's current pos / other / color / sh blobs: the asset's until the first resize, from then on -- also back at the
+        asset's own count -- those of the VeryHigh layout at splatCount (whole records only, where the importer pads its blobs)"""
+        a, n = self.m_Asset, self.m_SplatCount
+        if not self.m_Resized:
+            return len(a.posData), len(a.otherData), len(a.colorData), len(a.shData)
+        w, h = CalcTextureSize(n)
+        return 12 * n, 16 * n, w * h * 16, 192 * n
+
     def DownloadPosOther(self) -> Tuple[np.ndarray, np.ndarray]:
         """The renderer's current pos / other blobs as bytes (its private copies once it has been transformed, else the asset's).  Blocks."""
-        a = self.m_Asset
-        pos, other = np.zeros(len(a.posData), np.uint8), np.zeros(len(a.otherData), np.uint8)
+        sizes = self._blob_sizes()
+        pos, other = np.zeros(sizes[0], np.uint8), np.zeros(sizes[1], np.uint8)
         check(_lib.lib().gs_renderer_edit_download_pos_other(self._r_h, pos.ctypes.data, pos.nbytes, other.ctypes.data, other.nbytes), "gs_renderer_edit_download_pos_other")
         return pos, other
+
+    # -- editing: the merge (:960-1075; GaussianSplatRendererEditor.cs:213-235) ---------------------------------------
+    def _native_splat_count(self) -> int:
+        n = C.c_uint32(0)
+        check(_lib.lib().gs_renderer_splat_count(self._r_h, C.byref(n)), "gs_renderer_splat_count")
+        return int(n.value)
+
+    def EditSetSplatCount(self, newSplatCount: int) -> None:      # :960-1031
+        """Resizes the renderer: new zero-filled buffers of newSplatCount splats with the old splats copied into them (shrinking truncates); the
+        order, the view buffer, the selection and the mouse-down copies start over.  Returns silently where the C# logs an error.  The C# passes
+        its copy kernel worldToLocal x localToWorld of the one transform, the identity but for rounding; this passes the exact identity.  Blocks."""
+        newSplatCount = int(newSplatCount)
+        if newSplatCount <= 0 or newSplatCount > kMaxSplats:
+            return                                  # Invalid new splat count
+        if not self.HasValidAsset or not self.HasValidRenderSetup:
+            return
+        if self.m_Asset.chunkCount != 0:
+            return                                  # Only splats with VeryHigh quality can be resized
+        if newSplatCount == self.splatCount:
+            return
+        if not self.EnsureEditingBuffers():
+            return
+        self.UpdateCutoutsBuffer()                  # SetAssetDataOnCS, :507
+        check(_lib.lib().gs_renderer_edit_set_splat_count(self._r_h, newSplatCount, None), "gs_renderer_edit_set_splat_count")
+        self.m_GpuEditPosMouseDown = self.m_GpuEditOtherMouseDown = False      # DisposeBuffer(ref m_GpuEditPosMouseDown) ..., :1026-1027
+        self.m_SplatCount = self._native_splat_count()
+        self.m_Resized = True
+        self.editModified = True
+
+    def CopyParams(self, dst: "GaussianSplatRenderer") -> gs_copy_params:
+        """What EditCopySplats hands CSCopySplats (:1052-1054): copyMatrix = dst.worldToLocal x this.localToWorld in float32, its rotation and
+        its lossy scale (camera.matrix_rotation_scale)."""
+        m = mat_mul(dst.transform.worldToLocalMatrix, self.transform.localToWorldMatrix)
+        q, sc = matrix_rotation_scale(m)
+        p = gs_copy_params()
+        p.matrix[0:16] = [float(v) for v in np.asarray(m, np.float32).reshape(-1)]
+        p.rotation[0:4] = [float(np.float32(v)) for v in q]
+        p.scale[0:3] = [float(np.float32(v)) for v in sc]
+        return p
+
+    def EditCopySplatsInto(self, dst: "GaussianSplatRenderer", copySrcStartIndex: int, copyDstStartIndex: int, copyCount: int) -> None:      # :1033-1075
+        if not self.EnsureEditingBuffers():
+            return
+        self.UpdateCutoutsBuffer()                  # SetAssetDataOnCS, :507
+        p = self.CopyParams(dst)
+        check(_lib.lib().gs_renderer_edit_copy_splats_into(self._r_h, dst._r_h, C.byref(p), int(copySrcStartIndex), int(copyDstStartIndex), int(copyCount)),
+              "gs_renderer_edit_copy_splats_into")
+        dst.editModified = True
+
+    def DownloadSplatData(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """The renderer's current pos / other / color / sh blobs as bytes (private copies where they exist, else the asset's).  Blocks."""
+        out = [np.zeros(b, np.uint8) for b in self._blob_sizes()]
+        check(_lib.lib().gs_renderer_edit_download_splat_data(self._r_h, out[0].ctypes.data, out[0].nbytes, out[1].ctypes.data, out[1].nbytes,
+                                                              out[2].ctypes.data, out[2].nbytes, out[3].ctypes.data, out[3].nbytes), "gs_renderer_edit_download_splat_data")
+        return out[0], out[1], out[2], out[3]
 
     # -- editing: export (:936-958; GaussianSplatRendererEditor.cs:394-445) ------------------------------------------
     def ExportParams(self, bakeTransform: bool) -> gs_export_params:
@@ -876,3 +942,19 @@ class GaussianSplatRenderSystem:
 
 
 GaussianSplatRenderSystem.instance = GaussianSplatRenderSystem()
+
+
+def MergeSplatObjects(target: GaussianSplatRenderer, others: Sequence[GaussianSplatRenderer]) -> None:
+    """GaussianSplatRendererEditor.MergeSplatObjects (GaussianSplatRendererEditor.cs:213-235): `target` grows by the splats of every valid renderer
+    of `others`, which are copied behind its own in their order, each through dst.worldToLocal x src.localToWorld.  (The C# then deactivates the
+    merged objects; here the caller disposes or keeps them.)"""
+    valid = [gs for gs in others if gs is not target and gs.HasValidAsset and gs.HasValidRenderSetup]
+    totalSplats = target.splatCount + sum(gs.splatCount for gs in valid)
+    if totalSplats > kMaxSplats:
+        return
+    copyDstOffset = target.splatCount
+    target.EditSetSplatCount(totalSplats)
+    for gs in valid:
+        gs.EditCopySplatsInto(target, 0, copyDstOffset, gs.splatCount)
+        copyDstOffset += gs.splatCount
+    assert copyDstOffset == totalSplats, f"Merge count mismatch, {copyDstOffset} vs {totalSplats}"
