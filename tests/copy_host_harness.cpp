@@ -2,26 +2,15 @@
 // PackSmallest3Rotation, EncodeQuatToNorm10) compiled for the HOST, so that tests/test_copy_model.py can hold it to tests/copy_model.py bit for bit
 // on a box without a GPU.  Never part of the shipped library.  With -DCOPY_HARNESS_MAIN it is a stand-alone program (its own main) that copies a
 // small all-fp32 asset it makes itself and checks the identity's known answer: the form a sanitizer build runs.
-#include "../include/gsplat_c.h"
-#include "../unitygaussiansplatting_amd/csrc/gs_device_math.h"
+#include "../unitygaussiansplatting_amd/csrc/gs_params.h"
 
 extern "C" {
 uint32_t ch_sizes(uint32_t which) { return which == 0 ? (uint32_t)sizeof(gs_copy_params) : (which == 1 ? (uint32_t)sizeof(gsm::CopyXform) : (uint32_t)sizeof(gsm::CopyRec)); }
 
 // the records of the splats [first, first + n) of the asset: pos n x 3 floats, other n x 4 words, texel n x 4 floats, sh n x 45 floats.  p == NULL: the exact identity.
 void ch_copy(const gs_asset_desc* d, const gs_copy_params* p, uint32_t first, uint32_t n, float* pos, uint32_t* other, float* texel, float* sh) {
-    gsm::AssetView a;
-    a.pos = (const uint8_t*)d->pos_data; a.other = (const uint8_t*)d->other_data; a.color = (const uint8_t*)d->color_data;
-    a.sh = (const uint8_t*)d->sh_data; a.chunk = (const uint8_t*)d->chunk_data;
-    a.n = d->splat_count; a.posFmt = d->pos_format; a.scaleFmt = d->scale_format; a.colorFmt = d->color_format; a.shFmt = d->sh_format;
-    a.chunkCount = (d->chunk_data && d->chunk_size) ? (uint32_t)(d->chunk_size / 64) : 0;
-    static const gs_copy_params kIdentity = { { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 }, { 0, 0, 0, 1 }, { 1, 1, 1 } };
-    if (!p) p = &kIdentity;
-    gsm::CopyXform X;
-    memcpy(X.m, p->matrix, sizeof(X.m));
-    memcpy(X.rot, p->rotation, sizeof(X.rot));
-    memcpy(X.scale, p->scale, sizeof(X.scale));
-    gsm::CalcSHRot(p->matrix, X.sh);
+    const gsm::AssetView a = gs::asset_view_of(*d);
+    const gsm::CopyXform X = gs::copy_xform_of(p);
     for (uint32_t k = 0; k < n; ++k) {
         const uint32_t i = first + k;
         gsm::CopyRec r;

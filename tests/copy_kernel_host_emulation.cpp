@@ -7,8 +7,7 @@
 #include <thread>
 #include <vector>
 #include <atomic>
-#include "../include/gsplat_c.h"
-#include "../unitygaussiansplatting_amd/csrc/gs_device_math.h"
+#include "../unitygaussiansplatting_amd/csrc/gs_params.h"
 struct dim3s { uint32_t x, y, z; };
 static thread_local dim3s threadIdx, blockIdx;
 static std::barrier<>* g_bar;
@@ -39,14 +38,8 @@ namespace gs {
 }
 extern "C" void emu_copy(const gs_asset_desc* d, const uint32_t* srcDeleted, const gs_copy_params* p, uint8_t* pos, uint8_t* other, uint8_t* color, uint8_t* sh,
                          uint32_t* deleted, uint32_t dstN, uint32_t srcStart, uint32_t dstStart, uint32_t count) {
-    gsm::AssetView a;
-    a.pos = (const uint8_t*)d->pos_data; a.other = (const uint8_t*)d->other_data; a.color = (const uint8_t*)d->color_data;
-    a.sh = (const uint8_t*)d->sh_data; a.chunk = (const uint8_t*)d->chunk_data;
-    a.n = d->splat_count; a.posFmt = d->pos_format; a.scaleFmt = d->scale_format; a.colorFmt = d->color_format; a.shFmt = d->sh_format;
-    a.chunkCount = (d->chunk_data && d->chunk_size) ? (uint32_t)(d->chunk_size / 64) : 0;
-    gsm::CopyXform X;
-    memcpy(X.m, p->matrix, sizeof(X.m)); memcpy(X.rot, p->rotation, sizeof(X.rot)); memcpy(X.scale, p->scale, sizeof(X.scale));
-    gsm::CalcSHRot(p->matrix, X.sh);
+    const gsm::AssetView a = gs::asset_view_of(*d);
+    const gsm::CopyXform X = gs::copy_xform_of(p);
     gs::CopyDst dst = { pos, other, color, sh, deleted, dstN };
     // the host's clamp (copy_clamp in gs_copy.hip, restated: it sits behind the cut)
     if (srcStart >= a.n || dstStart >= dstN) return;

@@ -1,7 +1,6 @@
 // Test-only: the export's per-splat arithmetic (csrc/gs_device_math.h: LogDetFull, CalcSHRot, LoadSplatDataFull, ExportSplat) compiled for the
 // HOST, so that tests/test_export_model.py can hold it to tests/export_model.py bit for bit on a box without a GPU.  Never part of the shipped library.
-#include "../include/gsplat_c.h"
-#include "../unitygaussiansplatting_amd/csrc/gs_device_math.h"
+#include "../unitygaussiansplatting_amd/csrc/gs_params.h"
 
 extern "C" {
 void xh_logdet(const float* x, float* out, uint64_t n) {
@@ -19,19 +18,9 @@ uint32_t xh_sizes(uint32_t which) { return which == 0 ? (uint32_t)sizeof(gsm::SH
 
 // out: n x 62 floats, what export_records_kernel leaves in reference-shaped mode
 void xh_export(const gs_asset_desc* d, const gs_export_params* p, const gs_cutout* cutouts, uint32_t cutoutCount, float* out) {
-    gsm::AssetView a;
-    a.pos = (const uint8_t*)d->pos_data; a.other = (const uint8_t*)d->other_data; a.color = (const uint8_t*)d->color_data;
-    a.sh = (const uint8_t*)d->sh_data; a.chunk = (const uint8_t*)d->chunk_data;
-    a.n = d->splat_count; a.posFmt = d->pos_format; a.scaleFmt = d->scale_format; a.colorFmt = d->color_format; a.shFmt = d->sh_format;
-    a.chunkCount = (d->chunk_data && d->chunk_size) ? (uint32_t)(d->chunk_size / 64) : 0;
+    const gsm::AssetView a = gs::asset_view_of(*d);
     gsm::EditView e; e.deletedBits = nullptr; e.cutouts = (const uint32_t*)cutouts; e.cutoutCount = cutoutCount;
-    gsm::ExportXform X;
-    memset(&X, 0, sizeof(X));
-    X.bake = p->bake_transform ? 1u : 0u;
-    memcpy(X.o2w, p->matrix_object_to_world, sizeof(X.o2w));
-    memcpy(X.rot, p->rotation, sizeof(X.rot));
-    memcpy(X.scale, p->scale, sizeof(X.scale));
-    if (X.bake) gsm::CalcSHRot(p->matrix_object_to_world, X.sh);
+    const gsm::ExportXform X = gs::export_xform_of(*p);
     for (uint32_t i = 0; i < a.n; ++i) {
         const gsm::V3 pos = gsm::LoadSplatPosChunk(a, i, i >> 8);      // (the kernels pass the workgroup's chunk)
         const bool cut = gsm::IsSplatCut(e, pos.x, pos.y, pos.z);

@@ -1,27 +1,9 @@
 // Test-only: compiles the kernels' arithmetic header (csrc/gs_device_math.h) for the HOST so that it can be
 // compared with the oracle bit for bit on a box without a GPU.  Never part of the shipped library.
-#include "../include/gsplat_c.h"
-#include "../unitygaussiansplatting_amd/csrc/gs_device_math.h"
+#include "../unitygaussiansplatting_amd/csrc/gs_params.h"
 
-static gsm::AssetView mk(const gs_asset_desc* d) {
-    gsm::AssetView a;
-    a.pos = (const uint8_t*)d->pos_data; a.other = (const uint8_t*)d->other_data; a.color = (const uint8_t*)d->color_data;
-    a.sh = (const uint8_t*)d->sh_data; a.chunk = (const uint8_t*)d->chunk_data;
-    a.n = d->splat_count; a.posFmt = d->pos_format; a.scaleFmt = d->scale_format; a.colorFmt = d->color_format; a.shFmt = d->sh_format;
-    a.chunkCount = (d->chunk_data && d->chunk_size) ? (uint32_t)(d->chunk_size / 64) : 0;
-    return a;
-}
-static gsm::FrameConsts fl(const gs_frame_params* p) {
-    gsm::FrameConsts c;
-    memcpy(c.mv, p->matrix_mv, 48); memcpy(c.o2w, p->matrix_object_to_world, 48); memcpy(c.w2o, p->matrix_world_to_object, 48);
-    memcpy(c.vp, p->matrix_vp, 64);
-    gsm::FrameConstsFromProjection(c, p->proj_m00, p->proj_m11, p->screen_w); c.screenW = p->screen_w; c.screenH = p->screen_h;
-    c.camx = p->cam_pos_world[0]; c.camy = p->cam_pos_world[1]; c.camz = p->cam_pos_world[2];
-    c.splatScale = p->splat_scale; c.opacityScale = p->opacity_scale; c.shOrder = p->sh_order; c.shOnly = p->sh_only;
-    c.nearClip = p->near_clip; c.farClip = p->far_clip;
-    gsm::FrameConstsChunkCull(c);
-    return c;
-}
+static gsm::AssetView mk(const gs_asset_desc* d) { return gs::asset_view_of(*d); }
+static gsm::FrameConsts fl(const gs_frame_params* p) { gsm::FrameConsts c; gs::flatten_params(p, c); return c; }
 extern "C" {
 void hm_calc_view_ex(const gs_asset_desc* d, const gs_frame_params* p, const gs_cutout* cutouts, uint32_t cutoutCount,
                      const uint32_t* deletedBits, void* out) {

@@ -1,20 +1,13 @@
 // Test-only: the transform kernels' per-splat arithmetic (csrc/gs_device_math.h: EditTranslatePos, EditRotatePos, EditScalePos, EditRotateWord and the
 // codec under it) compiled for the HOST, so that tests/test_transform_model.py can hold it to tests/transform_model.py bit for bit on a box without
 // a GPU.  Never part of the shipped library.
-#include "../include/gsplat_c.h"
-#include "../unitygaussiansplatting_amd/csrc/gs_device_math.h"
+#include "../unitygaussiansplatting_amd/csrc/gs_params.h"
 
 extern "C" {
 // pos: n x 3 floats, words: n rotation words; delta3 for translate / scale, rot4 for rotate; out*: n x 3 floats, outW: n words
 void th_eval(const float* pos, const uint32_t* words, uint32_t n, const float* center, const float* o2w16, const float* w2o16, const float* delta3,
              const float* rot4, float* outT, float* outR, float* outS, uint32_t* outW) {
-    gsm::EditXform X;
-    memcpy(X.center, center, sizeof(X.center));
-    memcpy(X.o2w, o2w16, sizeof(X.o2w));
-    memcpy(X.w2o, w2o16, sizeof(X.w2o));
-    gsm::EditXform XR = X;
-    X.delta[0] = delta3[0]; X.delta[1] = delta3[1]; X.delta[2] = delta3[2]; X.delta[3] = 0.0f;
-    memcpy(XR.delta, rot4, sizeof(XR.delta));
+    const gsm::EditXform X = gs::edit_xform_of(center, o2w16, w2o16, delta3, 3), XR = gs::edit_xform_of(center, o2w16, w2o16, rot4, 4);
     for (uint32_t i = 0; i < n; ++i) {
         const gsm::V3 p = { pos[i * 3], pos[i * 3 + 1], pos[i * 3 + 2] };
         const gsm::V3 t = gsm::EditTranslatePos(X, p), r = gsm::EditRotatePos(XR, p), s = gsm::EditScalePos(X, p);

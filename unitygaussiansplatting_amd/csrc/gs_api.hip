@@ -204,11 +204,8 @@ int32_t gs_asset_create(gs_context* ctx, const gs_asset_desc* d, gs_asset** out)
         for (int k : {0, 1, 3})
             if (have[k] < need[k] + 4) { set_error_detail("borrowed blob %d needs 4 readable bytes after its last record (declare size >= %llu)", k, (unsigned long long)(need[k] + 4)); return GS_ERR_INVALID_ASSET; }
     }
-    uint32_t chunkCount = 0;
-    if (d->chunk_data && d->chunk_size) {
-        chunkCount = (uint32_t)(d->chunk_size / 64);
-        if ((uint64_t)chunkCount < (n + 255) / 256) return fail(GS_ERR_INVALID_ASSET, "chunk blob too small");
-    }
+    const gsm::AssetView view = asset_view_of(*d);
+    if (d->chunk_data && d->chunk_size && (uint64_t)view.chunkCount < (n + 255) / 256) return fail(GS_ERR_INVALID_ASSET, "chunk blob too small");
     GS_TRY(bind_device(ctx));
     gs_asset* a = new (std::nothrow) gs_asset();
     if (!a) return fail(GS_ERR_OUT_OF_MEMORY, "host allocation");
@@ -229,10 +226,9 @@ int32_t gs_asset_create(gs_context* ctx, const gs_asset_desc* d, gs_asset** out)
         }
     }
     if (a->owned) { hipError_t e = hipStreamSynchronize(ctx->stream); if (e != hipSuccess) { gs_asset_destroy(a); return fail_hip(e, "asset upload sync", __FILE__, __LINE__); } }
+    a->view = view;                                              // formats and counts; the pointers are the device blobs
     a->view.pos = (const uint8_t*)a->blobs[0]; a->view.other = (const uint8_t*)a->blobs[1]; a->view.color = (const uint8_t*)a->blobs[2];
     a->view.sh = (const uint8_t*)a->blobs[3]; a->view.chunk = (const uint8_t*)a->blobs[4];
-    a->view.n = d->splat_count; a->view.posFmt = d->pos_format; a->view.scaleFmt = d->scale_format;
-    a->view.colorFmt = d->color_format; a->view.shFmt = d->sh_format; a->view.chunkCount = chunkCount;
     *out = a;
     return GS_OK;
 }
@@ -265,9 +261,10 @@ int32_t gs_asset_device_blobs(const gs_asset* a, void* ptrs[5], uint64_t sizes[5
 // ---- renderer --------------------------------------------------------------------------------------------
 // ---- frames in flight inside the library: lanes ---------------------------------------------------------------
 // (gs_renderer_set_frames_in_flight, gsplat_c.h.)  A lane is an ordinary renderer on a context of its own; the owner tells every lane every sort matrix
-// (bookkeeping in GS_SORT_VISIBLE) and every setting, deals the frames round-robin at gs_renderer_calc_view and answers the whole-buffer questions
-// (gs_renderer_download_order, _distances, _sort_history) from its own copy of the bookkeeping.
-static inline bool lanes_on(const gs_renderer* r) { return !r->lanes.empty() && r->sortMode == GS_SORT_VISIBLE && r->renderMode == GS_RENDER_SPLATS; }
+// (bookkeeping in GS_SORT_VISIBLE) and every setting that owns memory (the plain values a lane reads from its owner: gs::settings), deals the frames
+// round-robin at gs_renderer_calc_view and answers the whole-buffer questions (gs_renderer_download_order, _distances, _sort_history) from its own copy
+// of the bookkeeping.
+static inline bool lanes_on(const gs_renderer* r) { return !r->lanes.empty() && r->sortMode == GS_SORT_VISIBLE && r->set.renderMode == GS_RENDER_SPLATS; }
 static inline gs_renderer* lane_cur(gs_renderer* r) { return lanes_on(r) && r->laneCur >= 0 ? r->lanes[(size_t)r->laneCur] : r; }
 
 static void lanes_destroy(gs_renderer* r) {
@@ -299,7 +296,6 @@ extern "C++" int32_t gs::lanes_resync(gs_renderer* r) {
         L->visBaseIdentity = r->visBaseIdentity; L->visRankValid = false; L->visOrderValid = false;
         L->visHistDepth = r->visHistDepth;
         memcpy(L->visHist, r->visHist, sizeof(r->visHist));
-        L->visHistLimit = r->visHistLimit;
         L->distancesStale = false;
     }
     return GS_OK;
@@ -327,25 +323,12 @@ int32_t gs_renderer_set_frames_in_flight(gs_renderer* r, int32_t frames) {
             if (e == hipSuccess) e = L->evBlendDone.create(hipEventDisableTiming);
             if (e != hipSuccess) rc = fail_hip(e, "create lane events", __FILE__, __LINE__);
         }
-        // the owner's settings as they are now; later changes are forwarded by the setters themselves
+        // what the owner's settings own of memory, as it is now (later changes are forwarded by those setters), and the shape the owner's draws have learned
         if (rc == GS_OK) {
-            L->blendMode = r->blendMode; L->alwaysWriteView = r->alwaysWriteView; L->kernelTiming = r->kernelTiming;
-            L->tileOverrideWL = r->tileOverrideWL; L->tileOverrideHL = r->tileOverrideHL; L->adaptTall = r->adaptTall;
-            L->visHistLimit = r->visHistLimit;
+            L->adaptTall = r->adaptTall;
             if (r->pairCapacity > L->pairCapacity) rc = gs_renderer_reserve_pairs(L, r->pairCapacity);
         }
         if (rc == GS_OK && r->cutoutCount) rc = gs_renderer_set_cutouts(L, (const gs_cutout*)r->cutoutsHost.get(), r->cutoutCount);
-        if (rc == GS_OK && r->deletedBits) {
-            const size_t words = ((size_t)r->n + 31) / 32;
-            uint32_t* h = new (std::nothrow) uint32_t[words];
-            if (!h) rc = fail(GS_ERR_OUT_OF_MEMORY, "host allocation");
-            else {
-                rc = bind_device(r->ctx);
-                if (rc == GS_OK && hipMemcpy(h, r->deletedBits, words * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(GS_ERR_HIP, "copy deleted bits");
-                if (rc == GS_OK) rc = gs_renderer_set_deleted_bits(L, h, words);
-                delete[] h;
-            }
-        }
         if (rc != GS_OK) {
             if (L) (void)gs_renderer_destroy(L);
             if (c) (void)gs_context_destroy(c);
@@ -354,6 +337,10 @@ int32_t gs_renderer_set_frames_in_flight(gs_renderer* r, int32_t frames) {
         }
         r->lanes.push_back(L);
         r->ctx->children.push_back(c);
+    }
+    if (r->deletedBits) {                                        // the new lanes' copies, device to device (everything is synchronised: nothing is in flight)
+        const int32_t rc = edit_deleted_to_lanes(r);
+        if (rc != GS_OK) { lanes_destroy(r); return rc; }
     }
     return lanes_resync(r);
 }
@@ -527,10 +514,9 @@ int32_t gs_renderer_calc_view(gs_renderer* r, const gs_frame_params* p) {
     }
     GS_TRY(bind_device(r->ctx));
     rec_ev(r, 7);
-    gsm::EditView e;
-    e.deletedBits = r->deletedBits; e.cutouts = r->cutouts; e.cutoutCount = r->cutoutCount;
-    GS_TRY(enqueue_calc_view(r->ctx, asset_view(r), p, e, view_outputs(r), r->alwaysWriteView));
-    r->viewMaterialised = r->alwaysWriteView;
+    const bool full = settings(r).alwaysWriteView;
+    GS_TRY(enqueue_calc_view(r->ctx, asset_view(r), p, edit_view(r), view_outputs(r), full));
+    r->viewMaterialised = full;
     r->movedSinceView = false;
     r->visOrderValid = false;                                    // the visible set may have changed
     r->lastParams = *p;
@@ -567,10 +553,11 @@ int32_t gs_renderer_draw(gs_renderer* r, const gs_frame_params* p, gs_target* rt
     if (rt->ctx != r->ctx && !(r->laneOf && rt->ctx == r->laneOf->ctx)) return fail(GS_ERR_INVALID_ARGUMENT, "target belongs to another context");
     if ((uint32_t)p->screen_w != rt->width || (uint32_t)p->screen_h != rt->height) return fail(GS_ERR_INVALID_ARGUMENT, "screen_w/h do not match the target");
     GS_TRY(bind_device(r->ctx));
-    if (r->renderMode == GS_RENDER_DEBUG_POINTS || r->renderMode == GS_RENDER_DEBUG_POINT_INDICES) return enqueue_debug_points(r, p, rt);
+    const int mode = settings(r).renderMode;
+    if (mode == GS_RENDER_DEBUG_POINTS || mode == GS_RENDER_DEBUG_POINT_INDICES) return enqueue_debug_points(r, p, rt);
     GS_TRY(maybe_grow_pairs(r));
-    if (r->renderMode == GS_RENDER_DEBUG_BOXES) return enqueue_debug_boxes(r, p, rt, false);
-    if (r->renderMode == GS_RENDER_DEBUG_CHUNK_BOUNDS) return enqueue_debug_boxes(r, p, rt, true);
+    if (mode == GS_RENDER_DEBUG_BOXES) return enqueue_debug_boxes(r, p, rt, false);
+    if (mode == GS_RENDER_DEBUG_CHUNK_BOUNDS) return enqueue_debug_boxes(r, p, rt, true);
     return enqueue_draw(r, p, rt);
 }
 
@@ -617,7 +604,7 @@ int32_t gs_renderer_set_cutouts(gs_renderer* r, const gs_cutout* cutouts, uint32
 int32_t gs_renderer_set_deleted_bits(gs_renderer* r, const uint32_t* words, size_t word_count) {
     if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
     GS_TRY(bind_device(r->ctx));
-    const size_t need = ((size_t)r->n + 31) / 32;
+    const size_t need = bit_words(r->n);
     if (!words) {                                           // _SplatBitsValid = 0
         if (r->deletedBits) { GS_HIP(hipStreamSynchronize(r->ctx->stream)); r->deletedBits.reset(); }
         for (gs_renderer* L : r->lanes) GS_TRY(gs_renderer_set_deleted_bits(L, nullptr, 0));
@@ -634,33 +621,30 @@ int32_t gs_renderer_set_deleted_bits(gs_renderer* r, const uint32_t* words, size
 
 int32_t gs_renderer_set_view_buffer_mode(gs_renderer* r, int32_t every_frame) {
     if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
-    r->alwaysWriteView = every_frame != 0;
-    for (gs_renderer* L : r->lanes) L->alwaysWriteView = r->alwaysWriteView;
+    r->set.alwaysWriteView = every_frame != 0;
     return GS_OK;
 }
 
 int32_t gs_renderer_set_render_mode(gs_renderer* r, int32_t mode, float point_display_size) {
     if (!r || mode < GS_RENDER_SPLATS || mode > GS_RENDER_DEBUG_CHUNK_BOUNDS) return fail(GS_ERR_INVALID_ARGUMENT, "render mode out of range");
     if (!(point_display_size >= 0.0f) || point_display_size > 4096.0f) return fail(GS_ERR_INVALID_ARGUMENT, "point_display_size out of range");
-    r->renderMode = mode;
-    r->pointDisplaySize = point_display_size;
+    r->set.renderMode = mode;
+    r->set.pointDisplaySize = point_display_size;
     return GS_OK;
 }
 
 int32_t gs_renderer_set_blend_mode(gs_renderer* r, int32_t mode) {
     if (!r || (mode != 0 && mode != 1)) return fail(GS_ERR_INVALID_ARGUMENT, "blend mode must be 0 or 1");
-    r->blendMode = mode;
-    for (gs_renderer* L : r->lanes) L->blendMode = mode;
+    r->set.blendMode = mode;
     return GS_OK;
 }
 
 int32_t gs_renderer_set_tile_shape(gs_renderer* r, uint32_t tile_w, uint32_t tile_h) {
     if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
-    for (gs_renderer* L : r->lanes) GS_TRY(gs_renderer_set_tile_shape(L, tile_w, tile_h));
-    if (tile_w == 0 && tile_h == 0) { r->tileOverrideWL = r->tileOverrideHL = 0; return GS_OK; }
+    if (tile_w == 0 && tile_h == 0) { r->set.tileOverrideWL = r->set.tileOverrideHL = 0; return GS_OK; }
     if (!((tile_w == 16 && tile_h == 16) || (tile_w == 32 && tile_h == 16) || (tile_w == 32 && tile_h == 32)))
         return fail(GS_ERR_INVALID_ARGUMENT, "tile shape must be 16x16, 32x16, 32x32 or 0x0 (automatic)");
-    r->tileOverrideWL = tile_w == 16 ? 4u : 5u; r->tileOverrideHL = tile_h == 16 ? 4u : 5u;
+    r->set.tileOverrideWL = tile_w == 16 ? 4u : 5u; r->set.tileOverrideHL = tile_h == 16 ? 4u : 5u;
     return GS_OK;
 }
 
@@ -691,8 +675,7 @@ int32_t gs_renderer_set_profiling(gs_renderer* r, int32_t frames) {
 
 int32_t gs_renderer_set_kernel_timing(gs_renderer* r, int32_t enabled) {
     if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
-    r->kernelTiming = enabled != 0;
-    for (gs_renderer* L : r->lanes) L->kernelTiming = r->kernelTiming;
+    r->set.kernelTiming = enabled != 0;
     return GS_OK;
 }
 
@@ -792,17 +775,19 @@ int32_t gs_renderer_sort_mode(const gs_renderer* r, int32_t* mode, int32_t* acti
 }
 int32_t gs_renderer_set_sort_history_limit(gs_renderer* r, uint32_t rows) {
     if (!r || rows < 2 || rows > (uint32_t)kVisHistory) return fail(GS_ERR_INVALID_ARGUMENT, "sort history limit must be in [2, 128]");
-    GS_TRY(bind_device(r->ctx));
-    for (gs_renderer* L : r->lanes) GS_TRY(gs_renderer_set_sort_history_limit(L, rows));
+    for (gs_renderer* L : r->lanes) {                            // each renderer consolidates if its own history is deeper than the new limit
+        GS_TRY(bind_device(L->ctx));
+        if ((uint32_t)L->visHistDepth > rows) GS_TRY(vis_consolidate(L));
+    }
     GS_TRY(bind_device(r->ctx));
     if ((uint32_t)r->visHistDepth > rows) GS_TRY(vis_consolidate(r));
-    r->visHistLimit = (int)rows;
+    r->set.visHistLimit = (int)rows;
     return GS_OK;
 }
 int32_t gs_renderer_sort_history(const gs_renderer* r, uint32_t* rows, uint32_t* limit, uint64_t* consolidations) {
     if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
     if (rows) *rows = (uint32_t)r->visHistDepth;
-    if (limit) *limit = (uint32_t)r->visHistLimit;
+    if (limit) *limit = (uint32_t)settings(r).visHistLimit;
     if (consolidations) *consolidations = r->visConsolidations;
     return GS_OK;
 }
@@ -834,9 +819,7 @@ int32_t gs_renderer_download_view(gs_renderer* r, void* out, size_t bytes) {
         // m_GpuView is materialised on demand: the per-frame launch skips it (nothing in this renderer reads it); re-run the
         // frame's launch as the reference's full kernel.  rec/rect/visibility are rewritten with identical values.
         GS_TRY(bind_device(r->ctx));
-        gsm::EditView e;
-        e.deletedBits = r->deletedBits; e.cutouts = r->cutouts; e.cutoutCount = r->cutoutCount;
-        GS_TRY(enqueue_calc_view(r->ctx, asset_view(r), &r->lastParams, e, view_outputs(r), true));
+        GS_TRY(enqueue_calc_view(r->ctx, asset_view(r), &r->lastParams, edit_view(r), view_outputs(r), true));
         r->viewMaterialised = true;
     }
     return download(r->ctx, out, r->view, bytes);

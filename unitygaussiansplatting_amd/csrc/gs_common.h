@@ -11,6 +11,7 @@
 #include "../../include/gsplat_c.h"
 #include "gs_device_math.h"
 #include "gs_handles.h"
+#include "gs_params.h"
 
 // Issue priority of the frame's latency-bound kernels (the sort passes, the key / binning / fix-up kernels, resolve): with frames in flight they share their SIMDs
 // with another frame's blend, whose heaviest tiles raise their own priority (gs_raster.hip); a chain kernel's few instructions between two waits then queue behind
@@ -229,9 +230,24 @@ struct gs_target {
     bool exposed = false;                   // gs_target_device_ptr handed the memory out: the host's own work on the context's stream may touch it (and the pointer stays put)
 };
 
-// gs_renderer_edit_set_splat_count (gs_copy.hip) builds a second gs_renderer of the new N and std::swap()s the two WHOLE structs.  So: no member may
-// point into the struct itself, and a member that is a SETTING (something a host set and expects to keep) must be carried over in resize_build() there
-// -- and, where lanes follow it, in gs_renderer_set_frames_in_flight (gs_api.hip) -- or a resize silently resets it.
+namespace gs {
+// The plain values a host sets on a renderer and expects to keep.  One copy, the owner's: a lane reads its owner's through gs::settings(), a resize
+// copies the struct.  renderMode and pointDisplaySize are safe to read from the owner too: lanes draw only while the owner's mode is GS_RENDER_SPLATS
+// (lanes_on, gs_api.hip), which is a lane's own default.
+struct RendererSettings {
+    int blendMode = 0;
+    int renderMode = 0;                     // gs_render_mode (GaussianSplatRenderer.RenderMode, :126-131)
+    float pointDisplaySize = 3.0f;          // m_PointDisplaySize
+    bool alwaysWriteView = false;           // gs_renderer_set_view_buffer_mode(1): write the view buffer every frame like the reference
+    bool kernelTiming = false;              // gs_renderer_set_kernel_timing: Onesweep launches carry their own start / stop events
+    uint32_t tileOverrideWL = 0, tileOverrideHL = 0;   // gs_renderer_set_tile_shape: log2 tile width / height, 0 = automatic
+    int visHistLimit = kVisHistory;         // rows kept before the base is consolidated (gs_renderer_set_sort_history_limit; GSPLAT_VIS_HISTORY)
+};
+} // namespace gs
+
+// A plain-value setting goes into gs::RendererSettings, and nothing else needs doing.
+// A setting that owns memory is forwarded to the lanes by its setter and re-applied in resize_build() (gs_copy.hip).
+// No member may point into the struct: gs_renderer_edit_set_splat_count builds a second gs_renderer of the new N and std::swap()s the two WHOLE structs.
 struct gs_renderer {
     gs_context* ctx = nullptr;
     gs_asset* asset = nullptr;
@@ -269,12 +285,9 @@ struct gs_renderer {
     // The renderer's own, writable copy of the two blobs the transform kernels write (CSTranslateSelection / CSRotateSelection / CSScaleSelection): made by
     // the first transform whose format gate can pass, null until then (gs::asset_view).  The asset itself -- shared between contexts, lanes and replicas --
     // is never written; lanes read their owner's copies in place.
-    gs::DevBuf<uint8_t> privPos;            // m_GpuPosData of this renderer
-    gs::DevBuf<uint8_t> privOther;          // m_GpuOtherData
-    // ... and of the two the merge writes as well (CSCopySplats; gs_copy.hip): made by the first copy INTO this renderer, or -- all four -- by a resize
-    gs::DevBuf<uint8_t> privColor;          // m_GpuColorData: 2048 x CalcTextureSize(N).h texels of four fp32
-    gs::DevBuf<uint8_t> privSH;             // m_GpuSHData
-    uint64_t privBytes[4] = {0, 0, 0, 0};   // bytes of each private blob (pos, other, color, sh) while it exists: gs::blob_bytes
+    // ... and of the two the merge writes as well (CSCopySplats; gs_copy.hip): made by the first copy INTO this renderer, or -- all four -- by a resize.
+    gs::DevBuf<uint8_t> priv[4];            // 0 m_GpuPosData of this renderer, 1 m_GpuOtherData, 2 m_GpuColorData (2048 x CalcTextureSize(N).h texels of four fp32), 3 m_GpuSHData
+    uint64_t privBytes[4] = {0, 0, 0, 0};   // bytes of each private blob while it exists: gs::blob_bytes
     gs::Event evCopySrcReady;               // (on the destination of a copy) source's stream -> this context's: the source's pending edits are done
     gs::Event evCopyDone;                   // ... and this context's stream -> the source's: the copy kernel has read the source
     gs::DevBuf<uint8_t> editPosMouseDown;   // m_GpuEditPosMouseDown: made only when the position gate can pass
@@ -286,7 +299,6 @@ struct gs_renderer {
     float viewW = 0.f, viewH = 0.f, viewNear = 0.f, viewFar = 0.f;   // what the last calc_view was run with
     bool viewValid = false;
     bool viewMaterialised = false;          // the N x 40 B view buffer holds the last calc_view's records (written on demand)
-    bool alwaysWriteView = false;           // gs_renderer_set_view_buffer_mode(1): write it every frame like the reference
     gs_frame_params lastParams;             // of the last gs_renderer_calc_view (for the on-demand FULL launch)
     gs::DevBuf<uint32_t> pairKeys;          // tile ids
     gs::DevBuf<uint32_t> pairVals;          // sorted positions
@@ -302,17 +314,13 @@ struct gs_renderer {
     int costIdx = 0;
     uint32_t costTiles[2] = {0, 0};         // tile count of the draw that wrote each copy (0 = none): a schedule can be made from it for the same count only
     uint32_t costShape[2] = {0, 0};         // ... and the same tile shape (log2 w | log2 h << 8)
-    uint32_t tileOverrideWL = 0, tileOverrideHL = 0;   // gs_renderer_set_tile_shape: log2 tile width / height, 0 = automatic
     uint32_t lastTileWL = 0, lastTileHL = 0;           // of the last draw (0 x 0: nothing drawn yet)
     bool adaptTall = false;                            // automatic shape: 32x32 instead of 32x16 (large splats; adapt_tile_shape)
     gs::DevBuf<uint32_t> tileOrderBuf;      // arenaTiles x u32: the blend's tile schedule of the draw in flight
     uint32_t binParts = 0;
-    int blendMode = 0;
-    int renderMode = 0;                     // gs_render_mode (GaussianSplatRenderer.RenderMode, :126-131)
-    float pointDisplaySize = 3.0f;          // m_PointDisplaySize
+    gs::RendererSettings set;               // read through gs::settings(): a lane's own copy is never looked at
     // profiling: a ring of per-frame hipEvent sets (slot advances at the end of gs_renderer_draw)
     bool profiling = false;
-    bool kernelTiming = false;              // gs_renderer_set_kernel_timing: Onesweep launches carry their own start / stop events
     std::vector<gs::Event> ev;              // profCapacity x kEvPerFrame
     std::vector<uint8_t> evValid;
     int profCapacity = 0, profCur = 0, profCompleted = 0;
@@ -339,7 +347,6 @@ struct gs_renderer {
     bool visDrawn = false;                  // the draw in flight was binned from visIdx
     float visHist[gs::kVisHistory][4];      // sort-matrix rows (m[8..11]) since the base, most recent first, no row twice
     int visHistDepth = 0;
-    int visHistLimit = gs::kVisHistory;     // rows kept before the base is consolidated (gs_renderer_set_sort_history_limit; GSPLAT_VIS_HISTORY)
     unsigned long long visConsolidations = 0;
     gs::DevBuf<uint32_t> visKeys;           // N x u32 each, allocated on first use: compacted (key, splat index) of the visible splats, sorted in place
     gs::DevBuf<uint32_t> visIdx;
@@ -402,7 +409,6 @@ inline const VisControl* vis_control(const gs_renderer* r) { return r->visContro
 // view (gs_view.hip)
 int32_t enqueue_calc_view(gs_context* ctx, const gsm::AssetView& a, const gs_frame_params* p, const gsm::EditView& e, const ViewOutputs& out, bool full);
 ViewOutputs view_outputs(gs_renderer* r);
-void flatten_params(const gs_frame_params* p, gsm::FrameConsts& c);
 // raster (gs_raster.hip)
 int32_t renderer_alloc_raster(gs_renderer* r);
 int32_t enqueue_draw(gs_renderer* r, const gs_frame_params* p, gs_target* rt);
@@ -417,6 +423,7 @@ void edit_free(gs_renderer* r);             // the selection buffers and the mou
 int32_t edit_ensure(gs_renderer* r);        // EnsureEditingBuffers: the zeroed selection buffers, made once
 int32_t edit_make_private(gs_renderer* r, int k);   // copy-on-write of blob k (0 pos, 1 other, 2 color, 3 sh) on the context's stream
 int32_t edit_deleted_to_lanes(gs_renderer* r);      // the lanes' copies of the deleted bits follow the owner's, by events
+int32_t ensure_deleted_bits(gs_renderer* r, hipStream_t st);   // a renderer without a deleted buffer gets one, zero-filled on st
 // what brackets a kernel that rewrites positions (the transforms, the merge): ordering against sorts, GS_SORT_VISIBLE's history and the lanes
 int32_t edit_before_move(gs_renderer* r);
 int32_t edit_after_move(gs_renderer* r);
@@ -430,21 +437,29 @@ int32_t lanes_resync(gs_renderer* r);
 inline gsm::AssetView asset_view(const gs_renderer* r) {
     const gs_renderer* o = r->laneOf ? r->laneOf : r;
     gsm::AssetView v = r->asset->view;
-    if (o->privPos) v.pos = o->privPos;
-    if (o->privOther) v.other = o->privOther;
-    if (o->privColor) v.color = o->privColor;
-    if (o->privSH) v.sh = o->privSH;
+    if (o->priv[0]) v.pos = o->priv[0];
+    if (o->priv[1]) v.other = o->priv[1];
+    if (o->priv[2]) v.color = o->priv[2];
+    if (o->priv[3]) v.sh = o->priv[3];
     v.n = o->n;
     return v;
 }
 // bytes of blob k (0 pos, 1 other, 2 color, 3 sh) as this renderer sees it
 inline uint64_t blob_bytes(const gs_renderer* r, int k) {
     const gs_renderer* o = r->laneOf ? r->laneOf : r;
-    const bool priv = k == 0 ? (bool)o->privPos : (k == 1 ? (bool)o->privOther : (k == 2 ? (bool)o->privColor : (bool)o->privSH));
-    return priv ? o->privBytes[k] : r->asset->sizes[k];
+    return o->priv[k] ? o->privBytes[k] : r->asset->sizes[k];
 }
 inline const uint8_t* blob_ptr(const gs_renderer* r, int k) {
     const gsm::AssetView a = asset_view(r);
     return k == 0 ? a.pos : (k == 1 ? a.other : (k == 2 ? a.color : a.sh));
 }
+// the settings this renderer draws with: its own, or its owner's if it is a lane
+inline const RendererSettings& settings(const gs_renderer* r) { return (r->laneOf ? r->laneOf : r)->set; }
+// the edit state calc_view and the edit kernels consult, of THIS renderer: a lane reads its own copy of the deleted bits
+inline gsm::EditView edit_view(const gs_renderer* r) {
+    gsm::EditView e;
+    e.deletedBits = r->deletedBits; e.cutouts = r->cutouts; e.cutoutCount = r->cutoutCount;
+    return e;
+}
+inline size_t bit_words(uint32_t n) { return ((size_t)n + 31) / 32; }   // words of a 1-bit-per-splat buffer
 } // namespace gs

@@ -75,7 +75,6 @@ __global__ __launch_bounds__(256) void copy_splats_kernel(gsm::AssetView a, cons
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------------
-static inline size_t copy_words(uint32_t n) { return ((size_t)n + 31) / 32; }
 // bytes of the four blobs of a VeryHigh, chunk-less renderer of n splats (the colour texture: 2048 x CalcTextureSize(n).h texels of 16 bytes)
 static inline size_t copy_blob_bytes(int k, uint32_t n) {
     if (k == 2) return (size_t)2048 * ((((size_t)n + 2047) / 2048 + 15) / 16 * 16) * 16;
@@ -89,14 +88,8 @@ static bool copy_dst_gate(const gs_renderer* r) {
     return a.chunkCount == 0 && a.posFmt == 0 && a.scaleFmt == 0 && a.shFmt == 0 && a.colorFmt == 0;
 }
 
-static void copy_xform(const gs_copy_params* p, gsm::CopyXform& X) {
-    static const gs_copy_params kIdentity = { { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 }, { 0, 0, 0, 1 }, { 1, 1, 1 } };
-    if (!p) p = &kIdentity;
-    memcpy(X.m, p->matrix, sizeof(X.m));
-    memcpy(X.rot, p->rotation, sizeof(X.rot));
-    memcpy(X.scale, p->scale, sizeof(X.scale));
-    gsm::CalcSHRot(p->matrix, X.sh);                               // once per call, not once per thread
-}
+// what the kernel writes of a renderer whose four blobs are private (a resize's new state, or after edit_make_private of all four)
+static CopyDst copy_dst_of(gs_renderer* r) { return { r->priv[0], r->priv[1], r->priv[2], r->priv[3], r->deletedBits, r->n }; }
 
 // count clamped so that srcStart + idx and dstStart + idx stay inside both renderers (what the kernel's two tests leave): 0 = nothing to launch
 static uint32_t copy_clamp(uint32_t srcN, uint32_t dstN, uint32_t srcStart, uint32_t dstStart, uint32_t count) {
@@ -125,19 +118,14 @@ static int32_t zeroed(DevBuf<uint8_t>& b, size_t bytes, hipStream_t st) {       
 // visible-sort history ...), with the four zero-filled private blobs, a zeroed deleted buffer, zeroed selection buffers and r's settings.
 static int32_t resize_build(gs_renderer* r, uint32_t newN, gs_renderer* f) {
     hipStream_t st = r->ctx->stream;
-    DevBuf<uint8_t>* const priv[4] = { &f->privPos, &f->privOther, &f->privColor, &f->privSH };
     for (int k = 0; k < 4; ++k) {
-        GS_TRY(zeroed(*priv[k], copy_blob_bytes(k, newN), st));
+        GS_TRY(zeroed(f->priv[k], copy_blob_bytes(k, newN), st));
         f->privBytes[k] = copy_blob_bytes(k, newN);
     }
-    GS_HIP(f->deletedBits.alloc(copy_words(newN) * 4));
-    GS_HIP(hipMemsetAsync(f->deletedBits, 0, copy_words(newN) * 4, st));
+    GS_TRY(ensure_deleted_bits(f, st));
     GS_TRY(edit_ensure(f));
-    // settings: kept
-    f->blendMode = r->blendMode; f->renderMode = r->renderMode; f->pointDisplaySize = r->pointDisplaySize;
-    f->alwaysWriteView = r->alwaysWriteView; f->kernelTiming = r->kernelTiming;
-    f->tileOverrideWL = r->tileOverrideWL; f->tileOverrideHL = r->tileOverrideHL;
-    f->visHistLimit = r->visHistLimit;
+    // settings: the plain values are one struct; what owns memory is applied again
+    f->set = r->set;
     if (r->pairCapacity > f->pairCapacity) GS_TRY(gs_renderer_reserve_pairs(f, r->pairCapacity));
     if (r->cutoutCount) GS_TRY(gs_renderer_set_cutouts(f, (const gs_cutout*)r->cutoutsHost.get(), r->cutoutCount));
     if (r->profCapacity > 0) {
@@ -156,8 +144,7 @@ static int32_t set_splat_count_impl(gs_renderer* r, uint32_t newN, const gs_copy
     if (newN == r->n) return GS_OK;
     GS_TRY(gs_context_synchronize(r->ctx));                        // the context's two streams and the lanes
     const int32_t lanes = r->lanes.empty() ? 1 : (int32_t)r->lanes.size();
-    gsm::CopyXform X;
-    copy_xform(p, X);
+    const gsm::CopyXform X = copy_xform_of(p);
     // everything new is allocated before anything old is released: on a failure the renderer is unchanged
     gs_renderer* f = nullptr;
     GS_TRY(renderer_create_n(r->ctx, r->asset, newN, &f));
@@ -165,8 +152,7 @@ static int32_t set_splat_count_impl(gs_renderer* r, uint32_t newN, const gs_copy
     if (rc == GS_OK) {
         // copy existing data over into the new buffers (EditCopySplats(transform, ..., newSplatCount, 0, 0, m_SplatCount), :1004); shrinking
         // truncates through the kernel's dstIdx >= dstN test
-        const CopyDst d = { f->privPos, f->privOther, f->privColor, f->privSH, f->deletedBits, newN };
-        rc = copy_launch(r->ctx->stream, asset_view(r), r->deletedBits, X, d, 0u, 0u, r->n);
+        rc = copy_launch(r->ctx->stream, asset_view(r), r->deletedBits, X, copy_dst_of(f), 0u, 0u, r->n);
     }
     if (rc == GS_OK && hipStreamSynchronize(r->ctx->stream) != hipSuccess) rc = fail(GS_ERR_HIP, "set_splat_count: the copy failed");
     if (rc != GS_OK) { (void)gs_renderer_destroy(f); return rc; }
@@ -188,17 +174,11 @@ static int32_t copy_splats_into_impl(gs_renderer* src, gs_renderer* dst, const g
     if (!copy_dst_gate(dst)) return fail(GS_ERR_INVALID_ARGUMENT, "copy_splats_into: the destination must be chunk-less with fp32 pos / scale / sh and Float32x4 colour");
     if (copy_clamp(src->n, dst->n, srcStart, dstStart, count) == 0u) return GS_OK;
     GS_HIP(hipSetDevice(dst->ctx->device));
-    gsm::CopyXform X;
-    copy_xform(p, X);
+    const gsm::CopyXform X = copy_xform_of(p);
     hipStream_t st = dst->ctx->stream;
     GS_TRY(edit_before_move(dst));                                 // positions change: the transform's ordering (gs_edit.hip)
     for (int k = 0; k < 4; ++k) GS_TRY(edit_make_private(dst, k));
-    if (src->deletedBits && !dst->deletedBits) {                   // a destination without a deleted buffer gets a zeroed one
-        DevBuf<uint32_t> del;
-        GS_HIP(del.alloc(copy_words(dst->n) * 4));
-        GS_HIP(hipMemsetAsync(del, 0, copy_words(dst->n) * 4, st));
-        dst->deletedBits = std::move(del);
-    }
+    if (src->deletedBits) GS_TRY(ensure_deleted_bits(dst, st));    // a destination without a deleted buffer gets a zeroed one
     const bool cross = src->ctx != dst->ctx;
     if (cross) {                                                   // the source's pending edits are visible to the kernel
         if (!dst->evCopySrcReady) GS_HIP(dst->evCopySrcReady.create(hipEventDisableTiming));
@@ -206,8 +186,7 @@ static int32_t copy_splats_into_impl(gs_renderer* src, gs_renderer* dst, const g
         GS_HIP(hipEventRecord(dst->evCopySrcReady, src->ctx->stream));
         GS_HIP(hipStreamWaitEvent(st, dst->evCopySrcReady, 0));
     }
-    const CopyDst d = { dst->privPos, dst->privOther, dst->privColor, dst->privSH, dst->deletedBits, dst->n };
-    GS_TRY(copy_launch(st, asset_view(src), src->deletedBits, X, d, srcStart, dstStart, count));
+    GS_TRY(copy_launch(st, asset_view(src), src->deletedBits, X, copy_dst_of(dst), srcStart, dstStart, count));
     if (cross) {                                                   // a later transform of the source does not race the read
         GS_HIP(hipEventRecord(dst->evCopyDone, st));
         GS_HIP(hipStreamWaitEvent(src->ctx->stream, dst->evCopyDone, 0));
@@ -261,12 +240,11 @@ __attribute__((visibility("default"))) int32_t gs_copy_kernel_time_for_scripts(g
     if (!src || !dst || !ms || src == dst || src->ctx != dst->ctx || !copy_dst_gate(dst)) return fail(GS_ERR_INVALID_ARGUMENT, "bad argument");
     GS_HIP(hipSetDevice(dst->ctx->device));
     for (int k = 0; k < 4; ++k) GS_TRY(edit_make_private(dst, k));
-    gsm::CopyXform X;
-    copy_xform(nullptr, X);
+    const gsm::CopyXform X = copy_xform_of(nullptr);
     Event ev[2];
     for (Event& e : ev) GS_HIP(e.create(hipEventDefault));
     hipStream_t st = dst->ctx->stream;
-    const CopyDst d = { dst->privPos, dst->privOther, dst->privColor, dst->privSH, dst->deletedBits, dst->n };
+    const CopyDst d = copy_dst_of(dst);
     hipError_t he = hipEventRecord(ev[0], st);
     const int32_t rc = copy_launch(st, asset_view(src), nullptr, X, d, 0u, 0u, src->n);
     if (he == hipSuccess) he = hipEventRecord(ev[1], st);

@@ -175,20 +175,12 @@ __global__ __launch_bounds__(256) void edit_transform_kernel(uint8_t* __restrict
     }
 }
 
-static inline size_t edit_words(const gs_renderer* r) { return ((size_t)r->n + 31) / 32; }
-
-static gsm::EditView edit_view(const gs_renderer* r) {
-    gsm::EditView e;
-    e.deletedBits = r->deletedBits; e.cutouts = r->cutouts; e.cutoutCount = r->cutoutCount;
-    return e;
-}
-
 // EnsureEditingBuffers (GaussianSplatRenderer.cs:767-786) without the deleted buffer, which is made when a delete first needs it
 int32_t edit_ensure(gs_renderer* r) {
     if (r->laneOf) return fail(GS_ERR_INVALID_ARGUMENT, "a lane holds no selection: edit its owner");
     GS_HIP(hipSetDevice(r->ctx->device));
     if (r->editSelected) return GS_OK;
-    const size_t bytes = edit_words(r) * 4;
+    const size_t bytes = bit_words(r->n) * 4;
     DevBuf<uint32_t> sel, md, cb;
     GS_HIP(sel.alloc(bytes));
     GS_HIP(md.alloc(bytes));
@@ -199,6 +191,15 @@ int32_t edit_ensure(gs_renderer* r) {
     return GS_OK;
 }
 
+int32_t ensure_deleted_bits(gs_renderer* r, hipStream_t st) {
+    if (r->deletedBits) return GS_OK;
+    DevBuf<uint32_t> d;
+    GS_HIP(d.alloc(bit_words(r->n) * 4));
+    GS_HIP(hipMemsetAsync(d, 0, bit_words(r->n) * 4, st));
+    r->deletedBits = std::move(d);
+    return GS_OK;
+}
+
 void edit_free(gs_renderer* r) {
     r->editSelected.reset(); r->editSelectedMouseDown.reset(); r->editCountsBounds.reset();
     r->editPosMouseDown.reset(); r->editOtherMouseDown.reset();
@@ -206,7 +207,7 @@ void edit_free(gs_renderer* r) {
 }
 
 static inline uint32_t splat_grid(const gs_renderer* r) { return (r->n + 255u) / 256u; }
-static inline uint32_t word_grid(const gs_renderer* r) { return (uint32_t)((edit_words(r) + 255) / 256); }
+static inline uint32_t word_grid(const gs_renderer* r) { return (uint32_t)((bit_words(r->n) + 255) / 256); }
 
 // The lanes' copies of the deleted bits follow a delete: a device-to-device copy on each lane's OWN stream, behind an event on the
 // context's stream -- no host synchronisation, and a frame already dealt to a lane keeps the bits of the time it was dealt (its calc_view is
@@ -214,7 +215,7 @@ static inline uint32_t word_grid(const gs_renderer* r) { return (uint32_t)((edit
 // next (another delete, gs_renderer_set_deleted_bits) comes after they have read it.
 int32_t edit_deleted_to_lanes(gs_renderer* r) {
     if (r->lanes.empty()) return GS_OK;
-    const size_t bytes = edit_words(r) * 4;
+    const size_t bytes = bit_words(r->n) * 4;
     if (!r->evEditDeleted) GS_HIP(r->evEditDeleted.create(hipEventDisableTiming));
     GS_HIP(hipEventRecord(r->evEditDeleted, r->ctx->stream));
     for (gs_renderer* L : r->lanes) {
@@ -236,20 +237,16 @@ static inline bool edit_rot_gate(const gs_renderer* r) { const gsm::AssetView& a
 // what a transform may touch of blob k (0 pos, 1 other): whole records only
 static inline size_t edit_blob_bytes(const gs_renderer* r, int k) { return (size_t)r->n * (k == 0 ? 12u : 16u); }
 
-// the renderer's current pos (k = 0) / other (1) blob, wherever it lives
-static inline const uint8_t* edit_current_blob(const gs_renderer* r, int k) { return blob_ptr(r, k); }
-
 // copy-on-write: the private copy of blob k (0 pos, 1 other, 2 color, 3 sh), made on the context's stream the first time a transform or a copy
 // is about to write it.  Padded like an owned upload of the asset (the dword stitching of LoadUInt may touch the dword after the last record).
 int32_t edit_make_private(gs_renderer* r, int k) {
-    DevBuf<uint8_t>& priv = k == 0 ? r->privPos : (k == 1 ? r->privOther : (k == 2 ? r->privColor : r->privSH));
-    if (priv) return GS_OK;
+    if (r->priv[k]) return GS_OK;
     const size_t bytes = (size_t)blob_bytes(r, k);
     DevBuf<uint8_t> b;
     GS_HIP(b.alloc(bytes + 16));
     GS_HIP(hipMemsetAsync(b + bytes, 0, 16, r->ctx->stream));
     GS_HIP(hipMemcpyAsync(b, blob_ptr(r, k), bytes, hipMemcpyDeviceToDevice, r->ctx->stream));
-    priv = std::move(b);
+    r->priv[k] = std::move(b);
     r->privBytes[k] = bytes;
     return GS_OK;
 }
@@ -261,7 +258,7 @@ static int32_t edit_store_mouse_down(gs_renderer* r, int k) {
     if (k == 0 ? edit_pos_gate(r) : edit_rot_gate(r)) {
         DevBuf<uint8_t>& md = k == 0 ? r->editPosMouseDown : r->editOtherMouseDown;
         if (!md) GS_HIP(md.alloc(edit_blob_bytes(r, k)));
-        GS_HIP(hipMemcpyAsync(md, edit_current_blob(r, k), edit_blob_bytes(r, k), hipMemcpyDeviceToDevice, r->ctx->stream));
+        GS_HIP(hipMemcpyAsync(md, blob_ptr(r, k), edit_blob_bytes(r, k), hipMemcpyDeviceToDevice, r->ctx->stream));
     }
     (k == 0 ? r->editPosStored : r->editOtherStored) = true;
     return GS_OK;
@@ -308,8 +305,8 @@ static int32_t edit_transform(gs_renderer* r, int op, const gsm::EditXform& X) {
     GS_TRY(edit_before_move(r));
     if (doPos) GS_TRY(edit_make_private(r, 0));
     if (doRot) GS_TRY(edit_make_private(r, 1));
-    uint8_t* pos = doPos ? r->privPos.get() : nullptr;
-    uint8_t* other = doRot ? r->privOther.get() : nullptr;
+    uint8_t* pos = doPos ? r->priv[0].get() : nullptr;
+    uint8_t* other = doRot ? r->priv[1].get() : nullptr;
     const uint8_t* posMD = r->editPosMouseDown, * otherMD = r->editOtherMouseDown;
     const uint32_t* sel = r->editSelected;
     const dim3 grid(splat_grid(r)), block(256);
@@ -318,12 +315,6 @@ static int32_t edit_transform(gs_renderer* r, int op, const gsm::EditXform& X) {
     else hipLaunchKernelGGL(edit_transform_kernel<kEditScale>, grid, block, 0, r->ctx->stream, pos, other, posMD, otherMD, sel, r->n, X);
     GS_HIP(hipGetLastError());
     return edit_after_move(r);
-}
-
-static void edit_xform_matrices(gsm::EditXform& X, const float center[3], const float o2w[16], const float w2o[16]) {
-    memcpy(X.center, center, sizeof(X.center));
-    memcpy(X.o2w, o2w, sizeof(X.o2w));
-    memcpy(X.w2o, w2o, sizeof(X.w2o));
 }
 
 } // namespace gs
@@ -336,7 +327,7 @@ int32_t gs_renderer_edit_select_all(gs_renderer* r) {
     if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
     GS_TRY(edit_ensure(r));
     hipLaunchKernelGGL(edit_select_all_kernel, dim3(splat_grid(r)), dim3(256), 0, r->ctx->stream, asset_view(r), edit_view(r), r->editSelected,
-                       (uint32_t)edit_words(r), 0u);
+                       (uint32_t)bit_words(r->n), 0u);
     GS_HIP(hipGetLastError());
     return GS_OK;
 }
@@ -345,7 +336,7 @@ int32_t gs_renderer_edit_invert_selection(gs_renderer* r) {
     if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
     GS_TRY(edit_ensure(r));
     hipLaunchKernelGGL(edit_select_all_kernel, dim3(splat_grid(r)), dim3(256), 0, r->ctx->stream, asset_view(r), edit_view(r), r->editSelected,
-                       (uint32_t)edit_words(r), 1u);
+                       (uint32_t)bit_words(r->n), 1u);
     GS_HIP(hipGetLastError());
     return GS_OK;
 }
@@ -353,27 +344,22 @@ int32_t gs_renderer_edit_invert_selection(gs_renderer* r) {
 int32_t gs_renderer_edit_deselect_all(gs_renderer* r) {
     if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
     GS_TRY(edit_ensure(r));
-    GS_HIP(hipMemsetAsync(r->editSelected, 0, edit_words(r) * 4, r->ctx->stream));          // CSClearBuffer
+    GS_HIP(hipMemsetAsync(r->editSelected, 0, bit_words(r->n) * 4, r->ctx->stream));          // CSClearBuffer
     return GS_OK;
 }
 
 int32_t gs_renderer_edit_store_selection(gs_renderer* r) {
     if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
     GS_TRY(edit_ensure(r));
-    GS_HIP(hipMemcpyAsync(r->editSelectedMouseDown, r->editSelected, edit_words(r) * 4, hipMemcpyDeviceToDevice, r->ctx->stream));
+    GS_HIP(hipMemcpyAsync(r->editSelectedMouseDown, r->editSelected, bit_words(r->n) * 4, hipMemcpyDeviceToDevice, r->ctx->stream));
     return GS_OK;
 }
 
 int32_t gs_renderer_edit_update_selection(gs_renderer* r, const gs_frame_params* p, const float selection_rect[4], int32_t subtract) {
     if (!r || !p || !selection_rect) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
     GS_TRY(edit_ensure(r));
-    gsm::EditSelect S;
-    memcpy(S.o2w, p->matrix_object_to_world, sizeof(S.o2w));
-    memcpy(S.vp, p->matrix_vp, sizeof(S.vp));
-    S.screenW = p->screen_w; S.screenH = p->screen_h;
-    memcpy(S.rect, selection_rect, sizeof(S.rect));
-    hipLaunchKernelGGL(edit_selection_update_kernel, dim3(splat_grid(r)), dim3(256), 0, r->ctx->stream, asset_view(r), edit_view(r), S,
-                       (const uint32_t*)r->editSelectedMouseDown, r->editSelected, (uint32_t)edit_words(r), subtract ? 0u : 1u);
+    hipLaunchKernelGGL(edit_selection_update_kernel, dim3(splat_grid(r)), dim3(256), 0, r->ctx->stream, asset_view(r), edit_view(r), edit_select_of(*p, selection_rect),
+                       (const uint32_t*)r->editSelectedMouseDown, r->editSelected, (uint32_t)bit_words(r->n), subtract ? 0u : 1u);
     GS_HIP(hipGetLastError());
     return GS_OK;
 }
@@ -381,14 +367,8 @@ int32_t gs_renderer_edit_update_selection(gs_renderer* r, const gs_frame_params*
 int32_t gs_renderer_edit_delete_selected(gs_renderer* r) {
     if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
     GS_TRY(edit_ensure(r));
-    const size_t bytes = edit_words(r) * 4;
-    if (!r->deletedBits) {
-        DevBuf<uint32_t> d;
-        GS_HIP(d.alloc(bytes));
-        GS_HIP(hipMemsetAsync(d, 0, bytes, r->ctx->stream));
-        r->deletedBits = std::move(d);
-    }
-    hipLaunchKernelGGL(edit_delete_kernel, dim3(word_grid(r)), dim3(256), 0, r->ctx->stream, r->deletedBits, r->editSelected, (uint32_t)edit_words(r));
+    GS_TRY(ensure_deleted_bits(r, r->ctx->stream));
+    hipLaunchKernelGGL(edit_delete_kernel, dim3(word_grid(r)), dim3(256), 0, r->ctx->stream, r->deletedBits, r->editSelected, (uint32_t)bit_words(r->n));
     GS_HIP(hipGetLastError());
     return edit_deleted_to_lanes(r);
 }
@@ -400,7 +380,7 @@ int32_t gs_renderer_edit_info(gs_renderer* r, gs_edit_info* out) {
     GS_HIP(hipSetDevice(r->ctx->device));
     hipLaunchKernelGGL(edit_init_data_kernel, dim3(1), dim3(64), 0, r->ctx->stream, r->editCountsBounds);
     hipLaunchKernelGGL(edit_update_data_kernel, dim3(splat_grid(r)), dim3(256), 0, r->ctx->stream, asset_view(r), edit_view(r),
-                       (const uint32_t*)r->editSelected, (uint32_t)edit_words(r), r->editCountsBounds);
+                       (const uint32_t*)r->editSelected, (uint32_t)bit_words(r->n), r->editCountsBounds);
     GS_HIP(hipGetLastError());
     uint32_t res[9];
     GS_HIP(hipMemcpyAsync(res, r->editCountsBounds, sizeof(res), hipMemcpyDeviceToHost, r->ctx->stream));
@@ -416,7 +396,7 @@ int32_t gs_renderer_edit_info(gs_renderer* r, gs_edit_info* out) {
 
 int32_t gs_renderer_edit_upload_selected_bits(gs_renderer* r, const uint32_t* words, size_t word_count) {
     if (!r || !words) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
-    if (word_count != edit_words(r)) return fail(GS_ERR_INVALID_ARGUMENT, "selected bits: word_count must be ceil(splat_count / 32)");
+    if (word_count != bit_words(r->n)) return fail(GS_ERR_INVALID_ARGUMENT, "selected bits: word_count must be ceil(splat_count / 32)");
     GS_TRY(edit_ensure(r));
     GS_HIP(hipMemcpyAsync(r->editSelected, words, word_count * 4, hipMemcpyHostToDevice, r->ctx->stream));
     GS_HIP(hipStreamSynchronize(r->ctx->stream));                  // `words` is only read during the call
@@ -425,7 +405,7 @@ int32_t gs_renderer_edit_upload_selected_bits(gs_renderer* r, const uint32_t* wo
 
 int32_t gs_renderer_edit_download_bits(gs_renderer* r, uint32_t* selected, uint32_t* selected_mouse_down, uint32_t* deleted, size_t word_count) {
     if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
-    if (word_count != edit_words(r)) return fail(GS_ERR_INVALID_ARGUMENT, "edit bits: word_count must be ceil(splat_count / 32)");
+    if (word_count != bit_words(r->n)) return fail(GS_ERR_INVALID_ARGUMENT, "edit bits: word_count must be ceil(splat_count / 32)");
     GS_HIP(hipSetDevice(r->ctx->device));
     const size_t bytes = word_count * 4;
     uint32_t* const dst[3] = { selected, selected_mouse_down, deleted };
@@ -452,10 +432,7 @@ int32_t gs_renderer_edit_store_other_mouse_down(gs_renderer* r) {
 int32_t gs_renderer_edit_translate_selection(gs_renderer* r, const float delta[3]) {
     if (!r || !delta) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
     GS_TRY(edit_ensure(r));
-    gsm::EditXform X;
-    memset(&X, 0, sizeof(X));
-    memcpy(X.delta, delta, 3 * sizeof(float));
-    return edit_transform(r, kEditTranslate, X);
+    return edit_transform(r, kEditTranslate, edit_xform_of(nullptr, nullptr, nullptr, delta, 3));
 }
 
 int32_t gs_renderer_edit_rotate_selection(gs_renderer* r, const float center[3], const float local_to_world[16], const float world_to_local[16],
@@ -464,11 +441,7 @@ int32_t gs_renderer_edit_rotate_selection(gs_renderer* r, const float center[3],
     GS_TRY(edit_ensure(r));
     if (!r->editPosStored || !r->editOtherStored)                  // "should have captured initial state" (:859)
         return fail(GS_ERR_INVALID_ARGUMENT, "rotate: the mouse-down copies of pos and other have not been stored");
-    gsm::EditXform X;
-    memset(&X, 0, sizeof(X));
-    edit_xform_matrices(X, center, local_to_world, world_to_local);
-    memcpy(X.delta, rotation_xyzw, 4 * sizeof(float));
-    return edit_transform(r, kEditRotate, X);
+    return edit_transform(r, kEditRotate, edit_xform_of(center, local_to_world, world_to_local, rotation_xyzw, 4));
 }
 
 int32_t gs_renderer_edit_scale_selection(gs_renderer* r, const float center[3], const float local_to_world[16], const float world_to_local[16],
@@ -476,19 +449,15 @@ int32_t gs_renderer_edit_scale_selection(gs_renderer* r, const float center[3], 
     if (!r || !center || !local_to_world || !world_to_local || !scale) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
     GS_TRY(edit_ensure(r));
     if (!r->editPosStored) return fail(GS_ERR_INVALID_ARGUMENT, "scale: the mouse-down copy of pos has not been stored");      // :880
-    gsm::EditXform X;
-    memset(&X, 0, sizeof(X));
-    edit_xform_matrices(X, center, local_to_world, world_to_local);
-    memcpy(X.delta, scale, 3 * sizeof(float));
-    return edit_transform(r, kEditScale, X);
+    return edit_transform(r, kEditScale, edit_xform_of(center, local_to_world, world_to_local, scale, 3));
 }
 
 int32_t gs_renderer_edit_download_pos_other(gs_renderer* r, void* pos, size_t pos_bytes, void* other, size_t other_bytes) {
     if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
     if ((pos && pos_bytes > blob_bytes(r, 0)) || (other && other_bytes > blob_bytes(r, 1))) return fail(GS_ERR_INVALID_ARGUMENT, "more bytes asked for than the blob holds");
     GS_HIP(hipSetDevice(r->ctx->device));
-    if (pos && pos_bytes) GS_HIP(hipMemcpyAsync(pos, edit_current_blob(r, 0), pos_bytes, hipMemcpyDeviceToHost, r->ctx->stream));
-    if (other && other_bytes) GS_HIP(hipMemcpyAsync(other, edit_current_blob(r, 1), other_bytes, hipMemcpyDeviceToHost, r->ctx->stream));
+    if (pos && pos_bytes) GS_HIP(hipMemcpyAsync(pos, blob_ptr(r, 0), pos_bytes, hipMemcpyDeviceToHost, r->ctx->stream));
+    if (other && other_bytes) GS_HIP(hipMemcpyAsync(other, blob_ptr(r, 1), other_bytes, hipMemcpyDeviceToHost, r->ctx->stream));
     GS_HIP(hipStreamSynchronize(r->ctx->stream));
     return GS_OK;
 }

@@ -123,21 +123,6 @@ __global__ __launch_bounds__(256) void export_records_kernel(gsm::AssetView a, g
 #endif
 }
 
-static gsm::EditView export_edit_view(const gs_renderer* r) {
-    gsm::EditView e;
-    e.deletedBits = r->deletedBits; e.cutouts = r->cutouts; e.cutoutCount = r->cutoutCount;
-    return e;
-}
-
-static void export_xform(const gs_export_params* p, gsm::ExportXform& X) {
-    memset(&X, 0, sizeof(X));
-    X.bake = p->bake_transform ? 1u : 0u;
-    memcpy(X.o2w, p->matrix_object_to_world, sizeof(X.o2w));
-    memcpy(X.rot, p->rotation, sizeof(X.rot));
-    memcpy(X.scale, p->scale, sizeof(X.scale));
-    if (X.bake) gsm::CalcSHRot(p->matrix_object_to_world, X.sh);   // once per call, not once per thread
-}
-
 static uint32_t export_batch_chunks() {
     unsigned long long b = kExportBatchDefault;
     if (const char* e = getenv("GSPLAT_EXPORT_BATCH")) {           // read per call
@@ -166,7 +151,7 @@ struct ExportRun {
         hostBase.resize((size_t)chunks + 1);                       // (may throw: before anything is in flight)
         GS_HIP(counts.alloc((size_t)chunks * 4));
         GS_HIP(base.alloc(((size_t)chunks + 1) * 4));
-        hipLaunchKernelGGL(export_count_kernel, dim3(chunks), dim3(256), 0, st, asset_view(r), export_edit_view(r), counts.get());
+        hipLaunchKernelGGL(export_count_kernel, dim3(chunks), dim3(256), 0, st, asset_view(r), edit_view(r), counts.get());
         hipLaunchKernelGGL(export_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, (const uint32_t*)counts.get(), base.get(), chunks);
         GS_HIP(hipGetLastError());
         GS_HIP(hipMemcpyAsync(hostBase.data(), base.get(), hostBase.size() * 4, hipMemcpyDeviceToHost, st));
@@ -181,7 +166,7 @@ struct ExportRun {
         return (uint32_t)((hi < r->n ? hi : r->n) - (uint64_t)c0 * 256u);
     }
     void launch(uint32_t c0, uint32_t c1, float* out) const {
-        hipLaunchKernelGGL(export_records_kernel, dim3(c1 - c0), dim3(256), 0, r->ctx->stream, asset_view(r), export_edit_view(r), X,
+        hipLaunchKernelGGL(export_records_kernel, dim3(c1 - c0), dim3(256), 0, r->ctx->stream, asset_view(r), edit_view(r), X,
                            compact ? (const uint32_t*)base.get() : (const uint32_t*)nullptr, c0, out);
     }
     // sink(data, bytes) != 0 stops the run with GS_ERR_INVALID_ARGUMENT (its own detail set)
@@ -233,7 +218,7 @@ static int32_t export_begin(gs_renderer* r, const gs_export_params* p, bool comp
     if (!r || !p) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
     GS_HIP(hipSetDevice(r->ctx->device));
     run.r = r; run.compact = compact;
-    export_xform(p, run.X);
+    run.X = export_xform_of(*p);
     return run.prepare();
 }
 
@@ -322,7 +307,7 @@ static int32_t export_kernel_times_impl(gs_renderer* r, const gs_export_params* 
     Event ev[4];
     for (Event& e : ev) GS_HIP(e.create(hipEventDefault));         // (nothing is in flight yet)
     hipError_t he = hipEventRecord(ev[0], st);
-    hipLaunchKernelGGL(export_count_kernel, dim3(run.chunks), dim3(256), 0, st, asset_view(r), export_edit_view(r), run.counts.get());
+    hipLaunchKernelGGL(export_count_kernel, dim3(run.chunks), dim3(256), 0, st, asset_view(r), edit_view(r), run.counts.get());
     if (he == hipSuccess) he = hipEventRecord(ev[1], st);
     hipLaunchKernelGGL(export_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, (const uint32_t*)run.counts.get(), run.base.get(), run.chunks);
     if (he == hipSuccess) he = hipEventRecord(ev[2], st);

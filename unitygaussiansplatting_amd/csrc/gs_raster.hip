@@ -1536,7 +1536,7 @@ void auto_tile_shape(uint32_t width, uint32_t height, uint32_t& wl, uint32_t& hl
     wl = shape == 1 ? 4u : 5u; hl = shape == 3 ? 5u : 4u;
 }
 void pick_tile_shape(const gs_renderer* r, uint32_t width, uint32_t height, uint32_t& wl, uint32_t& hl) {
-    if (r && r->tileOverrideWL) { wl = r->tileOverrideWL; hl = r->tileOverrideHL; return; }
+    if (r && settings(r).tileOverrideWL) { wl = settings(r).tileOverrideWL; hl = settings(r).tileOverrideHL; return; }
     auto_tile_shape(width, height, wl, hl);
     if (r && !forced_tile_shape() && wl == 5u && r->adaptTall) hl = 5u;      // large splats: 32x32 (adapt_tile_shape)
 }
@@ -1615,8 +1615,8 @@ int32_t enqueue_draw(gs_renderer* r, const gs_frame_params* p, gs_target* rt) {
                                              tileOrder, ds.costWrite, r->recs, rt->rgba16f, rc, dstIsZero, r->recW, rt->sceneDepth, \
                                              ds.binCtl, ds.pairSortError, r->hostReport.device())
 #define GS_LAUNCH_BLEND(M, D) do { if (twl == 4u) GS_LAUNCH_BLEND_S(M, D, 4, 4); else if (thl == 4u) GS_LAUNCH_BLEND_S(M, D, 5, 4); else GS_LAUNCH_BLEND_S(M, D, 5, 5); } while (0)
-    if (rt->sceneDepth) { if (r->blendMode == 0) GS_LAUNCH_BLEND(0, true); else GS_LAUNCH_BLEND(1, true); }
-    else { if (r->blendMode == 0) GS_LAUNCH_BLEND(0, false); else GS_LAUNCH_BLEND(1, false); }
+    if (rt->sceneDepth) { if (settings(r).blendMode == 0) GS_LAUNCH_BLEND(0, true); else GS_LAUNCH_BLEND(1, true); }
+    else { if (settings(r).blendMode == 0) GS_LAUNCH_BLEND(0, false); else GS_LAUNCH_BLEND(1, false); }
 #undef GS_LAUNCH_BLEND
 #undef GS_LAUNCH_BLEND_S
     prof_record(r, 6);
@@ -1667,8 +1667,8 @@ int32_t enqueue_debug_boxes(gs_renderer* r, const gs_frame_params* p, gs_target*
     }
 #define GS_LAUNCH_BOX(M, D) hipLaunchKernelGGL((blend_box_kernel<M, D>), dim3(ds.numTiles), dim3(256), 0, st, r->pairVals, ds.tileStart, ds.tileEnd, ds.tileOrder, \
                                            ds.costWrite, r->boxRecs, rt->rgba16f, ds.rc, ray, ds.dstIsZero, rt->sceneDepth)
-    if (rt->sceneDepth) { if (r->blendMode == 0) GS_LAUNCH_BOX(0, true); else GS_LAUNCH_BOX(1, true); }
-    else { if (r->blendMode == 0) GS_LAUNCH_BOX(0, false); else GS_LAUNCH_BOX(1, false); }
+    if (rt->sceneDepth) { if (settings(r).blendMode == 0) GS_LAUNCH_BOX(0, true); else GS_LAUNCH_BOX(1, true); }
+    else { if (settings(r).blendMode == 0) GS_LAUNCH_BOX(0, false); else GS_LAUNCH_BOX(1, false); }
 #undef GS_LAUNCH_BOX
     prof_record(r, 6);
     GS_HIP(hipGetLastError());
@@ -1690,10 +1690,10 @@ int32_t enqueue_debug_points(gs_renderer* r, const gs_frame_params* p, gs_target
     gsm::FrameConsts c;
     flatten_params(p, c);
     prof_record(r, 3);
-    hipLaunchKernelGGL(debug_points_kernel, dim3(div_up(r->n, 256)), dim3(256), 0, st, asset_view(r), c, 0.5f * r->pointDisplaySize, rt->width, rt->height,
+    hipLaunchKernelGGL(debug_points_kernel, dim3(div_up(r->n, 256)), dim3(256), 0, st, asset_view(r), c, 0.5f * settings(r).pointDisplaySize, rt->width, rt->height,
                        rt->sceneDepth, rt->zbuf);
     prof_record(r, 5);
-    hipLaunchKernelGGL(debug_points_resolve_kernel, dim3(div_up(numPix, 256)), dim3(256), 0, st, asset_view(r), numPix, r->renderMode == GS_RENDER_DEBUG_POINT_INDICES ? 1 : 0,
+    hipLaunchKernelGGL(debug_points_resolve_kernel, dim3(div_up(numPix, 256)), dim3(256), 0, st, asset_view(r), numPix, settings(r).renderMode == GS_RENDER_DEBUG_POINT_INDICES ? 1 : 0,
                        rt->zbuf, rt->rgba16f);
     prof_record(r, 6);
     GS_HIP(hipGetLastError());

@@ -664,7 +664,7 @@ int32_t enqueue_sort_passes(gs_context* ctx, hipStream_t stream, SortState& st, 
         // pass).  The timestamped launches cost ~6 us each themselves, which is why this is a mode of its own and not part of the
         // stage brackets (with it on, sort_ms / pair_sort_ms read ~25 us high).
         hipEvent_t evStart = nullptr, evStop = nullptr;
-        if (profR && profR->profiling && profR->kernelTiming && !profR->ev.empty() && evFirst >= 0) {
+        if (profR && profR->profiling && settings(profR).kernelTiming && !profR->ev.empty() && evFirst >= 0) {
             const int kb = profR->profCur * kEvPerFrame + (evFirst == 10 ? 14 : 22) + 2 * p;
             evStart = profR->ev[kb]; evStop = profR->ev[kb + 1];
             profR->evValid[kb] = profR->evValid[kb + 1] = 1;

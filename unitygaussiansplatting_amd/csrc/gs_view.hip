@@ -200,19 +200,6 @@ __global__ __launch_bounds__(256) void calc_view_kernel(gsm::AssetView a, gsm::F
 
 } // namespace
 
-void flatten_params(const gs_frame_params* p, gsm::FrameConsts& c) {
-    memcpy(c.mv, p->matrix_mv, 12 * sizeof(float));
-    memcpy(c.o2w, p->matrix_object_to_world, 12 * sizeof(float));
-    memcpy(c.w2o, p->matrix_world_to_object, 12 * sizeof(float));
-    memcpy(c.vp, p->matrix_vp, 16 * sizeof(float));
-    gsm::FrameConstsFromProjection(c, p->proj_m00, p->proj_m11, p->screen_w); c.screenW = p->screen_w; c.screenH = p->screen_h;
-    c.camx = p->cam_pos_world[0]; c.camy = p->cam_pos_world[1]; c.camz = p->cam_pos_world[2];
-    c.splatScale = p->splat_scale; c.opacityScale = p->opacity_scale;
-    c.shOrder = p->sh_order; c.shOnly = p->sh_only;
-    c.nearClip = p->near_clip; c.farClip = p->far_clip;
-    gsm::FrameConstsChunkCull(c);
-}
-
 template <bool FULL>
 static void launch_calc_view(int mode, uint32_t grid, hipStream_t st, const gsm::AssetView& a, const gsm::FrameConsts& c, const gsm::EditView& e,
                              const ViewOutputs& o) {

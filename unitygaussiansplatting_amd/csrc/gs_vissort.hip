@@ -479,7 +479,8 @@ int32_t vis_alloc(gs_renderer* r) {
     r->visKeys = std::move(k); r->visIdx = std::move(v); r->visRectX = std::move(x); r->visRectY = std::move(y); r->visPairOffset = std::move(po);
     r->visControl = std::move(c); r->visControlIdx = 0;
     static const int envLimit = [] { const char* s = getenv("GSPLAT_VIS_HISTORY"); const int v = s ? atoi(s) : 0; return (v >= 2 && v <= kVisHistory) ? v : 0; }();
-    if (envLimit && r->visHistLimit == kVisHistory) r->visHistLimit = envLimit;
+    RendererSettings& set = (r->laneOf ? r->laneOf : r)->set;      // (a lane's vis_alloc: its owner's settings)
+    if (envLimit && set.visHistLimit == kVisHistory) set.visHistLimit = envLimit;
     return GS_OK;
 }
 
@@ -494,7 +495,7 @@ int32_t vis_push_matrix(gs_renderer* r, const float* m) {
     for (int j = 0; j < r->visHistDepth && found < 0; ++j)
         if (memcmp(r->visHist[j], row, 16) == 0) found = j;
     if (found == 0) return GS_OK;
-    const int limit = r->visHistLimit < 2 ? 2 : (r->visHistLimit > kVisHistory ? kVisHistory : r->visHistLimit);
+    const int set = settings(r).visHistLimit, limit = set < 2 ? 2 : (set > kVisHistory ? kVisHistory : set);
     if (found < 0 && r->visHistDepth >= limit) GS_TRY(vis_consolidate(r));      // (leaves one row)
     const int last = found > 0 ? found : r->visHistDepth++;      // found > 0: rows 0 .. found-1 move down one, over the duplicate
     for (int j = last; j > 0; --j) memcpy(r->visHist[j], r->visHist[j - 1], 16);
