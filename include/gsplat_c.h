@@ -306,8 +306,9 @@ int32_t gs_renderer_set_deleted_bits(gs_renderer* r, const uint32_t* words, size
  * mouse-down copy, ceil(N/32) zeroed words each; the deleted buffer is the one gs_renderer_set_deleted_bits fills -- made (zeroed) by
  * the first delete, and read as zeros while it does not exist.  Every kernel tests the splats against the renderer's current
  * gs_renderer_set_cutouts list (IsSplatCut), as the reference's do.
- * Selection has NO VISUAL EFFECT: the reference's highlight of selected splats (RenderGaussianSplats.shader:63-73,87-101) is not built;
- * only deletion, the transforms and the merge below change a frame.  Exporting only reads the blobs: see below.
+ * Selection is DRAWN -- the reference's highlight of selected splats, RenderGaussianSplats.shader:63-73,87-101 -- once
+ * gs_renderer_set_selection_highlight (below) is on; by default it is off and only deletion, the transforms and the merge below change a
+ * frame.  Exporting only reads the blobs: see below.
  * Two literal quirks of the reference are kept: select-all / invert set the bits of the last word beyond N and the counts include them
  * (N = 33: select all reports 64 selected), and a splat whose pixel position is NaN is inside every rectangle.
  * The mutating calls are asynchronous on the context's stream like every other call; the info / download calls block.  Selection lives
@@ -333,6 +334,19 @@ int32_t gs_renderer_edit_upload_selected_bits(gs_renderer* r, const uint32_t* wo
 /* ceil(N/32) words each; any may be NULL; a buffer that does not exist reads as zeros; blocks */
 int32_t gs_renderer_edit_download_bits(gs_renderer* r, uint32_t* selected, uint32_t* selected_mouse_down, uint32_t* deleted, size_t word_count);
 int32_t gs_renderer_edit_release(gs_renderer* r);                   /* frees selected + mouse-down (bits, pos, other); deleted bits and moved splats stay */
+/* The reference's highlight of the selection (RenderGaussianSplats.shader:63-73,87-101; _SplatBitsValid, GaussianSplatRenderer.cs:518-520)
+ * (addition to ABI 9).  enabled != 0: every GS_RENDER_SPLATS frame whose gs_renderer_calc_view runs while the edit buffers exist draws the splats
+ * selected at that call as the reference does: tinted magenta (rgb = lerp(rgb, (1, 0, 1), 0.5)), with raised opacity (alpha = saturate(e + 0.3)
+ * where e = exp(-|q|^2) > 7/255, else e) and a solid magenta outline ring where 7/255 < e < 10/255.  The splat's own opacity plays no part: a
+ * selected splat of opacity 0 is drawn, with the footprint of an opacity-1 splat, so a large selection of faint splats raises the pair count
+ * (the pair buffers grow as for any other frame).  Deleted, cut and behind-the-camera splats are not drawn, selected or not; the debug render
+ * modes do not show the selection.  gs_renderer_download_view is unchanged (the reference marks the splat in the vertex stage, not in the view
+ * buffer); gs_renderer_download_raster_records shows the mark (alpha half = -1, 0xBC00) and the larger rectangles.  Default 0: frames are what
+ * they are without this call, and cost the same.  With no edit buffers (no edit call yet, or after gs_renderer_edit_release) the switch changes
+ * nothing.  A plain setting: kept by gs_renderer_edit_set_splat_count, shared by the lanes of gs_renderer_set_frames_in_flight, whose copies of
+ * the selected bits follow every selection change like the deleted bits follow a delete (a frame already dealt keeps the selection of the time
+ * it was dealt).  A host that wants the reference's editor behaviour sets it to 1 once. */
+int32_t gs_renderer_set_selection_highlight(gs_renderer* r, int32_t enabled);
 
 /* ---- moving the selection: EditTranslateSelection / EditRotateSelection / EditScaleSelection (GaussianSplatRenderer.cs:794-809,842-894;
  * CSTranslateSelection, CSRotateSelection, CSScaleSelection, SplatUtilities.compute:425-521)  (additions to ABI 9) ----

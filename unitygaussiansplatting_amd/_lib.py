@@ -64,6 +64,7 @@ SIGNATURES = {
     "gs_renderer_edit_upload_selected_bits": (C.c_int32, [_P, _P, C.c_size_t]),
     "gs_renderer_edit_download_bits": (C.c_int32, [_P, _P, _P, _P, C.c_size_t]),
     "gs_renderer_edit_release": (C.c_int32, [_P]),
+    "gs_renderer_set_selection_highlight": (C.c_int32, [_P, C.c_int32]),
     "gs_renderer_edit_store_pos_mouse_down": (C.c_int32, [_P]),
     "gs_renderer_edit_store_other_mouse_down": (C.c_int32, [_P]),
     "gs_renderer_edit_translate_selection": (C.c_int32, [_P, C.POINTER(C.c_float)]),

@@ -342,6 +342,10 @@ int32_t gs_renderer_set_frames_in_flight(gs_renderer* r, int32_t frames) {
         const int32_t rc = edit_deleted_to_lanes(r);
         if (rc != GS_OK) { lanes_destroy(r); return rc; }
     }
+    {                                                            // ... and of the selection, if it is highlighted
+        const int32_t rc = edit_selected_to_lanes(r);
+        if (rc != GS_OK) { lanes_destroy(r); return rc; }
+    }
     return lanes_resync(r);
 }
 
@@ -515,7 +519,9 @@ int32_t gs_renderer_calc_view(gs_renderer* r, const gs_frame_params* p) {
     GS_TRY(bind_device(r->ctx));
     rec_ev(r, 7);
     const bool full = settings(r).alwaysWriteView;
-    GS_TRY(enqueue_calc_view(r->ctx, asset_view(r), p, edit_view(r), view_outputs(r), full));
+    const gsm::EditView ev = edit_view(r);
+    GS_TRY(enqueue_calc_view(r->ctx, asset_view(r), p, ev, view_outputs(r), full));
+    r->viewHighlight = ev.selectedBits != nullptr;
     r->viewMaterialised = full;
     r->movedSinceView = false;
     r->visOrderValid = false;                                    // the visible set may have changed
@@ -637,6 +643,17 @@ int32_t gs_renderer_set_blend_mode(gs_renderer* r, int32_t mode) {
     if (!r || (mode != 0 && mode != 1)) return fail(GS_ERR_INVALID_ARGUMENT, "blend mode must be 0 or 1");
     r->set.blendMode = mode;
     return GS_OK;
+}
+
+int32_t gs_renderer_set_selection_highlight(gs_renderer* r, int32_t enabled) {
+    if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
+    if (r->laneOf) return fail(GS_ERR_INVALID_ARGUMENT, "a lane holds no selection: set its owner");
+    const bool on = enabled != 0;
+    if (on == r->set.selectionHighlight) return GS_OK;
+    r->set.selectionHighlight = on;
+    if (!on) return GS_OK;                                       // (the lanes keep their copies: nothing reads them while the switch is off)
+    GS_TRY(bind_device(r->ctx));
+    return edit_selected_to_lanes(r);                            // the lanes' copies of the selection as it is now
 }
 
 int32_t gs_renderer_set_tile_shape(gs_renderer* r, uint32_t tile_w, uint32_t tile_h) {
@@ -819,7 +836,11 @@ int32_t gs_renderer_download_view(gs_renderer* r, void* out, size_t bytes) {
         // m_GpuView is materialised on demand: the per-frame launch skips it (nothing in this renderer reads it); re-run the
         // frame's launch as the reference's full kernel.  rec/rect/visibility are rewritten with identical values.
         GS_TRY(bind_device(r->ctx));
-        GS_TRY(enqueue_calc_view(r->ctx, asset_view(r), &r->lastParams, edit_view(r), view_outputs(r), true));
+        // (a highlighted frame's marks are rewritten from the selection as it is now -- the reference reads the bits at draw time)
+        const gsm::EditView ev = edit_view(r);
+        GS_TRY(enqueue_calc_view(r->ctx, asset_view(r), &r->lastParams, ev, view_outputs(r), true));
+        if (ev.selectedBits || r->viewHighlight) r->visOrderValid = false;      // ... so the visible set may have changed
+        r->viewHighlight = ev.selectedBits != nullptr;
         r->viewMaterialised = true;
     }
     return download(r->ctx, out, r->view, bytes);

@@ -242,6 +242,7 @@ struct RendererSettings {
     bool kernelTiming = false;              // gs_renderer_set_kernel_timing: Onesweep launches carry their own start / stop events
     uint32_t tileOverrideWL = 0, tileOverrideHL = 0;   // gs_renderer_set_tile_shape: log2 tile width / height, 0 = automatic
     int visHistLimit = kVisHistory;         // rows kept before the base is consolidated (gs_renderer_set_sort_history_limit; GSPLAT_VIS_HISTORY)
+    bool selectionHighlight = false;        // gs_renderer_set_selection_highlight: splat frames draw the selection as the reference does (gs::edit_view)
 };
 } // namespace gs
 
@@ -282,6 +283,12 @@ struct gs_renderer {
     gs::DevBuf<uint32_t> editCountsBounds;  // m_GpuEditCountsBounds: 3 counts + 6 sortable uints
     gs::Event evEditDeleted;                // context's stream -> lanes: deletedBits holds a delete's result
     gs::Event evEditCopied;                 // (on a lane) lane's stream -> owner's: the lane has taken its copy
+    // the selection highlight (RendererSettings::selectionHighlight): what calc_view reads is editSelected itself on the owner and, on a lane, its own copy,
+    // which follows every change of the selection exactly as a lane's deletedBits follow a delete (gs::edit_selected_to_lanes)
+    gs::DevBuf<uint32_t> laneSelected;      // (on a lane) its copy of the owner's editSelected, made while the highlight is on; else null
+    gs::Event evEditSelected;               // context's stream -> lanes: editSelected holds the new selection
+    gs::Event evEditSelCopied;              // (on a lane) lane's stream -> owner's: the lane has taken its copy
+    bool viewHighlight = false;             // the last calc_view ran with the selected bits: the records carry its marks and the draw launches the highlight blend
     // The renderer's own, writable copy of the two blobs the transform kernels write (CSTranslateSelection / CSRotateSelection / CSScaleSelection): made by
     // the first transform whose format gate can pass, null until then (gs::asset_view).  The asset itself -- shared between contexts, lanes and replicas --
     // is never written; lanes read their owner's copies in place.
@@ -423,6 +430,7 @@ void edit_free(gs_renderer* r);             // the selection buffers and the mou
 int32_t edit_ensure(gs_renderer* r);        // EnsureEditingBuffers: the zeroed selection buffers, made once
 int32_t edit_make_private(gs_renderer* r, int k);   // copy-on-write of blob k (0 pos, 1 other, 2 color, 3 sh) on the context's stream
 int32_t edit_deleted_to_lanes(gs_renderer* r);      // the lanes' copies of the deleted bits follow the owner's, by events
+int32_t edit_selected_to_lanes(gs_renderer* r);     // ... and, while the highlight is on, their copies of the selection
 int32_t ensure_deleted_bits(gs_renderer* r, hipStream_t st);   // a renderer without a deleted buffer gets one, zero-filled on st
 // what brackets a kernel that rewrites positions (the transforms, the merge): ordering against sorts, GS_SORT_VISIBLE's history and the lanes
 int32_t edit_before_move(gs_renderer* r);
@@ -455,10 +463,13 @@ inline const uint8_t* blob_ptr(const gs_renderer* r, int k) {
 }
 // the settings this renderer draws with: its own, or its owner's if it is a lane
 inline const RendererSettings& settings(const gs_renderer* r) { return (r->laneOf ? r->laneOf : r)->set; }
-// the edit state calc_view and the edit kernels consult, of THIS renderer: a lane reads its own copy of the deleted bits
+// the edit state calc_view and the edit kernels consult, of THIS renderer: a lane reads its own copy of the deleted bits -- and of the selected bits,
+// which are there only for a splat frame of a renderer whose highlight is on and whose edit buffers exist (_SplatBitsValid, GaussianSplatRenderer.cs:518-520)
 inline gsm::EditView edit_view(const gs_renderer* r) {
     gsm::EditView e;
     e.deletedBits = r->deletedBits; e.cutouts = r->cutouts; e.cutoutCount = r->cutoutCount;
+    const RendererSettings& s = settings(r);
+    if (s.selectionHighlight && s.renderMode == GS_RENDER_SPLATS) e.selectedBits = r->laneOf ? r->laneSelected.get() : r->editSelected.get();
     return e;
 }
 inline size_t bit_words(uint32_t n) { return ((size_t)n + 31) / 32; }   // words of a 1-bit-per-splat buffer

@@ -61,6 +61,9 @@ struct EditView {
     const uint32_t* deletedBits;    // ceil(n/32) words, or null (_SplatBitsValid = 0)
     const uint32_t* cutouts;        // cutoutCount x 17 dwords: float4x4 (rows of 4) + typeAndFlags
     uint32_t cutoutCount;
+    // _SplatSelectedBits of the draw (RenderGaussianSplats.shader:63-73), ceil(n/32) words: the selection a splat frame highlights.  Null whenever the
+    // highlight is off or there are no edit buffers; only the highlight builds of calc_view read it (SplatSelected below).
+    const uint32_t* selectedBits = nullptr;
 };
 
 // The camera-only part of CalcCovariance2D (GaussianSplatting.hlsl:62-72), evaluated once per frame on the host with the
@@ -1069,6 +1072,50 @@ GS_HD float DecideAlpha(float alphaNative, float y, float a, bool& live) {
     return alphaNative;
 }
 
+// ---- the fragment of a SELECTED splat (RenderGaussianSplats.shader:87-101) ---------------------------------------------------------
+// vert() hands frag() col.a = -1 for a splat whose bit in _SplatSelectedBits is set (:63-73); the splat's own opacity then plays no part.
+// With e = exp(-dot(pos, pos)) (half is float here):
+//     alpha = e;  if (e > 7/255) { if (e < 10/255) { alpha = 1; rgb = (1, 0, 1); }  alpha = saturate(alpha + 0.3); }
+//     rgb = lerp(rgb, (1, 0, 1), 0.5);  discard if alpha < 1/255;  output (rgb alpha, alpha)
+// i.e. a magenta tint, raised opacity and a solid magenta ring where e is in (7/255, 10/255).  Literals are fp32 and folded as fp32
+// (7.0f / 255.0f ...), lerp is one fmaf, as oracle/_ref's fused build of the shader text evaluates them.
+// The three decisions on e are jumps of the OUTPUT (alpha 0.027 -> 1 -> 0.34 across the ring), and e comes from the one operation that is
+// not bit-identical on the host and the GPU (exp2, <= 1 ulp apart).  So, as DecideAlpha does for alpha at 1/255: when the native e lies
+// within kAlphaWindow / 2 ulps of ANY of the three thresholds, both sides recompute e = Exp2Det(y) and take all three decisions, and the
+// alpha, from that.  Outside the windows the native e is >= 8 ulps away from every threshold: no 1-ulp difference changes a decision.
+constexpr uint32_t kSelRingLoBits = 0x3CE0E0E1u;                       // 7.0f / 255.0f
+constexpr uint32_t kSelRingHiBits = 0x3D20A0A1u;                       // 10.0f / 255.0f
+GS_HD bool SplatSelected(const EditView& E, uint32_t idx) { return E.selectedBits && ((E.selectedBits[idx >> 5] >> (idx & 31u)) & 1u); }
+// The alpha half of a selected splat's raster record: -1.0 (what vert() puts into col.a).  The blend recognises it by the sign.
+constexpr uint32_t kSelectedAlphaHalf = 0xBC00u;
+GS_HD bool SelectedNearThreshold(float eNative) {
+    const uint32_t b = f2u(eNative), h = kAlphaWindow / 2u;
+    return (b - (kAlphaThresholdBits - h) < kAlphaWindow) | (b - (kSelRingLoBits - h) < kAlphaWindow) | (b - (kSelRingHiBits - h) < kAlphaWindow);
+}
+// eNative = exp2(y) with whatever exp2 the machine has, y = power * log2(e).  Returns the alpha to blend with; ring = the fragment lies on the
+// outline ring (its colour is (1, 0, 1) before the tint); live = not discarded.  windowed = false: the shader's arithmetic alone.
+GS_HD float DecideSelected(float eNative, float y, bool& ring, bool& live, bool windowed = true) {
+    float e = eNative;
+    if (windowed && SelectedNearThreshold(eNative)) e = Exp2Det(y);
+    float alpha = e;
+    ring = false;
+    if (e > u2f(kSelRingLoBits)) {
+        if (e < u2f(kSelRingHiBits)) { alpha = 1.0f; ring = true; }
+        alpha = fminf(fmaxf(alpha + 0.3f, 0.0f), 1.0f);
+    }
+    live = alpha >= u2f(kAlphaThresholdBits);
+    return alpha;
+}
+// The whole selected fragment: rgb = the splat's colour, out4 = (rgb alpha, alpha) premultiplied in fp32.  Returns live.
+GS_HD bool SelectedFragment(float eNative, float y, float r, float g, float b, float* out4, bool windowed = true) {
+    bool ring, live;
+    const float alpha = DecideSelected(eNative, y, ring, live, windowed);
+    if (ring) { r = 1.0f; g = 0.0f; b = 1.0f; }
+    r = fmaf(0.5f, 1.0f - r, r); g = fmaf(0.5f, 0.0f - g, g); b = fmaf(0.5f, 1.0f - b, b);      // lerp(rgb, (1, 0, 1), 0.5)
+    out4[0] = r * alpha; out4[1] = g * alpha; out4[2] = b * alpha; out4[3] = alpha;
+    return live;
+}
+
 // ln(x) for a positive normal x from fp32 operations only (bit manipulation, one division, explicit fmaf): the same bits
 // on the host and on the device, unlike logf().  |error| < 1e-6 (atanh series of the mantissa reduced to [0.707, 1.414)).
 GS_HD float LogDetCore(uint32_t u, int ebias) {                 // u: the bits of a positive normal float; ebias: -127 (or -150 for a denormal scaled by 2^23)
@@ -1142,6 +1189,17 @@ GS_HD bool PrepareSplat(const ViewData& v, float W, float H, float nearClip, flo
     fp.x0 = x0; fp.x1 = x1; fp.y0 = y0; fp.y1 = y1;
     return true;
 }
+
+// PrepareSplat for a draw that highlights the selection.  A SELECTED splat's visibility and pixel rectangle are those of opacity 1 -- no
+// opacity cull, r2 from a = 1 -- because its fragments are live wherever e >= 1/255 inside the quad, whatever the splat's own opacity
+// (DecideSelected).  The view record itself is not changed; an unselected splat is PrepareSplat's, bit for bit.
+GS_HD bool PrepareSplatHighlight(const ViewData& v, bool selected, float W, float H, float nearClip, float farClip, SplatFootprint& fp) {
+    ViewData o = v;
+    if (selected) o.color[1] = (v.color[1] & 0xffff0000u) | 0x3C00u;
+    return PrepareSplat(o, W, H, nearClip, farClip, fp);
+}
+// ... and the colour dword of its raster record: the alpha half becomes vert()'s col.a = -1
+GS_HD uint32_t RecordColor1(uint32_t color1, bool selected) { return selected ? ((color1 & 0xffff0000u) | kSelectedAlphaHalf) : color1; }
 
 // ---- export: CSExportData (SplatUtilities.compute:523-673; kernels in gs_export.hip) ---------------------------------------------
 // LogDet over every float: the IEEE results for the special inputs (-inf for +-0, NaN for a negative or NaN input, +inf for +inf), a

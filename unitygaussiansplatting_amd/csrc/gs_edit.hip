@@ -11,10 +11,10 @@
 // The last three are the only kernels that write splat data.  The asset's blobs are shared between contexts, lanes and replicas and stay
 // immutable: the first transform whose format gate can pass gives the renderer a private copy of the pos and / or other blob (copy-on-write,
 // gs::asset_view), and from then on every kernel of this renderer and of its lanes reads that copy.  CSExportData only reads: gs_export.hip.
-// CSCopySplats / EditSetSplatCount / EditCopySplatsInto -- the merge -- are gs_copy.hip.  Not built: the highlight of
-// selected splats in the fragment stage (RenderGaussianSplats.shader:63-73,87-101: it replaces a splat's
-// opacity by -1, which here would go through PrepareSplat's cull and footprint bound and the blend's alpha window).  Selection therefore
-// has NO VISUAL EFFECT: only deletion and the transforms change a frame.
+// CSCopySplats / EditSetSplatCount / EditCopySplatsInto -- the merge -- are gs_copy.hip.  The highlight of selected splats
+// (RenderGaussianSplats.shader:63-73,87-101) is drawn by calc_view and the blend (gs_view.hip, gs_raster.hip) when
+// gs_renderer_set_selection_highlight is on; what this file does for it is keep the lanes' copies of the selection in step
+// (edit_selected_to_lanes).  With the switch off -- the default -- selection has no visual effect.
 //
 // Shape (wave64; not the reference's, which runs one thread per WORD with a 32-iteration position loop, neighbouring threads reading
 // positions 32 records apart): one thread per SPLAT, 256-thread workgroups aligned to the 256-splat chunk so that the chunk header is
@@ -229,6 +229,24 @@ int32_t edit_deleted_to_lanes(gs_renderer* r) {
     return GS_OK;
 }
 
+// The same for the selection while it is highlighted: every call that changes editSelected ends here.  With the highlight off (or no lanes) it
+// does nothing; switching the highlight on, and making lanes, bring the copies up to date (gs_api.hip).
+int32_t edit_selected_to_lanes(gs_renderer* r) {
+    if (r->lanes.empty() || !r->set.selectionHighlight || !r->editSelected) return GS_OK;
+    const size_t bytes = bit_words(r->n) * 4;
+    if (!r->evEditSelected) GS_HIP(r->evEditSelected.create(hipEventDisableTiming));
+    GS_HIP(hipEventRecord(r->evEditSelected, r->ctx->stream));
+    for (gs_renderer* L : r->lanes) {
+        if (!L->laneSelected) GS_HIP(L->laneSelected.alloc(bytes));
+        if (!L->evEditSelCopied) GS_HIP(L->evEditSelCopied.create(hipEventDisableTiming));
+        GS_HIP(hipStreamWaitEvent(L->ctx->stream, r->evEditSelected, 0));
+        GS_HIP(hipMemcpyAsync(L->laneSelected, r->editSelected, bytes, hipMemcpyDeviceToDevice, L->ctx->stream));
+        GS_HIP(hipEventRecord(L->evEditSelCopied, L->ctx->stream));
+        GS_HIP(hipStreamWaitEvent(r->ctx->stream, L->evEditSelCopied, 0));
+    }
+    return GS_OK;
+}
+
 // ---- the transforms ---------------------------------------------------------------------------------------------------------------------
 // The reference's format gates, literally (SplatUtilities.compute:445,469,483): positions are written only in a chunk-less asset with fp32
 // positions, rotation words only in a chunk-less asset with fp32 scales and fp32 SH (so an other record is 4 + 12 bytes).
@@ -329,7 +347,7 @@ int32_t gs_renderer_edit_select_all(gs_renderer* r) {
     hipLaunchKernelGGL(edit_select_all_kernel, dim3(splat_grid(r)), dim3(256), 0, r->ctx->stream, asset_view(r), edit_view(r), r->editSelected,
                        (uint32_t)bit_words(r->n), 0u);
     GS_HIP(hipGetLastError());
-    return GS_OK;
+    return edit_selected_to_lanes(r);
 }
 
 int32_t gs_renderer_edit_invert_selection(gs_renderer* r) {
@@ -338,14 +356,14 @@ int32_t gs_renderer_edit_invert_selection(gs_renderer* r) {
     hipLaunchKernelGGL(edit_select_all_kernel, dim3(splat_grid(r)), dim3(256), 0, r->ctx->stream, asset_view(r), edit_view(r), r->editSelected,
                        (uint32_t)bit_words(r->n), 1u);
     GS_HIP(hipGetLastError());
-    return GS_OK;
+    return edit_selected_to_lanes(r);
 }
 
 int32_t gs_renderer_edit_deselect_all(gs_renderer* r) {
     if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
     GS_TRY(edit_ensure(r));
     GS_HIP(hipMemsetAsync(r->editSelected, 0, bit_words(r->n) * 4, r->ctx->stream));          // CSClearBuffer
-    return GS_OK;
+    return edit_selected_to_lanes(r);
 }
 
 int32_t gs_renderer_edit_store_selection(gs_renderer* r) {
@@ -361,7 +379,7 @@ int32_t gs_renderer_edit_update_selection(gs_renderer* r, const gs_frame_params*
     hipLaunchKernelGGL(edit_selection_update_kernel, dim3(splat_grid(r)), dim3(256), 0, r->ctx->stream, asset_view(r), edit_view(r), edit_select_of(*p, selection_rect),
                        (const uint32_t*)r->editSelectedMouseDown, r->editSelected, (uint32_t)bit_words(r->n), subtract ? 0u : 1u);
     GS_HIP(hipGetLastError());
-    return GS_OK;
+    return edit_selected_to_lanes(r);
 }
 
 int32_t gs_renderer_edit_delete_selected(gs_renderer* r) {
@@ -370,7 +388,8 @@ int32_t gs_renderer_edit_delete_selected(gs_renderer* r) {
     GS_TRY(ensure_deleted_bits(r, r->ctx->stream));
     hipLaunchKernelGGL(edit_delete_kernel, dim3(word_grid(r)), dim3(256), 0, r->ctx->stream, r->deletedBits, r->editSelected, (uint32_t)bit_words(r->n));
     GS_HIP(hipGetLastError());
-    return edit_deleted_to_lanes(r);
+    GS_TRY(edit_deleted_to_lanes(r));
+    return edit_selected_to_lanes(r);                              // (the delete cleared the selection)
 }
 
 int32_t gs_renderer_edit_info(gs_renderer* r, gs_edit_info* out) {
@@ -400,7 +419,7 @@ int32_t gs_renderer_edit_upload_selected_bits(gs_renderer* r, const uint32_t* wo
     GS_TRY(edit_ensure(r));
     GS_HIP(hipMemcpyAsync(r->editSelected, words, word_count * 4, hipMemcpyHostToDevice, r->ctx->stream));
     GS_HIP(hipStreamSynchronize(r->ctx->stream));                  // `words` is only read during the call
-    return GS_OK;
+    return edit_selected_to_lanes(r);
 }
 
 int32_t gs_renderer_edit_download_bits(gs_renderer* r, uint32_t* selected, uint32_t* selected_mouse_down, uint32_t* deleted, size_t word_count) {
@@ -467,6 +486,11 @@ int32_t gs_renderer_edit_release(gs_renderer* r) {
     if (!r->editSelected && !r->editPosStored && !r->editOtherStored) return GS_OK;
     GS_HIP(hipSetDevice(r->ctx->device));
     GS_HIP(hipStreamSynchronize(r->ctx->stream));
+    for (gs_renderer* L : r->lanes) {                              // no edit buffers, nothing to highlight: the lanes' copies go once their frames have read them
+        if (!L->laneSelected) continue;
+        GS_HIP(hipStreamSynchronize(L->ctx->stream));
+        L->laneSelected.reset();
+    }
     edit_free(r);
     return GS_OK;
 }

@@ -918,7 +918,12 @@ __device__ unsigned long long g_blendStats[8];
 // tile, HW_ID | XCC_ID << 32, 0.  Two clock reads and one 64-byte store per workgroup: the launch is not slowed measurably (unlike GS_BLEND_STATS' atomics).
 __device__ unsigned long long g_blendTl[8192 * 8];
 #endif
-template <int MODE, bool DEPTH, int TWL, int THL>
+// HL: the frame highlights the selection (gs_renderer_set_selection_highlight).  A record whose alpha half is negative (-1: calc_view's mark of a
+// selected splat, the reference's col.a = -1) is staged with the opacity-1 r2 / extents and its fragments take the reference's selected branch
+// (RenderGaussianSplats.shader:87-101; gsm::DecideSelected): from the same q, power, y2 and v_exp_f32 result as the plain path, premultiplied in fp32
+// and blended through blend_src.  A survivor's record is an LDS broadcast, so the test is wave-uniform: a scalar branch.  Early termination,
+// finished() / saturated() and the depth test apply unchanged.  HL = false is the kernel as it was: frames without highlight launch it.
+template <int MODE, bool DEPTH, int TWL, int THL, bool HL>
 __global__ __launch_bounds__(64 << (TWL + THL - 6)) void blend_kernel(const uint32_t* __restrict__ pairVals, const uint32_t* __restrict__ tileStart,
                                                     const uint32_t* __restrict__ tileEnd, const uint32_t* __restrict__ tileOrder,
                                                     uint32_t* __restrict__ tileCost, const SplatRec* __restrict__ recs,
@@ -1001,7 +1006,8 @@ __global__ __launch_bounds__(64 << (TWL + THL - 6)) void blend_kernel(const uint
         if ((uint32_t)tid < cnt) {
             const float inv1 = 1.0f / gsm::dot2f(r0.z, r0.w, r0.z, r0.w);
             const float inv2 = 1.0f / gsm::dot2f(r1.x, r1.y, r1.x, r1.y);
-            const float ca = gsm::f16tof32(gsm::f2u(r1.w));
+            float ca = gsm::f16tof32(gsm::f2u(r1.w));
+            if (HL) ca = (gsm::f2u(r1.w) & 0x8000u) ? 1.0f : ca;                  // a selected splat: the footprint of opacity 1
             // bounding box of  quad |q|<=2  INTERSECT  {exp(-|q|^2) a >= 1/255}  (same formula as PrepareSplat)
             const float exr = 2.0f * (fabsf(r0.z) + fabsf(r1.x)), eyr = 2.0f * (fabsf(r0.w) + fabsf(r1.y));
             const float r2 = fmaf(gsm::LogDet(255.0f * ca), 1.0001f, 1.0e-3f);
@@ -1045,6 +1051,23 @@ __global__ __launch_bounds__(64 << (TWL + THL - 6)) void blend_kernel(const uint
                     const float q1 = q.x, q2 = q.y;
                     const float power = -fmaf(q2, q2, q1 * q1);
                     const float y2 = power * 1.44269504088896340736f;                // exp(x) = exp2(x * log2 e), DESIGN.md section 5 #6
+                    if (HL && ((uint32_t)__builtin_amdgcn_readfirstlane((int)B4.w) & 0x8000u)) {       // a selected splat (wave-uniform: the record is a broadcast)
+                        const int inQuadS = (int)(fmaxf(fabsf(q1), fabsf(q2)) <= 2.0f);
+                        bool ring, liveS;
+                        const float alphaS = gsm::DecideSelected(__builtin_amdgcn_exp2f(y2), y2, ring, liveS);
+                        liveS = liveS && inQuadS;
+                        if (DEPTH) liveS = liveS && (s_e[rec].w <= sceneZ);
+                        if (MODE == 1) liveS = liveS && !acc.saturated();
+#ifdef GS_BLEND_STATS
+                        { const unsigned long long lv = __ballot(liveS); GS_STAT(4, __popcll(lv)); }
+#endif
+                        if (liveS) {
+                            float cr = ring ? 1.0f : half_hi(B4.z), cg = ring ? 0.0f : half_lo(B4.z), cb = ring ? 1.0f : half_hi(B4.w);
+                            cr = fmaf(0.5f, 1.0f - cr, cr); cg = fmaf(0.5f, 0.0f - cg, cg); cb = fmaf(0.5f, 1.0f - cb, cb);      // lerp(rgb, (1, 0, 1), 0.5)
+                            acc.blend_src(cr * alphaS, cg * alphaS, cb * alphaS, alphaS);
+                        }
+                        return;
+                    }
                     float alpha = mix_mul_lo_sat_after_trans(B4.w, __builtin_amdgcn_exp2f(y2));
                     const int inQuad = (int)(fmaxf(fabsf(q1), fabsf(q2)) <= 2.0f);     // one v_max with |.| modifiers + one compare (NaN q: not inside)
                     bool live;
@@ -1611,14 +1634,17 @@ int32_t enqueue_draw(gs_renderer* r, const gs_frame_params* p, gs_target* rt) {
         flatten_params(p, fc);
         hipLaunchKernelGGL(splat_depth_kernel, dim3(div_up(r->n, 256)), dim3(256), 0, st, asset_view(r), fc, (const uint32_t*)r->visMask.get(), r->recW);
     }
-#define GS_LAUNCH_BLEND_S(M, D, WL, HL) hipLaunchKernelGGL((blend_kernel<M, D, WL, HL>), dim3(numTiles), dim3(64u << (WL + HL - 6)), 0, st, r->pairVals, tileStart, tileEnd, \
+    // the records carry the selection's marks iff this frame's calc_view ran with the selected bits: then, and only then, the highlight build
+#define GS_LAUNCH_BLEND_K(M, D, WL, HL, SEL) hipLaunchKernelGGL((blend_kernel<M, D, WL, HL, SEL>), dim3(numTiles), dim3(64u << (WL + HL - 6)), 0, st, r->pairVals, tileStart, tileEnd, \
                                              tileOrder, ds.costWrite, r->recs, rt->rgba16f, rc, dstIsZero, r->recW, rt->sceneDepth, \
                                              ds.binCtl, ds.pairSortError, r->hostReport.device())
+#define GS_LAUNCH_BLEND_S(M, D, WL, HL) do { if (r->viewHighlight) GS_LAUNCH_BLEND_K(M, D, WL, HL, true); else GS_LAUNCH_BLEND_K(M, D, WL, HL, false); } while (0)
 #define GS_LAUNCH_BLEND(M, D) do { if (twl == 4u) GS_LAUNCH_BLEND_S(M, D, 4, 4); else if (thl == 4u) GS_LAUNCH_BLEND_S(M, D, 5, 4); else GS_LAUNCH_BLEND_S(M, D, 5, 5); } while (0)
     if (rt->sceneDepth) { if (settings(r).blendMode == 0) GS_LAUNCH_BLEND(0, true); else GS_LAUNCH_BLEND(1, true); }
     else { if (settings(r).blendMode == 0) GS_LAUNCH_BLEND(0, false); else GS_LAUNCH_BLEND(1, false); }
 #undef GS_LAUNCH_BLEND
 #undef GS_LAUNCH_BLEND_S
+#undef GS_LAUNCH_BLEND_K
     prof_record(r, 6);
     GS_HIP(hipGetLastError());
     if (foreignTarget) {

@@ -56,8 +56,23 @@ constexpr int cmax(int a, int b) { return a > b ? a : b; }
 // reaches a tile (a third of the scene for C2; culling is spatially coherent and the asset is in Morton order, so whole
 // waves and whole workgroups drop out), and no view write.  gs_renderer_download_view re-runs the frame's launch with
 // FULL = true on demand, so the parity surface is unchanged.  VALU-bound either way (~1200 instructions per splat FULL).
-template <int SHMODE, bool FULL>
-__global__ __launch_bounds__(256) void calc_view_kernel(gsm::AssetView a, gsm::FrameConsts P, gsm::EditView E, ViewOutputs O) {
+//
+// HL = the draw highlights the selection (gs_renderer_set_selection_highlight; RenderGaussianSplats.shader:63-73): a selected splat in front of
+// the camera is culled, bounded and binned as an opacity-1 splat (gsm::PrepareSplatHighlight) and the alpha half of its raster record is -1, which
+// is how the reference's vertex stage marks it for the fragment stage.  The bit is read by splat index, here, at the frame's calc_view.  The view
+// record is the reference's whatever the selection.  HL = false never reads E.selectedBits: the frame without highlight is the kernel it was.
+//
+// The kernel of a frame without highlight takes the edit state WITHOUT the selected bits: its SGPRs are full of frame constants (ViewOutputs, gs_common.h),
+// and eight more bytes of kernel arguments -- read or not -- change how they are allocated.  Its argument layout, and so its code, is what it was.
+struct EditViewPlain { const uint32_t* deletedBits; const uint32_t* cutouts; uint32_t cutoutCount; };
+template <bool HL> struct EditArg { typedef EditViewPlain type; };
+template <> struct EditArg<true> { typedef gsm::EditView type; };
+__device__ __forceinline__ gsm::EditView edit_view_of(const EditViewPlain& p) { gsm::EditView e; e.deletedBits = p.deletedBits; e.cutouts = p.cutouts; e.cutoutCount = p.cutoutCount; return e; }
+__device__ __forceinline__ gsm::EditView edit_view_of(const gsm::EditView& e) { return e; }
+
+template <int SHMODE, bool FULL, bool HL>
+__global__ __launch_bounds__(256) void calc_view_kernel(gsm::AssetView a, gsm::FrameConsts P, typename EditArg<HL>::type Earg, ViewOutputs O) {
+    const gsm::EditView E = edit_view_of(Earg);
     GS_VIEW_PRIORITY();
     gsm::ViewData* __restrict__ out = O.view;
     SplatRec* __restrict__ recs = O.recs;
@@ -122,6 +137,7 @@ __global__ __launch_bounds__(256) void calc_view_kernel(gsm::AssetView a, gsm::F
     gsm::SplatFootprint fp;
     uint2 rect = make_uint2(0u, 0u);
     bool visible = false;
+    bool selected = false;                                             // HL only
     const bool shStaged = SHMODE < 4;
 
     if (FULL) {
@@ -130,7 +146,13 @@ __global__ __launch_bounds__(256) void calc_view_kernel(gsm::AssetView a, gsm::F
         if (idx < a.n) {
             gsm::CalcViewGeom(a, P, E, idx, vp);
             if (vp.front) shade(vp);
-            const bool ok = gsm::PrepareSplat(vp.view, P.screenW, P.screenH, P.nearClip, P.farClip, fp);
+            bool ok;
+            if (HL) {
+                selected = vp.front && gsm::SplatSelected(E, idx);
+                ok = gsm::PrepareSplatHighlight(vp.view, selected, P.screenW, P.screenH, P.nearClip, P.farClip, fp);
+            } else {
+                ok = gsm::PrepareSplat(vp.view, P.screenW, P.screenH, P.nearClip, P.farClip, fp);
+            }
             visible = ok && fp.x0 <= fp.x1;
         }
     } else {
@@ -150,7 +172,13 @@ __global__ __launch_bounds__(256) void calc_view_kernel(gsm::AssetView a, gsm::F
         if (threadIdx.x == 0) s_any = 0;
         if (idx < a.n) {
             gsm::CalcViewGeom(a, P, E, idx, vp, true, true);       // early out for splats that cannot reach the screen; vp only read if drawn
-            const bool ok = vp.front && !vp.culled && gsm::PrepareSplat(vp.view, P.screenW, P.screenH, P.nearClip, P.farClip, fp);
+            bool ok;
+            if (HL) {
+                selected = vp.front && !vp.culled && gsm::SplatSelected(E, idx);
+                ok = vp.front && !vp.culled && gsm::PrepareSplatHighlight(vp.view, selected, P.screenW, P.screenH, P.nearClip, P.farClip, fp);
+            } else {
+                ok = vp.front && !vp.culled && gsm::PrepareSplat(vp.view, P.screenW, P.screenH, P.nearClip, P.farClip, fp);
+            }
             visible = ok && fp.x0 <= fp.x1;
         }
         __syncthreads();
@@ -168,7 +196,7 @@ __global__ __launch_bounds__(256) void calc_view_kernel(gsm::AssetView a, gsm::F
             // the blend kernel only ever reads records of splats that reach a tile
             uint4* rp = (uint4*)(recs + idx);
             rp[0] = make_uint4(gsm::f2u(fp.cx), gsm::f2u(fp.cy), gsm::f2u(vp.view.axis1[0]), gsm::f2u(vp.view.axis1[1]));
-            rp[1] = make_uint4(gsm::f2u(vp.view.axis2[0]), gsm::f2u(vp.view.axis2[1]), vp.view.color[0], vp.view.color[1]);
+            rp[1] = make_uint4(gsm::f2u(vp.view.axis2[0]), gsm::f2u(vp.view.axis2[1]), vp.view.color[0], HL ? gsm::RecordColor1(vp.view.color[1], selected) : vp.view.color[1]);
         }
         rects[idx] = rect;
     }
@@ -203,13 +231,17 @@ __global__ __launch_bounds__(256) void calc_view_kernel(gsm::AssetView a, gsm::F
 template <bool FULL>
 static void launch_calc_view(int mode, uint32_t grid, hipStream_t st, const gsm::AssetView& a, const gsm::FrameConsts& c, const gsm::EditView& e,
                              const ViewOutputs& o) {
+    const EditViewPlain ep = { e.deletedBits, e.cutouts, e.cutoutCount };
+#define GS_LAUNCH_VIEW(M) do { if (e.selectedBits) hipLaunchKernelGGL((calc_view_kernel<M, FULL, true>), dim3(grid), dim3(256), 0, st, a, c, e, o); \
+                               else hipLaunchKernelGGL((calc_view_kernel<M, FULL, false>), dim3(grid), dim3(256), 0, st, a, c, ep, o); } while (0)
     switch (mode) {
-        case 0: hipLaunchKernelGGL((calc_view_kernel<0, FULL>), dim3(grid), dim3(256), 0, st, a, c, e, o); break;
-        case 1: hipLaunchKernelGGL((calc_view_kernel<1, FULL>), dim3(grid), dim3(256), 0, st, a, c, e, o); break;
-        case 2: hipLaunchKernelGGL((calc_view_kernel<2, FULL>), dim3(grid), dim3(256), 0, st, a, c, e, o); break;
-        case 3: hipLaunchKernelGGL((calc_view_kernel<3, FULL>), dim3(grid), dim3(256), 0, st, a, c, e, o); break;
-        default: hipLaunchKernelGGL((calc_view_kernel<4, FULL>), dim3(grid), dim3(256), 0, st, a, c, e, o); break;
+        case 0: GS_LAUNCH_VIEW(0); break;
+        case 1: GS_LAUNCH_VIEW(1); break;
+        case 2: GS_LAUNCH_VIEW(2); break;
+        case 3: GS_LAUNCH_VIEW(3); break;
+        default: GS_LAUNCH_VIEW(4); break;
     }
+#undef GS_LAUNCH_VIEW
 }
 
 // full = true: also evaluate the colour of every splat in front of the camera and write the N x 40 B view buffer

@@ -88,7 +88,7 @@ namespace GaussianSplatting.Runtime
         public unsafe struct Cutout { public fixed float matrix[16]; public uint typeAndFlags; }
         [DllImport(Lib)] public static extern int gs_renderer_set_cutouts(IntPtr renderer, Cutout[] cutouts, uint count);
         [DllImport(Lib)] public static extern int gs_renderer_set_deleted_bits(IntPtr renderer, uint[] words, UIntPtr wordCount);
-        // selection and deletion (GaussianSplatRenderer.Edit*, GaussianSplatRenderer.cs:705-740,767-840,896-934); selection has no visual effect
+        // selection and deletion (GaussianSplatRenderer.Edit*, GaussianSplatRenderer.cs:705-740,767-840,896-934); the selection is drawn once gs_renderer_set_selection_highlight(r, 1) is set
         [StructLayout(LayoutKind.Sequential)]
         public unsafe struct EditInfo { public uint selected, deleted, cut; public fixed float boundsMin[3]; public fixed float boundsMax[3]; }
         [DllImport(Lib)] public static extern int gs_renderer_edit_select_all(IntPtr renderer);
@@ -101,6 +101,7 @@ namespace GaussianSplatting.Runtime
         [DllImport(Lib)] public static extern int gs_renderer_edit_upload_selected_bits(IntPtr renderer, uint[] words, UIntPtr wordCount);
         [DllImport(Lib)] public static extern int gs_renderer_edit_download_bits(IntPtr renderer, uint[] selected, uint[] selectedMouseDown, uint[] deleted, UIntPtr wordCount);
         [DllImport(Lib)] public static extern int gs_renderer_edit_release(IntPtr renderer);
+        [DllImport(Lib)] public static extern int gs_renderer_set_selection_highlight(IntPtr renderer, int enabled);
         // moving the selection (copy-on-write of the renderer's pos / other blobs); matrices row-major, quaternion x y z w
         [DllImport(Lib)] public static extern int gs_renderer_edit_store_pos_mouse_down(IntPtr renderer);
         [DllImport(Lib)] public static extern int gs_renderer_edit_store_other_mouse_down(IntPtr renderer);

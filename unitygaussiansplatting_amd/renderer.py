@@ -225,7 +225,7 @@ class GpuSorting:
 class GaussianSplatRenderer:
     """GaussianSplatRenderer component (GaussianSplatRenderer.cs:214-680): the render path, and of the editing half (:705-1075) selection,
     deletion, moving / rotating / scaling the selection, export and the merge (EditSetSplatCount / EditCopySplatsInto) -- Edit* below.  Selected
-    splats are not highlighted: selection has no visual effect, only deletion, the transforms and the merge change a frame."""
+    splats are drawn highlighted, as the reference's editor shows them, after SetSelectionHighlight(True); off by default."""
 
     def __init__(self, ctx: GpuContext, asset: Optional[GaussianSplatAsset] = None, transform: Optional[Transform] = None):
         self.ctx = ctx
@@ -247,6 +247,7 @@ class GaussianSplatRenderer:
         # mode the default of this host layer -- how the whole GPU test suite is run through it (profiles/r05_pytest_gpu_visible.log)
         self.sortMode = SortMode.Visible if os.environ.get("GSPLAT_SORT_MODE", "") == "visible" else SortMode.Full
         self.framesInFlight = max(1, int(os.environ.get("GSPLAT_FRAMES_IN_FLIGHT", "1") or 1))     # SetFramesInFlight
+        self.selectionHighlight = False           # SetSelectionHighlight
         self._asset_h = C.c_void_p()
         self._r_h = C.c_void_p()
         self._keep: list = []
@@ -303,6 +304,8 @@ class GaussianSplatRenderer:
             check(_lib.lib().gs_renderer_set_sort_mode(self._r_h, int(self.sortMode)), "gs_renderer_set_sort_mode")
         if self.framesInFlight > 1:
             check(_lib.lib().gs_renderer_set_frames_in_flight(self._r_h, int(self.framesInFlight)), "gs_renderer_set_frames_in_flight")
+        if self.selectionHighlight:
+            check(_lib.lib().gs_renderer_set_selection_highlight(self._r_h, 1), "gs_renderer_set_selection_highlight")
 
     def ShareResourcesOf(self, other: "GaussianSplatRenderer") -> None:
         """A second renderer over the SAME device blobs as `other` (no copy; `other` must outlive this one), on this renderer's own context =
@@ -678,6 +681,13 @@ class GaussianSplatRenderer:
         self.sortMode = SortMode(mode)
         if self._r_h:
             check(_lib.lib().gs_renderer_set_sort_mode(self._r_h, int(self.sortMode)), "gs_renderer_set_sort_mode")
+
+    def SetSelectionHighlight(self, enabled: bool) -> None:
+        """True: splat frames draw the selected splats as the reference does (RenderGaussianSplats.shader:63-73,87-101: magenta tint, raised
+        opacity, a solid outline ring) once the edit buffers exist; False (default): selection is not drawn (gs_renderer_set_selection_highlight)."""
+        self.selectionHighlight = bool(enabled)
+        if self._r_h:
+            check(_lib.lib().gs_renderer_set_selection_highlight(self._r_h, int(self.selectionHighlight)), "gs_renderer_set_selection_highlight")
 
     def SetFramesInFlight(self, frames: int) -> None:
         """Frames (or the views of a batch of cameras) in flight INSIDE the library, behind this one renderer: `frames` lanes on streams of their own, dealt
