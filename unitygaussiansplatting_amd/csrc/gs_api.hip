@@ -119,6 +119,8 @@ int32_t gs_context_create(int32_t device, void* hip_stream, gs_context** out) {
     // The default is therefore off; GSPLAT_OVERLAP=1 or gs_context_set_overlap(ctx, 1) turns it on.
     const char* ov = getenv("GSPLAT_OVERLAP");
     ctx->overlap = ov && ov[0] == '1';
+    const char* vg = getenv("GSPLAT_VIEW_GENERIC");
+    ctx->viewGeneric = vg && vg[0] == '1';
     // -1 = automatic: shared as soon as this process holds a second context on the device (gs_shared_gpu); GSPLAT_SHARED_GPU=1 / 0 or
     // gs_context_set_shared_gpu pin it (another PROCESS on the GPU is something only the host knows)
     const char* sh = getenv("GSPLAT_SHARED_GPU");
@@ -314,6 +316,7 @@ int32_t gs_renderer_set_frames_in_flight(gs_renderer* r, int32_t frames) {
         int32_t rc = gs_context_create(r->ctx->device, nullptr, &c);
         if (rc == GS_OK) {                                       // not a context of the host's: see gs_shared_gpu
             c->internalLane = true;
+            c->viewGeneric = r->ctx->viewGeneric;                 // a lane draws with its owner's kernels
             if (c->counted) { g_liveContexts[c->device % kMaxTrackedDevices].fetch_sub(1, std::memory_order_relaxed); c->counted = false; }
         }
         if (rc == GS_OK) rc = renderer_create_n(c, r->asset, r->n, &L);      // (N is the owner's: a resize may have changed it)

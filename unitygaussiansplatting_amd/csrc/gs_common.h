@@ -167,6 +167,9 @@ struct gs_context {
     // here, forked from / joined to `stream` with events, and the two latency-bound kernels share the GPU
     hipStream_t aux = nullptr;
     bool overlap = false;
+    // GSPLAT_VIEW_GENERIC=1 at context creation: every calc_view launch takes the kernel that reads the asset's formats at run time, never one
+    // with a preset's formats compiled in (gs_view.hip) -- the switch the tests use to compare the two
+    bool viewGeneric = false;
     // other kernels that spin on their own workgroups may share this GPU (another process running this library, another context of this process sorting
     // at the same time): the depth sort's gather pass then hands its partitions out in dependency order instead of in XCD blocks (gs_sort.hip)
     // -1 automatic (shared iff the process holds more than one context on the device), 0 / 1 pinned by the host

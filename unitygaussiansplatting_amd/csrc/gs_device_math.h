@@ -236,6 +236,23 @@ template <int FMT> GS_HD V3 DecodeRawT(const RawVec<FMT>& r, uint64_t a) {
 }
 template <int FMT> GS_HD V3 LoadVecT(const uint8_t* buf, uint64_t a) { return DecodeRawT<FMT>(LoadRawT<FMT>(buf, a), a); }
 template <int FMT> GS_HD uint32_t vecStrideT() { return FMT == 0 ? 12u : (FMT == 1 ? 6u : (FMT == 2 ? 4u : 2u)); }
+
+// What a kernel knows of an asset's layout when it is compiled.  A field of kFmtRuntime is read from the AssetView as it always
+// was; any other value stands in for the AssetView's field, so the loaders below fold to the one format's loads and strides --
+// the same expressions in the same order, with the branches of the other formats gone.  CHUNKED: 1 = every splat's chunk exists
+// (chunkCount covers all of n), 0 = the asset has no chunk blob, kFmtRuntime = compare the chunk index with chunkCount.
+// Whoever launches a kernel built on fixed formats checks that the AssetView really has them (gs_view.hip).
+constexpr int kFmtRuntime = -1;
+template <int POS, int SCALE, int COLOR, int SH, int CHUNKED> struct AssetFormats {
+    static constexpr int kPos = POS, kScale = SCALE, kColor = COLOR, kSH = SH, kChunked = CHUNKED;
+    static GS_HD uint32_t posFmt(const AssetView& a) { return POS == kFmtRuntime ? a.posFmt : (uint32_t)POS; }
+    static GS_HD uint32_t scaleFmt(const AssetView& a) { return SCALE == kFmtRuntime ? a.scaleFmt : (uint32_t)SCALE; }
+    static GS_HD uint32_t colorFmt(const AssetView& a) { return COLOR == kFmtRuntime ? a.colorFmt : (uint32_t)COLOR; }
+    static GS_HD uint32_t shFmt(const AssetView& a) { return SH == kFmtRuntime ? a.shFmt : (uint32_t)SH; }
+    static GS_HD bool chunked(const AssetView& a, uint32_t ci) { return CHUNKED == kFmtRuntime ? ci < a.chunkCount : CHUNKED != 0; }
+};
+typedef AssetFormats<kFmtRuntime, kFmtRuntime, kFmtRuntime, kFmtRuntime, kFmtRuntime> RuntimeFormats;
+
 // chunk de-normalisation of a decoded position (LoadSplatPos, GaussianSplatting.hlsl:394-421)
 GS_HD V3 ChunkLerpPos(const AssetView& a, V3 p, uint32_t ci) {
     if (ci < a.chunkCount) {
@@ -547,20 +564,21 @@ GS_HD uint32_t DecodeBC7Texel(const uint8_t* block, uint32_t texel) {
 
 // _SplatColor.Load(SplatIndexToPixelIndex(idx)) (GaussianSplatting.hlsl:456-458): the texel as the texture unit returns it,
 // before the chunk de-normalisation
-GS_HD V4 LoadColorTexel(const AssetView& a, uint32_t idx) {
+template <class F = RuntimeFormats> GS_HD V4 LoadColorTexel(const AssetView& a, uint32_t idx) {
     uint32_t tx, ty;
     SplatIndexToPixelIndex(idx, tx, ty);
     const uint64_t texel = (uint64_t)ty * 2048 + tx;
-    if (a.colorFmt == 0) {
+    const uint32_t colorFmt = F::colorFmt(a);
+    if (colorFmt == 0) {
         const uint8_t* c = a.color + texel * 16;
         return { u2f(ld32a(c, 0)), u2f(ld32a(c, 4)), u2f(ld32a(c, 8)), u2f(ld32a(c, 12)) };
     }
-    if (a.colorFmt == 1) {
+    if (colorFmt == 1) {
         const uint32_t lo = ld32a(a.color, texel * 8), hi = ld32a(a.color, texel * 8 + 4);
         return { f16tof32(lo), f16tof32(lo >> 16), f16tof32(hi), f16tof32(hi >> 16) };
     }
     uint32_t e;
-    if (a.colorFmt == 3) e = DecodeBC7Texel(a.color + ((uint64_t)(ty >> 2) * 512 + (tx >> 2)) * 16, (ty & 3u) * 4u + (tx & 3u));   // RGBA_BC7_UNorm, 512 blocks per row
+    if (colorFmt == 3) e = DecodeBC7Texel(a.color + ((uint64_t)(ty >> 2) * 512 + (tx >> 2)) * 16, (ty & 3u) * 4u + (tx & 3u));   // RGBA_BC7_UNorm, 512 blocks per row
     else e = ld32a(a.color, texel * 4);
     return { (float)(e & 255) * GS_R255, (float)((e >> 8) & 255) * GS_R255, (float)((e >> 16) & 255) * GS_R255, (float)(e >> 24) * GS_R255 };
 }
@@ -780,6 +798,7 @@ struct ViewPartial {
 
 // outputsOnlyIfDrawn: the caller reads vp (beyond front / culled) only for a splat that passes PrepareSplat -- the per-frame kernel --
 // so the record is not zero-filled first (a dozen register moves at every divergent exit of a VALU-bound kernel).
+template <class F = RuntimeFormats>
 GS_HD void CalcViewGeom(const AssetView& a, const FrameConsts& P, const EditView& E, uint32_t idx, ViewPartial& vp, bool allowCull = false,
                         bool outputsOnlyIfDrawn = false) {
     ViewData& view = vp.view;
@@ -793,9 +812,9 @@ GS_HD void CalcViewGeom(const AssetView& a, const FrameConsts& P, const EditView
     vp.front = false; vp.culled = false;
 
     // ---- LoadSplatData: position first (needed for the early out)
-    V3 pos = LoadVec(a.pos, (uint64_t)idx * vecStride(a.posFmt), a.posFmt);
+    V3 pos = LoadVec(a.pos, (uint64_t)idx * vecStride(F::posFmt(a)), F::posFmt(a));
     const uint32_t ci = idx >> 8;
-    const bool chunked = ci < a.chunkCount;
+    const bool chunked = F::chunked(a, ci);
     ChunkRaw ck;
     if (chunked) {
         ck = LoadChunk(a.chunk, ci);
@@ -816,11 +835,11 @@ GS_HD void CalcViewGeom(const AssetView& a, const FrameConsts& P, const EditView
     vp.front = true;
 
     // ---- scale (needed first: the early cull below bounds the footprint with it)
-    uint32_t otherStride = 4 + vecStride(a.scaleFmt);
-    if (a.shFmt > 3) otherStride += 2;
+    uint32_t otherStride = 4 + vecStride(F::scaleFmt(a));
+    if (F::shFmt(a) > 3) otherStride += 2;
     const uint64_t otherAddr = (uint64_t)idx * otherStride;
     vp.otherEnd = otherAddr + otherStride;
-    V3 scale = LoadVec(a.other, otherAddr + 4, a.scaleFmt);
+    V3 scale = LoadVec(a.other, otherAddr + 4, F::scaleFmt(a));
     if (chunked) {
         scale.x = lerpf(f16tof32(ck.w[10]), f16tof32(ck.w[10] >> 16), scale.x);
         scale.y = lerpf(f16tof32(ck.w[11]), f16tof32(ck.w[11] >> 16), scale.y);
@@ -874,7 +893,7 @@ GS_HD void CalcViewGeom(const AssetView& a, const FrameConsts& P, const EditView
     const V4 q = DecodeRotation(LoadUInt(a.other, otherAddr));
 
     // ---- colour texel
-    V4 col = LoadColorTexel(a, idx);
+    V4 col = LoadColorTexel<F>(a, idx);
 
     if (chunked) {
         col.x = lerpf(f16tof32(ck.w[0]), f16tof32(ck.w[0] >> 16), col.x);
@@ -884,7 +903,7 @@ GS_HD void CalcViewGeom(const AssetView& a, const FrameConsts& P, const EditView
         col.w = InvSquareCentered01(col.w);
         vp.shMin = { f16tof32(ck.w[13]), f16tof32(ck.w[14]), f16tof32(ck.w[15]) };
         vp.shMax = { f16tof32(ck.w[13] >> 16), f16tof32(ck.w[14] >> 16), f16tof32(ck.w[15] >> 16) };
-        vp.shLerp = a.shFmt > 0 && a.shFmt <= 3;
+        vp.shLerp = F::shFmt(a) > 0 && F::shFmt(a) <= 3;
     } else {
         // a chunk-less asset (VeryHigh fp32, or a lossy-format asset created without a chunk blob): CalcViewColor reads these
         // whatever the record's zero-fill above did (outputsOnlyIfDrawn skips it)
@@ -935,7 +954,7 @@ GS_HD void CalcViewGeom(const AssetView& a, const FrameConsts& P, const EditView
 
 // SH coefficients are consumed in order sh1..sh15 by three fmaf chains (degree 1, 2, 3), so they are decoded
 // one at a time instead of being held in 45 registers.
-template <class SHSource>
+template <class F = RuntimeFormats, class SHSource>
 GS_HD void CalcViewColor(const AssetView& a, const FrameConsts& P, uint32_t idx, ViewPartial& vp, SHSource& shsrc) {
     ViewData& view = vp.view;
     const V4 col = vp.col;
@@ -956,8 +975,8 @@ GS_HD void CalcViewColor(const AssetView& a, const FrameConsts& P, uint32_t idx,
     float b = onlySH ? 0.5f : col.z;
     if (P.shOrder >= 1) {
         uint32_t shIndex = idx;
-        if (a.shFmt > 3) shIndex = LoadUShort(a.other, vp.otherEnd - 2);
-        shsrc.begin(a.sh + (uint64_t)shIndex * shStrideOf(a.shFmt), a.shFmt);
+        if (F::shFmt(a) > 3) shIndex = LoadUShort(a.other, vp.otherEnd - 2);
+        shsrc.begin(a.sh + (uint64_t)shIndex * shStrideOf(F::shFmt(a)), F::shFmt(a));
         const F2 minRG = { shMin.x, shMin.y }, dRG = F2{ shMax.x, shMax.y } - minRG;      // lerp(a, b, t) = fma(t, b - a, a)
         const float minB = shMin.z, dB = shMax.z - shMin.z;
         auto SHK = [&](int k) -> RGB {

@@ -70,7 +70,13 @@ template <> struct EditArg<true> { typedef gsm::EditView type; };
 __device__ __forceinline__ gsm::EditView edit_view_of(const EditViewPlain& p) { gsm::EditView e; e.deletedBits = p.deletedBits; e.cutouts = p.cutouts; e.cutoutCount = p.cutoutCount; return e; }
 __device__ __forceinline__ gsm::EditView edit_view_of(const gsm::EditView& e) { return e; }
 
-template <int SHMODE, bool FULL, bool HL>
+//
+// F = what is known of the asset's formats when the kernel is compiled (gsm::AssetFormats).  gsm::RuntimeFormats reads all of them from the
+// AssetView: one kernel for every asset, which pays in every frame for the formats it does not run (runtime strides, the stitching of loads that
+// may be unaligned, branches and SGPRs for four formats of everything).  The per-frame launch of an asset made with one of the creator's quality
+// presets -- nearly every asset there is -- takes a kernel with that preset's formats compiled in instead: the same expressions in the same order,
+// so the same bits.  The argument list is the same for every F (see above: the AssetView travels whole, its format fields unread).
+template <int SHMODE, bool FULL, bool HL, class F = gsm::RuntimeFormats>
 __global__ __launch_bounds__(256) void calc_view_kernel(gsm::AssetView a, gsm::FrameConsts P, typename EditArg<HL>::type Earg, ViewOutputs O) {
     const gsm::EditView E = edit_view_of(Earg);
     GS_VIEW_PRIORITY();
@@ -126,10 +132,10 @@ __global__ __launch_bounds__(256) void calc_view_kernel(gsm::AssetView a, gsm::F
         if (SHMODE < 4) {
             SHFromLds<SHMODE < 4 ? SHMODE : 3> src;
             src.rec = s_dw + threadIdx.x * STRIDE;
-            gsm::CalcViewColor(a, P, idx, vp, src);
+            gsm::CalcViewColor<F>(a, P, idx, vp, src);
         } else {
             gsm::SHFromBlob src;
-            gsm::CalcViewColor(a, P, idx, vp, src);
+            gsm::CalcViewColor<F>(a, P, idx, vp, src);
         }
     };
 
@@ -144,7 +150,7 @@ __global__ __launch_bounds__(256) void calc_view_kernel(gsm::AssetView a, gsm::F
         // the loads are in flight while the positions are projected
         if (shStaged) { sh_issue(); sh_park(); __syncthreads(); }
         if (idx < a.n) {
-            gsm::CalcViewGeom(a, P, E, idx, vp);
+            gsm::CalcViewGeom<F>(a, P, E, idx, vp);
             if (vp.front) shade(vp);
             bool ok;
             if (HL) {
@@ -157,7 +163,7 @@ __global__ __launch_bounds__(256) void calc_view_kernel(gsm::AssetView a, gsm::F
         }
     } else {
         // whole-chunk frustum cull: lane c & 7 tests corner c of the chunk's position box against the 6 (pushed-out) planes
-        if (P.cullOn && blockIdx.x < a.chunkCount) {
+        if (P.cullOn && F::chunked(a, blockIdx.x)) {
             const uint32_t m = gsm::ChunkCornerOutside(a, P, blockIdx.x, threadIdx.x & 7u);
             bool outside = false;
 #pragma unroll
@@ -171,7 +177,7 @@ __global__ __launch_bounds__(256) void calc_view_kernel(gsm::AssetView a, gsm::F
         }
         if (threadIdx.x == 0) s_any = 0;
         if (idx < a.n) {
-            gsm::CalcViewGeom(a, P, E, idx, vp, true, true);       // early out for splats that cannot reach the screen; vp only read if drawn
+            gsm::CalcViewGeom<F>(a, P, E, idx, vp, true, true);      // early out for splats that cannot reach the screen; vp only read if drawn
             bool ok;
             if (HL) {
                 selected = vp.front && !vp.culled && gsm::SplatSelected(E, idx);
@@ -226,6 +232,15 @@ __global__ __launch_bounds__(256) void calc_view_kernel(gsm::AssetView a, gsm::F
     }
 }
 
+// The creator's quality presets (GaussianSplatAssetCreator.cs:189-228; creator.py QUALITY), each as the creator writes it: with a chunk blob
+// that covers every splat, except VeryHigh, which has none.  SHMODE is the one enqueue_calc_view derives for that SH format.
+//                          pos scale colour SH chunked
+typedef gsm::AssetFormats<0, 0, 0, 0, 0> FormatsVeryHigh;     // Float32, Float32, Float32x4, Float32
+typedef gsm::AssetFormats<1, 1, 1, 2, 1> FormatsHigh;         // Norm16, Norm16, Float16x4, Norm11
+typedef gsm::AssetFormats<2, 2, 2, 3, 1> FormatsMedium;       // Norm11, Norm11, Norm8x4, Norm6
+typedef gsm::AssetFormats<2, 3, 2, 6, 1> FormatsLow;          // Norm11, Norm6, Norm8x4, Cluster16k
+typedef gsm::AssetFormats<2, 3, 3, 8, 1> FormatsVeryLow;      // Norm11, Norm6, BC7, Cluster4k
+
 } // namespace
 
 template <bool FULL>
@@ -244,6 +259,22 @@ static void launch_calc_view(int mode, uint32_t grid, hipStream_t st, const gsm:
 #undef GS_LAUNCH_VIEW
 }
 
+// The per-frame launch without highlight of an asset that is exactly a preset: its four formats, its chunk blob (all of the splats, or none) and the SH
+// mode are F's.  Anything else -- another combination, a chunk count that stops short of n, an unaligned borrowed blob, SH switched off -- is not launched here.
+template <int SHMODE, class F>
+static bool try_calc_view_preset(int mode, uint32_t grid, hipStream_t st, const gsm::AssetView& a, const gsm::FrameConsts& c, const EditViewPlain& ep, const ViewOutputs& o) {
+    if (mode != SHMODE || a.posFmt != (uint32_t)F::kPos || a.scaleFmt != (uint32_t)F::kScale || a.colorFmt != (uint32_t)F::kColor || a.shFmt != (uint32_t)F::kSH) return false;
+    if (F::kChunked ? a.chunkCount < grid : a.chunkCount != 0u) return false;
+    hipLaunchKernelGGL((calc_view_kernel<SHMODE, false, false, F>), dim3(grid), dim3(256), 0, st, a, c, ep, o);
+    return true;
+}
+static bool launch_calc_view_preset(int mode, uint32_t grid, hipStream_t st, const gsm::AssetView& a, const gsm::FrameConsts& c, const gsm::EditView& e, const ViewOutputs& o) {
+    const EditViewPlain ep = { e.deletedBits, e.cutouts, e.cutoutCount };
+    return try_calc_view_preset<0, FormatsVeryHigh>(mode, grid, st, a, c, ep, o) || try_calc_view_preset<2, FormatsHigh>(mode, grid, st, a, c, ep, o) ||
+           try_calc_view_preset<3, FormatsMedium>(mode, grid, st, a, c, ep, o) || try_calc_view_preset<4, FormatsLow>(mode, grid, st, a, c, ep, o) ||
+           try_calc_view_preset<4, FormatsVeryLow>(mode, grid, st, a, c, ep, o);
+}
+
 // full = true: also evaluate the colour of every splat in front of the camera and write the N x 40 B view buffer
 int32_t enqueue_calc_view(gs_context* ctx, const gsm::AssetView& a, const gs_frame_params* p, const gsm::EditView& e, const ViewOutputs& out, bool full) {
     gsm::FrameConsts c;
@@ -252,7 +283,9 @@ int32_t enqueue_calc_view(gs_context* ctx, const gsm::AssetView& a, const gs_fra
     // per-splat SH records are staged through LDS (needs the blob 16-byte aligned, which hipMalloc and torch guarantee);
     // Cluster* tables, an unaligned borrowed blob, or SH switched off read straight from the blob
     const int mode = (a.shFmt <= 3 && (((uintptr_t)a.sh) & 15u) == 0 && p->sh_order >= 1) ? (int)a.shFmt : 4;
-    if (full) launch_calc_view<true>(mode, grid, ctx->stream, a, c, e, out);
+    const bool presetAllowed = !full && !e.selectedBits && !ctx->viewGeneric;
+    if (presetAllowed && launch_calc_view_preset(mode, grid, ctx->stream, a, c, e, out)) {}
+    else if (full) launch_calc_view<true>(mode, grid, ctx->stream, a, c, e, out);
     else launch_calc_view<false>(mode, grid, ctx->stream, a, c, e, out);
     GS_HIP(hipGetLastError());
     return GS_OK;
