@@ -546,6 +546,20 @@ int32_t gs_import_assign_clusters(gs_context* ctx, const float* x, uint64_t n, c
 int32_t gs_import_encode_on(gs_context* ctx, const gs_import_input* in, const gs_import_formats* formats,
                             void* const blobs[5], const uint64_t sizes[5], float bounds_min[3], float bounds_max[3]);
 
+/* ---- bake: an edited renderer back into a compressed asset, on the GPU (EditExportData + CreateAsset in one step) ----------------------
+ * The alive splats of r -- idx < N, not deleted, not cut by the current cutout list: ExportPlyFile's rule, GaussianSplatRendererEditor.cs:414-442 --
+ * decoded from whatever r holds (any preset, private blobs or the asset's) and encoded in `formats`, Morton-reordered and chunked as
+ * GaussianSplatAssetCreator does it: the five blobs are the bytes gs_import_encode (linearize = 0) makes of the same splats in index order.
+ * Runs on the context's stream after everything already enqueued there and on the lanes; only reads the renderer.
+ * Refused with GS_ERR_INVALID_ARGUMENT, nothing allocated and *out NULL: a NULL argument, a lane, a format enum out of range, linearize != 0,
+ * no alive splat, a GS_COLOR_BC7 or GS_SH_CLUSTER* target (any preset is accepted as the source). */
+/* formats->linearize must be 0 (the renderer's data is linear); formats->morton 0 or 1.  BLOCKS.  *out is a new asset owned by r's
+ * context (gs_asset_destroy); *alive its splat count; bounds as GaussianSplatAsset.boundsMin/Max (may be NULL). */
+int32_t gs_renderer_edit_bake_asset(gs_renderer* r, const gs_import_formats* formats, gs_asset** out, uint32_t* alive,
+                                    float bounds_min[3], float bounds_max[3]);
+/* the five blobs of any asset to host memory: sizes[k] bytes of blob k, at most what the asset holds (blobs[k] NULL or sizes[k] 0: skipped).  BLOCKS. */
+int32_t gs_asset_download_blobs(const gs_asset* asset, void* const blobs[5], const uint64_t sizes[5]);
+
 /* PLY input (PLYFileReader.cs:25-76 header rules; GaussianFileReader.cs:80-208 attribute mapping + ReorderSHs): binary
  * little-endian, float properties; x y z f_dc_0..2 opacity scale_0..2 rot_0..3 required, f_rest_* optional (0 if absent).
  * The arrays gs_ply_arrays points `out` at are owned by the handle and valid until gs_ply_close. */

@@ -1,0 +1,354 @@
+// gs_bake.hip -- the edit path's way back into the render path's format: gs_renderer_edit_bake_asset makes, from a renderer in its current state (any
+// preset, the asset's blobs or private ones, deleted bits, cutouts), a new immutable device-resident gs_asset of the ALIVE splats in the formats the
+// caller asks for, Morton-reordered and chunked as GaussianSplatAssetCreator does it (GaussianSplatAssetCreator.cs:362-429, 520-638, 727-805, 873-1037)
+// -- the bytes gs_import_encode (linearize = 0) produces from the same splats.  Nothing leaves the GPU.  The arithmetic is gsm::Bake* (gs_device_math.h),
+// host and device from one text.  gs_asset_download_blobs reads any asset back.
+//
+// Plain launches on the context's stream; the only kernels that wait on other workgroups are the library's Onesweep passes.
+//   1. alive list + bounds   export_count / export_scan (gs_export.hip), then bake_alive: alive[j] = source index of the j-th alive splat in index order,
+//                            and per workgroup the min / max of its alive positions; bake_bounds folds the partials (min / max: exact in any order).
+//   2. order                 morton = 1: bake_codes writes the 63-bit code of every alive splat as two words; two stable Onesweep sorts -- the low word
+//                            with payload = rank, then the high word gathered through the payload, 31 bits -- leave the payload in (code, rank) order.
+//                            The sort state is the bake's own: the renderer's may be in use.
+//   3. encode                one 256-thread workgroup per DESTINATION chunk, so that the chunk record is workgroup-uniform; lane k decodes source splat
+//                            alive[order[256 c + k]] (its own source chunk ci = src >> 8) with gsm::LoadSplatDataFull from the renderer's current view.  The
+//                            26 reductions run by cross-lane shuffles inside a wave and through LDS across the four.  Stores: pos / other per lane (2-16
+//                            bytes, contiguous across the wave), the colour texel per lane (a chunk is one 16 x 16 tile: 16 rows of 64-256 contiguous
+//                            bytes), the SH items (32 / 60 / 96 / 192 bytes) staged per wave in LDS and written as one contiguous, 16-byte aligned range
+//                            with dwordx4 stores -- the shape of the export and the merge (gs_export.hip, gs_copy.hip).
+// The five blobs are zero-filled first, as the importer's are: the pad bytes, the texels past N and the last chunk's tail are part of the bytes.
+#include <new>
+
+#include "gs_common.h"
+
+namespace gs {
+
+constexpr uint32_t kBakeReduceThreads = 1024;
+
+struct BakeDst { uint8_t* pos; uint8_t* other; uint8_t* color; uint8_t* sh; uint8_t* chunk; uint32_t n; gsm::BakeFormats f; };
+
+__device__ __forceinline__ float wave_min(float v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = fminf(v, __shfl_xor(v, d));
+    return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d));
+    return v;
+}
+
+// alive[base[chunk] + rank] = idx for the alive splats of source chunk blockIdx.x; partial[chunk][0..2 / 3..5] = min / max of their positions
+__global__ __launch_bounds__(256) void bake_alive_kernel(gsm::AssetView a, gsm::EditView e, const uint32_t* __restrict__ base, uint32_t* __restrict__ alive,
+                                                         float* __restrict__ partial) {
+    __shared__ uint32_t s_cnt[4];
+    __shared__ float s_red[4][6];
+    const uint32_t idx = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    gsm::V3 pos; bool cut;
+    const bool mine = export_alive(a, e, idx, blockIdx.x, pos, cut);
+    const unsigned long long bal = __ballot(mine);
+    const uint32_t slot = (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+    if (lane == 0u) s_cnt[wave] = (uint32_t)__popcll(bal);
+    const float inf = gsm::u2f(0x7f800000u);
+    const float p[3] = { pos.x, pos.y, pos.z };
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float mn = wave_min(mine ? p[c] : inf), mx = wave_max(mine ? p[c] : -inf);
+        if (lane == 0u) { s_red[wave][c] = mn; s_red[wave][3 + c] = mx; }
+    }
+    __syncthreads();
+    uint32_t first = base[blockIdx.x];
+    for (uint32_t w = 0; w < wave; ++w) first += s_cnt[w];
+    if (mine) alive[first + slot] = idx;
+    if (threadIdx.x < 3u) partial[blockIdx.x * 6u + threadIdx.x] = fminf(fminf(s_red[0][threadIdx.x], s_red[1][threadIdx.x]), fminf(s_red[2][threadIdx.x], s_red[3][threadIdx.x]));
+    else if (threadIdx.x < 6u) partial[blockIdx.x * 6u + threadIdx.x] = fmaxf(fmaxf(s_red[0][threadIdx.x], s_red[1][threadIdx.x]), fmaxf(s_red[2][threadIdx.x], s_red[3][threadIdx.x]));
+}
+
+// bounds[0..2 / 3..5] = min / max over the partials; one workgroup
+__global__ __launch_bounds__(kBakeReduceThreads) void bake_bounds_kernel(const float* __restrict__ partial, uint32_t chunks, float* __restrict__ bounds) {
+    __shared__ float s_red[kBakeReduceThreads / 64][6];
+    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+    const float inf = gsm::u2f(0x7f800000u);
+    float v[6] = { inf, inf, inf, -inf, -inf, -inf };
+    for (uint32_t i = t; i < chunks; i += kBakeReduceThreads) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { v[c] = fminf(v[c], partial[i * 6u + c]); v[3 + c] = fmaxf(v[3 + c], partial[i * 6u + 3 + c]); }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float mn = wave_min(v[c]), mx = wave_max(v[3 + c]);
+        if (lane == 0u) { s_red[wave][c] = mn; s_red[wave][3 + c] = mx; }
+    }
+    __syncthreads();
+    if (t < 6u) {
+        float r = s_red[0][t];
+        for (uint32_t w = 1; w < kBakeReduceThreads / 64; ++w) r = t < 3u ? fminf(r, s_red[w][t]) : fmaxf(r, s_red[w][t]);
+        bounds[t] = r;
+    }
+}
+
+// the Morton code of alive splat j as two sort keys, and the identity payload
+__global__ __launch_bounds__(256) void bake_codes_kernel(gsm::AssetView a, const uint32_t* __restrict__ alive, const float* __restrict__ bounds, uint32_t total,
+                                                         uint32_t* __restrict__ lo, uint32_t* __restrict__ hi, uint32_t* __restrict__ rank) {
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= total) return;
+    const uint32_t src = alive[j];
+    const unsigned long long code = gsm::BakeMortonCode(gsm::LoadSplatPosChunk(a, src, src >> 8), bounds, bounds + 3);
+    lo[j] = (uint32_t)code; hi[j] = (uint32_t)(code >> 32); rank[j] = j;
+}
+
+__global__ __launch_bounds__(256) void bake_gather_kernel(const uint32_t* __restrict__ hi, const uint32_t* __restrict__ rank, uint32_t total, uint32_t* __restrict__ out) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < total) out[i] = hi[rank[i]];
+}
+
+// bytes in { 2, 4, 6, 8, 10, 12, 16 } of w to p; p is `bytes`-strided from an aligned base: a multiple of 4 bytes = dword stores, else halfword stores
+__device__ __forceinline__ void bake_store(uint8_t* p, const uint32_t* w, uint32_t bytes) {
+    if ((bytes & 3u) == 0u) {
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; ++k) if (k * 4u < bytes) ((uint32_t*)p)[k] = w[k];
+    } else {
+#pragma unroll
+        for (uint32_t k = 0; k < 5u; ++k) if (k * 2u < bytes) ((uint16_t*)p)[k] = (uint16_t)(w[k >> 1] >> ((k & 1u) * 16u));
+    }
+}
+
+__global__ __launch_bounds__(256) void bake_encode_kernel(gsm::AssetView a, const uint32_t* __restrict__ alive, const uint32_t* __restrict__ order, BakeDst d) {
+    __shared__ float s_red[4][2 * gsm::kBakeCols];
+    __shared__ __attribute__((aligned(16))) uint32_t s_sh[4][64 * 48];
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const bool mine = i < d.n;
+    gsm::BakeRec rec;
+    if (mine) {
+        const uint32_t src = alive[order ? order[i] : i], ci = src >> 8;
+        gsm::SplatFull s;
+        gsm::LoadSplatDataFull(a, src, ci, gsm::LoadSplatPosChunk(a, src, ci), s);
+        gsm::BakeLinearRecord(s, rec);
+    }
+    if (d.f.chunked) {                                             // (workgroup-uniform)
+        gsm::BakeBounds b;
+        gsm::BakeBoundsEmpty(b);
+        if (mine) { gsm::BakeChunkSpace(rec); gsm::BakeBoundsOf(rec, b); }
+#pragma unroll
+        for (int c = 0; c < gsm::kBakeCols; ++c) {
+            const float mn = wave_min(b.mn[c]), mx = wave_max(b.mx[c]);
+            if (lane == 0u) { s_red[wave][c] = mn; s_red[wave][gsm::kBakeCols + c] = mx; }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int c = 0; c < gsm::kBakeCols; ++c) {
+            b.mn[c] = fminf(fminf(s_red[0][c], s_red[1][c]), fminf(s_red[2][c], s_red[3][c]));
+            b.mx[c] = fmaxf(fmaxf(s_red[0][gsm::kBakeCols + c], s_red[1][gsm::kBakeCols + c]), fmaxf(s_red[2][gsm::kBakeCols + c], s_red[3][gsm::kBakeCols + c]));
+        }
+        gsm::BakeBoundsWiden(b);
+        if (threadIdx.x == 0u) {
+            uint32_t w[16];
+            gsm::BakeChunkWords(b, w);
+            uint4* out = (uint4*)(d.chunk + (size_t)blockIdx.x * 64u);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) out[k] = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
+        }
+        if (mine) gsm::BakeNormalise(rec, b);
+    }
+    const uint32_t shWords = gsm::shStrideOf(d.f.sh) / 4u;
+    if (mine) {
+        uint32_t w[48];
+        gsm::BakeEmitSH(rec.sh, d.f.sh, w);
+        uint32_t* s = s_sh[wave] + lane * shWords;
+#pragma unroll
+        for (uint32_t k = 0; k < 48u; ++k) if (k < shWords) s[k] = w[k];
+    }
+    __syncthreads();
+    const uint32_t waveFirst = blockIdx.x * 256u + wave * 64u;      // the wave's first destination record; its lanes that write are a prefix
+    if (waveFirst < d.n) {
+        const uint32_t waveCount = d.n - waveFirst < 64u ? d.n - waveFirst : 64u, words = waveCount * shWords, quads = words / 4u;
+        uint8_t* dst = d.sh + (size_t)waveFirst * (shWords * 4u);   // 16-byte aligned: 64 records of a multiple of 4 bytes
+        for (uint32_t q = lane; q < quads; q += 64u) ((uint4*)dst)[q] = ((const uint4*)s_sh[wave])[q];
+        if (quads * 4u + lane < words) ((uint32_t*)dst)[quads * 4u + lane] = s_sh[wave][quads * 4u + lane];
+    }
+    if (!mine) return;
+    uint32_t w[4];
+    gsm::BakeEmitVec(rec.pos, d.f.pos, w);
+    const uint32_t posSz = gsm::vecStride(d.f.pos), sclSz = gsm::vecStride(d.f.scale);
+    bake_store(d.pos + (size_t)i * posSz, w, posSz);
+    w[0] = rec.rot;
+    gsm::BakeEmitVec(rec.scale, d.f.scale, w + 1);
+    bake_store(d.other + (size_t)i * (4u + sclSz), w, 4u + sclSz);
+    uint32_t px, py;
+    gsm::SplatIndexToPixelIndex(i, px, py);
+    gsm::BakeEmitColor(rec.col, d.f.color, w);
+    const uint32_t colSz = d.f.color == 0u ? 16u : (d.f.color == 1u ? 8u : 4u);
+    bake_store(d.color + ((size_t)py * 2048u + px) * colSz, w, colSz);
+}
+
+// ---- host -----------------------------------------------------------------------------------------------------------------------------
+// everything a bake holds besides the asset it makes: freed when the call returns
+struct BakeRun {
+    DevBuf<uint32_t> counts, base, alive, lo, hi, hi2, rank;
+    DevBuf<float> partial, bounds;
+    SortState sort;
+    DevBuf<SortControl> control;
+};
+
+static int32_t bake_sort(gs_context* ctx, BakeRun& run, uint32_t* keys, uint32_t total, uint32_t keyBits) {
+    const int passes = (int)((keyBits + 7u) / 8u);
+    const uint32_t lastMask = (1u << (keyBits - 8u * (uint32_t)(passes - 1))) - 1u;
+    GS_TRY(enqueue_histogram(ctx, ctx->stream, keys, total, nullptr, passes, lastMask, run.control, run.sort));
+    return enqueue_sort_passes(ctx, ctx->stream, run.sort, run.control, keys, run.rank, total, nullptr, passes, lastMask);
+}
+
+// steps 1 (second half) to 3 on the context's stream; the caller synchronises whatever this returns.  ev: null, or six events -- 2 .. 5 are recorded
+// here, before the alive list and after the bounds, the sorts and the encode
+static int32_t bake_enqueue(gs_renderer* r, const gs_import_formats* f, BakeRun& run, uint32_t chunks, uint32_t total, const BakeDst& d, Event* ev) {
+    gs_context* ctx = r->ctx;
+    hipStream_t st = ctx->stream;
+    const gsm::AssetView a = asset_view(r);
+    GS_HIP(run.alive.alloc(((size_t)total + 16) * 4));
+    GS_HIP(run.partial.alloc((size_t)chunks * 6 * 4));
+    GS_HIP(run.bounds.alloc(6 * 4));
+    const uint32_t blocks = (total + 255u) / 256u;
+    if (f->morton) {
+        for (DevBuf<uint32_t>* b : { &run.lo, &run.hi, &run.hi2, &run.rank }) GS_HIP(b->alloc(((size_t)total + 16) * 4));
+        GS_TRY(sort_state_create(ctx, run.sort, total, true));
+        GS_HIP(run.control.alloc(sizeof(SortControl)));
+    }
+    if (ev) GS_HIP(hipEventRecord(ev[2], st));
+    hipLaunchKernelGGL(bake_alive_kernel, dim3(chunks), dim3(256), 0, st, a, edit_view(r), (const uint32_t*)run.base.get(), run.alive.get(), run.partial.get());
+    hipLaunchKernelGGL(bake_bounds_kernel, dim3(1), dim3(kBakeReduceThreads), 0, st, (const float*)run.partial.get(), chunks, run.bounds.get());
+    GS_HIP(hipGetLastError());
+    if (ev) GS_HIP(hipEventRecord(ev[3], st));
+    if (f->morton) {
+        hipLaunchKernelGGL(bake_codes_kernel, dim3(blocks), dim3(256), 0, st, a, (const uint32_t*)run.alive.get(), (const float*)run.bounds.get(), total,
+                           run.lo.get(), run.hi.get(), run.rank.get());
+        GS_HIP(hipGetLastError());
+        GS_TRY(bake_sort(ctx, run, run.lo, total, 32u));
+        hipLaunchKernelGGL(bake_gather_kernel, dim3(blocks), dim3(256), 0, st, (const uint32_t*)run.hi.get(), (const uint32_t*)run.rank.get(), total, run.hi2.get());
+        GS_HIP(hipGetLastError());
+        GS_TRY(bake_sort(ctx, run, run.hi2, total, 31u));
+    }
+    if (ev) GS_HIP(hipEventRecord(ev[4], st));
+    hipLaunchKernelGGL(bake_encode_kernel, dim3(blocks), dim3(256), 0, st, a, (const uint32_t*)run.alive.get(),
+                       f->morton ? (const uint32_t*)run.rank.get() : (const uint32_t*)nullptr, d);
+    GS_HIP(hipGetLastError());
+    if (ev) GS_HIP(hipEventRecord(ev[5], st));
+    return GS_OK;
+}
+
+static int32_t bake_impl(gs_renderer* r, const gs_import_formats* f, gs_asset** out, uint32_t* alive, float bounds_min[3], float bounds_max[3], Event* ev = nullptr) {
+    if (out) *out = nullptr;
+    if (!r || !f || !out || !alive) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
+    if (r->laneOf) return fail(GS_ERR_INVALID_ARGUMENT, "a lane holds no edit state: bake its owner");
+    if (f->pos_format > 3 || f->scale_format > 3 || f->color_format > 3 || f->sh_format > 8) return fail(GS_ERR_INVALID_ARGUMENT, "format enum out of range");
+    if (f->linearize != 0) return fail(GS_ERR_INVALID_ARGUMENT, "bake: linearize must be 0 (the renderer's data is linear)");
+    if (f->morton > 1) return fail(GS_ERR_INVALID_ARGUMENT, "bake: morton must be 0 or 1");
+    if (f->color_format == GS_COLOR_BC7) return fail(GS_ERR_INVALID_ARGUMENT, "bake: a BC7 colour target is not supported");
+    if (f->sh_format > GS_SH_NORM6) return fail(GS_ERR_INVALID_ARGUMENT, "bake: a Cluster* SH target is not supported");
+    if (r->n == 0u) return fail(GS_ERR_INVALID_ARGUMENT, "bake: no alive splat");
+    GS_HIP(hipSetDevice(r->ctx->device));
+    // after everything already enqueued, the lanes' frames included: the sort below assumes its workgroups have the GPU to themselves the way the
+    // renderer's own full sorts do
+    GS_TRY(gs_context_synchronize(r->ctx));
+    hipStream_t st = r->ctx->stream;
+    const uint32_t chunks = (r->n + 255u) / 256u;
+    BakeRun run;
+    GS_HIP(run.counts.alloc((size_t)chunks * 4));
+    GS_HIP(run.base.alloc(((size_t)chunks + 1) * 4));
+    if (ev) GS_HIP(hipEventRecord(ev[0], st));
+    GS_TRY(enqueue_alive_counts(st, asset_view(r), edit_view(r), chunks, run.counts.get(), run.base.get()));
+    if (ev) GS_HIP(hipEventRecord(ev[1], st));
+    uint32_t total = 0;
+    {
+        const hipError_t he = hipMemcpyAsync(&total, run.base.get() + chunks, 4, hipMemcpyDeviceToHost, st);
+        const hipError_t hs = hipStreamSynchronize(st);            // nothing in flight outlives the buffers
+        GS_HIP(he);
+        GS_HIP(hs);
+    }
+    if (total == 0u) return fail(GS_ERR_INVALID_ARGUMENT, "bake: no alive splat");
+    uint64_t need[5];
+    GS_TRY(gs_import_blob_sizes(total, f, need));
+    // the new asset: every blob padded like an owned upload's (the decoders' trailing-dword reads) and zero-filled, as the importer's are
+    gs_asset* a = new (std::nothrow) gs_asset();
+    if (!a) return fail(GS_ERR_OUT_OF_MEMORY, "host allocation");
+    a->ctx = r->ctx; a->owned = true;
+    int32_t rc = GS_OK;
+    for (int k = 0; k < 5 && rc == GS_OK; ++k) {
+        a->sizes[k] = need[k];
+        if (!need[k]) continue;
+        hipError_t e = a->ownedBlobs[k].alloc((size_t)need[k] + 16);
+        a->blobs[k] = a->ownedBlobs[k];
+        if (e == hipSuccess) e = hipMemsetAsync(a->blobs[k], 0, (size_t)need[k] + 16, st);
+        if (e != hipSuccess) rc = fail_hip(e, "bake: allocate blob", __FILE__, __LINE__);
+    }
+    float hostBounds[6] = { 0, 0, 0, 0, 0, 0 };
+    uint32_t sortError = 0;
+    if (rc == GS_OK) {
+        BakeDst d;
+        d.pos = (uint8_t*)a->blobs[0]; d.other = (uint8_t*)a->blobs[1]; d.color = (uint8_t*)a->blobs[2]; d.sh = (uint8_t*)a->blobs[3]; d.chunk = (uint8_t*)a->blobs[4];
+        d.n = total;
+        d.f = { f->pos_format, f->scale_format, f->color_format, f->sh_format, need[4] != 0 ? 1u : 0u };
+        rc = bake_enqueue(r, f, run, chunks, total, d, ev);
+        hipError_t he = hipSuccess;
+        if (rc == GS_OK) he = hipMemcpyAsync(hostBounds, run.bounds.get(), sizeof(hostBounds), hipMemcpyDeviceToHost, st);
+        if (rc == GS_OK && he == hipSuccess && f->morton) he = hipMemcpyAsync(&sortError, &run.control.get()->error, 4, hipMemcpyDeviceToHost, st);
+        if (rc == GS_OK && he != hipSuccess) rc = fail_hip(he, "bake: read back", __FILE__, __LINE__);
+    }
+    {
+        const hipError_t hs = hipStreamSynchronize(st);            // whatever failed: nothing in flight outlives the transient buffers or the asset
+        if (rc == GS_OK && hs != hipSuccess) rc = fail_hip(hs, "bake", __FILE__, __LINE__);
+    }
+    if (rc == GS_OK && sortError) rc = fail(GS_ERR_SORT_TIMEOUT, "bake: a bounded look-back spin expired");
+    if (rc != GS_OK) { (void)gs_asset_destroy(a); return rc; }
+    gsm::AssetView& v = a->view;
+    v.pos = (const uint8_t*)a->blobs[0]; v.other = (const uint8_t*)a->blobs[1]; v.color = (const uint8_t*)a->blobs[2]; v.sh = (const uint8_t*)a->blobs[3];
+    v.chunk = (const uint8_t*)a->blobs[4];
+    v.n = total; v.posFmt = f->pos_format; v.scaleFmt = f->scale_format; v.colorFmt = f->color_format; v.shFmt = f->sh_format;
+    v.chunkCount = need[4] ? (total + 255u) / 256u : 0u;
+    *alive = total;
+    for (int c = 0; c < 3; ++c) {
+        if (bounds_min) bounds_min[c] = hostBounds[c];
+        if (bounds_max) bounds_max[c] = hostBounds[3 + c];
+    }
+    *out = a;
+    return GS_OK;
+}
+
+} // namespace gs
+
+using namespace gs;
+
+extern "C" {
+
+int32_t gs_renderer_edit_bake_asset(gs_renderer* r, const gs_import_formats* formats, gs_asset** out, uint32_t* alive, float bounds_min[3], float bounds_max[3]) {
+    return bake_impl(r, formats, out, alive, bounds_min, bounds_max);
+}
+
+int32_t gs_asset_download_blobs(const gs_asset* asset, void* const blobs[5], const uint64_t sizes[5]) {
+    if (!asset || !blobs || !sizes) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
+    for (int k = 0; k < 5; ++k)
+        if (blobs[k] && sizes[k] > (asset->blobs[k] ? asset->sizes[k] : 0u)) return fail(GS_ERR_INVALID_ARGUMENT, "more bytes asked for than the blob holds");
+    GS_HIP(hipSetDevice(asset->ctx->device));
+    hipStream_t st = asset->ctx->stream;
+    hipError_t he = hipSuccess;
+    for (int k = 0; k < 5 && he == hipSuccess; ++k)
+        if (blobs[k] && sizes[k]) he = hipMemcpyAsync(blobs[k], asset->blobs[k], (size_t)sizes[k], hipMemcpyDeviceToHost, st);
+    const hipError_t hs = hipStreamSynchronize(st);
+    GS_HIP(he);
+    GS_HIP(hs);
+    return GS_OK;
+}
+
+// A measurement aid of scripts/bake_timing.py, which binds it itself: not declared in gsplat_c.h, not part of the ABI.  One whole bake whose asset is
+// destroyed again; ms[0..3] = GPU milliseconds of export_count + export_scan, of the alive list + bounds, of the Morton codes + the two sorts, of the encode.
+__attribute__((visibility("default"))) int32_t gs_bake_stage_times_for_scripts(gs_renderer* r, const gs_import_formats* formats, float ms[4], uint32_t* alive) {
+    if (!r || !formats || !ms || !alive) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
+    GS_HIP(hipSetDevice(r->ctx->device));
+    Event ev[6];
+    for (Event& e : ev) GS_HIP(e.create(hipEventDefault));
+    gs_asset* a = nullptr;
+    GS_TRY(bake_impl(r, formats, &a, alive, nullptr, nullptr, ev));
+    (void)gs_asset_destroy(a);
+    for (int k = 0; k < 4; ++k) GS_HIP(hipEventElapsedTime(&ms[k], ev[k == 0 ? 0 : k + 1], ev[k == 0 ? 1 : k + 2]));
+    return GS_OK;
+}
+
+} // extern "C"

@@ -476,4 +476,16 @@ inline gsm::EditView edit_view(const gs_renderer* r) {
     return e;
 }
 inline size_t bit_words(uint32_t n) { return ((size_t)n + 31) / 32; }   // words of a 1-bit-per-splat buffer
+// export / bake (gs_export.hip): alive = idx < N, not deleted, not cut (ExportPlyFile's rule); also hands back the position and the cut flag
+__device__ __forceinline__ bool export_alive(const gsm::AssetView& a, const gsm::EditView& e, uint32_t idx, uint32_t ci, gsm::V3& pos, bool& cut) {
+    cut = false;
+    pos = { 0.0f, 0.0f, 0.0f };
+    if (idx >= a.n) return false;
+    pos = gsm::LoadSplatPosChunk(a, idx, ci);
+    cut = gsm::IsSplatCut(e, pos.x, pos.y, pos.z);
+    const bool deleted = e.deletedBits && ((e.deletedBits[idx >> 5] >> (idx & 31u)) & 1u);
+    return !cut && !deleted;
+}
+// export_count_kernel + export_scan_kernel on st: counts[c] = alive splats of chunk c, base[0 .. chunks] = their exclusive prefix and the total
+int32_t enqueue_alive_counts(hipStream_t st, const gsm::AssetView& a, const gsm::EditView& e, uint32_t chunks, uint32_t* counts, uint32_t* base);
 } // namespace gs

@@ -1417,4 +1417,178 @@ GS_HD void CopySplat(const AssetView& a, const CopyXform& X, uint32_t idx, uint3
     for (int k = 0; k < 15; ++k) o.sh[k] = s.sh[k];
 }
 
+// ---- bake: the per-chunk part of the importer (CalcChunkDataJob and the encoders, GaussianSplatAssetCreator.cs:520-638, 727-758, 776-805,
+// 873-932, 934-1037, in the operation order of gs_import.cpp with linearize = 0; kernels in gs_bake.hip) ---------------------------------
+// Only + - x /, sqrt, fmin / fmax, fp16 rounding and truncating conversions: a build with -ffp-contract=off gives the host importer's bytes.
+// One ambiguity is inherited from fmin / fmax: among values that compare equal they do not pin the sign of zero, so a column that holds both
+// +0 and -0 as an extreme may differ in the sign bit of its chunk bound.
+constexpr int kBakeCols = 13;                                      // pos 3, scale 3, colour 4 (rgb + opacity), sh 3 (over all 15 coefficients)
+struct BakeRec { V3 pos; uint32_t rot; V3 scale; V4 col; float sh[45]; };   // sh: coefficient-major, rgb inside
+struct BakeBounds { float mn[kBakeCols], mx[kBakeCols]; };
+struct BakeFormats { uint32_t pos, scale, color, sh, chunked; };
+
+// the linear record of one decoded splat.  The rotation word equals the importer's q(rot[k], 1023.5) | ... of PackSmallest3Rotation's output for
+// every value inside the field ranges
+GS_HD void BakeLinearRecord(const SplatFull& s, BakeRec& o) {
+    o.pos = s.pos;
+    o.rot = EncodeQuatToNorm10(PackSmallest3Rotation(s.rot));
+    o.scale = s.scale;
+    o.col = { s.col.x, s.col.y, s.col.z, s.opacity };
+#pragma unroll
+    for (int k = 0; k < 15; ++k) { o.sh[3 * k] = s.sh[k].x; o.sh[3 * k + 1] = s.sh[k].y; o.sh[3 * k + 2] = s.sh[k].z; }
+}
+GS_HD float SquareCentered01(float x) { x -= 0.5f; x = x * (x * sgn(x)); return x * 2.0f + 0.5f; }      // GaussianUtils.cs:25-30
+// what a chunked asset stores: scale^(1/8) as three square roots, the opacity squared about its centre (:546-548)
+GS_HD void BakeChunkSpace(BakeRec& o) {
+    o.scale.x = sqrtf(sqrtf(sqrtf(o.scale.x))); o.scale.y = sqrtf(sqrtf(sqrtf(o.scale.y))); o.scale.z = sqrtf(sqrtf(sqrtf(o.scale.z)));
+    o.col.w = SquareCentered01(o.col.w);
+}
+GS_HD void BakeBoundsEmpty(BakeBounds& b) {
+    const float inf = u2f(0x7f800000u);
+#pragma unroll
+    for (int c = 0; c < kBakeCols; ++c) { b.mn[c] = inf; b.mx[c] = -inf; }
+}
+GS_HD void BakeBoundsMerge(BakeBounds& b, const BakeBounds& o) {
+#pragma unroll
+    for (int c = 0; c < kBakeCols; ++c) { b.mn[c] = fminf(b.mn[c], o.mn[c]); b.mx[c] = fmaxf(b.mx[c], o.mx[c]); }
+}
+GS_HD void BakeBoundsOf(const BakeRec& o, BakeBounds& b) {         // the bounds of one splat (in chunk space)
+    b.mn[0] = b.mx[0] = o.pos.x; b.mn[1] = b.mx[1] = o.pos.y; b.mn[2] = b.mx[2] = o.pos.z;
+    b.mn[3] = b.mx[3] = o.scale.x; b.mn[4] = b.mx[4] = o.scale.y; b.mn[5] = b.mx[5] = o.scale.z;
+    b.mn[6] = b.mx[6] = o.col.x; b.mn[7] = b.mx[7] = o.col.y; b.mn[8] = b.mx[8] = o.col.z; b.mn[9] = b.mx[9] = o.col.w;
+    const float inf = u2f(0x7f800000u);
+    b.mn[10] = b.mn[11] = b.mn[12] = inf; b.mx[10] = b.mx[11] = b.mx[12] = -inf;
+#pragma unroll
+    for (int k = 0; k < 15; ++k) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) { b.mn[10 + d] = fminf(b.mn[10 + d], o.sh[3 * k + d]); b.mx[10 + d] = fmaxf(b.mx[10 + d], o.sh[3 * k + d]); }
+    }
+}
+// make sure the ranges are not empty (:591-594), then the 16-dword ChunkInfo: fp16 pairs for colour, scale and sh, raw fp32 for pos
+GS_HD void BakeBoundsWiden(BakeBounds& b) {
+#pragma unroll
+    for (int c = 0; c < kBakeCols; ++c) b.mx[c] = fmaxf(b.mx[c], b.mn[c] + 1.0e-5f);
+}
+GS_HD uint32_t BakeHalfPair(float lo, float hi) { return f32tof16(lo) | (f32tof16(hi) << 16); }
+GS_HD void BakeChunkWords(const BakeBounds& b, uint32_t* w) {
+#pragma unroll
+    for (int d = 0; d < 4; ++d) w[d] = BakeHalfPair(b.mn[6 + d], b.mx[6 + d]);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) { w[4 + 2 * d] = f2u(b.mn[d]); w[5 + 2 * d] = f2u(b.mx[d]); }
+#pragma unroll
+    for (int d = 0; d < 3; ++d) w[10 + d] = BakeHalfPair(b.mn[3 + d], b.mx[3 + d]);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) w[13 + d] = BakeHalfPair(b.mn[10 + d], b.mx[10 + d]);
+}
+// (v - min) / (max - min) against the unrounded fp32 bounds (:613-637); the position too, whatever its format
+GS_HD float BakeNorm(float v, float mn, float mx) { return (v - mn) / (mx - mn); }
+GS_HD void BakeNormalise(BakeRec& o, const BakeBounds& b) {
+    o.pos = { BakeNorm(o.pos.x, b.mn[0], b.mx[0]), BakeNorm(o.pos.y, b.mn[1], b.mx[1]), BakeNorm(o.pos.z, b.mn[2], b.mx[2]) };
+    o.scale = { BakeNorm(o.scale.x, b.mn[3], b.mx[3]), BakeNorm(o.scale.y, b.mn[4], b.mx[4]), BakeNorm(o.scale.z, b.mn[5], b.mx[5]) };
+    o.col = { BakeNorm(o.col.x, b.mn[6], b.mx[6]), BakeNorm(o.col.y, b.mn[7], b.mx[7]), BakeNorm(o.col.z, b.mn[8], b.mx[8]), BakeNorm(o.col.w, b.mn[9], b.mx[9]) };
+#pragma unroll
+    for (int k = 0; k < 15; ++k) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) o.sh[3 * k + d] = BakeNorm(o.sh[3 * k + d], b.mn[10 + d], b.mx[10 + d]);
+    }
+}
+// truncating (uint)(v * (max + 0.5f)) of the encoders (:705-758).  The values it meets are normalised ones: inside [0, 1], or a NaN, which the
+// importer's conversion leaves undefined -- 0 here, by a test
+GS_HD uint32_t BakeQ(float v, float k) { const float p = v * k; return p == p ? (uint32_t)p : 0u; }
+// EmitEncodedVector (:727-758, saturating): the words of one vector; the bytes used are vecStride(fmt)
+GS_HD void BakeEmitVec(const V3& v, uint32_t fmt, uint32_t* w) {
+    w[0] = f2u(v.x); w[1] = f2u(v.y); w[2] = f2u(v.z);
+    if (fmt == 0) return;
+    const float x = sat(v.x), y = sat(v.y), z = sat(v.z);
+    w[1] = w[2] = 0u;
+    if (fmt == 1) { w[0] = BakeQ(x, 65535.5f) | (BakeQ(y, 65535.5f) << 16); w[1] = BakeQ(z, 65535.5f); }
+    else if (fmt == 2) w[0] = BakeQ(x, 2047.5f) | (BakeQ(y, 1023.5f) << 11) | (BakeQ(z, 2047.5f) << 21);
+    else w[0] = BakeQ(x, 63.5f) | (BakeQ(y, 31.5f) << 6) | (BakeQ(z, 31.5f) << 11);
+}
+// the colour texel (:873-932): Float32x4 16 bytes, Float16x4 8, Norm8x4 4
+GS_HD void BakeEmitColor(const V4& c, uint32_t fmt, uint32_t* w) {
+    w[0] = f2u(c.x); w[1] = f2u(c.y); w[2] = f2u(c.z); w[3] = f2u(c.w);
+    if (fmt == 0) return;
+    w[2] = w[3] = 0u;
+    if (fmt == 1) { w[0] = BakeHalfPair(c.x, c.y); w[1] = BakeHalfPair(c.z, c.w); }
+    else { w[0] = BakeQ(sat(c.x), 255.5f) | (BakeQ(sat(c.y), 255.5f) << 8) | (BakeQ(sat(c.z), 255.5f) << 16) | (BakeQ(sat(c.w), 255.5f) << 24); w[1] = 0u; }
+}
+// the SH item (:934-1037; CreateSHDataJob does not saturate): all shStrideOf(fmt) / 4 words of it, the pad the importer leaves zero included.
+// w: 48 words
+GS_HD void BakeEmitSH(const float* sh, uint32_t fmt, uint32_t* w) {
+#pragma unroll
+    for (int k = 0; k < 48; ++k) w[k] = 0u;
+    if (fmt == 0) {
+#pragma unroll
+        for (int k = 0; k < 45; ++k) w[k] = f2u(sh[k]);
+    } else if (fmt == 1) {
+#pragma unroll
+        for (int k = 0; k < 45; ++k) w[k >> 1] |= f32tof16(sh[k]) << ((k & 1) * 16);
+    } else if (fmt == 2) {
+#pragma unroll
+        for (int j = 0; j < 15; ++j) w[j] = BakeQ(sh[3 * j], 2047.5f) | (BakeQ(sh[3 * j + 1], 1023.5f) << 11) | (BakeQ(sh[3 * j + 2], 2047.5f) << 21);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 15; ++j)
+            w[j >> 1] |= ((BakeQ(sh[3 * j], 31.5f) | (BakeQ(sh[3 * j + 1], 63.5f) << 5) | (BakeQ(sh[3 * j + 2], 31.5f) << 11)) & 0xffffu) << ((j & 1) * 16);
+    }
+}
+
+// Morton code of a position inside the bounds of all splats (:362-429; MortonEncode3, GaussianUtils.cs:81-95): 21 bits per axis, z highest.  A
+// component whose product is NaN -- a degenerate axis, max == min: 0 x inf -- is 0 by the test: the conversion of a NaN is undefined.
+GS_HD uint64_t MortonPart1By2(uint64_t x) {
+    x &= 0x1fffffull;
+    x = (x ^ (x << 32)) & 0x1f00000000ffffull;
+    x = (x ^ (x << 16)) & 0x1f0000ff0000ffull;
+    x = (x ^ (x << 8)) & 0x100f00f00f00f00full;
+    x = (x ^ (x << 4)) & 0x10c30c30c30c30c3ull;
+    x = (x ^ (x << 2)) & 0x1249249249249249ull;
+    return x;
+}
+GS_HD uint32_t BakeMortonComponent(float p, float mn, float inv) {
+    const float v = ((p - mn) * inv) * 2097151.0f;
+    return v == v ? (uint32_t)v : 0u;
+}
+GS_HD uint64_t BakeMortonCode(const V3& p, const float* mn, const float* mx) {
+    const float ix = 1.0f / (mx[0] - mn[0]), iy = 1.0f / (mx[1] - mn[1]), iz = 1.0f / (mx[2] - mn[2]);
+    return (MortonPart1By2(BakeMortonComponent(p.z, mn[2], iz)) << 2) | (MortonPart1By2(BakeMortonComponent(p.y, mn[1], iy)) << 1) |
+           MortonPart1By2(BakeMortonComponent(p.x, mn[0], ix));
+}
+
+// One destination chunk on one thread: the records of its cnt <= 256 splats (already linear) to the bytes of the five blobs at splat index
+// first + k -- what the kernel's workgroup does with one lane per splat, and what the host harness of the tests runs as it stands.
+GS_HD void BakeStoreBytes(uint8_t* dst, const uint32_t* w, uint32_t bytes) {
+    for (uint32_t k = 0; k < bytes; ++k) dst[k] = (uint8_t)(w[k >> 2] >> ((k & 3u) * 8u));
+}
+GS_HD void BakeEncodeChunkSerial(BakeRec* rec, uint32_t cnt, uint32_t first, const BakeFormats& f, uint8_t* pos, uint8_t* other, uint8_t* color,
+                                 uint8_t* sh, uint8_t* chunk) {
+    BakeBounds b;
+    if (f.chunked) {
+        BakeBoundsEmpty(b);
+        for (uint32_t k = 0; k < cnt; ++k) { BakeChunkSpace(rec[k]); BakeBounds one; BakeBoundsOf(rec[k], one); BakeBoundsMerge(b, one); }
+        BakeBoundsWiden(b);
+        uint32_t w[16];
+        BakeChunkWords(b, w);
+        BakeStoreBytes(chunk + (uint64_t)(first >> 8) * 64u, w, 64u);
+    }
+    const uint32_t posSz = vecStride(f.pos), othSz = 4u + vecStride(f.scale), colSz = f.color == 0 ? 16u : (f.color == 1 ? 8u : 4u), shSz = shStrideOf(f.sh);
+    for (uint32_t k = 0; k < cnt; ++k) {
+        BakeRec& o = rec[k];
+        if (f.chunked) BakeNormalise(o, b);
+        const uint64_t i = (uint64_t)first + k;
+        uint32_t w[48];
+        BakeEmitVec(o.pos, f.pos, w);
+        BakeStoreBytes(pos + i * posSz, w, posSz);
+        w[0] = o.rot;
+        BakeEmitVec(o.scale, f.scale, w + 1);
+        BakeStoreBytes(other + i * othSz, w, othSz);
+        uint32_t px, py;
+        SplatIndexToPixelIndex((uint32_t)i, px, py);
+        BakeEmitColor(o.col, f.color, w);
+        BakeStoreBytes(color + ((uint64_t)py * 2048u + px) * colSz, w, colSz);
+        BakeEmitSH(o.sh, f.sh, w);
+        BakeStoreBytes(sh + i * shSz, w, shSz);
+    }
+}
+
 } // namespace gsm

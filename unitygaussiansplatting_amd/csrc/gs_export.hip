@@ -34,17 +34,6 @@ constexpr uint32_t kScanThreads = 1024;
 constexpr uint32_t kExportBatchDefault = 131072;                  // splats per batch: 31 MB of records in the device buffer and in each pinned buffer
 static_assert(kRecFloats * 4 == GS_EXPORT_RECORD_BYTES && kRecFloats % 2 == 0, "records are whole dwordx2s");
 
-// alive = idx < N, not deleted, not cut; also hands back the position and the cut flag
-__device__ __forceinline__ bool export_alive(const gsm::AssetView& a, const gsm::EditView& e, uint32_t idx, uint32_t ci, gsm::V3& pos, bool& cut) {
-    cut = false;
-    pos = { 0.0f, 0.0f, 0.0f };
-    if (idx >= a.n) return false;
-    pos = gsm::LoadSplatPosChunk(a, idx, ci);
-    cut = gsm::IsSplatCut(e, pos.x, pos.y, pos.z);
-    const bool deleted = e.deletedBits && ((e.deletedBits[idx >> 5] >> (idx & 31u)) & 1u);
-    return !cut && !deleted;
-}
-
 __global__ __launch_bounds__(256) void export_count_kernel(gsm::AssetView a, gsm::EditView e, uint32_t* __restrict__ counts) {
     __shared__ uint32_t s_cnt[4];
     const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
@@ -82,6 +71,15 @@ __global__ __launch_bounds__(kScanThreads) void export_scan_kernel(const uint32_
         __syncthreads();
     }
     if (t == 0u) base[n] = s_carry;
+}
+
+// counts[c] = alive splats of chunk c, base = their exclusive prefix (base[chunks] = the total), on st: the two launches every compaction starts with
+// (the export's, and the bake's in gs_bake.hip)
+int32_t enqueue_alive_counts(hipStream_t st, const gsm::AssetView& a, const gsm::EditView& e, uint32_t chunks, uint32_t* counts, uint32_t* base) {
+    hipLaunchKernelGGL(export_count_kernel, dim3(chunks), dim3(256), 0, st, a, e, counts);
+    hipLaunchKernelGGL(export_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, (const uint32_t*)counts, base, chunks);
+    GS_HIP(hipGetLastError());
+    return GS_OK;
 }
 
 // out: the records of the chunks [firstChunk, firstChunk + gridDim.x).  base == null: record idx - firstChunk * 256 for every idx < N; else record
@@ -151,9 +149,7 @@ struct ExportRun {
         hostBase.resize((size_t)chunks + 1);                       // (may throw: before anything is in flight)
         GS_HIP(counts.alloc((size_t)chunks * 4));
         GS_HIP(base.alloc(((size_t)chunks + 1) * 4));
-        hipLaunchKernelGGL(export_count_kernel, dim3(chunks), dim3(256), 0, st, asset_view(r), edit_view(r), counts.get());
-        hipLaunchKernelGGL(export_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, (const uint32_t*)counts.get(), base.get(), chunks);
-        GS_HIP(hipGetLastError());
+        GS_TRY(enqueue_alive_counts(st, asset_view(r), edit_view(r), chunks, counts.get(), base.get()));
         GS_HIP(hipMemcpyAsync(hostBase.data(), base.get(), hostBase.size() * 4, hipMemcpyDeviceToHost, st));
         GS_HIP(hipStreamSynchronize(st));
         return GS_OK;

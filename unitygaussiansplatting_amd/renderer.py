@@ -19,9 +19,9 @@ import numpy as np
 
 from . import _lib
 from ._abi import (GS_ERR_PAIR_OVERFLOW, GS_SORT_FULL, GS_SORT_VISIBLE, VIEW_DTYPE, gs_copy_params, gs_edit_info, gs_export_params, gs_frame_params, gs_frame_stats,
-                   gs_stage_times, make_asset_desc)
+                   gs_import_formats, gs_stage_times, make_asset_desc)
 from ._lib import GsError, check
-from .asset import CalcTextureSize, GaussianSplatAsset, kCurrentVersion, kMaxSplats
+from .asset import CalcTextureSize, ColorFormat, GaussianSplatAsset, SHFormat, VectorFormat, kCurrentVersion, kMaxSplats
 from .camera import Camera, Transform, frame_params, mat_mul, matrix_rotation_scale, sort_matrix
 from .cutout import GaussianCutout, shader_data_array
 
@@ -116,8 +116,8 @@ class GpuContext:
 
     def Dispose(self) -> None:
         if self._h:
-            for ch in list(self._children):     # a child must never outlive its context (it holds a raw pointer to it)
-                ch.Dispose()
+            for ch in sorted(self._children, key=lambda c: isinstance(c, GpuAsset)):     # a child must never outlive its context (it holds a raw pointer
+                ch.Dispose()                                                             # to it), nor a device asset the renderers over it
             _lib.lib().gs_context_destroy(self._h)
             self._h = C.c_void_p()
 
@@ -214,6 +214,48 @@ class GpuSorting:
         if self._h:
             _lib.lib().gs_sorter_destroy(self._h)
             self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.Dispose()
+        except Exception:
+            pass
+
+
+class GpuAsset:
+    """A device-resident asset made on the GPU (GaussianSplatRenderer.EditBakeAsset): the native handle, its splat count, its four formats
+    (pos, scale, color, sh) and the position bounds.  Immutable; owned by this object until Dispose()."""
+
+    def __init__(self, ctx: "GpuContext", handle, splatCount: int, formats, boundsMin, boundsMax):
+        self.ctx = ctx
+        self.handle = handle
+        self.splatCount = int(splatCount)
+        self.formats = tuple(formats)
+        self.boundsMin, self.boundsMax = tuple(boundsMin), tuple(boundsMax)
+        ctx._adopt(self)
+
+    def Download(self, name: str = "baked") -> GaussianSplatAsset:
+        """The asset in host memory, dataHash computed: the five blobs at the importer's sizes (gs_import_blob_sizes).  Blocks."""
+        assert self.handle
+        fp, fs, fc, fsh = self.formats
+        fmt = gs_import_formats(int(fp), int(fs), int(fc), int(fsh), 0, 0)
+        sizes = (C.c_uint64 * 5)()
+        check(_lib.lib().gs_import_blob_sizes(self.splatCount, C.byref(fmt), sizes), "gs_import_blob_sizes")
+        blobs = [np.zeros(int(sz), np.uint8) if sz else None for sz in sizes]
+        ptrs = (C.c_void_p * 5)(*[b.ctypes.data if b is not None else None for b in blobs])
+        check(_lib.lib().gs_asset_download_blobs(self.handle, ptrs, sizes), "gs_asset_download_blobs")
+        a = GaussianSplatAsset(splatCount=self.splatCount, posFormat=VectorFormat(fp), scaleFormat=VectorFormat(fs), shFormat=SHFormat(fsh),
+                               colorFormat=ColorFormat(fc), posData=blobs[0], otherData=blobs[1], colorData=blobs[2], shData=blobs[3],
+                               chunkData=blobs[4], boundsMin=self.boundsMin, boundsMax=self.boundsMax, name=name)
+        a.dataHash = a.ComputeDataHash()
+        a.Validate()
+        return a
+
+    def Dispose(self) -> None:
+        """Every renderer created over the asset (CreateResourcesForGpuAsset) must have been disposed first."""
+        if self.handle:
+            _lib.lib().gs_asset_destroy(self.handle)
+            self.handle = C.c_void_p()
 
     def __del__(self):
         try:
@@ -319,6 +361,20 @@ class GaussianSplatRenderer:
         self.m_PrevAsset, self.m_PrevHash = other.m_PrevAsset, other.m_PrevHash
         if self.sortMode != SortMode.Full:
             check(_lib.lib().gs_renderer_set_sort_mode(self._r_h, int(self.sortMode)), "gs_renderer_set_sort_mode")
+
+    def CreateResourcesForGpuAsset(self, gpu_asset: "GpuAsset") -> None:
+        """A renderer over a device-resident asset (EditBakeAsset): borrowed like ShareResourcesOf's, no upload; `gpu_asset` must outlive it.
+        m_Asset stays None -- the data is on the GPU only; gpu_asset.Download() makes a host copy."""
+        assert gpu_asset.handle and not self._r_h
+        self._asset_h, self._asset_borrowed = gpu_asset.handle, True
+        check(_lib.lib().gs_renderer_create(self.ctx._h, self._asset_h, C.byref(self._r_h)), "gs_renderer_create")
+        self.m_SplatCount = self._native_splat_count()
+        if self.sortMode != SortMode.Full:
+            check(_lib.lib().gs_renderer_set_sort_mode(self._r_h, int(self.sortMode)), "gs_renderer_set_sort_mode")
+        if self.framesInFlight > 1:
+            check(_lib.lib().gs_renderer_set_frames_in_flight(self._r_h, int(self.framesInFlight)), "gs_renderer_set_frames_in_flight")
+        if self.selectionHighlight:
+            check(_lib.lib().gs_renderer_set_selection_highlight(self._r_h, 1), "gs_renderer_set_selection_highlight")
 
     def DisposeResourcesForAsset(self) -> None:     # :527-565
         l = _lib.lib()
@@ -641,6 +697,27 @@ class GaussianSplatRenderer:
         alive = C.c_uint32(0)
         check(_lib.lib().gs_renderer_edit_export_ply(self._r_h, C.byref(p), os.fsencode(path), C.byref(alive)), "gs_renderer_edit_export_ply")
         return int(alive.value)
+
+    # -- editing: bake (no counterpart in the reference, whose way back is ExportPlyFile + the importer) -------------------------------
+    def BakeFormats(self, quality="Medium", formatPos=None, formatScale=None, formatColor=None, formatSH=None, morton=True) -> gs_import_formats:
+        from .creator import QUALITY
+        fp, fs, fc, fsh = QUALITY[quality]
+        fp = VectorFormat(fp if formatPos is None else formatPos)
+        fs = VectorFormat(fs if formatScale is None else formatScale)
+        fc = ColorFormat(fc if formatColor is None else formatColor)
+        fsh = SHFormat(fsh if formatSH is None else formatSH)
+        return gs_import_formats(int(fp), int(fs), int(fc), int(fsh), 0, int(bool(morton)))
+
+    def EditBakeAsset(self, quality="Medium", *, formatPos=None, formatScale=None, formatColor=None, formatSH=None, morton=True) -> GpuAsset:
+        """The alive splats (not deleted, not cut) of the renderer as it is now -- edits, private blobs and all -- as a new device-resident asset in
+        the formats of `quality` (or the ones given), Morton-reordered and chunked like an imported one: the bytes the importer makes of
+        ExportAlive's splats, without leaving the GPU.  The renderer itself is left as it is.  BC7 and Cluster* targets are refused.  Blocks."""
+        self.UpdateCutoutsBuffer()
+        fmt = self.BakeFormats(quality, formatPos, formatScale, formatColor, formatSH, morton)
+        h, alive = C.c_void_p(), C.c_uint32(0)
+        bmin, bmax = (C.c_float * 3)(), (C.c_float * 3)()
+        check(_lib.lib().gs_renderer_edit_bake_asset(self._r_h, C.byref(fmt), C.byref(h), C.byref(alive), bmin, bmax), "gs_renderer_edit_bake_asset")
+        return GpuAsset(self.ctx, h, alive.value, (fmt.pos_format, fmt.scale_format, fmt.color_format, fmt.sh_format), tuple(bmin), tuple(bmax))
 
     def CalcViewData(self, cam: Camera) -> None:    # :579-610
         self.UpdateCutoutsBuffer()                  # SetAssetDataOnCS, :507
