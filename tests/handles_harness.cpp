@@ -1,9 +1,11 @@
 // handles_harness.cpp -- csrc/gs_handles.h against a fake HIP runtime: every allocation / event the handles make is tracked, a release of
-// something that is not live aborts, and the k-th creation can be made to fail.  A stand-alone program (tests/test_handles.py builds it with
+// something that is not live aborts, and the k-th creation can be made to fail.  The fake also has streams, each with a vector clock, so that
+// what gs::order_after promises -- and the sequences the library builds from it -- are checked as happens-before.  A stand-alone program (tests/test_handles.py builds it with
 // -fsanitize=address,undefined and runs it); it is NOT linked against the HIP runtime: the few hip* functions the header calls are defined here.
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <map>
 #include <set>
 #include <utility>
 #include <vector>
@@ -37,7 +39,58 @@ hipError_t hipHostGetDevicePointer(void** dev, void* host, unsigned int) {
 }
 hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { if (inject()) { *e = (hipEvent_t)0x1; return hipErrorOutOfMemory; } *e = (hipEvent_t)make(8); return hipSuccess; }
 hipError_t hipEventCreate(hipEvent_t* e) { return hipEventCreateWithFlags(e, 0); }
-hipError_t hipEventDestroy(hipEvent_t e) { release((void*)e, "hipEventDestroy of an event that is not live"); return hipSuccess; }
+static void forget_event(void* e);      // (the ordering model below)
+hipError_t hipEventDestroy(hipEvent_t e) { forget_event((void*)e); release((void*)e, "hipEventDestroy of an event that is not live"); return hipSuccess; }
+
+// Streams and ordering: a MODEL of what the library relies on, not a claim about HIP beyond it.  A stream is an in-order queue with a vector clock
+// (one component per stream); hipEventRecord snapshots the stream's clock into the event, hipStreamWaitEvent merges the event's snapshot AS IT IS AT
+// THAT CALL into the waiter's clock -- a wait refers to the record that preceded it, a later record does not move it.  An event recorded on a second
+// stream aborts: the rule csrc/gs_common.h's signal_to keeps by construction.
+using Clock = std::vector<long>;
+struct FakeStream { int id; Clock clock; };
+struct FakeEvent { const FakeStream* home = nullptr; Clock snap; };
+static std::vector<FakeStream*> g_streams;
+static std::map<void*, FakeEvent> g_events;     // by event handle, while the event is live
+static long g_records = 0, g_waits = 0;
+static void forget_event(void* e) { g_events.erase(e); }
+
+static void merge(Clock& into, const Clock& from) {
+    if (into.size() < from.size()) into.resize(from.size(), 0);
+    for (size_t k = 0; k < from.size(); ++k) if (from[k] > into[k]) into[k] = from[k];
+}
+static hipStream_t stream_create() {
+    FakeStream* s = new FakeStream{ (int)g_streams.size(), Clock() };
+    g_streams.push_back(s);
+    for (FakeStream* t : g_streams) t->clock.resize(g_streams.size(), 0);
+    return (hipStream_t)s;
+}
+static void streams_destroy() { for (FakeStream* s : g_streams) delete s; g_streams.clear(); }
+// a piece of work enqueued on a stream: the stamp it gets is what it has behind it
+struct Op { int stream; Clock at; };
+static Op op(hipStream_t st) {
+    FakeStream* s = (FakeStream*)st;
+    s->clock[(size_t)s->id]++;
+    return Op{ s->id, s->clock };
+}
+static bool before(const Op& a, const Op& b) {      // a happens-before b
+    return b.at.size() > (size_t)a.stream && b.at[(size_t)a.stream] >= a.at[(size_t)a.stream] && !(a.stream == b.stream && a.at == b.at);
+}
+
+hipError_t hipEventRecord(hipEvent_t e, hipStream_t st) {
+    if (!g_live.count((void*)e)) die("hipEventRecord on an event that is not live");
+    FakeEvent& ev = g_events[(void*)e];
+    if (ev.home && ev.home != (FakeStream*)st) die("an event was recorded on a second stream");
+    ev.home = (FakeStream*)st;
+    ev.snap = ev.home->clock;
+    g_records++;
+    return hipSuccess;
+}
+hipError_t hipStreamWaitEvent(hipStream_t st, hipEvent_t e, unsigned int) {
+    if (!g_live.count((void*)e)) die("hipStreamWaitEvent on an event that is not live");
+    merge(((FakeStream*)st)->clock, g_events[(void*)e].snap);      // (never recorded: an empty snapshot, no ordering -- as in HIP)
+    g_waits++;
+    return hipSuccess;
+}
 
 #define CHECK(c) do { if (!(c)) { fprintf(stderr, "FAIL %s:%d: %s\n", __FILE__, __LINE__, #c); exit(1); } } while (0)
 
@@ -179,6 +232,86 @@ static void commit_by_move() {
     CHECK(g_live.size() == base);
 }
 
+// ---- gs::order_after and the sequences the library builds from it ----------------------------------------------------------------------------
+// A context of the library: a stream and the one event that is recorded on it and nowhere else (gs_context::evOrder; gs::signal_to)
+struct Ctx {
+    hipStream_t stream = stream_create();
+    Event evOrder;
+    Ctx() { CHECK(evOrder.create(hipEventDisableTiming) == hipSuccess); }
+};
+static void signal_to(Ctx& from, hipStream_t waiter) { CHECK(gs::order_after(waiter, from.stream, from.evOrder) == hipSuccess); }
+
+static void basic_ordering() {
+    Ctx a, b;
+    const Op early = op(a.stream), lone = op(b.stream);
+    CHECK(before(early, op(a.stream)) && !before(early, lone) && !before(lone, early));      // (the model: in-order streams, unordered against each other)
+    const long rec = g_records, waits = g_waits;
+    signal_to(a, b.stream);
+    CHECK(g_records == rec + 1 && g_waits == waits + 1);       // one record, one wait: nothing is created, nothing else is called
+    const Op late = op(a.stream);                              // put on the signaller AFTER the call
+    const Op after = op(b.stream);
+    CHECK(before(early, after));
+    CHECK(!before(late, after));
+    CHECK(!before(lone, early) && !before(after, late));       // one direction only
+    CHECK(before(lone, after));
+}
+
+// mirror_bits_to_lanes (gs_edit.hip) with two lanes: per lane, the lane waits for the owner, copies, the owner waits for the lane
+static void mirror_sequence() {
+    Ctx owner, lane[2];
+    const Op frame[2] = { op(lane[0].stream), op(lane[1].stream) };    // a frame dealt to each lane before the delete
+    const Op write = op(owner.stream);                                   // the delete's kernel
+    Op copy[2];
+    for (int k = 0; k < 2; ++k) {
+        signal_to(owner, lane[k].stream);
+        copy[k] = op(lane[k].stream);
+        signal_to(lane[k], owner.stream);
+    }
+    const Op next = op(owner.stream);                                    // the owner's next write of the buffer
+    const Op later[2] = { op(lane[0].stream), op(lane[1].stream) };    // frames dealt afterwards read the copies
+    for (int k = 0; k < 2; ++k) {
+        CHECK(before(write, copy[k]));
+        CHECK(before(copy[k], next));
+        CHECK(before(frame[k], copy[k]) && !before(copy[k], frame[k]));  // the frame keeps the bits of the time it was dealt
+        CHECK(before(copy[k], later[k]) && before(write, later[k]));
+        CHECK(!before(next, later[k]));                                  // (the lanes do not wait for what the owner does afterwards)
+    }
+}
+
+// edit_before_move / edit_after_move (gs_edit.hip): the owner waits for every lane, the kernel runs, every lane waits for the owner
+static void move_sequence() {
+    Ctx owner, lane[3];
+    Op earlier[3], later[3];
+    for (int k = 0; k < 3; ++k) earlier[k] = op(lane[k].stream);
+    for (int k = 0; k < 3; ++k) signal_to(lane[k], owner.stream);
+    const Op kernel = op(owner.stream);
+    for (int k = 0; k < 3; ++k) signal_to(owner, lane[k].stream);       // the owner's event, recorded once per lane
+    const Op ownerNext = op(owner.stream);
+    for (int k = 0; k < 3; ++k) later[k] = op(lane[k].stream);
+    for (int k = 0; k < 3; ++k) {
+        CHECK(before(earlier[k], kernel));
+        CHECK(before(kernel, later[k]));
+        CHECK(!before(ownerNext, later[k]));
+        for (int j = 0; j < 3; ++j) CHECK(before(earlier[j], later[k]));  // through the kernel
+    }
+}
+
+// The assumption the library relies on, written down as the model: a wait enqueued earlier keeps the snapshot of ITS record when the event is
+// recorded again (a lane's evOrder every frame, the owner's once per lane in a fan-out).
+static void re_recording() {
+    Ctx a, b, c;
+    const Op first = op(a.stream);
+    signal_to(a, b.stream);
+    const Op second = op(a.stream);
+    signal_to(a, c.stream);                                    // the same event, recorded again on the same stream
+    const Op third = op(a.stream);
+    const Op onB = op(b.stream), onC = op(c.stream);
+    CHECK(before(first, onB) && !before(second, onB) && !before(third, onB));       // b's wait was not moved by the second record
+    CHECK(before(first, onC) && before(second, onC) && !before(third, onC));
+    signal_to(a, b.stream);                                    // ... and a new wait sees the new record
+    CHECK(before(third, op(b.stream)));
+}
+
 int main() {
     lifecycle<DevBuf<int>>();
     lifecycle<PinnedBuf<int>>();
@@ -186,7 +319,13 @@ int main() {
     pinned_device_address();
     event_ring();
     commit_by_move();
+    basic_ordering();
+    mirror_sequence();
+    move_sequence();
+    re_recording();
+    streams_destroy();
     if (!g_live.empty()) { fprintf(stderr, "FAIL: %zu handles still live at exit\n", g_live.size()); return 1; }
     printf("handles ok: %ld created, %ld released\n", g_created, g_released);
+    printf("ordering ok: %ld records, %ld waits, none on a second stream\n", g_records, g_waits);
     return 0;
 }

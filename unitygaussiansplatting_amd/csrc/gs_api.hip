@@ -111,6 +111,7 @@ int32_t gs_context_create(int32_t device, void* hip_stream, gs_context** out) {
         ctx->ownStream = true;
     }
     if (hipStreamCreateWithFlags(&ctx->aux, hipStreamNonBlocking) != hipSuccess) { gs_context_destroy(ctx); return fail(GS_ERR_HIP, "hipStreamCreate (aux)"); }
+    if (ctx->evOrder.create(hipEventDisableTiming) != hipSuccess) { gs_context_destroy(ctx); return fail(GS_ERR_HIP, "hipEventCreate (evOrder)"); }
     // Measured on MI355X: running the depth sort on the second queue does not shorten the frame -- neither beside
     // calc_view only (round 1: 0.995 ms overlapped vs 0.962 serial at C2) nor in the pipelined form, beside the previous
     // frame's pair sort / blend / resolve and this frame's calc_view (round 2: 0.679 vs 0.663 ms at C2, 0.981 vs 0.956 at C3;
@@ -320,12 +321,7 @@ int32_t gs_renderer_set_frames_in_flight(gs_renderer* r, int32_t frames) {
             if (c->counted) { g_liveContexts[c->device % kMaxTrackedDevices].fetch_sub(1, std::memory_order_relaxed); c->counted = false; }
         }
         if (rc == GS_OK) rc = renderer_create_n(c, r->asset, r->n, &L);      // (N is the owner's: a resize may have changed it)
-        if (rc == GS_OK) {
-            L->laneOf = r;
-            hipError_t e = L->evTargetFree.create(hipEventDisableTiming);
-            if (e == hipSuccess) e = L->evBlendDone.create(hipEventDisableTiming);
-            if (e != hipSuccess) rc = fail_hip(e, "create lane events", __FILE__, __LINE__);
-        }
+        if (rc == GS_OK) L->laneOf = r;
         // what the owner's settings own of memory, as it is now (later changes are forwarded by those setters), and the shape the owner's draws have learned
         if (rc == GS_OK) {
             L->adaptTall = r->adaptTall;
@@ -624,8 +620,7 @@ int32_t gs_renderer_set_deleted_bits(gs_renderer* r, const uint32_t* words, size
     // an edit-time operation (EditDeleteSelected): stream-ordered copy, then block so `words` is only read during the call
     GS_HIP(hipMemcpyAsync(r->deletedBits, words, need * 4, hipMemcpyHostToDevice, r->ctx->stream));
     GS_HIP(hipStreamSynchronize(r->ctx->stream));
-    for (gs_renderer* L : r->lanes) GS_TRY(gs_renderer_set_deleted_bits(L, words, word_count));
-    return GS_OK;
+    return edit_deleted_to_lanes(r);                        // the lanes' copies follow on their own streams, device to device
 }
 
 int32_t gs_renderer_set_view_buffer_mode(gs_renderer* r, int32_t every_frame) {

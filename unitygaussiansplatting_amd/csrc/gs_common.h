@@ -167,6 +167,8 @@ struct gs_context {
     // here, forked from / joined to `stream` with events, and the two latency-bound kernels share the GPU
     hipStream_t aux = nullptr;
     bool overlap = false;
+    // what puts another stream behind this context's: recorded on `stream` and nowhere else, and only by gs::signal_to (timing disabled)
+    gs::Event evOrder;
     // GSPLAT_VIEW_GENERIC=1 at context creation: every calc_view launch takes the kernel that reads the asset's formats at run time, never one
     // with a preset's formats compiled in (gs_view.hip) -- the switch the tests use to compare the two
     bool viewGeneric = false;
@@ -251,6 +253,8 @@ struct RendererSettings {
 
 // A plain-value setting goes into gs::RendererSettings, and nothing else needs doing.
 // A setting that owns memory is forwarded to the lanes by its setter and re-applied in resize_build() (gs_copy.hip).
+// A 1-bit-per-splat buffer that the device writes on the owner and a lane reads from a copy of its own (deletedBits, laneSelected) follows the owner's
+// through gs::mirror_bits_to_lanes (gs_edit.hip).  None of this needs an event here: one stream is put behind another's with gs::signal_to.
 // No member may point into the struct: gs_renderer_edit_set_splat_count builds a second gs_renderer of the new N and std::swap()s the two WHOLE structs.
 struct gs_renderer {
     gs_context* ctx = nullptr;
@@ -284,13 +288,9 @@ struct gs_renderer {
     gs::DevBuf<uint32_t> editSelected;      // m_GpuEditSelected: ceil(N/32) words
     gs::DevBuf<uint32_t> editSelectedMouseDown;  // m_GpuEditSelectedMouseDown
     gs::DevBuf<uint32_t> editCountsBounds;  // m_GpuEditCountsBounds: 3 counts + 6 sortable uints
-    gs::Event evEditDeleted;                // context's stream -> lanes: deletedBits holds a delete's result
-    gs::Event evEditCopied;                 // (on a lane) lane's stream -> owner's: the lane has taken its copy
     // the selection highlight (RendererSettings::selectionHighlight): what calc_view reads is editSelected itself on the owner and, on a lane, its own copy,
     // which follows every change of the selection exactly as a lane's deletedBits follow a delete (gs::edit_selected_to_lanes)
     gs::DevBuf<uint32_t> laneSelected;      // (on a lane) its copy of the owner's editSelected, made while the highlight is on; else null
-    gs::Event evEditSelected;               // context's stream -> lanes: editSelected holds the new selection
-    gs::Event evEditSelCopied;              // (on a lane) lane's stream -> owner's: the lane has taken its copy
     bool viewHighlight = false;             // the last calc_view ran with the selected bits: the records carry its marks and the draw launches the highlight blend
     // The renderer's own, writable copy of the two blobs the transform kernels write (CSTranslateSelection / CSRotateSelection / CSScaleSelection): made by
     // the first transform whose format gate can pass, null until then (gs::asset_view).  The asset itself -- shared between contexts, lanes and replicas --
@@ -298,13 +298,9 @@ struct gs_renderer {
     // ... and of the two the merge writes as well (CSCopySplats; gs_copy.hip): made by the first copy INTO this renderer, or -- all four -- by a resize.
     gs::DevBuf<uint8_t> priv[4];            // 0 m_GpuPosData of this renderer, 1 m_GpuOtherData, 2 m_GpuColorData (2048 x CalcTextureSize(N).h texels of four fp32), 3 m_GpuSHData
     uint64_t privBytes[4] = {0, 0, 0, 0};   // bytes of each private blob while it exists: gs::blob_bytes
-    gs::Event evCopySrcReady;               // (on the destination of a copy) source's stream -> this context's: the source's pending edits are done
-    gs::Event evCopyDone;                   // ... and this context's stream -> the source's: the copy kernel has read the source
     gs::DevBuf<uint8_t> editPosMouseDown;   // m_GpuEditPosMouseDown: made only when the position gate can pass
     gs::DevBuf<uint8_t> editOtherMouseDown; // m_GpuEditOtherMouseDown: ... the rotation gate
     bool editPosStored = false, editOtherStored = false;   // EditStorePosMouseDown / EditStoreOtherMouseDown have run since the last release
-    gs::Event evEditMoved;                  // context's stream -> lanes: a transform's kernel is behind this
-    gs::Event evEditLaneIdle;               // (on a lane) lane's stream -> owner's: the frames dealt so far have read the old positions
     bool movedSinceView = false;            // the splats were moved after the last calc_view: lastParams no longer reproduce the view buffer
     float viewW = 0.f, viewH = 0.f, viewNear = 0.f, viewFar = 0.f;   // what the last calc_view was run with
     bool viewValid = false;
@@ -373,11 +369,18 @@ struct gs_renderer {
     std::vector<gs_renderer*> lanes;
     int laneCur = -1;                       // the lane of the frame in progress (-1: none yet)
     gs_renderer* laneOf = nullptr;          // a lane's owner
-    gs::Event evTargetFree;                 // a lane drawing into its owner's target: target's stream -> lane (before the blend) ...
-    gs::Event evBlendDone;                  // ... and lane -> target's stream (after it)
 };
 
 namespace gs {
+// ctx->evOrder is recorded on ctx->stream and nowhere else: the one rule that keeps re-recording it harmless
+// (everything enqueued on `waiter` from here on starts after everything `from`'s stream holds now)
+inline int32_t signal_to(gs_context* from, hipStream_t waiter) {
+    GS_HIP(order_after(waiter, from->stream, from->evOrder));
+    return GS_OK;
+}
+// the renderer itself, or its owner if it is a lane
+inline gs_renderer* owner_of(gs_renderer* r) { return r->laneOf ? r->laneOf : r; }
+inline const gs_renderer* owner_of(const gs_renderer* r) { return r->laneOf ? r->laneOf : r; }
 void prof_record(gs_renderer* r, int k, hipStream_t st = nullptr);   // gs_api.hip: record event k of the current profiling slot (on st, default ctx->stream)
 int32_t target_touched(gs_target* t, hipStream_t st);   // gs_raster.hip: the last operation on the target's memory has just been enqueued on st
 int32_t join_sort(gs_renderer* r);          // make ctx->stream wait for a sort still running on ctx->aux
@@ -429,10 +432,10 @@ int32_t enqueue_debug_boxes(gs_renderer* r, const gs_frame_params* p, gs_target*
 int32_t enqueue_resolve(gs_target* t, const float bg[4], bool want8);
 int32_t flush_clear(gs_target* t);          // perform a pending gs_target_clear now
 // edit (gs_edit.hip)
-void edit_free(gs_renderer* r);             // the selection buffers and the mouse-down copies (not deletedBits, not the private blobs, not the edit events)
+void edit_free(gs_renderer* r);             // the selection buffers and the mouse-down copies (not deletedBits, not the private blobs)
 int32_t edit_ensure(gs_renderer* r);        // EnsureEditingBuffers: the zeroed selection buffers, made once
 int32_t edit_make_private(gs_renderer* r, int k);   // copy-on-write of blob k (0 pos, 1 other, 2 color, 3 sh) on the context's stream
-int32_t edit_deleted_to_lanes(gs_renderer* r);      // the lanes' copies of the deleted bits follow the owner's, by events
+int32_t edit_deleted_to_lanes(gs_renderer* r);      // the lanes' copies of the deleted bits follow the owner's, stream-ordered (mirror_bits_to_lanes)
 int32_t edit_selected_to_lanes(gs_renderer* r);     // ... and, while the highlight is on, their copies of the selection
 int32_t ensure_deleted_bits(gs_renderer* r, hipStream_t st);   // a renderer without a deleted buffer gets one, zero-filled on st
 // what brackets a kernel that rewrites positions (the transforms, the merge): ordering against sorts, GS_SORT_VISIBLE's history and the lanes
@@ -446,7 +449,7 @@ int32_t lanes_resync(gs_renderer* r);
 // The asset as THIS renderer sees it: the asset's view with the blobs replaced by the renderer's private copies where they exist and N the renderer's
 // (a resize changes it).  A lane sees what its owner sees.  Every launch that reads the blobs takes its view from here.
 inline gsm::AssetView asset_view(const gs_renderer* r) {
-    const gs_renderer* o = r->laneOf ? r->laneOf : r;
+    const gs_renderer* o = owner_of(r);
     gsm::AssetView v = r->asset->view;
     if (o->priv[0]) v.pos = o->priv[0];
     if (o->priv[1]) v.other = o->priv[1];
@@ -457,7 +460,7 @@ inline gsm::AssetView asset_view(const gs_renderer* r) {
 }
 // bytes of blob k (0 pos, 1 other, 2 color, 3 sh) as this renderer sees it
 inline uint64_t blob_bytes(const gs_renderer* r, int k) {
-    const gs_renderer* o = r->laneOf ? r->laneOf : r;
+    const gs_renderer* o = owner_of(r);
     return o->priv[k] ? o->privBytes[k] : r->asset->sizes[k];
 }
 inline const uint8_t* blob_ptr(const gs_renderer* r, int k) {
@@ -465,7 +468,7 @@ inline const uint8_t* blob_ptr(const gs_renderer* r, int k) {
     return k == 0 ? a.pos : (k == 1 ? a.other : (k == 2 ? a.color : a.sh));
 }
 // the settings this renderer draws with: its own, or its owner's if it is a lane
-inline const RendererSettings& settings(const gs_renderer* r) { return (r->laneOf ? r->laneOf : r)->set; }
+inline const RendererSettings& settings(const gs_renderer* r) { return owner_of(r)->set; }
 // the edit state calc_view and the edit kernels consult, of THIS renderer: a lane reads its own copy of the deleted bits -- and of the selected bits,
 // which are there only for a splat frame of a renderer whose highlight is on and whose edit buffers exist (_SplatBitsValid, GaussianSplatRenderer.cs:518-520)
 inline gsm::EditView edit_view(const gs_renderer* r) {

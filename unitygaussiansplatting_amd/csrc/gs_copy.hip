@@ -180,17 +180,9 @@ static int32_t copy_splats_into_impl(gs_renderer* src, gs_renderer* dst, const g
     for (int k = 0; k < 4; ++k) GS_TRY(edit_make_private(dst, k));
     if (src->deletedBits) GS_TRY(ensure_deleted_bits(dst, st));    // a destination without a deleted buffer gets a zeroed one
     const bool cross = src->ctx != dst->ctx;
-    if (cross) {                                                   // the source's pending edits are visible to the kernel
-        if (!dst->evCopySrcReady) GS_HIP(dst->evCopySrcReady.create(hipEventDisableTiming));
-        if (!dst->evCopyDone) GS_HIP(dst->evCopyDone.create(hipEventDisableTiming));
-        GS_HIP(hipEventRecord(dst->evCopySrcReady, src->ctx->stream));
-        GS_HIP(hipStreamWaitEvent(st, dst->evCopySrcReady, 0));
-    }
+    if (cross) GS_TRY(signal_to(src->ctx, st));                    // the source's pending edits are visible to the kernel
     GS_TRY(copy_launch(st, asset_view(src), src->deletedBits, X, copy_dst_of(dst), srcStart, dstStart, count));
-    if (cross) {                                                   // a later transform of the source does not race the read
-        GS_HIP(hipEventRecord(dst->evCopyDone, st));
-        GS_HIP(hipStreamWaitEvent(src->ctx->stream, dst->evCopyDone, 0));
-    }
+    if (cross) GS_TRY(signal_to(dst->ctx, src->ctx->stream));      // a later transform of the source does not race the read
     GS_TRY(edit_after_move(dst));
     if (src->deletedBits) GS_TRY(edit_deleted_to_lanes(dst));
     return GS_OK;

@@ -209,42 +209,33 @@ void edit_free(gs_renderer* r) {
 static inline uint32_t splat_grid(const gs_renderer* r) { return (r->n + 255u) / 256u; }
 static inline uint32_t word_grid(const gs_renderer* r) { return (uint32_t)((bit_words(r->n) + 255) / 256); }
 
-// The lanes' copies of the deleted bits follow a delete: a device-to-device copy on each lane's OWN stream, behind an event on the
-// context's stream -- no host synchronisation, and a frame already dealt to a lane keeps the bits of the time it was dealt (its calc_view is
-// ahead of the copy on that stream).  The context's stream then waits for the copies, so that whatever writes or frees the owner's buffer
-// next (another delete, gs_renderer_set_deleted_bits) comes after they have read it.
-int32_t edit_deleted_to_lanes(gs_renderer* r) {
-    if (r->lanes.empty()) return GS_OK;
+// A 1-bit-per-splat buffer of the owner's (src) mirrored into every lane's copy of it: a device-to-device copy on each lane's OWN stream, behind
+// the owner's stream -- no host synchronisation, and a frame already dealt to a lane keeps the bits of the time it was dealt (its calc_view is
+// ahead of the copy on that stream).  The owner's stream then waits for the copy, so that whatever writes or frees the owner's buffer
+// next (another delete, gs_renderer_set_deleted_bits) comes after the lanes have read it.
+static int32_t mirror_bits_to_lanes(gs_renderer* r, const uint32_t* src, DevBuf<uint32_t> gs_renderer::* copy) {
     const size_t bytes = bit_words(r->n) * 4;
-    if (!r->evEditDeleted) GS_HIP(r->evEditDeleted.create(hipEventDisableTiming));
-    GS_HIP(hipEventRecord(r->evEditDeleted, r->ctx->stream));
     for (gs_renderer* L : r->lanes) {
-        if (!L->deletedBits) GS_HIP(L->deletedBits.alloc(bytes));
-        if (!L->evEditCopied) GS_HIP(L->evEditCopied.create(hipEventDisableTiming));
-        GS_HIP(hipStreamWaitEvent(L->ctx->stream, r->evEditDeleted, 0));
-        GS_HIP(hipMemcpyAsync(L->deletedBits, r->deletedBits, bytes, hipMemcpyDeviceToDevice, L->ctx->stream));
-        GS_HIP(hipEventRecord(L->evEditCopied, L->ctx->stream));
-        GS_HIP(hipStreamWaitEvent(r->ctx->stream, L->evEditCopied, 0));
+        DevBuf<uint32_t>& dst = L->*copy;
+        if (!dst) GS_HIP(dst.alloc(bytes));
+        GS_TRY(signal_to(r->ctx, L->ctx->stream));
+        GS_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, L->ctx->stream));
+        GS_TRY(signal_to(L->ctx, r->ctx->stream));
     }
     return GS_OK;
+}
+
+// the lanes' copies of the deleted bits follow a delete (and an upload: gs_renderer_set_deleted_bits)
+int32_t edit_deleted_to_lanes(gs_renderer* r) {
+    if (r->lanes.empty()) return GS_OK;
+    return mirror_bits_to_lanes(r, r->deletedBits, &gs_renderer::deletedBits);
 }
 
 // The same for the selection while it is highlighted: every call that changes editSelected ends here.  With the highlight off (or no lanes) it
 // does nothing; switching the highlight on, and making lanes, bring the copies up to date (gs_api.hip).
 int32_t edit_selected_to_lanes(gs_renderer* r) {
     if (r->lanes.empty() || !r->set.selectionHighlight || !r->editSelected) return GS_OK;
-    const size_t bytes = bit_words(r->n) * 4;
-    if (!r->evEditSelected) GS_HIP(r->evEditSelected.create(hipEventDisableTiming));
-    GS_HIP(hipEventRecord(r->evEditSelected, r->ctx->stream));
-    for (gs_renderer* L : r->lanes) {
-        if (!L->laneSelected) GS_HIP(L->laneSelected.alloc(bytes));
-        if (!L->evEditSelCopied) GS_HIP(L->evEditSelCopied.create(hipEventDisableTiming));
-        GS_HIP(hipStreamWaitEvent(L->ctx->stream, r->evEditSelected, 0));
-        GS_HIP(hipMemcpyAsync(L->laneSelected, r->editSelected, bytes, hipMemcpyDeviceToDevice, L->ctx->stream));
-        GS_HIP(hipEventRecord(L->evEditSelCopied, L->ctx->stream));
-        GS_HIP(hipStreamWaitEvent(r->ctx->stream, L->evEditSelCopied, 0));
-    }
-    return GS_OK;
+    return mirror_bits_to_lanes(r, r->editSelected, &gs_renderer::laneSelected);
 }
 
 // ---- the transforms ---------------------------------------------------------------------------------------------------------------------
@@ -286,11 +277,7 @@ static int32_t edit_store_mouse_down(gs_renderer* r, int k) {
 int32_t edit_before_move(gs_renderer* r) {
     GS_TRY(join_sort(r));
     if (vis_active(r)) GS_TRY(vis_consolidate(r));
-    for (gs_renderer* L : r->lanes) {
-        if (!L->evEditLaneIdle) GS_HIP(L->evEditLaneIdle.create(hipEventDisableTiming));
-        GS_HIP(hipEventRecord(L->evEditLaneIdle, L->ctx->stream));
-        GS_HIP(hipStreamWaitEvent(r->ctx->stream, L->evEditLaneIdle, 0));
-    }
+    for (gs_renderer* L : r->lanes) GS_TRY(signal_to(L->ctx, r->ctx->stream));   // the frames dealt so far read the old positions
     return GS_OK;
 }
 
@@ -303,11 +290,7 @@ int32_t edit_after_move(gs_renderer* r) {
         vis_base_changed(r, r->visBaseIdentity);                   // (still CSSetIndices' identity if nothing had been sorted yet)
         GS_TRY(lanes_resync(r));
     }
-    if (!r->lanes.empty()) {
-        if (!r->evEditMoved) GS_HIP(r->evEditMoved.create(hipEventDisableTiming));
-        GS_HIP(hipEventRecord(r->evEditMoved, r->ctx->stream));
-        for (gs_renderer* L : r->lanes) GS_HIP(hipStreamWaitEvent(L->ctx->stream, r->evEditMoved, 0));
-    }
+    for (gs_renderer* L : r->lanes) GS_TRY(signal_to(r->ctx, L->ctx->stream));   // the kernel is behind this
     return GS_OK;
 }
 
@@ -316,7 +299,7 @@ int32_t edit_after_move(gs_renderer* r) {
 //   - GS_SORT_VISIBLE: the recorded sorts are sorts of the OLD positions, so they are carried out first (order[] = the reference's buffer now), and that
 //     order is the new base with an empty history -- from here on the reference, too, stably sorts that buffer by keys of the new positions;
 //   - lanes read the owner's private blobs in place: the context's stream waits for what each lane has been dealt (those frames finish with the old
-//     positions), the kernel runs, and every lane's stream waits for it.  Events only; edit_deleted_to_lanes turned round.
+//     positions), the kernel runs, and every lane's stream waits for it.  signal_to only; mirror_bits_to_lanes turned round.
 static int32_t edit_transform(gs_renderer* r, int op, const gsm::EditXform& X) {
     const bool doPos = edit_pos_gate(r), doRot = op == kEditRotate && edit_rot_gate(r);
     if (!doPos && !doRot) return GS_OK;                            // neither gate: the reference's kernel writes nothing

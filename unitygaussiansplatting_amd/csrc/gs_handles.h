@@ -3,6 +3,7 @@
 // A handle converts to the raw pointer / event it owns, so kernel launches, copies and pointer arithmetic read as they would with the raw pointer.
 // No destructor synchronises: whoever destroys an object that work in flight may still use waits for its streams first (the gs_*_destroy functions).
 // Several resources that are made or grown together are built in local handles and moved into their owner after the last step has succeeded.
+// order_after(), at the end, puts one stream behind another through an Event: the record and the wait in one step.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stddef.h>
@@ -87,5 +88,12 @@ public:
 private:
     hipEvent_t e_ = nullptr;
 };
+
+// Everything enqueued on `waiter` after this call starts only after everything enqueued on `signaller` before it has finished.
+// ev must exist.  The wait refers to THIS record: a later record of ev (on the same stream) does not move it.
+inline hipError_t order_after(hipStream_t waiter, hipStream_t signaller, Event& ev) {
+    const hipError_t e = hipEventRecord(ev, signaller);
+    return e != hipSuccess ? e : hipStreamWaitEvent(waiter, ev, 0);
+}
 
 } // namespace gs

@@ -1624,10 +1624,8 @@ int32_t enqueue_draw(gs_renderer* r, const gs_frame_params* p, gs_target* rt) {
         // the target's last use (target_touched); everything the context's stream holds only if the host may have put work of its own on the memory there
         // (it asked for the device pointers, or lent a depth buffer it fills itself)
         const bool borrowedDepth = rt->sceneDepth && rt->sceneDepth != rt->sceneDepthOwned;
-        if (rt->exposed || borrowedDepth) {
-            GS_HIP(hipEventRecord(r->evTargetFree, rt->ctx->stream));
-            GS_HIP(hipStreamWaitEvent(st, r->evTargetFree, 0));
-        } else if (rt->lastUseValid) GS_HIP(hipStreamWaitEvent(st, rt->evLastUse, 0));
+        if (rt->exposed || borrowedDepth) GS_TRY(signal_to(rt->ctx, st));
+        else if (rt->lastUseValid) GS_HIP(hipStreamWaitEvent(st, rt->evLastUse, 0));
     }
     if (rt->sceneDepth) {
         gsm::FrameConsts fc;
@@ -1647,10 +1645,7 @@ int32_t enqueue_draw(gs_renderer* r, const gs_frame_params* p, gs_target* rt) {
 #undef GS_LAUNCH_BLEND_K
     prof_record(r, 6);
     GS_HIP(hipGetLastError());
-    if (foreignTarget) {
-        GS_HIP(hipEventRecord(r->evBlendDone, st));
-        GS_HIP(hipStreamWaitEvent(rt->ctx->stream, r->evBlendDone, 0));
-    }
+    if (foreignTarget) GS_TRY(signal_to(r->ctx, rt->ctx->stream));
     GS_TRY(target_touched(rt, st));
     r->frameInFlight = true;
     prof_end_frame(r);

@@ -479,7 +479,7 @@ int32_t vis_alloc(gs_renderer* r) {
     r->visKeys = std::move(k); r->visIdx = std::move(v); r->visRectX = std::move(x); r->visRectY = std::move(y); r->visPairOffset = std::move(po);
     r->visControl = std::move(c); r->visControlIdx = 0;
     static const int envLimit = [] { const char* s = getenv("GSPLAT_VIS_HISTORY"); const int v = s ? atoi(s) : 0; return (v >= 2 && v <= kVisHistory) ? v : 0; }();
-    RendererSettings& set = (r->laneOf ? r->laneOf : r)->set;      // (a lane's vis_alloc: its owner's settings)
+    RendererSettings& set = owner_of(r)->set;      // (a lane's vis_alloc: its owner's settings)
     if (envLimit && set.visHistLimit == kVisHistory) set.visHistLimit = envLimit;
     return GS_OK;
 }
