@@ -542,6 +542,14 @@ int32_t gs_import_encode(const gs_import_input* in, const gs_import_formats* for
  * a device buffer of fixed size in batches (GSPLAT_IMPORT_BATCH = points per batch, read at every call, overrides the size). */
 /* nearest-mean assignment of n 45-float vectors to k means; ctx NULL = the host loop, else the context's GPU. Blocks. */
 int32_t gs_import_assign_clusters(gs_context* ctx, const float* x, uint64_t n, const float* means, uint32_t k, uint32_t* index_out);
+/* The whole palette of the Cluster* SH formats for n 45-float vectors (cluster_shs of the importer: GaussianSplatAssetCreator.cs:476-518 minus its
+ * RNG): seeds means[j] = x[(j n) / k]; training subset = all of x when n <= 200,000, else x[(i n) / 200,000]; four Lloyd passes on the subset --
+ * the assignment above, then for every cluster with points and every coefficient sum = sum + (double)x[p][c] over its points in ascending point
+ * index from 0.0, mean = (float)(sum / (double)count), an empty cluster keeping its mean; one assignment pass over all n.  means_out: k x 45,
+ * index_out: n.  ctx NULL: the host loop.  Otherwise the whole loop runs on the context's GPU (points up once, means and indices down at the end;
+ * csrc/gs_cluster.hip) and gives the same bits for finite input: a NaN a sum produces has no fixed sign or payload across the two.
+ * k in [1, 65536], n >= 1; n <= k is allowed (the seeds repeat).  Blocks. */
+int32_t gs_import_cluster_shs(gs_context* ctx, const float* x, uint64_t n, uint32_t k, float* means_out, uint32_t* index_out);
 /* gs_import_encode with the Cluster* assignment passes on ctx's GPU (ctx NULL: identical to gs_import_encode) */
 int32_t gs_import_encode_on(gs_context* ctx, const gs_import_input* in, const gs_import_formats* formats,
                             void* const blobs[5], const uint64_t sizes[5], float bounds_min[3], float bounds_max[3]);
@@ -551,8 +559,11 @@ int32_t gs_import_encode_on(gs_context* ctx, const gs_import_input* in, const gs
  * decoded from whatever r holds (any preset, private blobs or the asset's) and encoded in `formats`, Morton-reordered and chunked as
  * GaussianSplatAssetCreator does it: the five blobs are the bytes gs_import_encode (linearize = 0) makes of the same splats in index order.
  * Runs on the context's stream after everything already enqueued there and on the lanes; only reads the renderer.
+ * A GS_SH_CLUSTER* target gets the importer's palette of the alive splats' SH, computed on the GPU (gs_import_cluster_shs' loop on device
+ * pointers); those bytes are the importer's for finite SH values.
  * Refused with GS_ERR_INVALID_ARGUMENT, nothing allocated and *out NULL: a NULL argument, a lane, a format enum out of range, linearize != 0,
- * no alive splat, a GS_COLOR_BC7 or GS_SH_CLUSTER* target (any preset is accepted as the source). */
+ * no alive splat, a GS_SH_CLUSTER* target with no more alive splats than table entries (gs_import_blob_sizes' rule), a GS_COLOR_BC7 target --
+ * hence the preset VeryLow as a whole; VeryLow with another colour format is accepted (any preset is accepted as the source). */
 /* formats->linearize must be 0 (the renderer's data is linear); formats->morton 0 or 1.  BLOCKS.  *out is a new asset owned by r's
  * context (gs_asset_destroy); *alive its splat count; bounds as GaussianSplatAsset.boundsMin/Max (may be NULL). */
 int32_t gs_renderer_edit_bake_asset(gs_renderer* r, const gs_import_formats* formats, gs_asset** out, uint32_t* alive,

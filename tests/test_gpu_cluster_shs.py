@@ -1,0 +1,90 @@
+"""-m gpu: the device-resident Lloyd loop of the Cluster* SH palette (csrc/gs_cluster.hip through gs_import_cluster_shs with a context: seeds, training
+subset, four passes of assignment + stable sort + mean update, the final assignment, all on the GPU) against the host route of the same entry
+(tests/test_cluster_shs.py holds that one to the numpy model): means and indices bit for bit, no tolerance.  The largest table is compared with the
+model's mean update over GPU-assigned indices instead, so that the host does not spend 10^11 multiply-adds."""
+import numpy as np
+import pytest
+
+import cluster_model as CM
+from unitygaussiansplatting_amd import _abi, _lib, creator
+
+pytestmark = pytest.mark.gpu
+f32 = np.float32
+
+
+def check(ctx, x, k, want=None):
+    want_means, want_index = creator.ClusterSHsNative(x, k) if want is None else want
+    means, index = creator.ClusterSHsNative(x, k, context=ctx)
+    rows = np.flatnonzero((means.view(np.uint32) != want_means.view(np.uint32)).any(axis=1))
+    assert len(rows) == 0, f"{len(rows)} of {k} means differ, first {rows[:5]}: gpu {means[rows[0]][:4]} != host {want_means[rows[0]][:4]}"
+    bad = np.flatnonzero(index != want_index)
+    assert len(bad) == 0, f"{len(bad)} of {len(x)} indices differ, first at {bad[:5]}"
+    return means, index
+
+
+@pytest.mark.parametrize("k", [1, 2, 63, 65])
+@pytest.mark.parametrize("n", [1, 63, 257, 1_037])
+def test_device_loop_equals_host_sizes(gpu_ctx, n, k):
+    check(gpu_ctx, CM.random_points(n, 100 * n + k), k)
+
+
+def test_device_loop_one_more_point_than_entries(gpu_ctx):
+    check(gpu_ctx, CM.random_points(4_097, 41), 4_096)
+
+
+def test_device_loop_takes_the_training_subset(gpu_ctx):
+    check(gpu_ctx, CM.random_points(200_001, 7), 64)
+
+
+def test_device_loop_largest_table(gpu_ctx):
+    """K = 65,536 (16 key bits: two sort passes) with 70,000 points: the model's loop with the assignment on the GPU -- which
+    tests/test_gpu_import_cluster.py holds to the host's indices -- in place of 10^11 host multiply-adds"""
+    x = CM.random_points(70_000, 43)
+    want_means, want_index, cnt = CM.lloyd(x, 65_536, assign=lambda p, m: creator.AssignClusters(p, m, context=gpu_ctx))
+    assert cnt.max() > 1                                                # some clusters sum more than one point
+    check(gpu_ctx, x, 65_536, want=(want_means, want_index))
+
+
+def test_device_loop_long_cluster_and_empty_clusters(gpu_ctx):
+    """20,000 points of which 8,000 consecutive ones are one row and 2,000 another, K = 4,096: one cluster of thousands of points (several rounds of
+    64 point numbers, a tail that is no multiple of the rows in flight), more than a thousand clusters that never get a point"""
+    n, k = 20_000, 4_096
+    x = CM.clumped_points(n, 5)
+    means, index = check(gpu_ctx, x, k)
+    cnt = np.bincount(index, minlength=k)
+    assert cnt.max() >= 8_000 and (cnt == 0).sum() >= 1_000
+    seeds = CM.seeds(x, k)
+    dup = np.flatnonzero((seeds == x[2_000]).all(axis=1))               # the seeds inside the run are equal: one of them holds the run (the lowest until
+    assert len(dup) > 1_000 and cnt[dup].max() >= 8_000                 # a stray point moves its mean), the others never get a point and stay as they were
+    assert (cnt[dup] == 0).sum() >= 1_000 and (means[dup].view(np.uint32) == seeds[dup].view(np.uint32)).all(axis=1).sum() >= 1_000
+
+
+def test_device_loop_crafted_scene(gpu_ctx):
+    """the SH rows of the crafted scene of tests/test_gpu_bake_cluster.py, as tests/test_cluster_shs.py runs them on the host"""
+    x = np.ascontiguousarray(CM.crafted_decode()[:, 14:59], f32)
+    _, index = check(gpu_ctx, x, 4_096)
+    cnt = np.bincount(index, minlength=4_096)
+    assert (cnt == 0).sum() >= 1_500 and cnt.max() >= 2_500
+
+
+def test_device_loop_is_independent_of_the_batch_size(gpu_ctx, monkeypatch):
+    x = CM.random_points(1_037, 47)
+    whole = check(gpu_ctx, x, 65)
+    monkeypatch.setenv("GSPLAT_IMPORT_BATCH", "256")                    # read at every call: 4 full launches + one of 13 points per pass
+    again = creator.ClusterSHsNative(x, 65, context=gpu_ctx)
+    assert CM.same_bits(again[0], whole[0]) and np.array_equal(again[1], whole[1])
+    monkeypatch.setenv("GSPLAT_IMPORT_BATCH", "1")
+    check(gpu_ctx, x[:70], 9)
+
+
+def test_device_loop_validates_arguments_with_a_context(gpu_ctx):
+    lib = _lib.lib()
+    bad = _abi.GS_ERR_INVALID_ARGUMENT
+    x = CM.random_points(4, 1)
+    means, index = np.zeros((3, 45), f32), np.zeros(4, np.uint32)
+    assert lib.gs_import_cluster_shs(gpu_ctx._h, x.ctypes.data, 0, 3, means.ctypes.data, index.ctypes.data) == bad
+    assert lib.gs_import_cluster_shs(gpu_ctx._h, x.ctypes.data, 4, 0, means.ctypes.data, index.ctypes.data) == bad
+    assert lib.gs_import_cluster_shs(gpu_ctx._h, x.ctypes.data, 4, 65_537, means.ctypes.data, index.ctypes.data) == bad
+    assert lib.gs_import_cluster_shs(gpu_ctx._h, None, 4, 3, means.ctypes.data, index.ctypes.data) == bad
+    check(gpu_ctx, x, 3)                                                # n > k by one; and n <= k: the seeds repeat
+    check(gpu_ctx, x, 7)

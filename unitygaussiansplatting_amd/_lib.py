@@ -115,6 +115,7 @@ SIGNATURES = {
     "gs_import_encode": (C.c_int32, [C.POINTER(gs_import_input), C.POINTER(gs_import_formats), C.c_void_p * 5, C.c_uint64 * 5,
                                       C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "gs_import_assign_clusters": (C.c_int32, [_P, _P, C.c_uint64, _P, C.c_uint32, _P]),
+    "gs_import_cluster_shs": (C.c_int32, [_P, _P, C.c_uint64, C.c_uint32, _P, _P]),
     "gs_import_encode_on": (C.c_int32, [_P, C.POINTER(gs_import_input), C.POINTER(gs_import_formats), C.c_void_p * 5, C.c_uint64 * 5,
                                          C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "gs_renderer_edit_bake_asset": (C.c_int32, [_P, C.POINTER(gs_import_formats), _PP, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_float)]),

@@ -597,6 +597,19 @@ def AssignClusters(x, means, context=None) -> np.ndarray:
     return out
 
 
+def ClusterSHsNative(x, k: int, context=None):
+    """ClusterSHs through gs_import_cluster_shs: (means [k,45] float32, index [N] uint32) of the rows of `x` [N,45].  context None: the native
+    host loop (cluster_shs of csrc/gs_import.cpp).  context = a renderer.GpuContext: the whole Lloyd loop on its GPU (csrc/gs_cluster.hip), the
+    same bits for finite input."""
+    from . import _lib
+    x = np.ascontiguousarray(x, f32).reshape(-1, 45)
+    means = np.zeros((int(k), 45), f32)
+    index = np.zeros(len(x), np.uint32)
+    _lib.check(_lib.lib().gs_import_cluster_shs(context._h if context is not None else None, x.ctypes.data, len(x), int(k), means.ctypes.data,
+                                                index.ctypes.data), "gs_import_cluster_shs")
+    return means, index
+
+
 # --------------------------------------------------------------------------------------------------
 # SPZ (Niantic / Scaniverse), Editor/Utils/SPZFileReader.cs
 # --------------------------------------------------------------------------------------------------

@@ -16,6 +16,12 @@
 //                            bytes, contiguous across the wave), the colour texel per lane (a chunk is one 16 x 16 tile: 16 rows of 64-256 contiguous
 //                            bytes), the SH items (32 / 60 / 96 / 192 bytes) staged per wave in LDS and written as one contiguous, 16-byte aligned range
 //                            with dwordx4 stores -- the shape of the export and the merge (gs_export.hip, gs_copy.hip).
+// A Cluster* SH target (every one is chunked) puts the importer's palette between 2 and 3, on the GPU as well:
+//   2a. SH rows              bake_sh_rows: x[i] = the 45 raw SH floats of destination splat i (coefficient-major, before the chunk normalisation) in a
+//                            transient n x 180 byte buffer, staged per wave through LDS like the SH items (64 rows = 11,520 contiguous bytes).
+//   2b. palette              enqueue_cluster_shs (gs_cluster.hip): seeds, training subset, four Lloyd passes, the final assignment -> K means, n indices.
+//   2c. table                bake_sh_table: K x 45 floats -> K x 96 bytes (gsm::BakeEmitSHTableItem).
+//   3.  encode               as above, except that no SH item is staged or written and the u16 index follows the scale in `other` (gsm::BakeEmitOther).
 // The five blobs are zero-filled first, as the importer's are: the pad bytes, the texels past N and the last chunk's tail are part of the bytes.
 #include <new>
 
@@ -25,7 +31,7 @@ namespace gs {
 
 constexpr uint32_t kBakeReduceThreads = 1024;
 
-struct BakeDst { uint8_t* pos; uint8_t* other; uint8_t* color; uint8_t* sh; uint8_t* chunk; uint32_t n; gsm::BakeFormats f; };
+struct BakeDst { uint8_t* pos; uint8_t* other; uint8_t* color; uint8_t* sh; uint8_t* chunk; uint32_t n; gsm::BakeFormats f; const uint32_t* shIndex; };   // shIndex: Cluster* SH targets only
 
 __device__ __forceinline__ float wave_min(float v) {
 #pragma unroll
@@ -102,15 +108,57 @@ __global__ __launch_bounds__(256) void bake_gather_kernel(const uint32_t* __rest
     if (i < total) out[i] = hi[rank[i]];
 }
 
-// bytes in { 2, 4, 6, 8, 10, 12, 16 } of w to p; p is `bytes`-strided from an aligned base: a multiple of 4 bytes = dword stores, else halfword stores
+// bytes in { 2, 4, 6, 8, 10, 12, 16, 18 } of w (5 words) to p; p is `bytes`-strided from an aligned base: a multiple of 4 bytes = dword stores, else
+// halfword stores
 __device__ __forceinline__ void bake_store(uint8_t* p, const uint32_t* w, uint32_t bytes) {
     if ((bytes & 3u) == 0u) {
 #pragma unroll
         for (uint32_t k = 0; k < 4u; ++k) if (k * 4u < bytes) ((uint32_t*)p)[k] = w[k];
     } else {
 #pragma unroll
-        for (uint32_t k = 0; k < 5u; ++k) if (k * 2u < bytes) ((uint16_t*)p)[k] = (uint16_t)(w[k >> 1] >> ((k & 1u) * 16u));
+        for (uint32_t k = 0; k < 9u; ++k) if (k * 2u < bytes) ((uint16_t*)p)[k] = (uint16_t)(w[k >> 1] >> ((k & 1u) * 16u));
     }
+}
+
+// words [0, words) of a wave's LDS staging area to dst, contiguous and 16-byte aligned: dwordx4 stores, then the few words left
+__device__ __forceinline__ void bake_flush_wave(uint8_t* dst, const uint32_t* staged, uint32_t words, uint32_t lane) {
+    const uint32_t quads = words / 4u;
+    for (uint32_t q = lane; q < quads; q += 64u) ((uint4*)dst)[q] = ((const uint4*)staged)[q];
+    if (quads * 4u + lane < words) ((uint32_t*)dst)[quads * 4u + lane] = staged[quads * 4u + lane];
+}
+
+// rows[i] = the 45 raw SH floats of destination splat i: what cluster_shs of the importer is given (gs_import.cpp: x[i] = s[order[i]].sh)
+__global__ __launch_bounds__(256) void bake_sh_rows_kernel(gsm::AssetView a, const uint32_t* __restrict__ alive, const uint32_t* __restrict__ order, uint32_t n,
+                                                           float* __restrict__ rows) {
+    __shared__ __attribute__((aligned(16))) uint32_t s_sh[4][64 * 45];
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    if (i < n) {
+        const uint32_t src = alive[order ? order[i] : i], ci = src >> 8;
+        gsm::SplatFull s;
+        gsm::LoadSplatDataFull(a, src, ci, gsm::LoadSplatPosChunk(a, src, ci), s);
+        gsm::BakeRec rec;
+        gsm::BakeLinearRecord(s, rec);
+        uint32_t* row = s_sh[wave] + lane * 45u;
+#pragma unroll
+        for (int k = 0; k < 45; ++k) row[k] = gsm::f2u(rec.sh[k]);
+    }
+    __syncthreads();
+    const uint32_t waveFirst = blockIdx.x * 256u + wave * 64u;      // 64 rows of 180 bytes: every wave's range starts 16-byte aligned
+    if (waveFirst < n) bake_flush_wave((uint8_t*)rows + (size_t)waveFirst * 180u, s_sh[wave], (n - waveFirst < 64u ? n - waveFirst : 64u) * 45u, lane);
+}
+
+// the SH table of a Cluster* target: one thread per entry, 96 bytes = six dwordx4 stores
+__global__ __launch_bounds__(256) void bake_sh_table_kernel(const float* __restrict__ means, uint32_t K, uint8_t* __restrict__ table) {
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= K) return;
+    float m[45];
+#pragma unroll
+    for (int k = 0; k < 45; ++k) m[k] = means[(size_t)j * 45u + k];
+    uint32_t w[24];
+    gsm::BakeEmitSHTableItem(m, w);
+    uint4* out = (uint4*)(table + (size_t)j * 96u);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) out[k] = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
 }
 
 __global__ __launch_bounds__(256) void bake_encode_kernel(gsm::AssetView a, const uint32_t* __restrict__ alive, const uint32_t* __restrict__ order, BakeDst d) {
@@ -150,8 +198,9 @@ __global__ __launch_bounds__(256) void bake_encode_kernel(gsm::AssetView a, cons
         }
         if (mine) gsm::BakeNormalise(rec, b);
     }
+    const bool clustered = gsm::shIsClustered(d.f.sh);             // (kernel-uniform) the SH blob is the table: no item per splat
     const uint32_t shWords = gsm::shStrideOf(d.f.sh) / 4u;
-    if (mine) {
+    if (mine && !clustered) {
         uint32_t w[48];
         gsm::BakeEmitSH(rec.sh, d.f.sh, w);
         uint32_t* s = s_sh[wave] + lane * shWords;
@@ -160,20 +209,17 @@ __global__ __launch_bounds__(256) void bake_encode_kernel(gsm::AssetView a, cons
     }
     __syncthreads();
     const uint32_t waveFirst = blockIdx.x * 256u + wave * 64u;      // the wave's first destination record; its lanes that write are a prefix
-    if (waveFirst < d.n) {
-        const uint32_t waveCount = d.n - waveFirst < 64u ? d.n - waveFirst : 64u, words = waveCount * shWords, quads = words / 4u;
-        uint8_t* dst = d.sh + (size_t)waveFirst * (shWords * 4u);   // 16-byte aligned: 64 records of a multiple of 4 bytes
-        for (uint32_t q = lane; q < quads; q += 64u) ((uint4*)dst)[q] = ((const uint4*)s_sh[wave])[q];
-        if (quads * 4u + lane < words) ((uint32_t*)dst)[quads * 4u + lane] = s_sh[wave][quads * 4u + lane];
+    if (waveFirst < d.n && !clustered) {
+        const uint32_t waveCount = d.n - waveFirst < 64u ? d.n - waveFirst : 64u;
+        bake_flush_wave(d.sh + (size_t)waveFirst * (shWords * 4u), s_sh[wave], waveCount * shWords, lane);     // 16-byte aligned: 64 records of a multiple of 4 bytes
     }
     if (!mine) return;
-    uint32_t w[4];
+    uint32_t w[5];
     gsm::BakeEmitVec(rec.pos, d.f.pos, w);
-    const uint32_t posSz = gsm::vecStride(d.f.pos), sclSz = gsm::vecStride(d.f.scale);
+    const uint32_t posSz = gsm::vecStride(d.f.pos);
     bake_store(d.pos + (size_t)i * posSz, w, posSz);
-    w[0] = rec.rot;
-    gsm::BakeEmitVec(rec.scale, d.f.scale, w + 1);
-    bake_store(d.other + (size_t)i * (4u + sclSz), w, 4u + sclSz);
+    const uint32_t othSz = gsm::BakeEmitOther(rec.rot, rec.scale, d.f.scale, clustered, clustered ? d.shIndex[i] : 0u, w);
+    bake_store(d.other + (size_t)i * othSz, w, othSz);
     uint32_t px, py;
     gsm::SplatIndexToPixelIndex(i, px, py);
     gsm::BakeEmitColor(rec.col, d.f.color, w);
@@ -188,7 +234,11 @@ struct BakeRun {
     DevBuf<float> partial, bounds;
     SortState sort;
     DevBuf<SortControl> control;
+    DevBuf<float> shRows, shMeans;          // a Cluster* SH target: the n x 45 SH rows in destination order, the K x 45 means,
+    DevBuf<uint32_t> shIndex;               // the n table indices
+    ClusterRun cluster;                     // and the Lloyd loop's own state
 };
+
 
 static int32_t bake_sort(gs_context* ctx, BakeRun& run, uint32_t* keys, uint32_t total, uint32_t keyBits) {
     const int passes = (int)((keyBits + 7u) / 8u);
@@ -198,8 +248,9 @@ static int32_t bake_sort(gs_context* ctx, BakeRun& run, uint32_t* keys, uint32_t
 }
 
 // steps 1 (second half) to 3 on the context's stream; the caller synchronises whatever this returns.  ev: null, or six events -- 2 .. 5 are recorded
-// here, before the alive list and after the bounds, the sorts and the encode
-static int32_t bake_enqueue(gs_renderer* r, const gs_import_formats* f, BakeRun& run, uint32_t chunks, uint32_t total, const BakeDst& d, Event* ev) {
+// here, before the alive list and after the bounds, the sorts and the encode.  cev: null, or twelve events of a Cluster* target -- before and after the
+// SH rows, enqueue_cluster_shs' nine further ones, after the table + encode
+static int32_t bake_enqueue(gs_renderer* r, const gs_import_formats* f, BakeRun& run, uint32_t chunks, uint32_t total, BakeDst d, Event* ev, const hipEvent_t* cev) {
     gs_context* ctx = r->ctx;
     hipStream_t st = ctx->stream;
     const gsm::AssetView a = asset_view(r);
@@ -211,6 +262,13 @@ static int32_t bake_enqueue(gs_renderer* r, const gs_import_formats* f, BakeRun&
         for (DevBuf<uint32_t>* b : { &run.lo, &run.hi, &run.hi2, &run.rank }) GS_HIP(b->alloc(((size_t)total + 16) * 4));
         GS_TRY(sort_state_create(ctx, run.sort, total, true));
         GS_HIP(run.control.alloc(sizeof(SortControl)));
+    }
+    const uint32_t K = gsm::shClusterCount(f->sh_format);
+    if (K) {                                                       // n x 184 bytes + the subset and the sort state: freed with `run`
+        GS_HIP(run.shRows.alloc((size_t)total * 180));
+        GS_HIP(run.shIndex.alloc((size_t)total * 4));
+        GS_HIP(run.shMeans.alloc((size_t)K * 180));
+        GS_TRY(cluster_run_alloc(ctx, run.cluster, total, K));
     }
     if (ev) GS_HIP(hipEventRecord(ev[2], st));
     hipLaunchKernelGGL(bake_alive_kernel, dim3(chunks), dim3(256), 0, st, a, edit_view(r), (const uint32_t*)run.base.get(), run.alive.get(), run.partial.get());
@@ -227,14 +285,24 @@ static int32_t bake_enqueue(gs_renderer* r, const gs_import_formats* f, BakeRun&
         GS_TRY(bake_sort(ctx, run, run.hi2, total, 31u));
     }
     if (ev) GS_HIP(hipEventRecord(ev[4], st));
-    hipLaunchKernelGGL(bake_encode_kernel, dim3(blocks), dim3(256), 0, st, a, (const uint32_t*)run.alive.get(),
-                       f->morton ? (const uint32_t*)run.rank.get() : (const uint32_t*)nullptr, d);
+    const uint32_t* order = f->morton ? (const uint32_t*)run.rank.get() : (const uint32_t*)nullptr;
+    if (K) {
+        if (cev) GS_HIP(hipEventRecord(cev[0], st));
+        hipLaunchKernelGGL(bake_sh_rows_kernel, dim3(blocks), dim3(256), 0, st, a, (const uint32_t*)run.alive.get(), order, total, run.shRows.get());
+        GS_HIP(hipGetLastError());
+        GS_TRY(enqueue_cluster_shs(ctx, run.cluster, run.shRows, total, K, run.shMeans, run.shIndex, cev ? cev + 1 : nullptr));      // (records cev[1 .. 10])
+        hipLaunchKernelGGL(bake_sh_table_kernel, dim3((K + 255u) / 256u), dim3(256), 0, st, (const float*)run.shMeans.get(), K, d.sh);
+        d.shIndex = run.shIndex;
+    }
+    hipLaunchKernelGGL(bake_encode_kernel, dim3(blocks), dim3(256), 0, st, a, (const uint32_t*)run.alive.get(), order, d);
     GS_HIP(hipGetLastError());
     if (ev) GS_HIP(hipEventRecord(ev[5], st));
+    if (K && cev) GS_HIP(hipEventRecord(cev[11], st));
     return GS_OK;
 }
 
-static int32_t bake_impl(gs_renderer* r, const gs_import_formats* f, gs_asset** out, uint32_t* alive, float bounds_min[3], float bounds_max[3], Event* ev = nullptr) {
+static int32_t bake_impl(gs_renderer* r, const gs_import_formats* f, gs_asset** out, uint32_t* alive, float bounds_min[3], float bounds_max[3], Event* ev = nullptr,
+                         const hipEvent_t* cev = nullptr) {
     if (out) *out = nullptr;
     if (!r || !f || !out || !alive) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
     if (r->laneOf) return fail(GS_ERR_INVALID_ARGUMENT, "a lane holds no edit state: bake its owner");
@@ -242,7 +310,6 @@ static int32_t bake_impl(gs_renderer* r, const gs_import_formats* f, gs_asset** 
     if (f->linearize != 0) return fail(GS_ERR_INVALID_ARGUMENT, "bake: linearize must be 0 (the renderer's data is linear)");
     if (f->morton > 1) return fail(GS_ERR_INVALID_ARGUMENT, "bake: morton must be 0 or 1");
     if (f->color_format == GS_COLOR_BC7) return fail(GS_ERR_INVALID_ARGUMENT, "bake: a BC7 colour target is not supported");
-    if (f->sh_format > GS_SH_NORM6) return fail(GS_ERR_INVALID_ARGUMENT, "bake: a Cluster* SH target is not supported");
     if (r->n == 0u) return fail(GS_ERR_INVALID_ARGUMENT, "bake: no alive splat");
     GS_HIP(hipSetDevice(r->ctx->device));
     // after everything already enqueued, the lanes' frames included: the sort below assumes its workgroups have the GPU to themselves the way the
@@ -265,7 +332,7 @@ static int32_t bake_impl(gs_renderer* r, const gs_import_formats* f, gs_asset** 
     }
     if (total == 0u) return fail(GS_ERR_INVALID_ARGUMENT, "bake: no alive splat");
     uint64_t need[5];
-    GS_TRY(gs_import_blob_sizes(total, f, need));
+    GS_TRY(gs_import_blob_sizes(total, f, need));               // (a Cluster* SH target needs more alive splats than table entries: the importer's rule)
     // the new asset: every blob padded like an owned upload's (the decoders' trailing-dword reads) and zero-filled, as the importer's are
     gs_asset* a = new (std::nothrow) gs_asset();
     if (!a) return fail(GS_ERR_OUT_OF_MEMORY, "host allocation");
@@ -280,23 +347,25 @@ static int32_t bake_impl(gs_renderer* r, const gs_import_formats* f, gs_asset** 
         if (e != hipSuccess) rc = fail_hip(e, "bake: allocate blob", __FILE__, __LINE__);
     }
     float hostBounds[6] = { 0, 0, 0, 0, 0, 0 };
-    uint32_t sortError = 0;
+    uint32_t sortError = 0, clusterSortError = 0;
     if (rc == GS_OK) {
         BakeDst d;
         d.pos = (uint8_t*)a->blobs[0]; d.other = (uint8_t*)a->blobs[1]; d.color = (uint8_t*)a->blobs[2]; d.sh = (uint8_t*)a->blobs[3]; d.chunk = (uint8_t*)a->blobs[4];
         d.n = total;
         d.f = { f->pos_format, f->scale_format, f->color_format, f->sh_format, need[4] != 0 ? 1u : 0u };
-        rc = bake_enqueue(r, f, run, chunks, total, d, ev);
+        d.shIndex = nullptr;
+        rc = bake_enqueue(r, f, run, chunks, total, d, ev, cev);
         hipError_t he = hipSuccess;
         if (rc == GS_OK) he = hipMemcpyAsync(hostBounds, run.bounds.get(), sizeof(hostBounds), hipMemcpyDeviceToHost, st);
         if (rc == GS_OK && he == hipSuccess && f->morton) he = hipMemcpyAsync(&sortError, &run.control.get()->error, 4, hipMemcpyDeviceToHost, st);
+        if (rc == GS_OK && he == hipSuccess && f->sh_format > GS_SH_NORM6) he = hipMemcpyAsync(&clusterSortError, run.cluster.error.get(), 4, hipMemcpyDeviceToHost, st);
         if (rc == GS_OK && he != hipSuccess) rc = fail_hip(he, "bake: read back", __FILE__, __LINE__);
     }
     {
         const hipError_t hs = hipStreamSynchronize(st);            // whatever failed: nothing in flight outlives the transient buffers or the asset
         if (rc == GS_OK && hs != hipSuccess) rc = fail_hip(hs, "bake", __FILE__, __LINE__);
     }
-    if (rc == GS_OK && sortError) rc = fail(GS_ERR_SORT_TIMEOUT, "bake: a bounded look-back spin expired");
+    if (rc == GS_OK && (sortError | clusterSortError)) rc = fail(GS_ERR_SORT_TIMEOUT, "bake: a bounded look-back spin expired");
     if (rc != GS_OK) { (void)gs_asset_destroy(a); return rc; }
     gsm::AssetView& v = a->view;
     v.pos = (const uint8_t*)a->blobs[0]; v.other = (const uint8_t*)a->blobs[1]; v.color = (const uint8_t*)a->blobs[2]; v.sh = (const uint8_t*)a->blobs[3];
@@ -348,6 +417,25 @@ __attribute__((visibility("default"))) int32_t gs_bake_stage_times_for_scripts(g
     GS_TRY(bake_impl(r, formats, &a, alive, nullptr, nullptr, ev));
     (void)gs_asset_destroy(a);
     for (int k = 0; k < 4; ++k) GS_HIP(hipEventElapsedTime(&ms[k], ev[k == 0 ? 0 : k + 1], ev[k == 0 ? 1 : k + 2]));
+    return GS_OK;
+}
+
+// The same for a Cluster* SH target, for scripts/bake_cluster_timing.py: ms[0] = the SH rows (+ the gathers of the seeds and the subset),
+// ms[1 + 2 p] / ms[2 + 2 p] = the assignment / the mean update (sort included) of Lloyd pass p = 0..3, ms[9] = the final assignment, ms[10] = the
+// table + the encode, ms[11] = everything before the SH rows.
+__attribute__((visibility("default"))) int32_t gs_bake_cluster_stage_times_for_scripts(gs_renderer* r, const gs_import_formats* formats, float ms[12], uint32_t* alive) {
+    if (!r || !formats || !ms || !alive) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
+    if (formats->sh_format <= GS_SH_NORM6 || formats->sh_format > 8u) return fail(GS_ERR_INVALID_ARGUMENT, "not a Cluster* SH target");
+    GS_HIP(hipSetDevice(r->ctx->device));
+    Event ev[6], cevOwned[12];
+    hipEvent_t cev[12];
+    for (Event& e : ev) GS_HIP(e.create(hipEventDefault));
+    for (int k = 0; k < 12; ++k) { GS_HIP(cevOwned[k].create(hipEventDefault)); cev[k] = cevOwned[k]; }
+    gs_asset* a = nullptr;
+    GS_TRY(bake_impl(r, formats, &a, alive, nullptr, nullptr, ev, cev));
+    (void)gs_asset_destroy(a);
+    for (int k = 0; k < 11; ++k) GS_HIP(hipEventElapsedTime(&ms[k], cev[k], cev[k + 1]));
+    GS_HIP(hipEventElapsedTime(&ms[11], ev[0], cev[0]));
     return GS_OK;
 }
 

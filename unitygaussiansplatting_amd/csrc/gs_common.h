@@ -491,4 +491,15 @@ __device__ __forceinline__ bool export_alive(const gsm::AssetView& a, const gsm:
 }
 // export_count_kernel + export_scan_kernel on st: counts[c] = alive splats of chunk c, base[0 .. chunks] = their exclusive prefix and the total
 int32_t enqueue_alive_counts(hipStream_t st, const gsm::AssetView& a, const gsm::EditView& e, uint32_t chunks, uint32_t* counts, uint32_t* base);
+// the Cluster* SH palette on device pointers (gs_cluster.hip): what one run of the Lloyd loop holds besides the points, the means and the indices
+struct ClusterRun {
+    DevBuf<float> sub;                      // the stride-sampled training subset (only when n > 200,000)
+    DevBuf<double> c2;
+    DevBuf<uint32_t> keys, pts, range;      // (cluster, point) pairs of the subset and, per cluster, where its run of the sorted pairs starts / ends
+    SortState sort;
+    DevBuf<SortControl> control;            // zeroed before every sort, its error word included:
+    DevBuf<uint32_t> error;                 // != 0 after the loop: the look-back spin of ANY of its sorts expired (kept across the passes)
+};
+int32_t cluster_run_alloc(gs_context* ctx, ClusterRun& run, uint64_t n, uint32_t K);
+int32_t enqueue_cluster_shs(gs_context* ctx, ClusterRun& run, const float* x, uint64_t n, uint32_t K, float* means, uint32_t* index, const hipEvent_t* ev);
 } // namespace gs

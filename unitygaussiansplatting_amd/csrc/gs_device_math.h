@@ -1533,6 +1533,28 @@ GS_HD void BakeEmitSH(const float* sh, uint32_t fmt, uint32_t* w) {
             w[j >> 1] |= ((BakeQ(sh[3 * j], 31.5f) | (BakeQ(sh[3 * j + 1], 63.5f) << 5) | (BakeQ(sh[3 * j + 2], 31.5f) << 11)) & 0xffffu) << ((j & 1) * 16);
     }
 }
+// the `other` record (:776-805): the rotation word, the scale, and in an asset with a Cluster* SH table the u16 index of the splat's table entry
+// right behind the scale (:797-801).  w: 5 words; returns the bytes used: 4 + vecStride(scaleFmt), + 2 when clustered = 8, 10, 12 or 18
+GS_HD bool shIsClustered(uint32_t shFormat) { return shFormat > 3u; }
+// entries of the SH table: GS_SH_CLUSTER64K = 4 ... GS_SH_CLUSTER4K = 8; 0 for every other value (the importer's and the bake's one mapping)
+GS_HD uint32_t shClusterCount(uint32_t shFormat) { return shFormat >= 4u && shFormat <= 8u ? 65536u >> (shFormat - 4u) : 0u; }
+GS_HD uint32_t BakeEmitOther(uint32_t rot, const V3& scale, uint32_t scaleFmt, bool clustered, uint32_t shIndex, uint32_t* w) {
+    w[0] = rot; w[4] = 0u;
+    BakeEmitVec(scale, scaleFmt, w + 1);
+    const uint32_t at = 4u + vecStride(scaleFmt);                  // even: the halfword at byte `at` is the low or the high half of word at / 4
+    if (!clustered) return at;
+    const uint32_t sh = (at & 2u) * 8u;
+    w[at >> 2] = (w[at >> 2] & ~(0xffffu << sh)) | ((shIndex & 0xffffu) << sh);
+    return at + 2u;
+}
+// one entry of the Cluster* SH table (ConvertSHClustersJob :443-474, SHTableItemFloat16): the 45 floats of a mean as fp16, the Float16 SH item's
+// rounding, and 3 zero halfwords.  w: 24 words = 96 bytes
+GS_HD void BakeEmitSHTableItem(const float* mean, uint32_t* w) {
+#pragma unroll
+    for (int k = 0; k < 24; ++k) w[k] = 0u;
+#pragma unroll
+    for (int k = 0; k < 45; ++k) w[k >> 1] |= f32tof16(mean[k]) << ((k & 1) * 16);
+}
 
 // Morton code of a position inside the bounds of all splats (:362-429; MortonEncode3, GaussianUtils.cs:81-95): 21 bits per axis, z highest.  A
 // component whose product is NaN -- a degenerate axis, max == min: 0 x inf -- is 0 by the test: the conversion of a NaN is undefined.
@@ -1556,12 +1578,13 @@ GS_HD uint64_t BakeMortonCode(const V3& p, const float* mn, const float* mx) {
 }
 
 // One destination chunk on one thread: the records of its cnt <= 256 splats (already linear) to the bytes of the five blobs at splat index
-// first + k -- what the kernel's workgroup does with one lane per splat, and what the host harness of the tests runs as it stands.
+// first + k -- what the kernel's workgroup does with one lane per splat, and what the host harness of the tests runs as it stands.  A Cluster* SH
+// target (shIndex: the table index of every record, in destination order) writes the index into `other` and no SH item: the table is the caller's.
 GS_HD void BakeStoreBytes(uint8_t* dst, const uint32_t* w, uint32_t bytes) {
     for (uint32_t k = 0; k < bytes; ++k) dst[k] = (uint8_t)(w[k >> 2] >> ((k & 3u) * 8u));
 }
 GS_HD void BakeEncodeChunkSerial(BakeRec* rec, uint32_t cnt, uint32_t first, const BakeFormats& f, uint8_t* pos, uint8_t* other, uint8_t* color,
-                                 uint8_t* sh, uint8_t* chunk) {
+                                 uint8_t* sh, uint8_t* chunk, const uint32_t* shIndex = nullptr) {
     BakeBounds b;
     if (f.chunked) {
         BakeBoundsEmpty(b);
@@ -1571,7 +1594,8 @@ GS_HD void BakeEncodeChunkSerial(BakeRec* rec, uint32_t cnt, uint32_t first, con
         BakeChunkWords(b, w);
         BakeStoreBytes(chunk + (uint64_t)(first >> 8) * 64u, w, 64u);
     }
-    const uint32_t posSz = vecStride(f.pos), othSz = 4u + vecStride(f.scale), colSz = f.color == 0 ? 16u : (f.color == 1 ? 8u : 4u), shSz = shStrideOf(f.sh);
+    const bool clustered = shIsClustered(f.sh);
+    const uint32_t posSz = vecStride(f.pos), colSz = f.color == 0 ? 16u : (f.color == 1 ? 8u : 4u), shSz = shStrideOf(f.sh);
     for (uint32_t k = 0; k < cnt; ++k) {
         BakeRec& o = rec[k];
         if (f.chunked) BakeNormalise(o, b);
@@ -1579,13 +1603,13 @@ GS_HD void BakeEncodeChunkSerial(BakeRec* rec, uint32_t cnt, uint32_t first, con
         uint32_t w[48];
         BakeEmitVec(o.pos, f.pos, w);
         BakeStoreBytes(pos + i * posSz, w, posSz);
-        w[0] = o.rot;
-        BakeEmitVec(o.scale, f.scale, w + 1);
+        const uint32_t othSz = BakeEmitOther(o.rot, o.scale, f.scale, clustered, clustered ? shIndex[i] : 0u, w);
         BakeStoreBytes(other + i * othSz, w, othSz);
         uint32_t px, py;
         SplatIndexToPixelIndex((uint32_t)i, px, py);
         BakeEmitColor(o.col, f.color, w);
         BakeStoreBytes(color + ((uint64_t)py * 2048u + px) * colSz, w, colSz);
+        if (clustered) continue;
         BakeEmitSH(o.sh, f.sh, w);
         BakeStoreBytes(sh + i * shSz, w, shSz);
     }

@@ -9,6 +9,7 @@
 //                                       :776-805  other data, :863-932 colour texture (16x16 Morton tiles), :934-1037 SH items
 // The one stage that can also run on a GPU is the nearest-mean assignment of the Cluster* SH palette (gs_cluster.hip, through
 // gs_import_encode_on / gs_import_assign_clusters with a context): the same operations in the same order, the same bytes.
+// gs_import_cluster_shs exposes cluster_shs below as it is, and with a context runs the whole of it on the GPU instead (gs_cluster.hip).
 // Arithmetic is plain IEEE fp32, one rounding per operation (-ffp-contract=off), and the two transcendental steps are
 // written out (exp as Cephes-style range reduction + polynomial, x^(1/8) as three correctly rounded square roots) so that
 // the bytes are a function of this source only: unitygaussiansplatting_amd/creator.py performs the same operations with
@@ -32,10 +33,12 @@
 #include <zlib.h>
 
 #include "../../include/gsplat_c.h"
+#include "gs_device_math.h"     // gsm::shClusterCount: the one format -> table size mapping, shared with the bake
 
 namespace gs {
 int32_t fail(int32_t code, const char* what);
 int32_t assign_clusters_gpu(gs_context* ctx, const float* x, uint64_t n, const float* means, uint32_t K, uint32_t* out);   // gs_cluster.hip
+int32_t cluster_shs_gpu(gs_context* ctx, const float* x, uint64_t n, uint32_t K, float* means_out, uint32_t* index_out);         // gs_cluster.hip
 }
 
 namespace {
@@ -152,7 +155,7 @@ inline void texel_of(uint32_t idx, uint32_t& px, uint32_t& py) {       // Gaussi
 uint32_t vec_size(uint32_t f) { return f == 0 ? 12u : (f == 1 ? 6u : (f == 2 ? 4u : 2u)); }
 uint32_t color_size(uint32_t f) { return f == 0 ? 16u : (f == 1 ? 8u : (f == 2 ? 4u : 1u)); }            // BC7: 16-byte blocks of 4x4 texels
 uint32_t sh_size(uint32_t f) { return f == 0 ? 192u : (f == 2 ? 60u : (f == 3 ? 32u : 96u)); }          // Float16 and the Cluster* table items: 96 B
-uint32_t sh_clusters(uint32_t f) { return f == 4 ? 65536u : (f == 5 ? 32768u : (f == 6 ? 16384u : (f == 7 ? 8192u : (f == 8 ? 4096u : 0u)))); }
+uint32_t sh_clusters(uint32_t f) { return gsm::shClusterCount(f); }
 uint64_t pad8(uint64_t n) { return (n + 7) / 8 * 8; }
 
 void emit_vec(const float v[3], uint8_t* out, uint32_t fmt) {           // EmitEncodedVector :727-758 (saturating)
@@ -331,6 +334,22 @@ int32_t gs_import_encode(const gs_import_input* in, const gs_import_formats* f, 
 int32_t gs_import_assign_clusters(gs_context* ctx, const float* x, uint64_t n, const float* means, uint32_t k, uint32_t* index_out) {
     if (!x || !means || !index_out || n == 0 || k == 0) return gs::fail(GS_ERR_INVALID_ARGUMENT, "null argument / no points / no means");
     try { return assign_clusters_on(ctx, x, (size_t)n, means, k, index_out); }
+    catch (const std::bad_alloc&) { return gs::fail(GS_ERR_OUT_OF_MEMORY, "host allocation"); }
+    catch (...) { return gs::fail(GS_ERR_INVALID_ARGUMENT, "unexpected failure in the importer"); }
+}
+
+int32_t gs_import_cluster_shs(gs_context* ctx, const float* x, uint64_t n, uint32_t k, float* means_out, uint32_t* index_out) {
+    if (!x || !means_out || !index_out || n == 0 || k == 0 || k > 65536u) return gs::fail(GS_ERR_INVALID_ARGUMENT, "null argument / no points / k outside [1, 65536]");
+    if (ctx) return gs::cluster_shs_gpu(ctx, x, n, k, means_out, index_out);      // the whole loop on the context's GPU: nothing of it runs here
+    try {
+        std::vector<float> means;
+        std::vector<uint32_t> index;
+        const int32_t rc = cluster_shs(nullptr, x, (size_t)n, k, means, index);
+        if (rc != GS_OK) return rc;
+        memcpy(means_out, means.data(), means.size() * 4);
+        memcpy(index_out, index.data(), index.size() * 4);
+        return GS_OK;
+    }
     catch (const std::bad_alloc&) { return gs::fail(GS_ERR_OUT_OF_MEMORY, "host allocation"); }
     catch (...) { return gs::fail(GS_ERR_INVALID_ARGUMENT, "unexpected failure in the importer"); }
 }

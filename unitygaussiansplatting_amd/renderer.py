@@ -711,7 +711,9 @@ class GaussianSplatRenderer:
     def EditBakeAsset(self, quality="Medium", *, formatPos=None, formatScale=None, formatColor=None, formatSH=None, morton=True) -> GpuAsset:
         """The alive splats (not deleted, not cut) of the renderer as it is now -- edits, private blobs and all -- as a new device-resident asset in
         the formats of `quality` (or the ones given), Morton-reordered and chunked like an imported one: the bytes the importer makes of
-        ExportAlive's splats, without leaving the GPU.  The renderer itself is left as it is.  BC7 and Cluster* targets are refused.  Blocks."""
+        ExportAlive's splats, without leaving the GPU.  The renderer itself is left as it is.  A Cluster* SH target ("Low"; the importer's palette
+        of the alive splats' SH, computed on the GPU) needs more alive splats than table entries, as an import does.  Still refused: a BC7 colour
+        target, hence the preset "VeryLow" as a whole -- EditBakeAsset("VeryLow", formatColor=ColorFormat.Norm8x4) works.  Blocks."""
         self.UpdateCutoutsBuffer()
         fmt = self.BakeFormats(quality, formatPos, formatScale, formatColor, formatSH, morton)
         h, alive = C.c_void_p(), C.c_uint32(0)
