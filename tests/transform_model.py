@@ -182,6 +182,15 @@ class TransformModel(EM.EditModel):
         if self._cut_args is not None:
             super().set_cutouts(*self._cut_args)
 
+    def set_asset(self, asset) -> None:
+        """the renderer's data replaced as a whole at the same N (EditCopySplatsInto wrote into it; tests/session_model.py): the bit buffers, the
+        mouse-down copies and the cutouts stay as they are"""
+        assert asset.splatCount == self.n
+        self.asset = asset
+        self.pos_blob = np.array(asset.posData, np.uint8, copy=True)
+        self.other_blob = np.array(asset.otherData, np.uint8, copy=True)
+        self._moved()
+
     # -- the calls ----------------------------------------------------------------------------------------------------------------------------
     def store_pos(self) -> None:                                   # EditStorePosMouseDown
         self.pos_stored = True
