@@ -76,8 +76,3 @@ def crafted_decode(n: int = 6000, big: int = 2500, small: int = 500, seed: int =
     dec[rows[:big], 14:59] = dec[rows[0], 14:59]
     dec[rows[big:big + small], 14:59] = dec[rows[big], 14:59]
     return dec
-
-
-def same_bits(a, b) -> bool:
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))

@@ -1,11 +1,25 @@
 """Shared helpers for the tests: small deterministic scenes and cameras."""
 from __future__ import annotations
 
+import ctypes as C
 import functools
 
 import numpy as np
 
 from unitygaussiansplatting_amd import camera, creator, scenes
+
+PRESETS = ["VeryLow", "Low", "Medium", "High", "VeryHigh"]
+
+
+def _p(a):
+    """the address of an array's data for a ctypes call; None stays NULL"""
+    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def same_bits(a, b, dtype=np.float32) -> bool:
+    """the same shape and the same bits, both read as `dtype`; dtype=None: as they are, and then of the same dtype too"""
+    a, b = np.ascontiguousarray(a, dtype), np.ascontiguousarray(b, dtype)
+    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
 
 
 @functools.lru_cache(maxsize=16)

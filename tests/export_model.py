@@ -13,8 +13,9 @@ from __future__ import annotations
 import numpy as np
 
 import edit_model as EM
+from transform_model import mul_point, quat_mul          # QuatMul and mul(M, float4(p, 1)) of GaussianSplatting.hlsl: one restatement for every model
 from unitygaussiansplatting_amd import creator
-from unitygaussiansplatting_amd.creator import LogDet, fma32
+from unitygaussiansplatting_amd.creator import LogDet
 
 f32 = np.float32
 def sh_rot_matrix(o2w, dtype=f32):
@@ -100,24 +101,6 @@ def rotate_sh(sh, bands, dtype=f32):
                     acc = (acc + (sh[:, first + j, :] * mat[k][j]).astype(dtype)).astype(dtype)
                 out[:, first + k, :] = acc
     return out
-
-
-def quat_mul(a, b):
-    """QuatMul (GaussianSplatting.hlsl:19-22), xyzw, a: one quaternion, b: [N, 4]"""
-    ax, ay, az, aw = (f32(v) for v in a)
-    bx, by, bz, bw = (b[:, k].astype(f32) for k in range(4))
-    x = (aw * bx + (ax * bw + ay * bz)) - az * by
-    y = (aw * by + (ay * bw + az * bx)) - ax * bz
-    z = (aw * bz + (az * bw + ax * by)) - ay * bx
-    w = (aw * bw + -(ax * bx + ay * by)) - az * bz
-    return np.stack([x, y, z, w], axis=1).astype(f32)
-
-
-def mul_point(o2w, pos):
-    """rows 0..2 of mul(M, float4(pos, 1)) as calc_view forms them: fmaf(m2, z, fmaf(m1, y, fmaf(m0, x, m3)))"""
-    m = np.asarray(o2w, f32).reshape(4, 4)
-    x, y, z = pos[:, 0], pos[:, 1], pos[:, 2]
-    return np.stack([fma32(m[r, 2], z, fma32(m[r, 1], y, fma32(m[r, 0], x, m[r, 3]))) for r in range(3)], axis=1)
 
 
 def export_records(dec, cut, transform=None):

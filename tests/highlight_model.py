@@ -6,30 +6,23 @@ blends like gso_blend_f16 (mode 0) or in fp32 (mode 1).  Test infrastructure onl
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 import oracle_lib as O
+from common import _p
+from harness import build_harness
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 SELECTED_ALPHA_HALF = 0xBC00           # -1.0: the mark calc_view leaves in a selected splat's raster record
 
 
 def build(tmpdir) -> C.CDLL:
-    so = os.path.join(str(tmpdir), "libhl.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-o", so, os.path.join(HERE, "highlight_host_harness.cpp")])
-    L = C.CDLL(so)
+    L = C.CDLL(build_harness(tmpdir, "highlight_host_harness.cpp"))
     L.hl_half_of.restype = C.c_uint16
     L.hl_half_of.argtypes = [C.c_double]
     L.hl_native_e.restype = C.c_float
     L.hl_fragment_from.argtypes = [C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int32]
     return L
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
 def bits_of(mask: np.ndarray) -> np.ndarray:

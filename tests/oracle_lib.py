@@ -8,6 +8,7 @@ import subprocess
 
 import numpy as np
 
+from common import _p
 from unitygaussiansplatting_amd._abi import VIEW_DTYPE, gs_asset_desc, gs_frame_params, make_asset_desc
 
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -38,10 +39,6 @@ def lib():
         _lib.gso_blend_f16.argtypes = [C.c_float, C.c_float, C.c_float]
         _lib.gso_num_threads.restype = C.c_int32
     return _lib
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 # The compositor tile the (tile, splat) pair count refers to is a performance parameter of the build under test (16x16, 32x16 or

@@ -13,6 +13,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from common import _p
 from unitygaussiansplatting_amd import asset as A
 from unitygaussiansplatting_amd import bc7
 from unitygaussiansplatting_amd._abi import VIEW_DTYPE, gs_frame_params, make_asset_desc
@@ -49,10 +50,6 @@ def lib(which: str):
         L.gsr_cs_encode_quat_norm10.restype = C.c_uint32
         _libs[which] = L
     return _libs[which]
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 # The oracle's canonical arithmetic is BIT-equal to the `fused` build as g++ 11.4 contracts the shader text: a

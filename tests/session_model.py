@@ -1,6 +1,6 @@
 """One model of an edit session (helper, not a test): the models of the edit features composed -- edit_model / transform_model (selection, deletion,
 the three transforms), copy_model (resize and copy-into), export_model (the export records) and bake_model / the Cluster yardstick of
-test_gpu_bake_cluster.py (the bake) -- under the rules DESIGN.md sections 4.7-4.10 state about what one feature leaves for another.  No arithmetic of its
+tests/gpu_rig.py (the bake) -- under the rules DESIGN.md sections 4.7-4.10 state about what one feature leaves for another.  No arithmetic of its
 own: every number comes out of one of those models.
 
 A session holds up to three renderers' worth of state: T, the target (VeryHigh, 300 splats, under DST_TR); S, a source (one preset per seed, under
@@ -25,10 +25,8 @@ import edit_model as EM
 import export_model as XM
 import oracle_lib as O
 import transform_model as TM
+from builders import CAMS, CLUSTER4K, DST_TR, SRC_TR, TOOL
 from common import default_camera, small_asset
-from test_gpu_bake_cluster import CLUSTER4K                        # (these three modules import without a GPU: only their tests need one)
-from test_gpu_copy import CAMS, DST_TR, SRC_TR
-from test_gpu_transform import TOOL
 from unitygaussiansplatting_amd import _abi, asset as A, camera
 from unitygaussiansplatting_amd.cutout import shader_data_array
 from unitygaussiansplatting_amd.renderer import GaussianSplatRenderer, SortMode

@@ -4,8 +4,6 @@ SH item) with the palette of gs_import_cluster_shs' host route in between -- the
 tests/bake_model.py, the native importer, byte for byte; and the harness as a stand-alone program under the host sanitizers."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,20 +11,17 @@ import pytest
 import bake_model as BM
 import copy_model as CM
 from common import small_asset
+from harness import build_harness, run_under_sanitizers
 from unitygaussiansplatting_amd import _abi, _lib, asset as A, creator
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 f32 = np.float32
-FLAGS = ["-std=c++17", "-ffp-contract=off", "-fno-fast-math"]
 N = 4500
 VF, CF, SF = A.VectorFormat, A.ColorFormat, A.SHFormat
 
 
 @pytest.fixture(scope="module")
 def bch(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("bch") / "libbch.so")
-    subprocess.check_call(["g++", "-O2", "-fPIC", "-shared"] + FLAGS + ["-o", so, os.path.join(HERE, "bake_cluster_host_harness.cpp")])
-    lib = C.CDLL(so)
+    lib = C.CDLL(build_harness(tmp_path_factory.mktemp("bch"), "bake_cluster_host_harness.cpp"))
     lib.bch_other.restype = C.c_uint32
     return lib
 
@@ -105,8 +100,5 @@ def test_other_record_words(bch):
 
 
 def test_stand_alone_harness_runs_clean_under_the_host_sanitizers(tmp_path):
-    exe = str(tmp_path / "bake_cluster_harness")
-    subprocess.check_call(["g++", "-O1", "-g", "-DBAKE_CLUSTER_HARNESS_MAIN", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] + FLAGS +
-                          ["-o", exe, os.path.join(HERE, "bake_cluster_host_harness.cpp")])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    out = run_under_sanitizers(tmp_path, "bake_cluster_host_harness.cpp", "BAKE_CLUSTER_HARNESS_MAIN")
     assert out.returncode == 0 and "bake cluster harness ok" in out.stdout, (out.stdout, out.stderr[-2000:])

@@ -4,37 +4,23 @@ yardstick of tests/bake_model.py -- the native importer with linearize = 0 fed w
 sizes 1 / 255 / 256, sources of all five presets; the Morton key against the importer's order, duplicates included; the premise of the degenerate
 axis; and the harness as a stand-alone program under the host sanitizers."""
 import ctypes as C
-import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import bake_model as BM
-import copy_model as CM
-from common import small_asset
+from builders import decode_of
+from common import PRESETS, small_asset
+from harness import build_harness, run_under_sanitizers
 from unitygaussiansplatting_amd import _abi, _lib, asset as A, creator, renderer
 from unitygaussiansplatting_amd.renderer import GaussianSplatRenderer, GpuAsset
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 f32 = np.float32
-PRESETS = ["VeryLow", "Low", "Medium", "High", "VeryHigh"]
-FLAGS = ["-std=c++17", "-ffp-contract=off", "-fno-fast-math"]
 
 
 @pytest.fixture(scope="module")
 def bh(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("bh") / "libbh.so")
-    subprocess.check_call(["g++", "-O2", "-fPIC", "-shared"] + FLAGS + ["-o", so, os.path.join(HERE, "bake_host_harness.cpp")])
-    return C.CDLL(so)
-
-
-@functools.lru_cache(maxsize=None)
-def decode_of(n: int, quality: str) -> np.ndarray:
-    dec = CM.decode(small_asset(n, 5, quality))
-    dec.setflags(write=False)
-    return dec
+    return C.CDLL(build_harness(tmp_path_factory.mktemp("bh"), "bake_host_harness.cpp"))
 
 
 def host_bake(bh, asset, src, formats, morton=True) -> A.GaussianSplatAsset:
@@ -181,8 +167,5 @@ def test_premise_degenerate_axis(bh):
 
 # ---- 4. the harness as a stand-alone program under the host sanitizers ---------------------------------------------------------------------------
 def test_stand_alone_harness_runs_clean_under_the_host_sanitizers(tmp_path):
-    exe = str(tmp_path / "bake_harness")
-    subprocess.check_call(["g++", "-O1", "-g", "-DBAKE_HARNESS_MAIN", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] + FLAGS +
-                          ["-o", exe, os.path.join(HERE, "bake_host_harness.cpp")])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    out = run_under_sanitizers(tmp_path, "bake_host_harness.cpp", "BAKE_HARNESS_MAIN")
     assert out.returncode == 0 and "bake harness ok" in out.stdout, (out.stdout, out.stderr[-2000:])

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import cluster_model as CM
+from common import same_bits
 from unitygaussiansplatting_amd import _abi, _lib, creator
 
 f32 = np.float32
@@ -15,7 +16,7 @@ def check(x, k):
     want_means, want_index, cnt = CM.lloyd(x, k)
     means, index = creator.ClusterSHsNative(x, k)
     assert means.shape == (k, 45) and means.dtype == f32 and index.shape == (len(x),) and index.dtype == np.uint32
-    assert CM.same_bits(means, want_means), np.flatnonzero((means.view(np.uint32) != want_means.view(np.uint32)).any(axis=1))[:8]
+    assert same_bits(means, want_means, dtype=None), np.flatnonzero((means.view(np.uint32) != want_means.view(np.uint32)).any(axis=1))[:8]
     assert np.array_equal(index, want_index)
     return cnt
 
@@ -28,7 +29,7 @@ def test_host_route_equals_the_model(n, k):
 
 def test_host_route_takes_the_training_subset():
     x = CM.random_points(200_001, 7)
-    assert len(CM.subset(x)) == 200_000 and CM.same_bits(CM.subset(x)[-1], x[199_999]) and CM.same_bits(CM.subset(x)[100_000], x[100_000])
+    assert len(CM.subset(x)) == 200_000 and same_bits(CM.subset(x)[-1], x[199_999], dtype=None) and same_bits(CM.subset(x)[100_000], x[100_000], dtype=None)
     check(x, 64)
 
 
@@ -40,7 +41,7 @@ def test_host_route_empty_and_long_clusters():
     assert ((cnt == 0).sum(axis=1) >= 20).all() and (cnt.max(axis=1) >= int(n * 0.4)).all()
     means, _ = creator.ClusterSHsNative(x, k)
     empty = np.flatnonzero((cnt == 0).all(axis=0))
-    assert len(empty) >= 20 and CM.same_bits(means[empty], CM.seeds(x, k)[empty])     # empty in all four passes: still its seed
+    assert len(empty) >= 20 and same_bits(means[empty], CM.seeds(x, k)[empty], dtype=None)     # empty in all four passes: still its seed
 
 
 def test_host_route_crafted_scene():
@@ -64,5 +65,5 @@ def test_argument_validation_without_a_device():
     assert lib.gs_import_cluster_shs(None, px, 4, 65_537, pm, pi) == bad
     assert not means.any() and not index.any()                          # a refusal writes nothing
     assert lib.gs_import_cluster_shs(None, px, 4, 3, pm, pi) == 0
-    assert CM.same_bits(means, CM.lloyd(x, 3)[0])
+    assert same_bits(means, CM.lloyd(x, 3)[0], dtype=None)
     assert lib.gs_abi_version() == 9                                    # an addition to ABI 9

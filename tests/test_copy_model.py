@@ -3,48 +3,28 @@ the host build of gsm::CopySplat (tests/copy_host_harness.cpp) against the numpy
 equal to any NaN -- over every source preset, the identity's known answers, the literal idx / srcIdx split, and the resize bookkeeping."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import copy_model as CM
 import edit_model as EM
-import export_model as XM
 import transform_model as TM
-from common import small_asset
+from builders import DST_TR, SRC_TR, params_of
+from common import PRESETS, _p, small_asset
+from harness import FP, build_harness, run_under_sanitizers
 from unitygaussiansplatting_amd import _abi, _lib, asset as A, camera, creator, renderer
 from unitygaussiansplatting_amd.renderer import GaussianSplatRenderer
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 f32 = np.float32
-PRESETS = ["VeryLow", "Low", "Medium", "High", "VeryHigh"]
-FLAGS = ["-std=c++17", "-ffp-contract=off", "-fno-fast-math"]
-# non-uniform, mirrored in x, rotated: the transform of the export's bake tests, as the source's; the destination sits elsewhere
-SRC_TR = camera.Transform(**XM.BAKE_TRANSFORM)
-DST_TR = camera.Transform(position=(-0.4, 0.1, 0.2), rotation=(0.5, -0.5, 0.5, 0.5), scale=(0.8, 1.25, 2.0))
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 @pytest.fixture(scope="module")
 def ch(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("ch") / "libch.so")
-    subprocess.check_call(["g++", "-O2", "-fPIC", "-shared"] + FLAGS + ["-o", so, os.path.join(HERE, "copy_host_harness.cpp")])
-    L = C.CDLL(so)
+    L = C.CDLL(build_harness(tmp_path_factory.mktemp("ch"), "copy_host_harness.cpp"))
     L.ch_sizes.restype = C.c_uint32
     return L
-
-
-def params_of(transform) -> _abi.gs_copy_params:
-    m, q, s = transform
-    p = _abi.gs_copy_params()
-    p.matrix[0:16] = [float(v) for v in np.asarray(m, f32).reshape(-1)]
-    p.rotation[0:4] = [float(f32(v)) for v in q]
-    p.scale[0:3] = [float(f32(v)) for v in s]
-    return p
 
 
 def host_records(ch, asset, transform=None, first=0, n=None):
@@ -237,10 +217,7 @@ def test_kernel_text_run_thread_for_thread_equals_the_model(tmp_path):
     clamps, count = 0, the SH pad and the texels nobody writes -- all four blobs and the deleted words byte for byte after every call"""
     inc = tmp_path / "kernel_text.inc"
     inc.write_text(kernel_text())
-    so = str(tmp_path / "libemu.so")
-    subprocess.check_call(["g++", "-O1", "-std=c++20", "-fPIC", "-shared", "-pthread", "-ffp-contract=off", "-fno-fast-math", f'-DCOPY_KERNEL_TEXT="{inc}"', "-o", so,
-                           os.path.join(HERE, "copy_kernel_host_emulation.cpp")])
-    L = C.CDLL(so)
+    L = C.CDLL(build_harness(tmp_path, "copy_kernel_host_emulation.cpp", ["-O1", "-std=c++20", "-pthread"] + FP, [f'COPY_KERNEL_TEXT="{inc}"']))
 
     def bits(n):
         flags = np.zeros(n, bool)
@@ -268,8 +245,5 @@ def test_kernel_text_run_thread_for_thread_equals_the_model(tmp_path):
 
 # ---- 6. the harness as a stand-alone program under the host sanitizers --------------------------------------------------------------------
 def test_stand_alone_harness_runs_clean_under_the_host_sanitizers(tmp_path):
-    exe = str(tmp_path / "copy_harness")
-    subprocess.check_call(["g++", "-O1", "-g", "-DCOPY_HARNESS_MAIN", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] + FLAGS +
-                          ["-o", exe, os.path.join(HERE, "copy_host_harness.cpp")])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    out = run_under_sanitizers(tmp_path, "copy_host_harness.cpp", "COPY_HARNESS_MAIN")
     assert out.returncode == 0 and "copy harness ok" in out.stdout, (out.stdout, out.stderr[-2000:])

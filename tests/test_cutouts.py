@@ -3,69 +3,17 @@
 CPU: known-answer tests of the oracle's IsSplatCut against the shader's decision table, and the kernels' arithmetic header
 compiled for the host against the oracle, bit for bit.  GPU (-m gpu): the same through the C-ABI, plus a composite."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import oracle_lib as O
+from builders import CUTOUT_SETS, _decoded_positions, _expected_cut, _margin_ok
 from common import RT_TOL, default_camera, rt_err, small_asset, views_equal
+from harness import hm  # noqa: F401  (the fixture: builds tests/host_math_harness.cpp)
 from unitygaussiansplatting_amd import camera
 from unitygaussiansplatting_amd._abi import VIEW_DTYPE, gs_cutout
-from unitygaussiansplatting_amd.cutout import GaussianCutout, Type, shader_data_array
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def _decoded_positions(orc):
-    return orc.decode_all()[:, 0:3].astype(np.float64)
-
-
-def _expected_cut(pos, cutouts, renderer_matrix):
-    """IsSplatCut written independently in float64 numpy (decision table of SplatUtilities.compute:164-187)."""
-    n = len(pos)
-    decided = np.zeros(n, bool)
-    result = np.zeros(n, bool)
-    final = np.zeros(n, bool)
-    for c in cutouts:
-        if c is None or not c.isActiveAndEnabled:
-            continue
-        m = c.transform.worldToLocalMatrix.astype(np.float64) @ np.asarray(renderer_matrix, np.float64)
-        q = pos @ m[:3, :3].T + m[:3, 3]
-        inside = (q * q).sum(1) <= 1.0 if c.m_Type == Type.Ellipsoid else (np.abs(q) <= 1.0).all(1)
-        take = inside & ~decided
-        result[take] = c.m_Invert
-        decided |= take
-        if not c.m_Invert:
-            final[~decided] = True
-    return np.where(decided, result, final)
-
-
-def _margin_ok(pos, cutouts, renderer_matrix, eps=1e-4):
-    """Splats not within eps of any cutout surface (fp32 vs fp64 may legitimately disagree there)."""
-    ok = np.ones(len(pos), bool)
-    for c in cutouts:
-        if c is None or not c.isActiveAndEnabled:
-            continue
-        m = c.transform.worldToLocalMatrix.astype(np.float64) @ np.asarray(renderer_matrix, np.float64)
-        q = pos @ m[:3, :3].T + m[:3, 3]
-        d = (q * q).sum(1) - 1.0 if c.m_Type == Type.Ellipsoid else np.abs(q).max(1) - 1.0
-        ok &= np.abs(d) > eps
-    return ok
-
-
-CUTOUT_SETS = {
-    "crop_box": [GaussianCutout(Type.Box, False, camera.Transform(position=(0.2, 0.0, -0.1), scale=(1.5, 1.0, 2.0)))],
-    "hole_ellipsoid": [GaussianCutout(Type.Ellipsoid, True, camera.Transform(position=(0.5, 0.3, 0.0), rotation=(0.0, 0.3826834, 0.0, 0.9238795), scale=(1.2, 0.6, 0.9)))],
-    "hole_then_crop": [GaussianCutout(Type.Ellipsoid, True, camera.Transform(scale=(0.8, 0.8, 0.8))),
-                       None,
-                       GaussianCutout(Type.Box, False, camera.Transform(scale=(2.0, 2.0, 2.0))),
-                       GaussianCutout(Type.Box, False, camera.Transform(position=(3, 3, 3)), isActiveAndEnabled=False)],
-    "crop_then_hole": [GaussianCutout(Type.Box, False, camera.Transform(scale=(2.0, 2.0, 2.0))),
-                       GaussianCutout(Type.Ellipsoid, True, camera.Transform(scale=(0.8, 0.8, 0.8)))],
-    "only_null": [None],
-}
+from unitygaussiansplatting_amd.cutout import shader_data_array
 
 
 @pytest.mark.parametrize("name", list(CUTOUT_SETS))
@@ -125,14 +73,6 @@ def test_oracle_deleted_bits():
     assert np.array_equal(v[~deleted].view(np.uint32), base[~deleted].view(np.uint32))
     zero = orc.calc_view(P, deleted_bits=np.zeros_like(bits)).copy()
     assert np.array_equal(zero.view(np.uint32), base.view(np.uint32))
-
-
-@pytest.fixture(scope="module")
-def hm(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("hmc") / "libhm.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-o", so,
-                           os.path.join(HERE, "host_math_harness.cpp")])
-    return C.CDLL(so)
 
 
 @pytest.mark.parametrize("name", ["hole_then_crop", "hole_ellipsoid"])

@@ -10,7 +10,7 @@ import pytest
 
 import oracle_lib as O
 from common import default_camera, small_asset
-from test_cutouts import _decoded_positions, _expected_cut, _margin_ok
+from builders import _decoded_positions, _expected_cut, _margin_ok
 from unitygaussiansplatting_amd import camera
 from unitygaussiansplatting_amd.cutout import GaussianCutout, Type, shader_data_array
 

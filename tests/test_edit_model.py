@@ -2,19 +2,17 @@
 (tests/edit_model.py), the premises of the cases those tests use -- asserted, so that no case passes vacuously -- and the host build of the kernels'
 per-splat arithmetic (csrc/gs_device_math.h through tests/edit_host_harness.cpp) against the model, bit for bit."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import edit_model as EM
 from common import default_camera, small_asset
+from harness import build_harness
 from unitygaussiansplatting_amd import _abi, _lib, camera
 from unitygaussiansplatting_amd.cutout import shader_data_array
 from unitygaussiansplatting_amd.renderer import GaussianSplatRenderer
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 f32 = np.float32
 
 
@@ -146,10 +144,7 @@ def test_every_cutout_list_leaves_a_tenth_on_each_side(n, quality):
 # ---- 4. the host build of the kernels' arithmetic against the model ---------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def eh(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("eh") / "libeh.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-o", so,
-                           os.path.join(HERE, "edit_host_harness.cpp")])
-    return C.CDLL(so)
+    return C.CDLL(build_harness(tmp_path_factory.mktemp("eh"), "edit_host_harness.cpp"))
 
 
 @pytest.mark.parametrize("quality", ["Medium", "VeryHigh"])

@@ -2,8 +2,6 @@
 documented bound of the exact logarithm), the decode premise (the reference's own LoadSplatData under the model = the host build of ExportSplat, bit
 for bit), the SH rotation (host build = model in float32; model in float64 = the defining property of a rotation) and the premises of the GPU cases."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,26 +9,18 @@ import pytest
 import edit_model as EM
 import export_model as XM
 import ref_lib
-from common import small_asset
+from common import PRESETS, _p, same_bits, small_asset
+from harness import build_harness
 from unitygaussiansplatting_amd import _abi, _lib, camera, creator
 from unitygaussiansplatting_amd.cutout import shader_data_array
 from unitygaussiansplatting_amd.renderer import GaussianSplatRenderer
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 f32 = np.float32
-PRESETS = ["VeryLow", "Low", "Medium", "High", "VeryHigh"]
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 @pytest.fixture(scope="module")
 def xh(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("xh") / "libxh.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-o", so,
-                           os.path.join(HERE, "export_host_harness.cpp")])
-    L = C.CDLL(so)
+    L = C.CDLL(build_harness(tmp_path_factory.mktemp("xh"), "export_host_harness.cpp"))
     L.xh_sizes.restype = C.c_uint32
     return L
 
@@ -50,10 +40,6 @@ def host_records(xh, asset, tr=None, bake=False, cuts=None) -> np.ndarray:
     out = np.zeros((asset.splatCount, 62), f32)
     xh.xh_export(C.byref(desc), C.byref(p), arr, C.c_uint32(cnt), _p(out))
     return out
-
-
-def same_bits(a, b) -> bool:
-    return np.array_equal(np.ascontiguousarray(a, f32).view(np.uint32), np.ascontiguousarray(b, f32).view(np.uint32))
 
 
 # ---- 1. the ABI ---------------------------------------------------------------------------------------------------------------------------

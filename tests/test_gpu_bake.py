@@ -8,7 +8,6 @@ merges the two INTO a small VeryHigh one; and a lane is an object the C ABI neve
 library.  The coplanar case orders the yardstick's input by the model's key with the degenerate component forced to 0 and imports it with morton = 0:
 the form that does not lean on the host's conversion of a NaN (tests/test_bake_model.py::test_premise_degenerate_axis shows the two agree here)."""
 import ctypes as C
-import functools
 
 import numpy as np
 import pytest
@@ -19,68 +18,15 @@ import crafted
 import edit_model as EM
 import export_model as XM
 import transform_model as TM
-from common import default_camera, small_asset
+from builders import decode_of
+from common import PRESETS, default_camera, small_asset
+from gpu_rig import BAD, CAM, bake, check_bake, frame_of, keep_only, pinned_renderer as make_renderer, same_frame
 from unitygaussiansplatting_amd import _abi, _lib, asset as A, camera
 from unitygaussiansplatting_amd.cutout import GaussianCutout, Type
 from unitygaussiansplatting_amd.renderer import GaussianSplatRenderer, MergeSplatObjects, RenderTarget, SortMode
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
-PRESETS = ["VeryLow", "Low", "Medium", "High", "VeryHigh"]
-BAD = _abi.GS_ERR_INVALID_ARGUMENT
-CAM = default_camera(az=25.0)
-
-
-@functools.lru_cache(maxsize=None)
-def decode_of(n: int, quality: str, seed: int = 5) -> np.ndarray:
-    """one oracle decode per source asset, shared by the tests that use it and left unchanged"""
-    dec = CM.decode(small_asset(n, seed, quality))
-    dec.setflags(write=False)
-    return dec
-
-
-def make_renderer(ctx, asset, tr=None, mode=SortMode.Full, frames=1) -> GaussianSplatRenderer:
-    r = GaussianSplatRenderer(ctx, asset, tr)
-    r.sortMode = mode
-    r.framesInFlight = frames
-    r.CreateResourcesForAsset()
-    return r
-
-
-def bake(r, formats, morton=True):
-    fp, fs, fc, fsh = formats
-    return r.EditBakeAsset(formatPos=fp, formatScale=fs, formatColor=fc, formatSH=fsh, morton=morton)
-
-
-def check_bake(r, dec_alive, formats, what, morton=True, want=None):
-    """one bake against the yardstick; returns the yardstick asset"""
-    want = BM.yardstick(dec_alive, formats, morton) if want is None else want
-    g = bake(r, formats, morton)
-    try:
-        assert g.splatCount == len(dec_alive), (what, g.splatCount, len(dec_alive))
-        BM.assert_same_asset(g.Download(), want, what)
-    finally:
-        g.Dispose()
-    return want
-
-
-def keep_only(r, n: int, src: np.ndarray) -> None:
-    """deleted bits that leave exactly the splats `src` alive"""
-    flags = np.ones(n, bool)
-    flags[src] = False
-    r.SetDeletedBits(EM.pack_bits(flags, (n + 31) // 32))
-
-
-def frame_of(r, ctx, cam=CAM):
-    rt = RenderTarget(ctx, cam.pixelWidth, cam.pixelHeight)
-    r.SortPoints(cam); r.CalcViewData(cam); rt.Clear(); r.Draw(cam, rt)
-    out = (r.DownloadOrder(), r.DownloadView(), rt.Download())
-    rt.Dispose()
-    return out
-
-
-def same_frame(a, b) -> bool:
-    return np.array_equal(a[0], b[0]) and np.array_equal(a[1].view(np.uint8), b[1].view(np.uint8)) and np.array_equal(a[2], b[2])
 
 
 # ---- 1. chunk tails ---------------------------------------------------------------------------------------------------------------------------

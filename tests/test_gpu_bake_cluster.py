@@ -8,7 +8,6 @@ Two yardsticks are too slow for the host importer's assignment passes (200,300 x
 are built with CreateAssetFromSplatsNative(context=gpu_ctx), whose bytes tests/test_gpu_import_cluster.py holds to the host's.  That route still sums
 the means on the host: only the assignment kernel is shared with the code under test."""
 import ctypes as C
-import functools
 
 import numpy as np
 import pytest
@@ -18,65 +17,21 @@ import cluster_model as KM
 import copy_model as CM
 import edit_model as EM
 import export_model as XM
-from common import default_camera, small_asset
+from builders import CLUSTER4K, LOW, decode_of
+from common import PRESETS, default_camera, small_asset
+from gpu_rig import BAD, CAM, check_bake, frame_of, keep_only, pinned_renderer as make_renderer, same_frame, yardstick
 from unitygaussiansplatting_amd import _abi, _lib, asset as A, camera, creator
 from unitygaussiansplatting_amd.cutout import GaussianCutout, Type
-from unitygaussiansplatting_amd.renderer import GaussianSplatRenderer, RenderTarget, SortMode
+from unitygaussiansplatting_amd.renderer import GaussianSplatRenderer
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 VF, CF, SF = A.VectorFormat, A.ColorFormat, A.SHFormat
-BAD = _abi.GS_ERR_INVALID_ARGUMENT
-CAM = default_camera(az=25.0)
-CLUSTER4K = (VF.Norm11, VF.Norm6, CF.Norm8x4, SF.Cluster4k)           # VeryLow with a colour format the bake has
-LOW = (VF.Norm11, VF.Norm6, CF.Norm8x4, SF.Cluster16k)
 
 
-@functools.lru_cache(maxsize=None)
-def decode_of(n: int, quality: str, seed: int = 5) -> np.ndarray:
-    """one oracle decode per source asset, shared by the tests that use it and left unchanged"""
-    dec = CM.decode(small_asset(n, seed, quality))
-    dec.setflags(write=False)
-    return dec
-
-
-def yardstick(dec_alive, formats, morton=True, ctx=None) -> A.GaussianSplatAsset:
-    raw = BM.columns(dec_alive)
-    BM.assert_no_negative_zero(raw)
-    assert all(np.isfinite(np.asarray(c)).all() for c in (raw.pos, raw.scale, raw.dc0, raw.opacity, raw.sh, raw.rot))
-    fp, fs, fc, fsh = formats
-    return creator.CreateAssetFromSplatsNative(raw, formatPos=fp, formatScale=fs, formatColor=fc, formatSH=fsh, linearize=False, morton=morton, name="yardstick",
-                                               context=ctx)
-
-
-def make_renderer(ctx, asset) -> GaussianSplatRenderer:
-    r = GaussianSplatRenderer(ctx, asset)
-    r.sortMode = SortMode.Full
-    r.framesInFlight = 1
-    r.CreateResourcesForAsset()
-    return r
-
-
-def bake(r, formats, morton=True):
-    fp, fs, fc, fsh = formats
-    return r.EditBakeAsset(formatPos=fp, formatScale=fs, formatColor=fc, formatSH=fsh, morton=morton)
-
-
-def check_bake(r, dec_alive, formats, what, morton=True, ctx=None):
-    want = yardstick(dec_alive, formats, morton, ctx)
-    g = bake(r, formats, morton)
-    try:
-        assert g.splatCount == len(dec_alive), (what, g.splatCount, len(dec_alive))
-        BM.assert_same_asset(g.Download(), want, what)
-    finally:
-        g.Dispose()
-    return want
-
-
-def keep_only(r, n: int, src: np.ndarray) -> None:
-    flags = np.ones(n, bool)
-    flags[src] = False
-    r.SetDeletedBits(EM.pack_bits(flags, (n + 31) // 32))
+def check_cluster_bake(r, dec_alive, formats, what, morton=True, ctx=None):
+    """one bake against the Cluster yardstick (ctx: its assignment passes on the GPU)"""
+    return check_bake(r, dec_alive, formats, what, morton, want=yardstick(dec_alive, formats, morton, ctx))
 
 
 def table_index(asset: A.GaussianSplatAsset) -> np.ndarray:
@@ -90,7 +45,7 @@ def table_index(asset: A.GaussianSplatAsset) -> np.ndarray:
 def test_very_high_to_cluster4k(gpu_ctx, morton):
     r = make_renderer(gpu_ctx, small_asset(4500, 5, "VeryHigh"))
     try:
-        want = check_bake(r, decode_of(4500, "VeryHigh"), CLUSTER4K, ("Cluster4k", morton), morton)
+        want = check_cluster_bake(r, decode_of(4500, "VeryHigh"), CLUSTER4K, ("Cluster4k", morton), morton)
         assert len(want.shData) == 4096 * 96 and len(np.unique(table_index(want))) > 3000
     finally:
         r.DisposeResourcesForAsset()
@@ -102,7 +57,7 @@ def test_other_record_sizes(gpu_ctx, scale, record):
     formats = (VF.Norm11, scale, CF.Norm8x4, SF.Cluster4k)
     r = make_renderer(gpu_ctx, small_asset(4500, 5, "VeryHigh"))
     try:
-        want = check_bake(r, decode_of(4500, "VeryHigh"), formats, formats)
+        want = check_cluster_bake(r, decode_of(4500, "VeryHigh"), formats, formats)
         assert len(want.otherData) == (4500 * record + 7) // 8 * 8
     finally:
         r.DisposeResourcesForAsset()
@@ -112,19 +67,19 @@ def test_cluster8k(gpu_ctx):
     formats = (VF.Norm16, VF.Float32, CF.Float16x4, SF.Cluster8k)
     r = make_renderer(gpu_ctx, small_asset(9000, 5, "VeryHigh"))
     try:
-        check_bake(r, decode_of(9000, "VeryHigh"), formats, "Cluster8k")
+        check_cluster_bake(r, decode_of(9000, "VeryHigh"), formats, "Cluster8k")
     finally:
         r.DisposeResourcesForAsset()
 
 
 # ---- 3. every source preset ------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("quality", ["VeryLow", "Low", "Medium", "High", "VeryHigh"])
+@pytest.mark.parametrize("quality", PRESETS)
 def test_source_presets(gpu_ctx, quality):
     """the first 4,500 splats of a 20,000-splat asset of each preset (a Cluster palette as the SOURCE needs more splats than entries), the rest deleted"""
     r = make_renderer(gpu_ctx, small_asset(20000, 5, quality))
     keep_only(r, 20000, np.arange(4500))
     try:
-        check_bake(r, decode_of(20000, quality)[:4500], CLUSTER4K, quality)
+        check_cluster_bake(r, decode_of(20000, quality)[:4500], CLUSTER4K, quality)
     finally:
         r.DisposeResourcesForAsset()
 
@@ -142,7 +97,7 @@ def test_deleted_bits_and_cutouts(gpu_ctx):
         m.edit.set_deleted_bits(words); m.edit.set_cutouts(cuts, r.transform.localToWorldMatrix)
         alive = m.alive()
         assert 4096 < alive.sum() < n * 4 // 5 and m.edit.cut.sum() > 50
-        check_bake(r, m.dec[alive], CLUSTER4K, "bits + cutouts")
+        check_cluster_bake(r, m.dec[alive], CLUSTER4K, "bits + cutouts")
     finally:
         r.DisposeResourcesForAsset()
 
@@ -164,7 +119,7 @@ def test_as_many_alive_as_entries_is_refused_one_more_is_accepted(gpu_ctx):
             assert refused(), alive
             assert b"more splats than table entries" in lib.gs_last_error_string()
         keep_only(r, n, np.arange(4097))
-        check_bake(r, decode_of(n, "VeryHigh")[:4097], CLUSTER4K, "4,097 alive")
+        check_cluster_bake(r, decode_of(n, "VeryHigh")[:4097], CLUSTER4K, "4,097 alive")
     finally:
         r.DisposeResourcesForAsset()
 
@@ -179,7 +134,7 @@ def test_crafted_empty_and_long_clusters(gpu_ctx):
     assert np.array_equal(dec2[:, 14:59].view(np.uint32), np.ascontiguousarray(dec[:, 14:59]).view(np.uint32))
     r = make_renderer(gpu_ctx, asset)
     try:
-        want = check_bake(r, dec2, CLUSTER4K, "crafted")
+        want = check_cluster_bake(r, dec2, CLUSTER4K, "crafted")
         cnt = np.bincount(table_index(want), minlength=4096)
         assert (cnt == 0).sum() >= 1500 and cnt.max() >= 2500
     finally:
@@ -192,20 +147,12 @@ def test_more_than_200k_alive_takes_the_subset(gpu_ctx):
     n = 200300
     r = make_renderer(gpu_ctx, small_asset(n, 6, "VeryHigh"))
     try:
-        check_bake(r, decode_of(n, "VeryHigh", 6), CLUSTER4K, "200,300", ctx=gpu_ctx)
+        check_cluster_bake(r, decode_of(n, "VeryHigh", 6), CLUSTER4K, "200,300", ctx=gpu_ctx)
     finally:
         r.DisposeResourcesForAsset()
 
 
 # ---- 8. the asset is usable --------------------------------------------------------------------------------------------------------------------------
-def frame_of(r, ctx, cam):
-    rt = RenderTarget(ctx, cam.pixelWidth, cam.pixelHeight)
-    r.SortPoints(cam); r.CalcViewData(cam); rt.Clear(); r.Draw(cam, rt)
-    out = (r.DownloadOrder(), r.DownloadView(), rt.Download())
-    rt.Dispose()
-    return out
-
-
 def test_baked_low_asset_renders_like_the_uploaded_yardstick(gpu_ctx):
     n = 20000
     src = make_renderer(gpu_ctx, small_asset(n, 5, "High"))
@@ -223,7 +170,7 @@ def test_baked_low_asset_renders_like_the_uploaded_yardstick(gpu_ctx):
         assert host.dataHash == want.dataHash and host.dataHash
         for cam in (CAM, default_camera(az=110.0, elev=-20.0)):
             a, b = frame_of(baked, gpu_ctx, cam), frame_of(uploaded, gpu_ctx, cam)
-            assert np.array_equal(a[0], b[0]) and np.array_equal(a[1].view(np.uint8), b[1].view(np.uint8)) and np.array_equal(a[2], b[2]) and a[2].any()
+            assert same_frame(a, b) and a[2].any()
     finally:
         baked.DisposeResourcesForAsset(); uploaded.DisposeResourcesForAsset(); src.DisposeResourcesForAsset()
         g.Dispose()

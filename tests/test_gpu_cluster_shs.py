@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import cluster_model as CM
+from common import same_bits
 from unitygaussiansplatting_amd import _abi, _lib, creator
 
 pytestmark = pytest.mark.gpu
@@ -72,7 +73,7 @@ def test_device_loop_is_independent_of_the_batch_size(gpu_ctx, monkeypatch):
     whole = check(gpu_ctx, x, 65)
     monkeypatch.setenv("GSPLAT_IMPORT_BATCH", "256")                    # read at every call: 4 full launches + one of 13 points per pass
     again = creator.ClusterSHsNative(x, 65, context=gpu_ctx)
-    assert CM.same_bits(again[0], whole[0]) and np.array_equal(again[1], whole[1])
+    assert same_bits(again[0], whole[0], dtype=None) and np.array_equal(again[1], whole[1])
     monkeypatch.setenv("GSPLAT_IMPORT_BATCH", "1")
     check(gpu_ctx, x[:70], 9)
 

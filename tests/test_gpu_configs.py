@@ -20,6 +20,7 @@ import pytest
 
 import oracle_lib as O
 from common import RT_TOL, rt_err, views_equal
+from gpu_rig import check_raster_records
 from unitygaussiansplatting_amd import camera, creator, scenes
 from unitygaussiansplatting_amd.renderer import GaussianSplatRenderer, RenderTarget
 
@@ -35,18 +36,6 @@ def rt_close(img, ref, rare=0):
 def cam_of(cfg, az=0.0):
     return camera.Camera(position=scenes.orbit_eye(cfg.eye_radius, cfg.eye_elev_deg, az), pixelWidth=cfg.width, pixelHeight=cfg.height,
                          fieldOfView=cfg.fov_y)
-
-
-def check_raster_records(r, orc, P):
-    """rec / rect / visibility of the PER-FRAME calc_view launch (FULL = false: early cull, chunk cull, colour only for visible
-    splats) against the oracle's prepare() -- the view-parity tests only ever read the on-demand full kernel."""
-    recs, rects, vis = r.DownloadRasterRecords()
-    orecs, orects, ovis = orc.raster_records(P)
-    assert np.array_equal(vis, ovis), "visibility bits differ"
-    assert np.array_equal(rects, orects), "tile rectangles differ"
-    m = (np.unpackbits(ovis.view(np.uint8), bitorder="little")[:orc.n]).astype(bool)
-    assert np.array_equal(recs[m], orecs[m]), "blend records of visible splats differ"
-    return int(m.sum())
 
 
 def full_frame_vs_oracle(gpu_ctx, a, cfg, azimuths=(0.0,), window=None, check_rt=True, rare=0, tile=None, redraw_expect_tile=None):

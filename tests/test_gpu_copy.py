@@ -16,26 +16,14 @@ import pytest
 import copy_model as CM
 import edit_model as EM
 import export_model as XM
-import oracle_lib as O
-from common import RT_TOL, default_camera, rt_err, small_asset, views_equal
-from unitygaussiansplatting_amd import _abi, _lib, asset as A, camera
+from builders import CAMS, DST_TR, SRC_TR, decode_of
+from common import PRESETS, small_asset
+from gpu_rig import BAD, assert_same_frames, asset_tails, check_state, download, frames_of, native_count, oracle_frames, pinned_renderer as make_renderer
+from unitygaussiansplatting_amd import _lib, asset as A, camera
 from unitygaussiansplatting_amd.renderer import GaussianSplatRenderer, GpuContext, MergeSplatObjects, RenderTarget, SortMode
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
-PRESETS = ["VeryLow", "Low", "Medium", "High", "VeryHigh"]
-SRC_TR = camera.Transform(**XM.BAKE_TRANSFORM)                      # rotated, non-uniformly scaled, mirrored in x
-DST_TR = camera.Transform(position=(-0.4, 0.1, 0.2), rotation=(0.5, -0.5, 0.5, 0.5), scale=(0.8, 1.25, 2.0))
-CAMS = [default_camera(az=25.0), default_camera(az=110.0, elev=-20.0), default_camera(az=250.0, elev=35.0, radius=7.0)]
-BAD = _abi.GS_ERR_INVALID_ARGUMENT
-
-
-@functools.lru_cache(maxsize=None)
-def decode_of(n: int, quality: str, seed: int = 5) -> np.ndarray:
-    """one oracle decode per source asset, shared by the tests that use it and left unchanged"""
-    dec = CM.decode(small_asset(n, seed, quality))
-    dec.setflags(write=False)
-    return dec
 
 
 def boundary_bits(n: int) -> np.ndarray:
@@ -43,89 +31,6 @@ def boundary_bits(n: int) -> np.ndarray:
     flags = np.zeros(n, bool)
     flags[[k for k in (0, 31, 32, 63, 64, 255, 256, n - 1) if k < n]] = True
     return EM.pack_bits(flags, (n + 31) // 32)
-
-
-def make_renderer(ctx, asset, tr=None, mode=SortMode.Full, frames=1) -> GaussianSplatRenderer:
-    r = GaussianSplatRenderer(ctx, asset, tr)
-    r.sortMode = mode
-    r.framesInFlight = frames
-    r.CreateResourcesForAsset()
-    return r
-
-
-def native_count(r) -> int:
-    n = C.c_uint32(0)
-    _lib.check(_lib.lib().gs_renderer_splat_count(r._r_h, C.byref(n)), "gs_renderer_splat_count")
-    return int(n.value)
-
-
-def download(r) -> CM.Blobs:
-    pos, other, color, sh = r.DownloadSplatData()
-    return CM.Blobs(r.splatCount, pos, other, color, sh, r.DownloadEditBits()[2])
-
-
-def check_state(r, want: CM.Blobs, what, tails=None, selected=None, order=None):
-    """everything the renderer holds against the model.  tails: the bytes an unresized renderer's blobs carry behind whole records (the asset's)"""
-    assert native_count(r) == want.n == r.splatCount, what
-    got = download(r)
-    for k, name in enumerate(("pos", "other", "color", "sh")):
-        g, w = getattr(got, name), getattr(want, name)
-        tail = b"" if tails is None else tails[k]
-        assert len(g) == len(w) + len(tail), (what, name, len(g), len(w))
-        assert np.array_equal(g[:len(w)], w), (what, name, np.flatnonzero(g[:len(w)] != w)[:8])
-        assert g[len(w):].tobytes() == tail, (what, name, "tail")
-    sel, md, deleted = r.DownloadEditBits()
-    assert np.array_equal(deleted, want.deleted_words()), (what, "deleted", deleted, want.deleted_words())
-    zeros = np.zeros(want.words, np.uint32)
-    assert np.array_equal(sel, zeros if selected is None else selected[0]) and np.array_equal(md, zeros if selected is None else selected[1]), (what, "selection")
-    if order is not None:
-        assert np.array_equal(r.DownloadOrder(), order), (what, "order")
-    return got
-
-
-def asset_tails(asset):
-    n = asset.splatCount
-    w, h = A.CalcTextureSize(n)
-    sizes = (12 * n, 16 * n, w * h * 16, 192 * n)
-    return [np.ascontiguousarray(b, np.uint8)[s:].tobytes() for b, s in zip((asset.posData, asset.otherData, asset.colorData, asset.shData), sizes)]
-
-
-def frames_of(r, ctx, cams=CAMS):
-    """SortPoints / CalcViewData / Draw on every camera: [(view records, frame)] and the order buffer at the end"""
-    out = []
-    for cam in cams:
-        rt = RenderTarget(ctx, cam.pixelWidth, cam.pixelHeight)
-        r.SortPoints(cam); r.CalcViewData(cam); rt.Clear(); r.Draw(cam, rt)
-        out.append((r.DownloadView(), rt.Download()))
-        rt.Dispose()
-    return out, r.DownloadOrder()
-
-
-def oracle_frames(asset, words, tr, cams=CAMS):
-    orc = O.Oracle(asset)
-    probe = GaussianSplatRenderer.__new__(GaussianSplatRenderer)   # no context: FrameParams reads the transform and the serialized fields only
-    probe.transform, probe.m_SplatScale, probe.m_OpacityScale, probe.m_SHOrder, probe.m_SHOnly = tr, 1.0, 1.0, 3, False
-    out = []
-    for cam in cams:
-        orc.sort(camera.sort_matrix(cam, tr.localToWorldMatrix))
-        P = probe.FrameParams(cam)
-        view = orc.calc_view(P, deleted_bits=words).copy()
-        out.append((view, orc.draw(P, 0)))
-    return out, orc.order.copy()
-
-
-def assert_same_frames(got, want, what, bits=True):
-    (gf, go), (wf, wo) = got, want
-    assert np.array_equal(go, wo), (what, "order")
-    for k, ((gv, gi), (wv, wi)) in enumerate(zip(gf, wf)):
-        if bits:
-            assert np.array_equal(gv.view(np.uint32), wv.view(np.uint32)) or views_equal(gv, wv), (what, k, "view")
-            assert np.array_equal(gi, wi), (what, k, "frame", int((gi != wi).sum()))
-        else:
-            assert views_equal(gv, wv), (what, k, "view vs oracle")
-            e = rt_err(gi, wi)
-            print(what, "camera", k, "rt_err vs oracle", e)
-            assert e <= RT_TOL, (what, k, e)
 
 
 # ---- 1. counts and offsets ------------------------------------------------------------------------------------------------------------------

@@ -114,7 +114,7 @@ def test_framebuffer_parity_other_formats(gpu_ctx, quality):
 
 
 def test_everything_culled_and_single_splat(gpu_ctx):
-    from test_oracle import fp32_point_asset
+    from builders import fp32_point_asset
     a = fp32_point_asset([[0.3, 0.1, 0.0]])
     cam = camera.Camera(position=(0, 0, 5), target=(0, 0, 0), pixelWidth=128, pixelHeight=96)
     res = render_both(gpu_ctx, a, cam)

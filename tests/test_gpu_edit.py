@@ -9,7 +9,8 @@ import pytest
 import edit_model as EM
 import oracle_lib as O
 from common import RT_TOL, default_camera, rt_err, small_asset, views_equal
-from unitygaussiansplatting_amd import _abi, _lib, camera
+from gpu_rig import Rig
+from unitygaussiansplatting_amd import _lib, camera
 from unitygaussiansplatting_amd.renderer import GaussianSplatRenderer, RenderTarget, SortMode
 
 pytestmark = pytest.mark.gpu
@@ -18,80 +19,6 @@ OFF_SCREEN = (-900.0, -900.0, -800.0, -800.0)
 EMPTY = (200.0, 50.0, 100.0, 150.0)                 # x_min > x_max
 WHOLE = (0.0, 0.0, 320.0, 200.0)
 SECOND_RECT = (150.5, 20.0, 310.0, 120.25)          # overlaps the premise rectangle
-
-
-class Rig:
-    """one renderer and the model of its edit state, moved in lock step; every step ends with the comparison"""
-
-    def __init__(self, ctx, asset, transform=None):
-        self.r = GaussianSplatRenderer(ctx, asset, transform)
-        self.r.CreateResourcesForAsset()
-        self.m = EM.EditModel(asset)
-        self.lib = _lib.lib()
-        self.steps = 0
-        self.check("fresh")
-
-    def close(self):
-        self.r.DisposeResourcesForAsset()
-
-    def raw_info(self) -> np.ndarray:
-        info = _abi.gs_edit_info()
-        _lib.check(self.lib.gs_renderer_edit_info(self.r._r_h, C.byref(info)), "gs_renderer_edit_info")
-        return EM.info_words(info)
-
-    def check(self, what):
-        self.steps += 1
-        got, want = self.r.DownloadEditBits(), self.m.bits()
-        for name, g, w in zip(("selected", "mouse-down", "deleted"), got, want):
-            assert np.array_equal(g, w), f"step {self.steps} ({what}): {name} words differ at {np.flatnonzero(g != w)[:8]}"
-        gi, wi = self.raw_info(), self.m.info()
-        assert np.array_equal(gi, wi), f"step {self.steps} ({what}): info {gi.tolist()} != {wi.tolist()}"
-        r = self.r
-        if r.m_GpuEditSelected:                                    # the host mirror's fields are that record decoded (UpdateEditCountsAndBounds)
-            r.UpdateEditCountsAndBounds()
-            assert (r.editSelectedSplats, r.editDeletedSplats, r.editCutSplats) == tuple(int(v) for v in wi[:3])
-
-    # -- the calls, on both sides ---------------------------------------------------------------------------------------------------------
-    def select_all(self):
-        self.r.EditSelectAll(); self.m.select_all(); self.check("select all")
-
-    def deselect_all(self):
-        self.r.EditDeselectAll(); self.m.deselect_all(); self.check("deselect all")
-
-    def invert(self):
-        self.r.EditInvertSelection(); self.m.invert_selection(); self.check("invert")
-
-    def store(self):
-        self.r.EditStoreSelectionMouseDown(); self.m.store_selection(); self.check("store")
-
-    def update(self, cam, rect, subtract):
-        x0, y0, x1, y1 = rect
-        self.r.EditUpdateSelection((x0, y1), (x1, y0), cam, subtract)      # rectMin = (x_min, y_max), rectMax = (x_max, y_min): GaussianSplatRenderer.cs:835
-        self.m.update_selection(self.r.FrameParams(cam), rect, subtract)
-        self.check(f"update {rect} subtract={subtract}")
-
-    def delete(self):
-        self.r.EditDeleteSelected(); self.m.delete_selected(); self.check("delete")
-        if self.m.info()[1] != 0:
-            assert self.r.editModified                             # GaussianSplatRenderer.cs:902-903
-
-    def upload_selected(self, words):
-        self.r.UploadSelectedBits(words); self.m.upload_selected(words); self.check("upload selected")
-
-    def set_cutouts(self, cuts):
-        self.r.m_Cutouts = cuts
-        self.r.UpdateCutoutsBuffer()
-        self.m.set_cutouts(cuts, self.r.transform.localToWorldMatrix)
-        self.check("set cutouts")
-
-    def set_deleted_bits(self, words):
-        self.r.SetDeletedBits(words); self.m.set_deleted_bits(words); self.check("set deleted bits")
-
-    def release(self):
-        _lib.check(self.lib.gs_renderer_edit_release(self.r._r_h), "gs_renderer_edit_release")
-        self.r.m_GpuEditSelected = False
-        self.m.release()
-        self.check("release")
 
 
 def walk(rig: Rig, cam):

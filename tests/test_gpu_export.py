@@ -3,21 +3,20 @@ ExportPlyFile) against the numpy model of CSExportData and ExportPlyFile (tests/
 tests/test_export_model.py): every record bit for bit, every file byte for byte."""
 import ctypes as C
 import functools
-import os
 
 import numpy as np
 import pytest
 
 import edit_model as EM
 import export_model as XM
-from common import default_camera, small_asset
+from common import PRESETS, default_camera, same_bits, small_asset
+from gpu_rig import edit_info, make_renderer
 from unitygaussiansplatting_amd import _abi, _lib, camera, creator
 from unitygaussiansplatting_amd._lib import GsError
 from unitygaussiansplatting_amd.renderer import GaussianSplatRenderer, RenderTarget, SortMode
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
-PRESETS = ["VeryLow", "Low", "Medium", "High", "VeryHigh"]
 
 
 @functools.lru_cache(maxsize=None)
@@ -30,29 +29,12 @@ def asset_of(kind: str, n: int):
     return EM.point_asset(n) if kind == "points" else small_asset(n, 5, kind)
 
 
-def same_bits(a, b) -> bool:
-    a, b = np.ascontiguousarray(a, f32), np.ascontiguousarray(b, f32)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
-def make_renderer(ctx, asset, tr=None) -> GaussianSplatRenderer:
-    r = GaussianSplatRenderer(ctx, asset, tr)
-    r.CreateResourcesForAsset()
-    return r
-
-
 def set_pattern(r: GaussianSplatRenderer, m: XM.ExportModel, name: str) -> None:
     words, cuts = XM.pattern(name, m.n)
     r.SetDeletedBits(words)
     r.m_Cutouts = cuts
     r.UpdateCutoutsBuffer()
     XM.apply_pattern(m, name, r.transform.localToWorldMatrix)
-
-
-def edit_info(r) -> _abi.gs_edit_info:
-    info = _abi.gs_edit_info()
-    _lib.check(_lib.lib().gs_renderer_edit_info(r._r_h, C.byref(info)), "gs_renderer_edit_info")
-    return info
 
 
 def three_outputs(r, path, bake=False):

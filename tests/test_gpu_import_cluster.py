@@ -8,7 +8,7 @@ import pytest
 import cluster_cases as CC
 import oracle_lib as O
 from common import default_camera
-from test_import import _same
+from builders import _same
 from unitygaussiansplatting_amd import creator, scenes
 from unitygaussiansplatting_amd.renderer import GaussianSplatRenderer, RenderTarget
 

@@ -14,8 +14,7 @@ import pytest
 
 import oracle_lib as O
 from common import default_camera
-from test_cutouts import CUTOUT_SETS
-from test_vissort_model import tie_heavy_asset
+from builders import CUTOUT_SETS, tie_heavy_asset
 from unitygaussiansplatting_amd import camera
 from unitygaussiansplatting_amd._abi import GS_SORT_VISIBLE
 from unitygaussiansplatting_amd.renderer import GaussianSplatRenderer, RenderTarget, SortMode

@@ -16,51 +16,15 @@ import pytest
 
 import oracle_lib as O
 from common import RT_TOL, rt_err, views_equal
-from test_cutouts import CUTOUT_SETS
+from builders import CUTOUT_SETS, _case
 from unitygaussiansplatting_amd import camera, creator, scenes
 from unitygaussiansplatting_amd._lib import GsError
 from unitygaussiansplatting_amd.cutout import shader_data_array
-from unitygaussiansplatting_amd.renderer import GaussianSplatRenderer, RenderTarget, SortMode
+from unitygaussiansplatting_amd.renderer import GaussianSplatRenderer, RenderTarget
 
 pytestmark = pytest.mark.gpu
 
 _SEEDS = [1, 2, 3] + [int(os.environ.get("GSPLAT_PARITY_SEED0", "100")) + k for k in range(int(os.environ.get("GSPLAT_PARITY_SEEDS", "0")))]
-_SIZES = [(320, 200), (333, 217), (17, 9), (8, 8), (640, 360), (1280, 720), (48, 1024), (1024, 48), (1, 1), (31, 33)]
-
-
-def _case(seed):
-    rng = np.random.default_rng(7000 + seed)
-    n = int(rng.choice([257, 1_000, 5_003, 20_011, 60_000]))
-    quality = str(rng.choice(["VeryHigh", "High", "Medium", "Low", "VeryLow"]))
-    if quality in ("Low", "VeryLow"):
-        # Cluster16k / Cluster4k SH: the importer refuses fewer splats than table entries (the reference's creator skips the clustering there and writes a
-        # blob its own shader cannot index: GaussianSplatAssetCreator.cs:481-483, 1046-1065), and the k-means is slow on the host beyond ~20 k splats
-        n = 20_011 if quality == "Low" else min(max(n, 5_003), 20_011)
-    extent = float(rng.choice([0.5, 3.0, 10.0]))
-    W, H = _SIZES[int(rng.integers(len(_SIZES)))]
-    kind = str(rng.choice(["orbit", "inside", "grazing", "far"], p=[0.5, 0.25, 0.15, 0.1]))
-    radius = {"orbit": rng.uniform(1.5, 3.0) * extent, "inside": rng.uniform(0.05, 0.6) * extent, "grazing": rng.uniform(0.9, 1.1) * extent,
-              "far": rng.uniform(20.0, 60.0) * extent}[kind]
-    cam = camera.Camera(position=scenes.orbit_eye(float(radius), float(rng.uniform(-60, 60)), float(rng.uniform(0, 360))), pixelWidth=W, pixelHeight=H,
-                        fieldOfView=float(rng.choice([10.0, 39.0965, 60.0, 110.0])))
-    tr = None
-    if rng.random() < 0.4:
-        q = rng.normal(size=4); q /= np.linalg.norm(q)
-        sc = rng.uniform(0.5, 2.0, 3) * (np.array([-1.0, 1.0, 1.0]) if rng.random() < 0.3 else 1.0)      # (mirrored: the sample scene's transform is)
-        tr = camera.Transform(position=tuple(rng.uniform(-0.5, 0.5, 3) * extent), rotation=tuple(q), scale=tuple(sc))
-    fields = dict(m_SplatScale=float(rng.choice([1.0, 0.3, 2.0])), m_OpacityScale=float(rng.choice([1.0, 0.5, 1.7])), m_SHOrder=int(rng.integers(0, 4)),
-                  m_SHOnly=bool(rng.random() < 0.15))
-    mode = SortMode.Visible if rng.random() < 0.5 else SortMode.Full
-    tile = [(0, 0), (16, 16), (32, 16), (32, 32)][int(rng.integers(4))]
-    asset_seed = int(rng.integers(1, 50))
-    # (drawn last, so that the cases above are the ones of the first campaign) cutouts, deleted bits, the fast blend mode
-    cut = str(rng.choice(list(CUTOUT_SETS))) if rng.random() < 0.3 else None
-    bits_seed = int(rng.integers(1, 1000)) if rng.random() < 0.25 else None
-    blend = 1 if rng.random() < 0.2 else 0
-    return dict(n=n, quality=quality, extent=extent, cam=cam, tr=tr, fields=fields, mode=mode, tile=tile, kind=kind, asset_seed=asset_seed, cut=cut,
-                bits_seed=bits_seed, blend=blend)
-
-
 @pytest.mark.parametrize("seed", _SEEDS)
 def test_random_case_against_the_oracle(gpu_ctx, seed):
     c = _case(seed)

@@ -23,19 +23,13 @@ import pytest
 import bake_model as BM
 import session_model as SM
 from common import RT_TOL, rt_err
-from test_gpu_bake_cluster import yardstick as cluster_yardstick
-from test_gpu_copy import assert_same_frames, check_state, download, frames_of, make_renderer, native_count
+from gpu_rig import assert_same_frames, check_state, download, draw_frame, edit_info, fptr, frames_of, native_count, pinned_renderer as make_renderer, yardstick as cluster_yardstick
 from unitygaussiansplatting_amd import _abi, _lib, creator
 from unitygaussiansplatting_amd.renderer import GaussianSplatRenderer, GpuAsset, GpuContext, RenderTarget, SortMode
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 SEEDS = list(SM.SUITE_SEEDS) + [100 + k for k in range(int(os.environ.get("GSPLAT_SESSION_SEEDS", "0")))]
-
-
-def fptr(v):
-    a = np.ascontiguousarray(v, f32).reshape(-1)
-    return a, a.ctypes.data_as(C.POINTER(C.c_float))
 
 
 def ply_body(path) -> np.ndarray:
@@ -167,7 +161,7 @@ class Run:
         if name == "frame":
             cam = SM.CAMS[a[0]]
             rt = RenderTarget(r.ctx, cam.pixelWidth, cam.pixelHeight)
-            r.SortPoints(cam); r.CalcViewData(cam); rt.Clear(); r.Draw(cam, rt)
+            draw_frame(r, cam, rt)
             res_box["rt"] = rt
             return 0
         if name == "export":
@@ -301,8 +295,7 @@ class Run:
                 pos, other = r.DownloadPosOther()
                 wp, wo = st.tm.blobs()
                 assert SM.TM.blobs_equal(pos, wp, floats=st.tm.pos_gate) and SM.TM.blobs_equal(other, wo, floats=False), "DownloadPosOther"
-                info = _abi.gs_edit_info()
-                _lib.check(self.lib.gs_renderer_edit_info(r._r_h, C.byref(info)), "gs_renderer_edit_info")
+                info = edit_info(r)
                 assert np.array_equal(SM.EM.info_words(info), st.tm.info()), ("info", SM.EM.info_words(info).tolist(), st.tm.info().tolist())
 
     def twin(self, who):

@@ -6,7 +6,8 @@ import pytest
 
 import edit_model as EM
 from common import default_camera, small_asset
-from test_gpu_copy import DST_TR, download, make_renderer
+from builders import DST_TR
+from gpu_rig import download, draw_frame, pinned_renderer as make_renderer
 from unitygaussiansplatting_amd.renderer import RenderTarget, SortMode
 
 pytestmark = pytest.mark.gpu
@@ -26,7 +27,7 @@ def apply_settings(r, history=None, view_every_frame=False):
 def frame(r, ctx, cam):
     """one SortPoints / CalcViewData / Draw: (view records, pixels, visible order)"""
     rt = RenderTarget(ctx, cam.pixelWidth, cam.pixelHeight)
-    r.SortPoints(cam); r.CalcViewData(cam); rt.Clear(); r.Draw(cam, rt)
+    draw_frame(r, cam, rt)
     out = (r.DownloadView(), rt.Download(), r.DownloadVisibleOrder(), r.FrameStats())
     rt.Dispose()
     return out

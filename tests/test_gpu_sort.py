@@ -90,7 +90,7 @@ def test_sorter_reuse_many_times(gpu_ctx):
 
 
 def test_depth_keys_signs_zeros_denormals(gpu_ctx):
-    from test_oracle import fp32_point_asset
+    from builders import fp32_point_asset
     rng = np.random.default_rng(2)
     z = np.concatenate([rng.standard_normal(5000).astype(np.float32) * 10, np.zeros(50, np.float32), -np.zeros(50, np.float32),
                         (rng.standard_normal(200) * 1e-41).astype(np.float32), np.array([np.inf, -np.inf, 3.4e38, -3.4e38], np.float32)])

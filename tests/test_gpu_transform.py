@@ -2,8 +2,6 @@
 GaussianSplatRenderer.Edit*) against the numpy model of the reference's three kernels (tests/transform_model.py; its premises and its codec are asserted
 on the CPU by tests/test_transform_model.py).  After EVERY call the renderer's current pos / other blobs (DownloadPosOther: every byte, a NaN position
 equal to a NaN), the three bit buffers and the nine words of gs_renderer_edit_info are compared with the model."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
@@ -11,29 +9,22 @@ import edit_model as EM
 import export_model as XM
 import oracle_lib as O
 import transform_model as TM
+from builders import TOOL, pos_only_asset
 from common import RT_TOL, default_camera, rt_err, small_asset, views_equal
-from test_gpu_edit import Rig
-from test_transform_model import pos_only_asset
-from unitygaussiansplatting_amd import _abi, _lib, camera
+from gpu_rig import BAD, Rig, draw_frame, fptr
+from unitygaussiansplatting_amd import _lib, camera
 from unitygaussiansplatting_amd.renderer import GaussianSplatRenderer, RenderTarget, SortMode
 from vissort_model import visible_bits
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
-TOOL = camera.Transform(position=(0.2, -0.1, 0.3), rotation=(0.1, 0.2, 0.05, 0.9695), scale=(1.25, 0.75, -1.5))      # non-uniform and mirrored
 CENTRE = (0.3, -0.2, 0.1)
 Q1 = (0.18257419, 0.36514837, 0.54772256, 0.73029674)
 Q2 = (-0.5, 0.5, 0.5, 0.5)
-BAD = _abi.GS_ERR_INVALID_ARGUMENT
-
-
-def fptr(v):
-    a = np.ascontiguousarray(v, f32).reshape(-1)
-    return a, a.ctypes.data_as(C.POINTER(C.c_float))
 
 
 class TRig(Rig):
-    """test_gpu_edit.Rig over a TransformModel: the blobs are part of every comparison"""
+    """gpu_rig.Rig over a TransformModel: the blobs are part of every comparison"""
 
     def __init__(self, ctx, asset, transform=None, sort_mode=None):
         self.r = GaussianSplatRenderer(ctx, asset, transform)
@@ -194,7 +185,7 @@ def test_rotate_and_scale_need_the_mouse_down_copies(gpu_ctx):
 
 # ---- 3. the asset and other renderers never see an edit ----------------------------------------------------------------------------------------
 def _frame(r, cam, rt):
-    r.SortPoints(cam); r.CalcViewData(cam); rt.Clear(); r.Draw(cam, rt)
+    draw_frame(r, cam, rt)
     return rt.Download()
 
 

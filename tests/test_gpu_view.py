@@ -38,7 +38,7 @@ def test_view_data_bit_exact_all_formats(gpu_ctx, quality, fmt):
 
 
 def test_behind_camera_and_nan_axes_records(gpu_ctx):
-    from test_oracle import fp32_point_asset
+    from builders import fp32_point_asset
     pts = np.array([[0, 0, 0], [0.3, 0.1, 0], [0, 0, 9.0], [0, 0, 5.0], [1e30, 0, 0]], np.float32)    # on axis, off axis, behind, at the eye, far away
     a = fp32_point_asset(pts)
     oth = a.otherData.view(np.uint32).reshape(-1, 4).copy()
@@ -121,7 +121,7 @@ def test_chunkless_lossy_sh_asset_on_the_per_frame_path(gpu_ctx, shfmt):
     """An asset with a lossy SH format but NO chunk blob (gs_asset_create accepts it: _SplatChunkCount = 0, so nothing is chunk-lerped,
     SplatUtilities.compute / GaussianSplatting.hlsl:521-527): the per-frame calc_view launch (which does not zero-fill its per-splat
     record) must see shLerp = false like the full kernel and the oracle do -- records, visibility and the frame itself."""
-    from test_gpu_configs import check_raster_records
+    from gpu_rig import check_raster_records
     from common import RT_TOL, rt_err
     from unitygaussiansplatting_amd.renderer import RenderTarget
     a0 = small_asset(20_000, 9, "VeryHigh", formatSH=getattr(A.SHFormat, shfmt))

@@ -22,8 +22,8 @@ import pytest
 
 import oracle_lib as O
 from common import views_equal
-from test_cutouts import CUTOUT_SETS
-from test_gpu_configs import check_raster_records
+from builders import CUTOUT_SETS
+from gpu_rig import check_raster_records
 from unitygaussiansplatting_amd import asset as A
 from unitygaussiansplatting_amd import camera, creator, scenes
 from unitygaussiansplatting_amd.cutout import shader_data_array

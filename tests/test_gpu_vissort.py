@@ -12,7 +12,7 @@ import pytest
 
 import oracle_lib as O
 from common import default_camera, small_asset
-from test_vissort_model import cams_for, tie_heavy_asset
+from builders import cams_for, tie_heavy_asset
 from unitygaussiansplatting_amd import camera, creator, scenes
 from unitygaussiansplatting_amd._abi import GS_SORT_VISIBLE
 from unitygaussiansplatting_amd.renderer import GaussianSplatRenderer, RenderTarget, SortMode
@@ -467,7 +467,7 @@ def test_frames_in_flight_inside_the_library(gpu_ctx):
 def test_library_lanes_get_every_setting(gpu_ctx):
     """Cutouts, deleted bits, the blend mode, a pinned tile shape, the view-buffer mode and a scene-depth attachment reach the lanes -- set before the lanes exist
     and changed while they do: every frame equals the one-at-a-time renderer's, the 40-byte view records the oracle's."""
-    from test_cutouts import CUTOUT_SETS
+    from builders import CUTOUT_SETS
     from unitygaussiansplatting_amd.cutout import shader_data_array
     a = small_asset(30_011, 7, "Medium")
     seq = GaussianSplatRenderer(gpu_ctx, a)

@@ -3,32 +3,16 @@
 This runs on the CPU box: it catches any divergence between the HIP kernels' op order and the oracle's canonical
 arithmetic before a GPU is involved.  (The GPU tests then check the same thing through the C-ABI on the device.)"""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import oracle_lib as O
 from common import default_camera, small_asset
+from harness import hm  # noqa: F401  (the fixture: builds tests/host_math_harness.cpp)
 from unitygaussiansplatting_amd import asset as A
 from unitygaussiansplatting_amd import camera
 from unitygaussiansplatting_amd._abi import VIEW_DTYPE
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-@pytest.fixture(scope="module")
-def hm(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("hm") / "libhm.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-o", so,
-                           os.path.join(HERE, "host_math_harness.cpp")])
-    lib = C.CDLL(so)
-    lib.hm_f16tof32.restype = C.c_float
-    lib.hm_f16tof32.argtypes = [C.c_uint32]
-    lib.hm_f32tof16.restype = C.c_uint32
-    lib.hm_f32tof16.argtypes = [C.c_float]
-    return lib
 
 
 CASES = [("Medium", {}), ("High", {}), ("VeryHigh", {}),

@@ -16,8 +16,8 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-from test_gpu_random_parity import _case
-from test_host_math import hm  # noqa: F401  (the fixture: builds tests/host_math_harness.cpp)
+from builders import _case
+from harness import hm  # noqa: F401  (the fixture: builds tests/host_math_harness.cpp)
 from unitygaussiansplatting_amd import camera, creator, scenes
 from unitygaussiansplatting_amd._abi import VIEW_DTYPE
 

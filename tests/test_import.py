@@ -6,27 +6,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from builders import _same
 from unitygaussiansplatting_amd import _lib, creator, scenes
 from unitygaussiansplatting_amd import asset as A
 from unitygaussiansplatting_amd._abi import gs_import_formats
-
-BLOBS = ("posData", "otherData", "colorData", "shData", "chunkData")
-
-
-def _same(a, b):
-    for nm in BLOBS:
-        x, y = getattr(a, nm), getattr(b, nm)
-        if x is None or y is None or len(x) == 0 or len(y) == 0:
-            assert (x is None or len(x) == 0) and (y is None or len(y) == 0), nm
-            continue
-        x, y = np.asarray(x, np.uint8), np.asarray(y, np.uint8)
-        assert len(x) == len(y), (nm, len(x), len(y))
-        bad = np.flatnonzero(x != y)
-        assert len(bad) == 0, f"{nm}: {len(bad)} bytes differ, first at {bad[:5]}"
-    assert np.array_equal(np.asarray(a.boundsMin, np.float32), np.asarray(b.boundsMin, np.float32))
-    assert np.array_equal(np.asarray(a.boundsMax, np.float32), np.asarray(b.boundsMax, np.float32))
-    assert a.dataHash == b.dataHash
-
 
 @pytest.mark.parametrize("quality", ["Medium", "High", "VeryHigh"])
 @pytest.mark.parametrize("n", [1, 255, 256, 257, 30_011])

@@ -9,7 +9,7 @@ import os
 import numpy as np
 import pytest
 
-from test_import import _same
+from builders import _same
 from unitygaussiansplatting_amd import asset as A
 from unitygaussiansplatting_amd import creator, scenes
 

@@ -10,27 +10,13 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from builders import fp32_point_asset
 from unitygaussiansplatting_amd import asset as A
 from unitygaussiansplatting_amd._abi import VIEW_DTYPE, gs_frame_params
 
 
 def f16(x):
     return np.asarray(x, np.float32).astype(np.float16).view(np.uint16)
-
-
-def fp32_point_asset(points):
-    """All-fp32, chunk-less asset whose decode is the identity on positions."""
-    pts = np.asarray(points, np.float32).reshape(-1, 3)
-    n = len(pts)
-    other = np.zeros((n, 4), np.uint32)
-    other[:, 0] = (511 | (511 << 10) | (511 << 20) | (3 << 30))          # ~identity rotation, largest = w
-    other[:, 1:4] = np.float32(0.05).view(np.uint32)
-    col = np.zeros((A.CalcTextureSize(n)[0] * A.CalcTextureSize(n)[1], 4), np.float32)
-    col[:, :] = (0.5, 0.5, 0.5, 1.0)
-    return A.GaussianSplatAsset(splatCount=n, posFormat=A.VectorFormat.Float32, scaleFormat=A.VectorFormat.Float32,
-                                shFormat=A.SHFormat.Float32, colorFormat=A.ColorFormat.Float32x4,
-                                posData=pts.view(np.uint8).reshape(-1).copy(), otherData=other.view(np.uint8).reshape(-1).copy(),
-                                colorData=col.view(np.uint8).reshape(-1).copy(), shData=np.zeros(n * 192, np.uint8))
 
 
 def test_sortable_uint_is_monotone():

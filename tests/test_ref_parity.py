@@ -28,7 +28,7 @@ from unitygaussiansplatting_amd import camera, cutout
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
 import make_golden as G  # noqa: E402
-from test_golden import load as load_golden  # noqa: E402
+from builders import load_golden  # noqa: E402
 
 FORMAT_CASES = [("Medium", {}), ("High", {}), ("VeryHigh", {}), ("Low", {}), ("VeryLow", {}),
                 ("Medium", dict(formatPos=A.VectorFormat.Norm16, formatScale=A.VectorFormat.Norm6, formatSH=A.SHFormat.Float16, formatColor=A.ColorFormat.Float16x4)),

@@ -25,8 +25,8 @@ import pytest
 import oracle_lib as O
 import ref_lib as R
 from common import RT_TOL, rt_diff
-from test_cutouts import CUTOUT_SETS
-from test_gpu_random_parity import _case
+from builders import CUTOUT_SETS
+from builders import _case
 from unitygaussiansplatting_amd import camera, creator, scenes
 from unitygaussiansplatting_amd.cutout import shader_data_array
 

@@ -12,7 +12,7 @@ import pytest
 
 import oracle_lib as O
 from common import RT_TOL, default_camera, rt_err, small_asset
-from test_oracle import fp32_point_asset
+from builders import fp32_point_asset
 from unitygaussiansplatting_amd import camera
 from unitygaussiansplatting_amd.renderer import GaussianSplatRenderer, RenderMode, RenderTarget
 

@@ -5,8 +5,6 @@ one program's transform, resize and copy steps replayed through the host builds 
 tests/copy_host_harness.cpp), bit for bit.  No renderer is made: FrameParams comes from a context-free probe."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,10 +14,11 @@ import copy_model as CM
 import edit_model as EM
 import session_model as SM
 import transform_model as TM
-from test_copy_model import FLAGS, params_of
+from builders import params_of
+from common import _p
+from harness import build_harness
 from unitygaussiansplatting_amd import _abi, creator
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 f32 = np.float32
 TRANSFORMS = ("translate", "rotate", "scale")
 
@@ -206,17 +205,10 @@ def test_a_broken_rule_is_observed(broken):
 
 
 # ---- 4. the composed model against the host build of gs_device_math.h -----------------------------------------------------------------------------------
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
 @pytest.fixture(scope="module")
 def harnesses(tmp_path_factory):
     d = tmp_path_factory.mktemp("session")
-    th, ch = str(d / "libth.so"), str(d / "libch.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-o", th, os.path.join(HERE, "transform_host_harness.cpp")])
-    subprocess.check_call(["g++", "-O2", "-fPIC", "-shared"] + FLAGS + ["-o", ch, os.path.join(HERE, "copy_host_harness.cpp")])
-    return C.CDLL(th), C.CDLL(ch)
+    return C.CDLL(build_harness(d, "transform_host_harness.cpp")), C.CDLL(build_harness(d, "copy_host_harness.cpp"))
 
 
 def host_transform(th, name, st, args):

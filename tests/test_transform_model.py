@@ -2,8 +2,6 @@
 model the GPU tests are held to (tests/transform_model.py), its rotation codec against the reference's own compiled text (oracle/_ref), the clamp, and
 the host build of the kernels' per-splat arithmetic (csrc/gs_device_math.h through tests/transform_host_harness.cpp) against the model, bit for bit."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,10 +9,12 @@ import pytest
 import edit_model as EM
 import ref_lib
 import transform_model as TM
+from builders import pos_only_asset
+from common import _p
+from harness import build_harness
 from unitygaussiansplatting_amd import _abi, _lib, camera
 from unitygaussiansplatting_amd.renderer import GaussianSplatRenderer
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 f32 = np.float32
 EYE = np.eye(4, dtype=f32)
 IDENT_Q = (0.0, 0.0, 0.0, 1.0)
@@ -169,14 +169,6 @@ def test_the_format_gates():
     assert np.array_equal(half.other_blob, o0) and not np.array_equal(half.pos_blob, p0)
 
 
-def pos_only_asset(n, seed=5):
-    """fp32 positions and scales, no chunks, but Norm11 SH: the position gate passes, the rotation gate does not"""
-    import dataclasses
-    from unitygaussiansplatting_amd import asset as A
-    a = EM.point_asset(n, seed)
-    return dataclasses.replace(a, shFormat=A.SHFormat.Norm11, shData=np.zeros(n * 60, np.uint8))
-
-
 # ---- 3. the codec against the reference's compiled text -------------------------------------------------------------------------------------
 def codec_quaternions():
     rng = np.random.default_rng(31)
@@ -258,14 +250,7 @@ def test_a_delta_quaternion_of_length_two_stays_inside_the_fields():
 # ---- 5. the host build of the kernels' arithmetic against the model ---------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def th(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("th") / "libth.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-o", so,
-                           os.path.join(HERE, "transform_host_harness.cpp")])
-    return C.CDLL(so)
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
+    return C.CDLL(build_harness(tmp_path_factory.mktemp("th"), "transform_host_harness.cpp"))
 
 
 def test_host_build_of_the_codec_equals_the_model(th):

@@ -7,40 +7,9 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-from common import default_camera
-from unitygaussiansplatting_amd import camera, creator, scenes
+from builders import cams_for, tie_heavy_asset
+from unitygaussiansplatting_amd import camera, scenes
 from vissort_model import VisibleSortModel, visible_bits
-
-
-def tie_heavy_asset(kind: str, n: int = 6000, seed: int = 3, quality: str = "VeryHigh"):
-    """Positions arranged so that MANY splats share a sort key (VeryHigh: fp32, exact; Medium: the same geometry on Norm11 lattices per chunk)."""
-    raw = scenes.make_splats(n, seed, 3.0)
-    rng = np.random.default_rng(seed)
-    pos = raw.pos.copy()
-    if kind == "lattice":            # columns of equal (x, z): a yaw-only camera ties each column
-        g = np.stack(np.meshgrid(np.arange(10), np.arange(30), np.arange(10), indexing="ij"), -1).reshape(-1, 3).astype(np.float32)
-        pos = ((g[rng.integers(0, len(g), n)] - np.array([4.5, 14.5, 4.5], np.float32)) * np.float32(0.25)).astype(np.float32)
-    elif kind == "planes":           # two planes facing a camera on the z axis
-        pos[:, 2] = np.where(rng.random(n) < 0.5, np.float32(-0.5), np.float32(0.75))
-    elif kind == "duplicates":       # every position three times
-        base = pos[: n // 3]
-        pos = np.concatenate([base, base, base, pos[: n - 3 * (n // 3)]])[:n]
-    elif kind == "colocated":        # 150 splats at each of 8 points (runs of > 64 equal keys that NO matrix separates), the rest random
-        pts = pos[:8].copy()
-        pos[: 8 * 150] = np.repeat(pts, 150, axis=0)[rng.permutation(8 * 150)]
-    raw = creator.InputSplatData(pos.astype(np.float32), raw.dc0, raw.sh, raw.opacity, raw.scale, raw.rot)
-    return creator.CreateAssetFromSplats(raw, quality, name=f"ties_{kind}_{quality}")
-
-
-def cams_for(kind: str):
-    z_axis = camera.Camera(position=(0.0, 0.0, 6.0), pixelWidth=320, pixelHeight=200)
-    yaw = lambda deg: camera.Camera(position=scenes.orbit_eye(6.0, 0.0, deg), pixelWidth=320, pixelHeight=200)
-    pitched = lambda deg: camera.Camera(position=scenes.orbit_eye(6.0, 25.0, deg), pixelWidth=320, pixelHeight=200)
-    if kind == "lattice":
-        return [pitched(10.0), yaw(20.0), yaw(20.0), pitched(40.0), yaw(20.0), yaw(33.0), pitched(10.0)]
-    if kind == "planes":
-        return [pitched(15.0), z_axis, z_axis, yaw(8.0), z_axis]
-    return [default_camera(az=a) for a in (0.0, 5.0, 5.0, 10.0, 0.0, 15.0)]
 
 
 @pytest.mark.parametrize("kind", ["lattice", "planes", "duplicates", "colocated", "random"])

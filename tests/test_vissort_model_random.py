@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-from test_vissort_model import tie_heavy_asset
+from builders import tie_heavy_asset
 from unitygaussiansplatting_amd import camera, scenes
 from vissort_model import VisibleSortModel
 
