@@ -568,6 +568,23 @@ int32_t gs_import_encode_on(gs_context* ctx, const gs_import_input* in, const gs
  * context (gs_asset_destroy); *alive its splat count; bounds as GaussianSplatAsset.boundsMin/Max (may be NULL). */
 int32_t gs_renderer_edit_bake_asset(gs_renderer* r, const gs_import_formats* formats, gs_asset** out, uint32_t* alive,
                                     float bounds_min[3], float bounds_max[3]);
+/* ---- import on the GPU: raw splat arrays to a device-resident asset, every preset (GaussianSplatAssetCreator's whole pipeline on the context's GPU) --
+ * The six arrays of `in` -- memory_kind 0: host memory, copied into transient device buffers (N x 236 bytes); memory_kind 1: device memory on the
+ * context's GPU, 4-byte aligned, read during the call only and not modified -- linearised (formats->linearize = 1), bounded, Morton-reordered
+ * (formats->morton = 1), chunked and encoded into a new immutable asset owned by ctx: exactly what gs_renderer_edit_bake_asset returns, for
+ * gs_renderer_create, gs_asset_download_blobs, gs_asset_info and gs_asset_destroy.  Nothing but the upload of memory_kind 0 is host work.
+ * THE IMPORTER'S BYTES: the five blobs, over gs_import_blob_sizes bytes each, are what gs_import_encode(in, formats, ...) writes for the same input --
+ * pad bytes, texels past N, the last chunk's tail and every BC7 block of the colour texture included (GS_COLOR_BC7 is accepted here: mode-6 blocks,
+ * the tiles past the last chunk holding the encoding of an all-zero block) -- and the bounds match bit for bit, for every value of the four format
+ * enums, linearize 0 and 1, morton 0 and 1.  Premises: the input is finite; with linearize = 0 the rot values lie inside their field ranges
+ * ([0, 1]: the host's conversion of anything else is undefined); no -0 is an extreme of a chunk column or of a bounds axis (fmin / fmax do not
+ * pin the sign of zero among equal values); a GS_SH_CLUSTER* palette has finite SH (gs_import_cluster_shs' limit).
+ * Runs on the context's stream after gs_context_synchronize: its sorts need the GPU the way the bake's do.  BLOCKS.
+ * Refused with GS_ERR_INVALID_ARGUMENT, *out NULL and nothing left allocated: a NULL ctx, in, formats or out; a NULL array; splat_count == 0; a
+ * format enum out of range; linearize > 1 or morton > 1; memory_kind > 1; a GS_SH_CLUSTER* target with no more splats than table entries
+ * (gs_import_blob_sizes' rule).  bounds_min / bounds_max may be NULL. */
+int32_t gs_import_encode_to_asset(gs_context* ctx, const gs_import_input* in, uint32_t memory_kind, const gs_import_formats* formats, gs_asset** out,
+                                  float bounds_min[3], float bounds_max[3]);
 /* the five blobs of any asset to host memory: sizes[k] bytes of blob k, at most what the asset holds (blobs[k] NULL or sizes[k] 0: skipped).  BLOCKS. */
 int32_t gs_asset_download_blobs(const gs_asset* asset, void* const blobs[5], const uint64_t sizes[5]);
 

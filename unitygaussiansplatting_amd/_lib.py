@@ -119,6 +119,7 @@ SIGNATURES = {
     "gs_import_encode_on": (C.c_int32, [_P, C.POINTER(gs_import_input), C.POINTER(gs_import_formats), C.c_void_p * 5, C.c_uint64 * 5,
                                          C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "gs_renderer_edit_bake_asset": (C.c_int32, [_P, C.POINTER(gs_import_formats), _PP, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "gs_import_encode_to_asset": (C.c_int32, [_P, C.POINTER(gs_import_input), C.c_uint32, C.POINTER(gs_import_formats), _PP, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "gs_asset_download_blobs": (C.c_int32, [_P, C.c_void_p * 5, C.c_uint64 * 5]),
     "gs_ply_open": (C.c_int32, [C.c_char_p, _PP, C.POINTER(C.c_uint32)]),
     "gs_spz_open": (C.c_int32, [C.c_char_p, _PP, C.POINTER(C.c_uint32)]),

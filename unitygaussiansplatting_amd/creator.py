@@ -583,6 +583,43 @@ def CreateAssetFromSplatsNative(raw: InputSplatData, quality: str = "Medium", *,
     return a
 
 
+def CreateGpuAssetFromSplats(raw, quality: str = "Medium", *, formatPos=None, formatScale=None, formatColor=None, formatSH=None,
+                             morton: bool = True, linearize: bool = True, context):
+    """The importer on the context's GPU (gs_import_encode_to_asset, csrc/gs_bake.hip): a renderer.GpuAsset holding the bytes
+    CreateAssetFromSplatsNative makes of the same input, every preset -- VeryLow's BC7 colour texture and the Cluster* palettes included -- with
+    only the upload left on the host.  raw: InputSplatData of numpy arrays (copied to the GPU), or of six objects exposing data_ptr() -- device
+    tensors on the context's GPU, float32 and contiguous, read in place (memory_kind = 1) and left as they are.  GpuAsset.Download() gives the
+    host copy, GaussianSplatRenderer.CreateResourcesForGpuAsset the renderer.  Blocks."""
+    import ctypes as C
+    from . import _lib
+    from ._abi import gs_import_formats, gs_import_input
+    from .renderer import GpuAsset
+    fp, fs, fc, fsh = QUALITY[quality]
+    fp = VectorFormat(fp if formatPos is None else formatPos)
+    fs = VectorFormat(fs if formatScale is None else formatScale)
+    fc = ColorFormat(fc if formatColor is None else formatColor)
+    fsh = SHFormat(fsh if formatSH is None else formatSH)
+    fields = (raw.pos, raw.dc0, raw.sh, raw.opacity, raw.scale, raw.rot)
+    n = len(raw.pos)
+    on_device = all(hasattr(a, "data_ptr") for a in fields)
+    if on_device:
+        for a, width in zip(fields, (3, 3, 45, 1, 3, 4)):
+            if a.element_size() != 4 or not a.is_floating_point() or not a.is_contiguous() or a.numel() != n * width:
+                raise ValueError("CreateGpuAssetFromSplats: device arrays must be contiguous float32 of N x (3, 3, 45, 1, 3, 4)")
+        arrs = list(fields)                                                    # kept alive over the call
+        ptrs = [a.data_ptr() for a in arrs]
+    else:
+        arrs = [np.ascontiguousarray(a, f32) for a in (raw.pos, raw.dc0, np.asarray(raw.sh).reshape(n, 45), raw.opacity, raw.scale, raw.rot)]
+        ptrs = [a.ctypes.data for a in arrs]
+    inp = gs_import_input(n, *ptrs)
+    fmt = gs_import_formats(int(fp), int(fs), int(fc), int(fsh), int(bool(linearize)), int(bool(morton)))
+    h = C.c_void_p()
+    bmin, bmax = (C.c_float * 3)(), (C.c_float * 3)()
+    _lib.check(_lib.lib().gs_import_encode_to_asset(context._h, C.byref(inp), 1 if on_device else 0, C.byref(fmt), C.byref(h), bmin, bmax),
+               "gs_import_encode_to_asset")
+    return GpuAsset(context, h, n, (fmt.pos_format, fmt.scale_format, fmt.color_format, fmt.sh_format), tuple(bmin), tuple(bmax))
+
+
 def AssignClusters(x, means, context=None) -> np.ndarray:
     """Index of the nearest of `means` [K,45] for every row of `x` [N,45] (fp32 in, distances in float64 as ClusterSHs' assign; first
     minimum) through gs_import_assign_clusters: the native host loop, or with context = a renderer.GpuContext the HIP kernel of

@@ -23,6 +23,12 @@
 //   2c. table                bake_sh_table: K x 45 floats -> K x 96 bytes (gsm::BakeEmitSHTableItem).
 //   3.  encode               as above, except that no SH item is staged or written and the u16 index follows the scale in `other` (gsm::BakeEmitOther).
 // The five blobs are zero-filled first, as the importer's are: the pad bytes, the texels past N and the last chunk's tail are part of the bytes.
+//
+// The same file is the import on the GPU, gs_import_encode_to_asset: steps 2 and 3 are templates over where a splat comes
+// from -- BakeRendererSource, the above, or BakeArraySource, the six raw arrays of gs_import_input in device memory (uploaded first when they are the
+// host's), linearised on the fly by gsm::ImportRecord -- and step 1 is then only the bounds: every input splat is alive.  That route accepts a BC7
+// colour target: bake_encode_kernel<Src, true> compresses a chunk's 16 x 16 tile in place as sixteen mode-6 blocks, sixteen lanes (one DPP row) per
+// block, and writes the texture's tiles behind the last chunk as the encoding of an all-zero block.  The bake itself still refuses BC7.
 #include <new>
 
 #include "gs_common.h"
@@ -43,6 +49,25 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d));
     return v;
 }
+
+// Where the kernels of steps 2 and 3 take splat j from (j: a place in the source's own order, before the Morton reorder).
+// BakeRendererSource: the j-th alive splat of a renderer, decoded from its current view.  BakeArraySource: splat j of six raw arrays in device
+// memory (gs_import_encode_to_asset), linearised on the fly: every one of them is alive, so there is no alive list.
+struct BakeRendererSource {
+    gsm::AssetView a; const uint32_t* alive;
+    __device__ __forceinline__ gsm::V3 position(uint32_t j) const { const uint32_t src = alive[j]; return gsm::LoadSplatPosChunk(a, src, src >> 8); }
+    __device__ __forceinline__ void record(uint32_t j, gsm::BakeRec& rec) const {
+        const uint32_t src = alive[j], ci = src >> 8;
+        gsm::SplatFull s;
+        gsm::LoadSplatDataFull(a, src, ci, gsm::LoadSplatPosChunk(a, src, ci), s);
+        gsm::BakeLinearRecord(s, rec);
+    }
+};
+struct BakeArraySource {
+    gsm::ImportSrc in; uint32_t linearize;
+    __device__ __forceinline__ gsm::V3 position(uint32_t j) const { return { in.pos[(size_t)j * 3u], in.pos[(size_t)j * 3u + 1u], in.pos[(size_t)j * 3u + 2u] }; }
+    __device__ __forceinline__ void record(uint32_t j, gsm::BakeRec& rec) const { gsm::ImportRecord(in, j, linearize, rec); }
+};
 
 // alive[base[chunk] + rank] = idx for the alive splats of source chunk blockIdx.x; partial[chunk][0..2 / 3..5] = min / max of their positions
 __global__ __launch_bounds__(256) void bake_alive_kernel(gsm::AssetView a, gsm::EditView e, const uint32_t* __restrict__ base, uint32_t* __restrict__ alive,
@@ -70,6 +95,23 @@ __global__ __launch_bounds__(256) void bake_alive_kernel(gsm::AssetView a, gsm::
     else if (threadIdx.x < 6u) partial[blockIdx.x * 6u + threadIdx.x] = fmaxf(fmaxf(s_red[0][threadIdx.x], s_red[1][threadIdx.x]), fmaxf(s_red[2][threadIdx.x], s_red[3][threadIdx.x]));
 }
 
+// the same partials for raw arrays: partial[block][0..2 / 3..5] = min / max of positions [256 block, 256 block + 256) below n
+__global__ __launch_bounds__(256) void bake_array_bounds_kernel(const float* __restrict__ pos, uint32_t n, float* __restrict__ partial) {
+    __shared__ float s_red[4][6];
+    const uint32_t idx = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const bool mine = idx < n;
+    const float inf = gsm::u2f(0x7f800000u);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float p = mine ? pos[(size_t)idx * 3u + c] : 0.0f;
+        const float mn = wave_min(mine ? p : inf), mx = wave_max(mine ? p : -inf);
+        if (lane == 0u) { s_red[wave][c] = mn; s_red[wave][3 + c] = mx; }
+    }
+    __syncthreads();
+    if (threadIdx.x < 3u) partial[blockIdx.x * 6u + threadIdx.x] = fminf(fminf(s_red[0][threadIdx.x], s_red[1][threadIdx.x]), fminf(s_red[2][threadIdx.x], s_red[3][threadIdx.x]));
+    else if (threadIdx.x < 6u) partial[blockIdx.x * 6u + threadIdx.x] = fmaxf(fmaxf(s_red[0][threadIdx.x], s_red[1][threadIdx.x]), fmaxf(s_red[2][threadIdx.x], s_red[3][threadIdx.x]));
+}
+
 // bounds[0..2 / 3..5] = min / max over the partials; one workgroup
 __global__ __launch_bounds__(kBakeReduceThreads) void bake_bounds_kernel(const float* __restrict__ partial, uint32_t chunks, float* __restrict__ bounds) {
     __shared__ float s_red[kBakeReduceThreads / 64][6];
@@ -93,13 +135,13 @@ __global__ __launch_bounds__(kBakeReduceThreads) void bake_bounds_kernel(const f
     }
 }
 
-// the Morton code of alive splat j as two sort keys, and the identity payload
-__global__ __launch_bounds__(256) void bake_codes_kernel(gsm::AssetView a, const uint32_t* __restrict__ alive, const float* __restrict__ bounds, uint32_t total,
+// the Morton code of the source's splat j as two sort keys, and the identity payload
+template <class Src>
+__global__ __launch_bounds__(256) void bake_codes_kernel(Src src, const float* __restrict__ bounds, uint32_t total,
                                                          uint32_t* __restrict__ lo, uint32_t* __restrict__ hi, uint32_t* __restrict__ rank) {
     const uint32_t j = blockIdx.x * 256u + threadIdx.x;
     if (j >= total) return;
-    const uint32_t src = alive[j];
-    const unsigned long long code = gsm::BakeMortonCode(gsm::LoadSplatPosChunk(a, src, src >> 8), bounds, bounds + 3);
+    const unsigned long long code = gsm::BakeMortonCode(src.position(j), bounds, bounds + 3);
     lo[j] = (uint32_t)code; hi[j] = (uint32_t)(code >> 32); rank[j] = j;
 }
 
@@ -128,16 +170,13 @@ __device__ __forceinline__ void bake_flush_wave(uint8_t* dst, const uint32_t* st
 }
 
 // rows[i] = the 45 raw SH floats of destination splat i: what cluster_shs of the importer is given (gs_import.cpp: x[i] = s[order[i]].sh)
-__global__ __launch_bounds__(256) void bake_sh_rows_kernel(gsm::AssetView a, const uint32_t* __restrict__ alive, const uint32_t* __restrict__ order, uint32_t n,
-                                                           float* __restrict__ rows) {
+template <class Src>
+__global__ __launch_bounds__(256) void bake_sh_rows_kernel(Src src, const uint32_t* __restrict__ order, uint32_t n, float* __restrict__ rows) {
     __shared__ __attribute__((aligned(16))) uint32_t s_sh[4][64 * 45];
     const uint32_t i = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     if (i < n) {
-        const uint32_t src = alive[order ? order[i] : i], ci = src >> 8;
-        gsm::SplatFull s;
-        gsm::LoadSplatDataFull(a, src, ci, gsm::LoadSplatPosChunk(a, src, ci), s);
         gsm::BakeRec rec;
-        gsm::BakeLinearRecord(s, rec);
+        src.record(order ? order[i] : i, rec);
         uint32_t* row = s_sh[wave] + lane * 45u;
 #pragma unroll
         for (int k = 0; k < 45; ++k) row[k] = gsm::f2u(rec.sh[k]);
@@ -161,18 +200,64 @@ __global__ __launch_bounds__(256) void bake_sh_table_kernel(const float* __restr
     for (int k = 0; k < 6; ++k) out[k] = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
 }
 
-__global__ __launch_bounds__(256) void bake_encode_kernel(gsm::AssetView a, const uint32_t* __restrict__ alive, const uint32_t* __restrict__ order, BakeDst d) {
+// One step of a reduction over a DPP row: the sixteen lanes whose index shares its upper bits, which in bake_encode_kernel are the sixteen texels of
+// one BC7 block.  Quad swaps (lane ^ 1, lane ^ 2), then the half-row and the row mirrored: after the four steps every lane holds the row's result.
+// All lanes of the wave are active where this is used.
+template <int CTRL> __device__ __forceinline__ uint32_t row_dpp(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false); }
+constexpr int kDppQuadXor1 = 0xB1, kDppQuadXor2 = 0x4E, kDppRowHalfMirror = 0x141, kDppRowMirror = 0x140;
+__device__ __forceinline__ float row_min(float v) {
+    v = fminf(v, gsm::u2f(row_dpp<kDppQuadXor1>(gsm::f2u(v))));
+    v = fminf(v, gsm::u2f(row_dpp<kDppQuadXor2>(gsm::f2u(v))));
+    v = fminf(v, gsm::u2f(row_dpp<kDppRowHalfMirror>(gsm::f2u(v))));
+    return fminf(v, gsm::u2f(row_dpp<kDppRowMirror>(gsm::f2u(v))));
+}
+__device__ __forceinline__ float row_max(float v) {
+    v = fmaxf(v, gsm::u2f(row_dpp<kDppQuadXor1>(gsm::f2u(v))));
+    v = fmaxf(v, gsm::u2f(row_dpp<kDppQuadXor2>(gsm::f2u(v))));
+    v = fmaxf(v, gsm::u2f(row_dpp<kDppRowHalfMirror>(gsm::f2u(v))));
+    return fmaxf(v, gsm::u2f(row_dpp<kDppRowMirror>(gsm::f2u(v))));
+}
+__device__ __forceinline__ uint32_t row_or(uint32_t v) {
+    v |= row_dpp<kDppQuadXor1>(v);
+    v |= row_dpp<kDppQuadXor2>(v);
+    v |= row_dpp<kDppRowHalfMirror>(v);
+    return v | row_dpp<kDppRowMirror>(v);
+}
+
+// The BC7 colour texel of a chunk's lane (gsm::BC7*: bc7_encode_mode6 of the importer with one texel per lane): the sixteen lanes of a row are one
+// 4 x 4 block of the chunk's 16 x 16 tile.  Channel minima / maxima over the row, the endpoints redundantly per lane, the lane's own index, the
+// sixteen indices gathered in the block's texel order, one 16-byte store by the row's first lane.  A lane past N takes part with a zero texel, as
+// the importer's zero-initialised texture has it.
+__device__ __forceinline__ void bake_store_bc7(uint8_t* color, uint32_t i, bool mine, const gsm::V4& col) {
+    float px[4], lo[4], hi[4];
+    gsm::BC7Texel(mine ? col : gsm::V4{ 0.0f, 0.0f, 0.0f, 0.0f }, px);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) { lo[c] = row_min(px[c]); hi[c] = row_max(px[c]); }
+    gsm::BC7Block b;
+    gsm::BC7Endpoints(lo, hi, b);
+    const uint32_t at = gsm::BC7TexelOfLane(i) * 4u;
+    const uint32_t index = gsm::BC7TexelIndex(b, px);
+    const uint32_t nibLo = row_or(at < 32u ? index << at : 0u), nibHi = row_or(at < 32u ? 0u : index << (at - 32u));
+    if ((i & 15u) != 0u) return;
+    uint32_t w[4];
+    gsm::BC7Pack(b, ((uint64_t)nibHi << 32) | nibLo, w);
+    *(uint4*)(color + gsm::BC7BlockOfSplat(i) * 16u) = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// BC7: the colour target is GS_COLOR_BC7 (d.f.color == 3), and the grid covers every 16 x 16 tile of the texture, not only the chunks: a workgroup
+// past the last chunk writes its tile's sixteen blocks as the encoding of an all-zero block, which is not zero bytes.
+template <class Src, bool BC7>
+__global__ __launch_bounds__(256) void bake_encode_kernel(Src src, const uint32_t* __restrict__ order, BakeDst d) {
     __shared__ float s_red[4][2 * gsm::kBakeCols];
     __shared__ __attribute__((aligned(16))) uint32_t s_sh[4][64 * 48];
     const uint32_t i = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    if (BC7 && blockIdx.x * 256u >= d.n) {                         // (workgroup-uniform: the texture has tiles behind the last chunk)
+        if (threadIdx.x < 16u) *(uint4*)(d.color + gsm::BC7BlockOfSplat(blockIdx.x * 256u + threadIdx.x * 16u) * 16u) = make_uint4(0x40u, 0u, 0u, 0u);
+        return;
+    }
     const bool mine = i < d.n;
     gsm::BakeRec rec;
-    if (mine) {
-        const uint32_t src = alive[order ? order[i] : i], ci = src >> 8;
-        gsm::SplatFull s;
-        gsm::LoadSplatDataFull(a, src, ci, gsm::LoadSplatPosChunk(a, src, ci), s);
-        gsm::BakeLinearRecord(s, rec);
-    }
+    if (mine) src.record(order ? order[i] : i, rec);
     if (d.f.chunked) {                                             // (workgroup-uniform)
         gsm::BakeBounds b;
         gsm::BakeBoundsEmpty(b);
@@ -213,6 +298,7 @@ __global__ __launch_bounds__(256) void bake_encode_kernel(gsm::AssetView a, cons
         const uint32_t waveCount = d.n - waveFirst < 64u ? d.n - waveFirst : 64u;
         bake_flush_wave(d.sh + (size_t)waveFirst * (shWords * 4u), s_sh[wave], waveCount * shWords, lane);     // 16-byte aligned: 64 records of a multiple of 4 bytes
     }
+    if (BC7) bake_store_bc7(d.color, i, mine, rec.col);            // (every lane of the workgroup: the rows reduce across lanes past N too)
     if (!mine) return;
     uint32_t w[5];
     gsm::BakeEmitVec(rec.pos, d.f.pos, w);
@@ -220,6 +306,7 @@ __global__ __launch_bounds__(256) void bake_encode_kernel(gsm::AssetView a, cons
     bake_store(d.pos + (size_t)i * posSz, w, posSz);
     const uint32_t othSz = gsm::BakeEmitOther(rec.rot, rec.scale, d.f.scale, clustered, clustered ? d.shIndex[i] : 0u, w);
     bake_store(d.other + (size_t)i * othSz, w, othSz);
+    if (BC7) return;
     uint32_t px, py;
     gsm::SplatIndexToPixelIndex(i, px, py);
     gsm::BakeEmitColor(rec.col, d.f.color, w);
@@ -247,17 +334,9 @@ static int32_t bake_sort(gs_context* ctx, BakeRun& run, uint32_t* keys, uint32_t
     return enqueue_sort_passes(ctx, ctx->stream, run.sort, run.control, keys, run.rank, total, nullptr, passes, lastMask);
 }
 
-// steps 1 (second half) to 3 on the context's stream; the caller synchronises whatever this returns.  ev: null, or six events -- 2 .. 5 are recorded
-// here, before the alive list and after the bounds, the sorts and the encode.  cev: null, or twelve events of a Cluster* target -- before and after the
-// SH rows, enqueue_cluster_shs' nine further ones, after the table + encode
-static int32_t bake_enqueue(gs_renderer* r, const gs_import_formats* f, BakeRun& run, uint32_t chunks, uint32_t total, BakeDst d, Event* ev, const hipEvent_t* cev) {
-    gs_context* ctx = r->ctx;
-    hipStream_t st = ctx->stream;
-    const gsm::AssetView a = asset_view(r);
-    GS_HIP(run.alive.alloc(((size_t)total + 16) * 4));
-    GS_HIP(run.partial.alloc((size_t)chunks * 6 * 4));
+// what steps 2 and 3 need besides the source: the sort's buffers and state (morton = 1), the palette's (a Cluster* SH target)
+static int32_t bake_run_alloc(gs_context* ctx, const gs_import_formats* f, BakeRun& run, uint32_t total) {
     GS_HIP(run.bounds.alloc(6 * 4));
-    const uint32_t blocks = (total + 255u) / 256u;
     if (f->morton) {
         for (DevBuf<uint32_t>* b : { &run.lo, &run.hi, &run.hi2, &run.rank }) GS_HIP(b->alloc(((size_t)total + 16) * 4));
         GS_TRY(sort_state_create(ctx, run.sort, total, true));
@@ -270,14 +349,27 @@ static int32_t bake_enqueue(gs_renderer* r, const gs_import_formats* f, BakeRun&
         GS_HIP(run.shMeans.alloc((size_t)K * 180));
         GS_TRY(cluster_run_alloc(ctx, run.cluster, total, K));
     }
-    if (ev) GS_HIP(hipEventRecord(ev[2], st));
-    hipLaunchKernelGGL(bake_alive_kernel, dim3(chunks), dim3(256), 0, st, a, edit_view(r), (const uint32_t*)run.base.get(), run.alive.get(), run.partial.get());
-    hipLaunchKernelGGL(bake_bounds_kernel, dim3(1), dim3(kBakeReduceThreads), 0, st, (const float*)run.partial.get(), chunks, run.bounds.get());
-    GS_HIP(hipGetLastError());
-    if (ev) GS_HIP(hipEventRecord(ev[3], st));
+    return GS_OK;
+}
+
+// the encode of `total` splats of `src` in `order`: a BC7 colour target takes the kernel with the block encoder compiled in, over every tile of the
+// colour texture (256 texels of one byte each)
+template <class Src>
+static void bake_launch_encode(hipStream_t st, const Src& src, const uint32_t* order, uint32_t total, const BakeDst& d, uint64_t colorBytes) {
+    if (d.f.color == GS_COLOR_BC7) hipLaunchKernelGGL((bake_encode_kernel<Src, true>), dim3((uint32_t)(colorBytes / 256u)), dim3(256), 0, st, src, order, d);
+    else hipLaunchKernelGGL((bake_encode_kernel<Src, false>), dim3((total + 255u) / 256u), dim3(256), 0, st, src, order, d);
+}
+
+// steps 2 and 3 for any source, run.bounds already enqueued.  ev: null, or six events -- 4 and 5 are recorded here, after the sorts and after the
+// encode.  cev: null, or twelve events of a Cluster* target -- before and after the SH rows, enqueue_cluster_shs' nine further ones, after the
+// table + encode
+template <class Src>
+static int32_t bake_enqueue_from(gs_context* ctx, const Src& src, const gs_import_formats* f, BakeRun& run, uint32_t total, BakeDst d, uint64_t colorBytes,
+                                 Event* ev, const hipEvent_t* cev) {
+    hipStream_t st = ctx->stream;
+    const uint32_t blocks = (total + 255u) / 256u;
     if (f->morton) {
-        hipLaunchKernelGGL(bake_codes_kernel, dim3(blocks), dim3(256), 0, st, a, (const uint32_t*)run.alive.get(), (const float*)run.bounds.get(), total,
-                           run.lo.get(), run.hi.get(), run.rank.get());
+        hipLaunchKernelGGL(bake_codes_kernel<Src>, dim3(blocks), dim3(256), 0, st, src, (const float*)run.bounds.get(), total, run.lo.get(), run.hi.get(), run.rank.get());
         GS_HIP(hipGetLastError());
         GS_TRY(bake_sort(ctx, run, run.lo, total, 32u));
         hipLaunchKernelGGL(bake_gather_kernel, dim3(blocks), dim3(256), 0, st, (const uint32_t*)run.hi.get(), (const uint32_t*)run.rank.get(), total, run.hi2.get());
@@ -286,18 +378,92 @@ static int32_t bake_enqueue(gs_renderer* r, const gs_import_formats* f, BakeRun&
     }
     if (ev) GS_HIP(hipEventRecord(ev[4], st));
     const uint32_t* order = f->morton ? (const uint32_t*)run.rank.get() : (const uint32_t*)nullptr;
+    const uint32_t K = gsm::shClusterCount(f->sh_format);
     if (K) {
         if (cev) GS_HIP(hipEventRecord(cev[0], st));
-        hipLaunchKernelGGL(bake_sh_rows_kernel, dim3(blocks), dim3(256), 0, st, a, (const uint32_t*)run.alive.get(), order, total, run.shRows.get());
+        hipLaunchKernelGGL(bake_sh_rows_kernel<Src>, dim3(blocks), dim3(256), 0, st, src, order, total, run.shRows.get());
         GS_HIP(hipGetLastError());
         GS_TRY(enqueue_cluster_shs(ctx, run.cluster, run.shRows, total, K, run.shMeans, run.shIndex, cev ? cev + 1 : nullptr));      // (records cev[1 .. 10])
         hipLaunchKernelGGL(bake_sh_table_kernel, dim3((K + 255u) / 256u), dim3(256), 0, st, (const float*)run.shMeans.get(), K, d.sh);
         d.shIndex = run.shIndex;
     }
-    hipLaunchKernelGGL(bake_encode_kernel, dim3(blocks), dim3(256), 0, st, a, (const uint32_t*)run.alive.get(), order, d);
+    bake_launch_encode(st, src, order, total, d, colorBytes);
     GS_HIP(hipGetLastError());
     if (ev) GS_HIP(hipEventRecord(ev[5], st));
     if (K && cev) GS_HIP(hipEventRecord(cev[11], st));
+    return GS_OK;
+}
+
+// steps 1 (second half) to 3 of a renderer's bake on the context's stream; the caller synchronises whatever this returns.  ev: null, or six events --
+// 2 and 3 are recorded here, before the alive list and after the bounds, 4 and 5 by bake_enqueue_from
+static int32_t bake_enqueue(gs_renderer* r, const gs_import_formats* f, BakeRun& run, uint32_t chunks, uint32_t total, BakeDst d, uint64_t colorBytes, Event* ev,
+                            const hipEvent_t* cev) {
+    gs_context* ctx = r->ctx;
+    hipStream_t st = ctx->stream;
+    GS_HIP(run.alive.alloc(((size_t)total + 16) * 4));
+    GS_HIP(run.partial.alloc((size_t)chunks * 6 * 4));
+    GS_TRY(bake_run_alloc(ctx, f, run, total));
+    const BakeRendererSource src = { asset_view(r), run.alive.get() };
+    if (ev) GS_HIP(hipEventRecord(ev[2], st));
+    hipLaunchKernelGGL(bake_alive_kernel, dim3(chunks), dim3(256), 0, st, src.a, edit_view(r), (const uint32_t*)run.base.get(), run.alive.get(), run.partial.get());
+    hipLaunchKernelGGL(bake_bounds_kernel, dim3(1), dim3(kBakeReduceThreads), 0, st, (const float*)run.partial.get(), chunks, run.bounds.get());
+    GS_HIP(hipGetLastError());
+    if (ev) GS_HIP(hipEventRecord(ev[3], st));
+    return bake_enqueue_from(ctx, src, f, run, total, d, colorBytes, ev, cev);
+}
+
+// the new asset of a bake or an import: every blob padded like an owned upload's (the decoders' trailing-dword reads) and zero-filled on the
+// context's stream, as the importer's are.  On failure nothing is left allocated
+static int32_t bake_asset_alloc(gs_context* ctx, const uint64_t need[5], gs_asset** out) {
+    gs_asset* a = new (std::nothrow) gs_asset();
+    if (!a) return fail(GS_ERR_OUT_OF_MEMORY, "host allocation");
+    a->ctx = ctx; a->owned = true;
+    for (int k = 0; k < 5; ++k) {
+        a->sizes[k] = need[k];
+        if (!need[k]) continue;
+        hipError_t e = a->ownedBlobs[k].alloc((size_t)need[k] + 16);
+        a->blobs[k] = a->ownedBlobs[k];
+        if (e == hipSuccess) e = hipMemsetAsync(a->blobs[k], 0, (size_t)need[k] + 16, ctx->stream);
+        if (e != hipSuccess) {
+            const int32_t rc = fail_hip(e, "bake: allocate blob", __FILE__, __LINE__);
+            (void)hipStreamSynchronize(ctx->stream);
+            (void)gs_asset_destroy(a);
+            return rc;
+        }
+    }
+    *out = a;
+    return GS_OK;
+}
+static BakeDst bake_dst_of(const gs_asset* a, uint32_t total, const gs_import_formats* f) {
+    BakeDst d;
+    d.pos = (uint8_t*)a->blobs[0]; d.other = (uint8_t*)a->blobs[1]; d.color = (uint8_t*)a->blobs[2]; d.sh = (uint8_t*)a->blobs[3]; d.chunk = (uint8_t*)a->blobs[4];
+    d.n = total;
+    d.f = { f->pos_format, f->scale_format, f->color_format, f->sh_format, a->sizes[4] != 0 ? 1u : 0u };
+    d.shIndex = nullptr;
+    return d;
+}
+// what follows the enqueue (rc: its result): the bounds and the sorts' error words read back, the stream drained -- whatever failed, nothing in
+// flight outlives the transient buffers or the asset -- and the asset's view filled in, or the asset destroyed
+static int32_t bake_finish(gs_context* ctx, int32_t rc, BakeRun& run, const gs_import_formats* f, gs_asset* a, uint32_t total, float hostBounds[6]) {
+    hipStream_t st = ctx->stream;
+    uint32_t sortError = 0, clusterSortError = 0;
+    if (rc == GS_OK) {
+        hipError_t he = hipMemcpyAsync(hostBounds, run.bounds.get(), 6 * sizeof(float), hipMemcpyDeviceToHost, st);
+        if (he == hipSuccess && f->morton) he = hipMemcpyAsync(&sortError, &run.control.get()->error, 4, hipMemcpyDeviceToHost, st);
+        if (he == hipSuccess && f->sh_format > GS_SH_NORM6) he = hipMemcpyAsync(&clusterSortError, run.cluster.error.get(), 4, hipMemcpyDeviceToHost, st);
+        if (he != hipSuccess) rc = fail_hip(he, "bake: read back", __FILE__, __LINE__);
+    }
+    {
+        const hipError_t hs = hipStreamSynchronize(st);
+        if (rc == GS_OK && hs != hipSuccess) rc = fail_hip(hs, "bake", __FILE__, __LINE__);
+    }
+    if (rc == GS_OK && (sortError | clusterSortError)) rc = fail(GS_ERR_SORT_TIMEOUT, "bake: a bounded look-back spin expired");
+    if (rc != GS_OK) { (void)gs_asset_destroy(a); return rc; }
+    gsm::AssetView& v = a->view;
+    v.pos = (const uint8_t*)a->blobs[0]; v.other = (const uint8_t*)a->blobs[1]; v.color = (const uint8_t*)a->blobs[2]; v.sh = (const uint8_t*)a->blobs[3];
+    v.chunk = (const uint8_t*)a->blobs[4];
+    v.n = total; v.posFmt = f->pos_format; v.scaleFmt = f->scale_format; v.colorFmt = f->color_format; v.shFmt = f->sh_format;
+    v.chunkCount = a->sizes[4] ? (total + 255u) / 256u : 0u;
     return GS_OK;
 }
 
@@ -333,46 +499,69 @@ static int32_t bake_impl(gs_renderer* r, const gs_import_formats* f, gs_asset** 
     if (total == 0u) return fail(GS_ERR_INVALID_ARGUMENT, "bake: no alive splat");
     uint64_t need[5];
     GS_TRY(gs_import_blob_sizes(total, f, need));               // (a Cluster* SH target needs more alive splats than table entries: the importer's rule)
-    // the new asset: every blob padded like an owned upload's (the decoders' trailing-dword reads) and zero-filled, as the importer's are
-    gs_asset* a = new (std::nothrow) gs_asset();
-    if (!a) return fail(GS_ERR_OUT_OF_MEMORY, "host allocation");
-    a->ctx = r->ctx; a->owned = true;
-    int32_t rc = GS_OK;
-    for (int k = 0; k < 5 && rc == GS_OK; ++k) {
-        a->sizes[k] = need[k];
-        if (!need[k]) continue;
-        hipError_t e = a->ownedBlobs[k].alloc((size_t)need[k] + 16);
-        a->blobs[k] = a->ownedBlobs[k];
-        if (e == hipSuccess) e = hipMemsetAsync(a->blobs[k], 0, (size_t)need[k] + 16, st);
-        if (e != hipSuccess) rc = fail_hip(e, "bake: allocate blob", __FILE__, __LINE__);
-    }
+    gs_asset* a = nullptr;
+    GS_TRY(bake_asset_alloc(r->ctx, need, &a));
     float hostBounds[6] = { 0, 0, 0, 0, 0, 0 };
-    uint32_t sortError = 0, clusterSortError = 0;
-    if (rc == GS_OK) {
-        BakeDst d;
-        d.pos = (uint8_t*)a->blobs[0]; d.other = (uint8_t*)a->blobs[1]; d.color = (uint8_t*)a->blobs[2]; d.sh = (uint8_t*)a->blobs[3]; d.chunk = (uint8_t*)a->blobs[4];
-        d.n = total;
-        d.f = { f->pos_format, f->scale_format, f->color_format, f->sh_format, need[4] != 0 ? 1u : 0u };
-        d.shIndex = nullptr;
-        rc = bake_enqueue(r, f, run, chunks, total, d, ev, cev);
-        hipError_t he = hipSuccess;
-        if (rc == GS_OK) he = hipMemcpyAsync(hostBounds, run.bounds.get(), sizeof(hostBounds), hipMemcpyDeviceToHost, st);
-        if (rc == GS_OK && he == hipSuccess && f->morton) he = hipMemcpyAsync(&sortError, &run.control.get()->error, 4, hipMemcpyDeviceToHost, st);
-        if (rc == GS_OK && he == hipSuccess && f->sh_format > GS_SH_NORM6) he = hipMemcpyAsync(&clusterSortError, run.cluster.error.get(), 4, hipMemcpyDeviceToHost, st);
-        if (rc == GS_OK && he != hipSuccess) rc = fail_hip(he, "bake: read back", __FILE__, __LINE__);
-    }
-    {
-        const hipError_t hs = hipStreamSynchronize(st);            // whatever failed: nothing in flight outlives the transient buffers or the asset
-        if (rc == GS_OK && hs != hipSuccess) rc = fail_hip(hs, "bake", __FILE__, __LINE__);
-    }
-    if (rc == GS_OK && (sortError | clusterSortError)) rc = fail(GS_ERR_SORT_TIMEOUT, "bake: a bounded look-back spin expired");
-    if (rc != GS_OK) { (void)gs_asset_destroy(a); return rc; }
-    gsm::AssetView& v = a->view;
-    v.pos = (const uint8_t*)a->blobs[0]; v.other = (const uint8_t*)a->blobs[1]; v.color = (const uint8_t*)a->blobs[2]; v.sh = (const uint8_t*)a->blobs[3];
-    v.chunk = (const uint8_t*)a->blobs[4];
-    v.n = total; v.posFmt = f->pos_format; v.scaleFmt = f->scale_format; v.colorFmt = f->color_format; v.shFmt = f->sh_format;
-    v.chunkCount = need[4] ? (total + 255u) / 256u : 0u;
+    const int32_t rc = bake_enqueue(r, f, run, chunks, total, bake_dst_of(a, total, f), need[2], ev, cev);
+    GS_TRY(bake_finish(r->ctx, rc, run, f, a, total, hostBounds));
     *alive = total;
+    for (int c = 0; c < 3; ++c) {
+        if (bounds_min) bounds_min[c] = hostBounds[c];
+        if (bounds_max) bounds_max[c] = hostBounds[3 + c];
+    }
+    *out = a;
+    return GS_OK;
+}
+
+// gs_import_encode_to_asset: the importer's pipeline with the six raw arrays as the source.  memory_kind 0 copies them into transient device buffers
+// (N x 236 bytes) first; then per-workgroup bounds partials + the bake's fold, and steps 2 and 3 as the bake runs them.  One stream; everything
+// transient is freed when the call returns.  ev: null, or six events -- 0 / 1 around the upload, 3 after the bounds, 4 / 5 by bake_enqueue_from
+static int32_t import_impl(gs_context* ctx, const gs_import_input* in, uint32_t memory_kind, const gs_import_formats* f, gs_asset** out, float bounds_min[3],
+                           float bounds_max[3], Event* ev = nullptr, const hipEvent_t* cev = nullptr) {
+    if (out) *out = nullptr;
+    if (!ctx || !in || !f || !out) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
+    if (!in->pos || !in->dc0 || !in->sh || !in->opacity || !in->scale || !in->rot) return fail(GS_ERR_INVALID_ARGUMENT, "an input array is null");
+    if (f->linearize > 1 || f->morton > 1) return fail(GS_ERR_INVALID_ARGUMENT, "import: linearize and morton must be 0 or 1");
+    if (memory_kind > 1) return fail(GS_ERR_INVALID_ARGUMENT, "import: memory_kind must be 0 (host arrays) or 1 (device arrays)");
+    const uint32_t total = in->splat_count;
+    uint64_t need[5];
+    GS_TRY(gs_import_blob_sizes(total, f, need));               // (no splats, an enum out of range, a Cluster* target with too few splats)
+    GS_HIP(hipSetDevice(ctx->device));
+    GS_TRY(gs_context_synchronize(ctx));                        // the sorts need the GPU the way the bake's do
+    hipStream_t st = ctx->stream;
+    BakeRun run;
+    DevBuf<float> up[6];
+    const float* arrays[6] = { in->pos, in->dc0, in->sh, in->opacity, in->scale, in->rot };
+    if (ev) GS_HIP(hipEventRecord(ev[0], st));
+    if (memory_kind == 0u) {
+        const size_t floats[6] = { 3, 3, 45, 1, 3, 4 };
+        for (int k = 0; k < 6; ++k) GS_HIP(up[k].alloc((size_t)total * floats[k] * 4));
+        hipError_t he = hipSuccess;
+        for (int k = 0; k < 6 && he == hipSuccess; ++k) he = hipMemcpyAsync(up[k].get(), arrays[k], (size_t)total * floats[k] * 4, hipMemcpyHostToDevice, st);
+        if (he != hipSuccess) { (void)hipStreamSynchronize(st); return fail_hip(he, "import: upload", __FILE__, __LINE__); }
+        for (int k = 0; k < 6; ++k) arrays[k] = up[k].get();
+    }
+    if (ev) GS_HIP(hipEventRecord(ev[1], st));
+    const uint32_t blocks = (total + 255u) / 256u;
+    {
+        const int32_t rcAlloc = [&]() -> int32_t { GS_HIP(run.partial.alloc((size_t)blocks * 6 * 4)); return bake_run_alloc(ctx, f, run, total); }();
+        if (rcAlloc != GS_OK) { (void)hipStreamSynchronize(st); return rcAlloc; }       // (the uploads may still be in flight)
+    }
+    gs_asset* a = nullptr;
+    {
+        const int32_t rcAsset = bake_asset_alloc(ctx, need, &a);
+        if (rcAsset != GS_OK) { (void)hipStreamSynchronize(st); return rcAsset; }
+    }
+    const BakeArraySource src = { { arrays[0], arrays[1], arrays[2], arrays[3], arrays[4], arrays[5] }, f->linearize };
+    int32_t rc = [&]() -> int32_t {
+        hipLaunchKernelGGL(bake_array_bounds_kernel, dim3(blocks), dim3(256), 0, st, arrays[0], total, run.partial.get());
+        hipLaunchKernelGGL(bake_bounds_kernel, dim3(1), dim3(kBakeReduceThreads), 0, st, (const float*)run.partial.get(), blocks, run.bounds.get());
+        GS_HIP(hipGetLastError());
+        if (ev) GS_HIP(hipEventRecord(ev[3], st));
+        return bake_enqueue_from(ctx, src, f, run, total, bake_dst_of(a, total, f), need[2], ev, cev);
+    }();
+    float hostBounds[6] = { 0, 0, 0, 0, 0, 0 };
+    GS_TRY(bake_finish(ctx, rc, run, f, a, total, hostBounds));
     for (int c = 0; c < 3; ++c) {
         if (bounds_min) bounds_min[c] = hostBounds[c];
         if (bounds_max) bounds_max[c] = hostBounds[3 + c];
@@ -389,6 +578,11 @@ extern "C" {
 
 int32_t gs_renderer_edit_bake_asset(gs_renderer* r, const gs_import_formats* formats, gs_asset** out, uint32_t* alive, float bounds_min[3], float bounds_max[3]) {
     return bake_impl(r, formats, out, alive, bounds_min, bounds_max);
+}
+
+int32_t gs_import_encode_to_asset(gs_context* ctx, const gs_import_input* in, uint32_t memory_kind, const gs_import_formats* formats, gs_asset** out,
+                                  float bounds_min[3], float bounds_max[3]) {
+    return import_impl(ctx, in, memory_kind, formats, out, bounds_min, bounds_max);
 }
 
 int32_t gs_asset_download_blobs(const gs_asset* asset, void* const blobs[5], const uint64_t sizes[5]) {
@@ -436,6 +630,31 @@ __attribute__((visibility("default"))) int32_t gs_bake_cluster_stage_times_for_s
     (void)gs_asset_destroy(a);
     for (int k = 0; k < 11; ++k) GS_HIP(hipEventElapsedTime(&ms[k], cev[k], cev[k + 1]));
     GS_HIP(hipEventElapsedTime(&ms[11], ev[0], cev[0]));
+    return GS_OK;
+}
+
+// The same for scripts/import_gpu_timing.py: one whole gs_import_encode_to_asset whose asset is destroyed again; ms[0..4] = GPU milliseconds of the
+// upload (memory_kind 0; else next to nothing), the bounds, the Morton codes + the two sorts, the palette (SH rows + the Lloyd loop; 0 without a
+// Cluster* target), the encode (+ the SH table).
+__attribute__((visibility("default"))) int32_t gs_import_gpu_stage_times_for_scripts(gs_context* ctx, const gs_import_input* in, uint32_t memory_kind,
+                                                                                     const gs_import_formats* formats, float ms[5]) {
+    if (!ctx || !in || !formats || !ms) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
+    GS_HIP(hipSetDevice(ctx->device));
+    Event ev[6], cevOwned[12];
+    hipEvent_t cev[12];
+    for (Event& e : ev) GS_HIP(e.create(hipEventDefault));
+    for (int k = 0; k < 12; ++k) { GS_HIP(cevOwned[k].create(hipEventDefault)); cev[k] = cevOwned[k]; }
+    gs_asset* a = nullptr;
+    GS_TRY(import_impl(ctx, in, memory_kind, formats, &a, nullptr, nullptr, ev, cev));
+    (void)gs_asset_destroy(a);
+    const bool palette = formats->sh_format > GS_SH_NORM6;
+    GS_HIP(hipEventElapsedTime(&ms[0], ev[0], ev[1]));
+    GS_HIP(hipEventElapsedTime(&ms[1], ev[1], ev[3]));
+    GS_HIP(hipEventElapsedTime(&ms[2], ev[3], ev[4]));
+    ms[3] = 0.0f;
+    if (palette) GS_HIP(hipEventElapsedTime(&ms[3], cev[0], cev[10]));
+    if (palette) GS_HIP(hipEventElapsedTime(&ms[4], cev[10], cev[11]));
+    else GS_HIP(hipEventElapsedTime(&ms[4], ev[4], ev[5]));
     return GS_OK;
 }
 

@@ -1577,6 +1577,144 @@ GS_HD uint64_t BakeMortonCode(const V3& p, const float* mn, const float* mx) {
            MortonPart1By2(BakeMortonComponent(p.x, mn[0], ix));
 }
 
+// ---- import: raw splat arrays as the bake's source (gs_import.cpp:372-392, LinearizeData of GaussianFileReader.cs:211-233; kernels in
+// gs_bake.hip) ------------------------------------------------------------------------------------------------------------------------
+// The six arrays of gs_import_input, host or device memory
+struct ImportSrc { const float* pos; const float* dc0; const float* sh; const float* opacity; const float* scale; const float* rot; };
+// exp(x), the importer's exp_det: n = rint(x log2 e), r = x - n ln2 in two parts, the degree-5 polynomial of Cephes' expf, the scale by 2^n as an
+// exponent splice.  fmin / fmax, nearbyintf and x + - only: the same bits on the host and on the device
+GS_HD float ImportExpDet(float x) {
+    x = fminf(fmaxf(x, -87.0f), 88.0f);
+    const float n = nearbyintf(x * 1.44269504f);
+    float r = x - n * 0.693359375f;
+    r = r - n * -2.12194440e-4f;
+    float p = 1.9875691500e-4f;
+    p = p * r + 1.3981999507e-3f;
+    p = p * r + 8.3334519073e-3f;
+    p = p * r + 4.1665795894e-2f;
+    p = p * r + 1.6666665459e-1f;
+    p = p * r + 5.0000001201e-1f;
+    p = p * (r * r) + r;
+    p = p + 1.0f;
+    return p * u2f((uint32_t)((int)n + 127) << 23);
+}
+// LinearizeData on one splat: SH0ToColor, |exp(scale)|, Sigmoid(opacity), normalize(wxyz).yzwx packed smallest-three.  rot: (w, x, y, z) in,
+// the packed three + index / 3 out
+GS_HD void ImportLinearize(V3& dc0, V3& scale, float& opacity, V4& rot) {
+    dc0 = { dc0.x * 0.2820948f + 0.5f, dc0.y * 0.2820948f + 0.5f, dc0.z * 0.2820948f + 0.5f };
+    scale = { fabsf(ImportExpDet(scale.x)), fabsf(ImportExpDet(scale.y)), fabsf(ImportExpDet(scale.z)) };
+    opacity = 1.0f / (1.0f + ImportExpDet(-opacity));
+    const float len = sqrtf(((rot.x * rot.x + rot.y * rot.y) + rot.z * rot.z) + rot.w * rot.w);
+    rot = PackSmallest3Rotation({ rot.y / len, rot.z / len, rot.w / len, rot.x / len });
+}
+// splat i of the raw arrays as the record the Bake* functions consume.  The rotation word is the importer's q(rot[k], 1023.5) | ... |
+// q(rot[3], 3.5) << 30 of the four floats as they are (inside their field ranges: a premise with linearize = 0), not a re-pack of a quaternion
+GS_HD void ImportRecord(const ImportSrc& in, uint32_t i, uint32_t linearize, BakeRec& o) {
+    const uint64_t i3 = (uint64_t)i * 3u;
+    o.pos = { in.pos[i3], in.pos[i3 + 1], in.pos[i3 + 2] };
+    V3 dc0 = { in.dc0[i3], in.dc0[i3 + 1], in.dc0[i3 + 2] };
+    o.scale = { in.scale[i3], in.scale[i3 + 1], in.scale[i3 + 2] };
+    float opacity = in.opacity[i];
+    const float* r = in.rot + (uint64_t)i * 4u;
+    V4 rot = { r[0], r[1], r[2], r[3] };
+    if (linearize) ImportLinearize(dc0, o.scale, opacity, rot);
+    o.rot = BakeQ(rot.x, 1023.5f) | (BakeQ(rot.y, 1023.5f) << 10) | (BakeQ(rot.z, 1023.5f) << 20) | (BakeQ(rot.w, 3.5f) << 30);
+    o.col = { dc0.x, dc0.y, dc0.z, opacity };
+    const float* sh = in.sh + (uint64_t)i * 45u;
+#pragma unroll
+    for (int k = 0; k < 45; ++k) o.sh[k] = sh[k];
+}
+
+// ---- BC7 mode-6 colour blocks (bc7_encode_mode6 of gs_import.cpp, operation for operation): the colour texture of the VeryLow preset ------------
+// Three steps, so that one thread can own a block (BC7EncodeMode6) or sixteen lanes can, each with its texel: the per-block endpoints from
+// the channel minima / maxima, the per-texel index, the per-block packing of the sixteen indices.
+struct BC7Block { int q0[4], q1[4], p0, p1; float e0[4], axis[4], den; };
+// a texel as the encoder sees it: clamp(v, 0, 1) x 255
+GS_HD void BC7Texel(const V4& c, float* px) { px[0] = sat(c.x) * 255.0f; px[1] = sat(c.y) * 255.0f; px[2] = sat(c.z) * 255.0f; px[3] = sat(c.w) * 255.0f; }
+// the two-p-bit endpoint quantiser: floor((v - p) / 2 + 0.5) clamped to 0..127, the squared error summed left to right, p = 1 only when strictly better
+GS_HD void BC7QuantEndpoint(const float* v, int* q, int& pbit) {
+    float berr = 0.0f;
+    pbit = 0;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        float qq[4], err = 0.0f;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            qq[c] = fminf(fmaxf(floorf((v[c] - (float)p) / 2.0f + 0.5f), 0.0f), 127.0f);
+            const float d = (qq[c] * 2.0f + (float)p) - v[c];
+            const float d2 = d * d;
+            err = c == 0 ? d2 : err + d2;
+        }
+        if (p == 0 || err < berr) {
+            berr = err; pbit = p;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) q[c] = (int)qq[c];
+        }
+    }
+}
+GS_HD void BC7Endpoints(const float* lo, const float* hi, BC7Block& b) {
+    BC7QuantEndpoint(lo, b.q0, b.p0);
+    BC7QuantEndpoint(hi, b.q1, b.p1);
+    b.den = 0.0f;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        b.e0[c] = (float)(b.q0[c] * 2 + b.p0);
+        b.axis[c] = (float)(b.q1[c] * 2 + b.p1) - b.e0[c];
+        const float a2 = b.axis[c] * b.axis[c];
+        b.den = c == 0 ? a2 : b.den + a2;
+    }
+}
+// the nearest of the 16 mode-6 weights to the texel's projection on the endpoint axis: the first minimum wins
+GS_HD uint32_t BC7TexelIndex(const BC7Block& b, const float* px) {
+    float num = 0.0f;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) { const float m = (px[c] - b.e0[c]) * b.axis[c]; num = c == 0 ? m : num + m; }
+    const float tt = num / fmaxf(b.den, 1.0e-6f);
+    uint32_t best = 0;
+    float bd = fabsf(tt - 0.0f);
+#pragma unroll
+    for (uint32_t k = 1; k < 16u; ++k) {
+        const float w = (float)((k * 64u + 7u) / 15u) / 64.0f;      // 0 4 9 13 17 21 26 30 34 38 43 47 51 55 60 64, over 64
+        const float d = fabsf(tt - w);
+        if (d < bd) { bd = d; best = k; }
+    }
+    return best;
+}
+// the 128 bits of the block; nib: the index of texel t (row-major in the block) in bits 4 t .. 4 t + 3.  Texel 0 is the anchor: its index must
+// have the top bit clear, so with an index >= 8 there every index is flipped and the endpoints change places
+GS_HD void BC7Pack(const BC7Block& b, uint64_t nib, uint32_t* w) {
+    const bool flip = (nib & 8u) != 0u;
+    if (flip) nib = ~nib;
+    uint64_t lo = 1ull << 6;
+    uint32_t at = 7;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        lo |= (uint64_t)(uint32_t)(flip ? b.q1[c] : b.q0[c]) << at; at += 7;
+        lo |= (uint64_t)(uint32_t)(flip ? b.q0[c] : b.q1[c]) << at; at += 7;
+    }
+    lo |= (uint64_t)(uint32_t)(flip ? b.p1 : b.p0) << 63;
+    const uint64_t hi = (uint64_t)(uint32_t)(flip ? b.p0 : b.p1) | ((nib & 7ull) << 1) | (nib & ~0xfull);
+    w[0] = (uint32_t)lo; w[1] = (uint32_t)(lo >> 32); w[2] = (uint32_t)hi; w[3] = (uint32_t)(hi >> 32);
+}
+// one block on one thread: px = 16 texels (row-major) x RGBA as BC7Texel gives them
+GS_HD void BC7EncodeMode6(const float (*px)[4], uint32_t* w) {
+    float lo[4], hi[4];
+    for (int c = 0; c < 4; ++c) { lo[c] = hi[c] = px[0][c]; for (int t = 1; t < 16; ++t) { lo[c] = fminf(lo[c], px[t][c]); hi[c] = fmaxf(hi[c], px[t][c]); } }
+    BC7Block b;
+    BC7Endpoints(lo, hi, b);
+    uint64_t nib = 0;
+    for (int t = 0; t < 16; ++t) nib |= (uint64_t)BC7TexelIndex(b, px[t]) << (4 * t);
+    BC7Pack(b, nib, w);
+}
+// where a splat's texel lies among the BC7 blocks: destination records 16 b .. 16 b + 15 of a chunk are one 4 x 4 block (SplatIndexToPixelIndex
+// de-interleaves the low 8 bits), and record bits 0, 2, 1, 3 are the bits of the texel's row-major place inside it
+GS_HD uint32_t BC7TexelOfLane(uint32_t i) { return (i & 9u) | ((i & 4u) >> 1) | ((i & 2u) << 1); }
+GS_HD uint64_t BC7BlockOfSplat(uint32_t i) {
+    uint32_t px, py;
+    SplatIndexToPixelIndex(i, px, py);
+    return (uint64_t)(py >> 2) * 512u + (px >> 2);
+}
+
 // One destination chunk on one thread: the records of its cnt <= 256 splats (already linear) to the bytes of the five blobs at splat index
 // first + k -- what the kernel's workgroup does with one lane per splat, and what the host harness of the tests runs as it stands.  A Cluster* SH
 // target (shIndex: the table index of every record, in destination order) writes the index into `other` and no SH item: the table is the caller's.
@@ -1608,10 +1746,22 @@ GS_HD void BakeEncodeChunkSerial(BakeRec* rec, uint32_t cnt, uint32_t first, con
         uint32_t px, py;
         SplatIndexToPixelIndex((uint32_t)i, px, py);
         BakeEmitColor(o.col, f.color, w);
-        BakeStoreBytes(color + ((uint64_t)py * 2048u + px) * colSz, w, colSz);
+        if (f.color != 3u) BakeStoreBytes(color + ((uint64_t)py * 2048u + px) * colSz, w, colSz);
         if (clustered) continue;
         BakeEmitSH(o.sh, f.sh, w);
         BakeStoreBytes(sh + i * shSz, w, shSz);
+    }
+    if (f.color != 3u) return;
+    for (uint32_t blk = 0; blk < 16u; ++blk) {                     // a BC7 colour target: the chunk's tile is sixteen blocks, a record past cnt a zero texel
+        float px[16][4];
+        for (uint32_t l = 0; l < 16u; ++l) {
+            const uint32_t k = blk * 16u + l;
+            const V4 zero = { 0.0f, 0.0f, 0.0f, 0.0f };
+            BC7Texel(k < cnt ? rec[k].col : zero, px[BC7TexelOfLane(l)]);
+        }
+        uint32_t w[4];
+        BC7EncodeMode6(px, w);
+        BakeStoreBytes(color + BC7BlockOfSplat(first + blk * 16u) * 16u, w, 16u);
     }
 }
 

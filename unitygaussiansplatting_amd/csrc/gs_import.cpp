@@ -10,6 +10,7 @@
 // The one stage that can also run on a GPU is the nearest-mean assignment of the Cluster* SH palette (gs_cluster.hip, through
 // gs_import_encode_on / gs_import_assign_clusters with a context): the same operations in the same order, the same bytes.
 // gs_import_cluster_shs exposes cluster_shs below as it is, and with a context runs the whole of it on the GPU instead (gs_cluster.hip).
+// The whole of import_encode_impl on the GPU, to a device-resident asset holding these bytes, is gs_import_encode_to_asset (gs_bake.hip).
 // Arithmetic is plain IEEE fp32, one rounding per operation (-ffp-contract=off), and the two transcendental steps are
 // written out (exp as Cephes-style range reduction + polynomial, x^(1/8) as three correctly rounded square roots) so that
 // the bytes are a function of this source only: unitygaussiansplatting_amd/creator.py performs the same operations with

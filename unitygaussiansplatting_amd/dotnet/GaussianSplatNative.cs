@@ -171,6 +171,7 @@ namespace GaussianSplatting.Runtime
         [DllImport(Lib)] public static extern int gs_import_cluster_shs(IntPtr ctx, float[] x, ulong n, uint k, [Out] float[] meansOut, [Out] uint[] indexOut);
         [DllImport(Lib)] public static extern int gs_import_encode_on(IntPtr ctx, ref ImportInput input, ref ImportFormats formats, IntPtr[] blobs5, ulong[] sizes5, float[] boundsMin3, float[] boundsMax3);
         [DllImport(Lib)] public static extern int gs_renderer_edit_bake_asset(IntPtr renderer, ref ImportFormats formats, out IntPtr asset, out uint alive, [Out] float[] boundsMin3, [Out] float[] boundsMax3);
+        [DllImport(Lib)] public static extern int gs_import_encode_to_asset(IntPtr ctx, ref ImportInput input, uint memoryKind, ref ImportFormats formats, out IntPtr asset, [Out] float[] boundsMin3, [Out] float[] boundsMax3);
         [DllImport(Lib)] public static extern int gs_asset_download_blobs(IntPtr asset, IntPtr[] blobs5, ulong[] sizes5);
 
         [DllImport(Lib)] public static extern int gs_ply_open([MarshalAs(UnmanagedType.LPStr)] string path, out IntPtr ply, out uint splatCount);

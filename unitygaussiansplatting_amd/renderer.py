@@ -223,7 +223,7 @@ class GpuSorting:
 
 
 class GpuAsset:
-    """A device-resident asset made on the GPU (GaussianSplatRenderer.EditBakeAsset): the native handle, its splat count, its four formats
+    """A device-resident asset made on the GPU (GaussianSplatRenderer.EditBakeAsset, creator.CreateGpuAssetFromSplats): the native handle, its splat count, its four formats
     (pos, scale, color, sh) and the position bounds.  Immutable; owned by this object until Dispose()."""
 
     def __init__(self, ctx: "GpuContext", handle, splatCount: int, formats, boundsMin, boundsMax):
