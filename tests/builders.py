@@ -9,6 +9,7 @@ import os
 
 import numpy as np
 
+import bake_model as BM
 import copy_model as CM
 import edit_model as EM
 import export_model as XM
@@ -168,6 +169,172 @@ def _same(a, b):
     assert np.array_equal(np.asarray(a.boundsMin, np.float32), np.asarray(b.boundsMin, np.float32)), ("boundsMin", a.boundsMin, b.boundsMin)
     assert np.array_equal(np.asarray(a.boundsMax, np.float32), np.asarray(b.boundsMax, np.float32)), ("boundsMax", a.boundsMax, b.boundsMax)
     assert a.dataHash == b.dataHash, ("dataHash", a.dataHash, b.dataHash)
+
+
+# ---- the importer suites: inputs at and beyond the edges ---------------------------------------------------------------------------------------------
+BC7_TARGET = (VF.Norm11, VF.Norm11, CF.BC7, SF.Norm6)              # Medium with BC7 colour
+# the format tuples of the adversarial walks: the bake's targets (every value of the four enums outside BC7 / Cluster*) and three BC7 mixes
+EDGE_FORMATS = BM.FORMAT_TARGETS + [BC7_TARGET, (VF.Norm6, VF.Float32, CF.BC7, SF.Float16), (VF.Norm16, VF.Norm16, CF.BC7, SF.Norm11)]
+EDGE_SEEDS = list(range(1, 13))
+
+
+def adversarial_splats(raw, rng, negative_zero):
+    """raw made adversarial in place: coincident positions (a whole chunk may collapse), scale and opacity logits at, next to and far beyond the
+    clamps of exp / sigmoid ([-87, 88]; 1 / (1 + exp(88)) is a denormal), tied, zero, near-zero and all-zero quaternions, SH and dc0 far outside the
+    Norm clamp and denormals of both signs; -0 only when negative_zero (it breaks the premise of the byte comparisons against the GPU).
+    normalize() gives NaN for the zero quaternion and the reference's own (uint)(NaN * 1023.5f) is unspecified -- GaussianUtils.cs:46-76 picks index 0,
+    GaussianSplatAssetCreator.cs:604-640 casts; every importer here defines the cast as 0"""
+    n = len(raw)
+    pick = lambda frac: rng.random(n) < frac
+    values = lambda *v: np.array(v + ((-0.0,) if negative_zero else ()), f32)
+    m = pick(0.1); raw.pos[m] = raw.pos[rng.integers(n)]
+    m = pick(0.05); raw.scale[m] = rng.choice(np.array([-1000.0, -88.5, -87.0, -30.0, -20.0, 0.0, 3.0, 10.0, 87.5, 88.0, 1000.0], f32), (int(m.sum()), 3))
+    m = pick(0.05); raw.opacity[m] = rng.choice(np.array([-1000.0, -88.0, -87.5, -60.0, -40.0, 0.0, 40.0, 80.0, 88.5, 1000.0], f32), int(m.sum()))
+    m = pick(0.05); raw.rot[m] = rng.choice(np.array([0.5, -0.5, 0.0, 1.0, 1e-20], f32), (int(m.sum()), 4))
+    m = pick(0.02); raw.rot[m] = f32(0.0)
+    m = pick(0.05); raw.sh[m] = rng.choice(values(-8.0, 8.0, 0.25, 1e-40, -1e-40), (int(m.sum()), 15, 3))
+    m = pick(0.05); raw.dc0[m] = rng.choice(values(-6.0, 6.0, 0.0, 1e-39), (int(m.sum()), 3))
+    return raw
+
+
+def without_negative_zero(raw):
+    """every -0 of the six arrays replaced by +0, in place (x == 0 holds for both zeros)"""
+    for x in (raw.pos, raw.dc0, raw.sh, raw.opacity, raw.scale, raw.rot):
+        x[x == 0] = 0
+    return raw
+
+
+def linear_input(raw) -> creator.InputSplatData:
+    """LinearizeData(raw) as an input that meets the premises of linearize = 0 (finite, rot inside its field ranges): the NaN rotation of a zero
+    quaternion is replaced by 0, the value both importers give its fields, and a component that a quaternion of denormal squares leaves a rounding
+    step past 1 is clipped"""
+    with np.errstate(invalid="ignore"):
+        lin = creator.LinearizeData(raw)
+    lin.rot[np.isnan(lin.rot).any(axis=1)] = f32(0.0)
+    np.clip(lin.rot, f32(0.0), f32(1.0), out=lin.rot)
+    return lin
+
+
+@functools.lru_cache(maxsize=None)
+def edge_case(seed: int) -> creator.InputSplatData:
+    """the seeded adversarial input of the walks (host pipeline against the importer on the CPU, the GPU import against the importer): shared and
+    left unchanged"""
+    rng = np.random.default_rng(52_000 + seed)
+    n = int(rng.choice([1, 2, 255, 256, 257, 511, 513, 2_047, 2_049, 4_099]))
+    raw = scenes.make_splats(n, int(rng.integers(1, 1000)), float(rng.choice([0.01, 1.0, 50.0])))
+    raw = without_negative_zero(adversarial_splats(without_negative_zero(raw), rng, negative_zero=False))
+    for x in (raw.pos, raw.dc0, raw.sh, raw.opacity, raw.scale, raw.rot):
+        x.setflags(write=False)
+    return raw
+
+
+def assert_import_premises(raw, linearize) -> None:
+    """what DESIGN.md section 4.11 asks of an input whose GPU import is held to the host importer's bytes"""
+    for a in (raw.pos, raw.dc0, raw.sh, raw.opacity, raw.scale, raw.rot):
+        assert np.isfinite(np.asarray(a)).all()
+    with np.errstate(invalid="ignore"):                            # (the zero quaternion)
+        lin = creator.LinearizeData(raw) if linearize else raw
+    cols = [lin.pos, lin.scale, lin.dc0, lin.opacity, BM.square_centered01(lin.opacity), lin.sh]
+    assert not any((np.signbit(c) & (np.asarray(c) == 0)).any() or np.isnan(c).any() for c in cols)
+    if not linearize:
+        assert (np.asarray(raw.rot) >= 0).all() and (np.asarray(raw.rot) <= 1).all()
+
+
+# ---- the BC7 block set: crafted blocks, random, low-contrast and grey ones, laid into chunks for an importer ------------------------------------------
+def crafted_blocks() -> np.ndarray:
+    """[B, 16, 4] texels in 0..1"""
+    rng = np.random.default_rng(5)
+    out = []
+    out.append(np.zeros((16, 4), f32))                                                            # all zero: 40 00 .. 00
+    for v in (0.25, 1.0, 0.5 / 255.0, 127.5 / 255.0):                                             # all texels equal: den = 0
+        out.append(np.full((16, 4), v, f32))
+    ramp = np.linspace(0.05, 0.95, 16, dtype=f32)
+    out.append(np.repeat(ramp[::-1, None], 4, axis=1).copy())                                     # texel 0 the brightest: the anchor flip
+    out.append(np.repeat(ramp[:, None], 4, axis=1).copy())                                        # texel 0 the darkest: no flip
+    for at in (0, 7, 15):                                                                         # a single differing texel
+        b = np.full((16, 4), 0.3, f32)
+        b[at] = (0.9, 0.1, 0.6, 1.0)
+        out.append(b)
+    steps = (np.arange(0, 511, dtype=f32) * f32(0.5) / f32(255.0)).astype(f32)                    # 0, 0.5 / 255, ..., 1: the p-bit ties
+    for k in range(0, 496, 16):
+        out.append(np.repeat(steps[k:k + 16, None], 4, axis=1).copy())
+    for k in range(0, 500, 25):                                                                   # two-valued blocks half a step apart
+        b = np.full((16, 4), steps[k], f32)
+        b[rng.integers(0, 2, 16).astype(bool)] = steps[k + 3]
+        out.append(b)
+    out.append(rng.integers(0, 2, (16, 4)).astype(f32))                                           # 0 and 1 only
+    return np.stack(out).astype(f32)
+
+
+@functools.lru_cache(maxsize=None)
+def block_set() -> np.ndarray:
+    rng = np.random.default_rng(17)
+    rnd = rng.random((20000, 16, 4)).astype(f32)
+    narrow = (rng.random((4000, 1, 4)) * 0.8 + rng.random((4000, 16, 4)) * 0.2).astype(f32)       # low contrast: the endpoints sit close together
+    gray = np.repeat(rng.random((2000, 16, 1)).astype(f32), 4, axis=2)
+    blocks = np.concatenate([crafted_blocks(), rnd, narrow, gray]).astype(f32)
+    blocks.setflags(write=False)
+    return blocks
+
+
+def bc7_texel_of_lane(lane):
+    """numpy restatement of gsm::BC7TexelOfLane: record bits 0, 2, 1, 3 of a block's sixteen are the bits of the texel's row-major place in it"""
+    lane = np.asarray(lane, np.uint32)
+    return (lane & 9) | ((lane & 4) >> 1) | ((lane & 2) << 1)
+
+
+def bc7_block_offset_of_splat(i):
+    """numpy restatement of gsm::BC7BlockOfSplat x 16: the byte offset in the colour blob of the BC7 block that holds splat i's texel"""
+    at = creator.SplatIndexToTextureIndex(i)
+    px, py = at % 2048, at // 2048
+    return ((py >> 2) * 512 + (px >> 2)) * 16
+
+
+@functools.lru_cache(maxsize=None)
+def block_set_input():
+    """block_set() as an importer's input: fifteen blocks per chunk of 256 splats, morton = 0 so that input order is texel order, and in every chunk
+    a sixteenth block holding a 0 and a 1 in every colour column, so that the chunk normalisation (v - 0) / (1 - 0) leaves every texel as it is.
+    The alpha texel is SquareCentered01(opacity): the input opacity is chosen freely and the texel computed from it (importer_blocks).  Already
+    linear: linearize = 0.  Returns (the InputSplatData, the byte offset in the colour blob of every block of block_set())"""
+    blocks = block_set()
+    nb = len(blocks)
+    chunks = (nb + 14) // 15
+    n = chunks * 256
+    lane_texel = bc7_texel_of_lane(np.arange(16))
+    col = np.full((chunks, 16, 16, 4), 0.5, f32)                   # [chunk, block, lane, rgba]
+    flat = col.reshape(chunks * 16, 16, 4)
+    slots = np.array([c * 16 + b for c in range(chunks) for b in range(15)])[:nb]
+    flat[slots] = blocks[:, lane_texel, :]                        # lane l holds texel lane_texel[l]
+    col[:, 15, 0, :] = 0.0
+    col[:, 15, 1, :] = 1.0
+    col = col.reshape(n, 4)
+    raw = creator.InputSplatData(pos=np.random.default_rng(1).random((n, 3)).astype(f32), dc0=col[:, :3].copy(), sh=np.full((n, 15, 3), 0.5, f32),
+                                 opacity=col[:, 3].copy(), scale=np.full((n, 3), 0.5, f32), rot=np.tile(np.array([0.5, 0.5, 0.5, 1.0], f32), (n, 1)))
+    offs = bc7_block_offset_of_splat(slots * 16).astype(np.int64)
+    offs.setflags(write=False)
+    return raw, offs
+
+
+def blocks_at(asset, offs) -> np.ndarray:
+    """[B, 16] bytes: the BC7 blocks of the asset's colour blob at the byte offsets offs"""
+    return np.ascontiguousarray(np.asarray(asset.colorData, np.uint8)[offs[:, None] + np.arange(16)[None, :]])
+
+
+@functools.lru_cache(maxsize=None)
+def block_set_asset():
+    """the native importer's asset of block_set_input(): shared and left unchanged"""
+    raw, _ = block_set_input()
+    return creator.CreateAssetFromSplatsNative(raw, formatPos=BC7_TARGET[0], formatScale=BC7_TARGET[1], formatColor=BC7_TARGET[2], formatSH=BC7_TARGET[3],
+                                               linearize=False, morton=False)
+
+
+@functools.lru_cache(maxsize=None)
+def importer_blocks():
+    """(the texels of block_set() as the colour texture holds them [B, 16, 4], the importer's [B, 16] bytes of them)"""
+    _, offs = block_set_input()
+    texels = block_set().copy()
+    texels[:, :, 3] = BM.square_centered01(texels[:, :, 3])
+    return np.ascontiguousarray(texels, f32), blocks_at(block_set_asset(), offs)
 
 
 # ---- the golden vectors ---------------------------------------------------------------------------------------------------------------------------

@@ -1,21 +1,22 @@
 """The GPU import on the CPU box: the host build of its arithmetic (tests/import_gpu_host_harness.cpp over csrc/gs_device_math.h: gsm::ImportExpDet,
 gsm::ImportLinearize, gsm::ImportRecord, the BC7 mode-6 block encoder gsm::BC7* as one thread per block and as sixteen lanes per block, and the whole
-pipeline run serially) against the native importer of the built library (gs_import_encode), byte for byte; the C-ABI surface of
+pipeline run serially, on friendly input and on the twelve adversarial inputs that tests/test_gpu_import_edges.py gives the GPU) against the native
+importer of the built library (gs_import_encode), byte for byte; the C-ABI surface of
 gs_import_encode_to_asset; and the harness as a stand-alone program under the host sanitizers."""
 import ctypes as C
-import functools
 
 import numpy as np
 import pytest
 
 import bake_model as BM
+from builders import (BC7_TARGET, EDGE_FORMATS, EDGE_SEEDS, assert_import_premises, bc7_block_offset_of_splat, bc7_texel_of_lane, crafted_blocks, edge_case,
+                      importer_blocks, linear_input)
 from common import _p
 from harness import build_harness, run_under_sanitizers
 from unitygaussiansplatting_amd import _abi, _lib, asset as A, creator, scenes
 
 f32 = np.float32
 VF, CF, SF = A.VectorFormat, A.ColorFormat, A.SHFormat
-BC7_TARGET = (VF.Norm11, VF.Norm11, CF.BC7, SF.Norm6)
 
 
 class ImportSrc(C.Structure):
@@ -70,73 +71,15 @@ def test_entry_point_validates_its_arguments_without_a_device():
 
 
 # ---- 2. the BC7 mode-6 block encoder --------------------------------------------------------------------------------------------------------------
-def crafted_blocks() -> np.ndarray:
-    """[B, 16, 4] texels in 0..1"""
-    rng = np.random.default_rng(5)
-    out = []
-    out.append(np.zeros((16, 4), f32))                                                            # all zero: 40 00 .. 00
-    for v in (0.25, 1.0, 0.5 / 255.0, 127.5 / 255.0):                                             # all texels equal: den = 0
-        out.append(np.full((16, 4), v, f32))
-    ramp = np.linspace(0.05, 0.95, 16, dtype=f32)
-    out.append(np.repeat(ramp[::-1, None], 4, axis=1).copy())                                     # texel 0 the brightest: the anchor flip
-    out.append(np.repeat(ramp[:, None], 4, axis=1).copy())                                        # texel 0 the darkest: no flip
-    for at in (0, 7, 15):                                                                         # a single differing texel
-        b = np.full((16, 4), 0.3, f32)
-        b[at] = (0.9, 0.1, 0.6, 1.0)
-        out.append(b)
-    steps = (np.arange(0, 511, dtype=f32) * f32(0.5) / f32(255.0)).astype(f32)                    # 0, 0.5 / 255, ..., 1: the p-bit ties
-    for k in range(0, 496, 16):
-        out.append(np.repeat(steps[k:k + 16, None], 4, axis=1).copy())
-    for k in range(0, 500, 25):                                                                   # two-valued blocks half a step apart
-        b = np.full((16, 4), steps[k], f32)
-        b[rng.integers(0, 2, 16).astype(bool)] = steps[k + 3]
-        out.append(b)
-    out.append(rng.integers(0, 2, (16, 4)).astype(f32))                                           # 0 and 1 only
-    return np.stack(out).astype(f32)
-
-
-@functools.lru_cache(maxsize=None)
-def block_set() -> np.ndarray:
-    rng = np.random.default_rng(17)
-    rnd = rng.random((20000, 16, 4)).astype(f32)
-    narrow = (rng.random((4000, 1, 4)) * 0.8 + rng.random((4000, 16, 4)) * 0.2).astype(f32)       # low contrast: the endpoints sit close together
-    gray = np.repeat(rng.random((2000, 16, 1)).astype(f32), 4, axis=2)
-    blocks = np.concatenate([crafted_blocks(), rnd, narrow, gray]).astype(f32)
-    blocks.setflags(write=False)
-    return blocks
-
-
-@functools.lru_cache(maxsize=None)
-def importer_blocks(igh):
-    """the blocks the native importer makes of block_set(): fifteen blocks per chunk of 256 splats, morton = 0 so that input order is texel order, and in
-    every chunk a sixteenth block holding a 0 and a 1 in every colour column, so that the chunk normalisation (v - 0) / (1 - 0) leaves every texel as
-    it is.  The alpha texel is SquareCentered01(opacity): the input opacity is chosen freely and the texel computed from it.  Returns (texels as the
-    colour texture holds them [B, 16, 4], the importer's [B, 16] bytes)"""
-    blocks = block_set()
-    nb = len(blocks)
-    chunks = (nb + 14) // 15
-    n = chunks * 256
-    lane_texel = np.array([igh.igh_bc7_texel_of_lane(l) for l in range(16)])
-    col = np.full((chunks, 16, 16, 4), 0.5, f32)                   # [chunk, block, lane, rgba]
-    flat = col.reshape(chunks * 16, 16, 4)
-    slots = np.array([c * 16 + b for c in range(chunks) for b in range(15)])[:nb]
-    flat[slots] = blocks[:, lane_texel, :]                        # lane l holds texel lane_texel[l]
-    col[:, 15, 0, :] = 0.0
-    col[:, 15, 1, :] = 1.0
-    col = col.reshape(n, 4)
-    raw = creator.InputSplatData(pos=np.random.default_rng(1).random((n, 3)).astype(f32), dc0=col[:, :3].copy(), sh=np.full((n, 15, 3), 0.5, f32),
-                                 opacity=col[:, 3].copy(), scale=np.full((n, 3), 0.5, f32), rot=np.tile(np.array([0.5, 0.5, 0.5, 1.0], f32), (n, 1)))
-    a = creator.CreateAssetFromSplatsNative(raw, formatPos=BC7_TARGET[0], formatScale=BC7_TARGET[1], formatColor=BC7_TARGET[2], formatSH=BC7_TARGET[3],
-                                            linearize=False, morton=False)
-    texels = blocks.copy()
-    texels[:, :, 3] = BM.square_centered01(blocks[:, :, 3])
-    offs = np.array([igh.igh_bc7_block_of_splat(int(s) * 16) for s in slots], np.int64)
-    got = a.colorData[offs[:, None] + np.arange(16)[None, :]]
-    return np.ascontiguousarray(texels, f32), np.ascontiguousarray(got, np.uint8)
+def test_block_places_of_the_builders_are_the_headers(igh):
+    """tests/builders.py lays the block set out with numpy restatements of gsm::BC7TexelOfLane and gsm::BC7BlockOfSplat"""
+    assert [igh.igh_bc7_texel_of_lane(l) for l in range(16)] == bc7_texel_of_lane(np.arange(16)).tolist()
+    at = np.concatenate([np.arange(0, 70000, 16), np.arange(440000, 446000)]).astype(np.uint32)
+    assert [igh.igh_bc7_block_of_splat(int(i)) for i in at] == bc7_block_offset_of_splat(at).tolist()
 
 
 def test_bc7_blocks_equal_the_importers(igh):
-    texels, want = importer_blocks(igh)
+    texels, want = importer_blocks()
     nb = len(texels)
     assert nb >= 20000 + len(crafted_blocks())
     got, flags = np.zeros((nb, 16), np.uint8), np.zeros(nb, np.uint32)
@@ -153,7 +96,7 @@ def test_bc7_blocks_equal_the_importers(igh):
 
 
 def test_bc7_sixteen_lane_formulation_gives_the_same_blocks(igh):
-    texels, want = importer_blocks(igh)
+    texels, want = importer_blocks()
     got = np.zeros((len(texels), 16), np.uint8)
     igh.igh_bc7_blocks_lanes(_p(texels), C.c_uint32(len(texels)), _p(got))
     bad = np.flatnonzero((got != want).any(axis=1))
@@ -247,6 +190,31 @@ def test_serial_pipeline_equals_the_importer_clustered(igh, quality, linearize):
     raw = input_of(4500, linearize)
     formats = creator.QUALITY["VeryLow"] if quality == "VeryLow" else creator.QUALITY["Low"][:3] + (SF.Cluster4k,)
     BM.assert_same_asset(host_import(igh, raw, formats, linearize), want_of(raw, formats, linearize), (quality, linearize))
+
+
+# the adversarial walk: the yardstick's side of tests/test_gpu_import_edges.py, held without a GPU
+@pytest.mark.parametrize("seed", EDGE_SEEDS)
+def test_serial_pipeline_equals_the_importer_on_adversarial_input(igh, seed):
+    raw = edge_case(seed)
+    for linearize in (True, False):
+        src = raw if linearize else linear_input(raw)
+        assert_import_premises(src, linearize)
+        for morton in (True, False):
+            for formats in EDGE_FORMATS:
+                BM.assert_same_asset(host_import(igh, src, formats, linearize, morton), want_of(src, formats, linearize, morton), (seed, formats, linearize, morton))
+
+
+def test_adversarial_inputs_hold_what_they_are_there_for():
+    raws = [edge_case(seed) for seed in EDGE_SEEDS]
+    rot, opacity, scale, sh = (np.concatenate([np.asarray(getattr(r, name)).reshape(len(r), -1) for r in raws]) for name in ("rot", "opacity", "scale", "sh"))
+    assert (rot == 0).all(axis=1).any()                            # the zero quaternion: normalize() divides by 0
+    low = opacity[opacity <= -88]
+    lin = creator.Sigmoid(low)
+    tiny = np.finfo(f32).tiny
+    assert len(low) and ((lin > 0) & (lin < tiny)).any()            # 1 / (1 + exp(88)): the sigmoid's division lands in the denormals
+    assert (scale < -87).any() and (scale > 88).any()              # both sides of exp's clamp
+    assert ((sh != 0) & (np.abs(sh) < tiny)).any()                 # an SH denormal
+    assert len({len(r) for r in raws}) >= 4                        # several of the sizes around the chunk boundaries
 
 
 def test_bc7_tiles_past_the_last_chunk_hold_the_zero_block(igh):
