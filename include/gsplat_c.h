@@ -600,6 +600,41 @@ int32_t gs_spz_open(const char* path, gs_ply** out, uint32_t* splat_count);
 int32_t gs_ply_arrays(const gs_ply* ply, gs_import_input* out);
 int32_t gs_ply_close(gs_ply* ply);
 
+/* ---- a PLY or SPZ file straight into a device asset on the GPU (additions to ABI 9) ------------------------------------------------------
+ * gs_splat_file_open reads and checks the file the way gs_ply_open / gs_spz_open do -- the same header rules, the same error code and the same
+ * gs_last_error_string text for every file either of them refuses -- but builds no arrays: of a PLY it keeps the stream, positioned at the vertex
+ * rows, after holding the file's length against splat_count x stride; of an SPZ the gunzipped stream in host memory.  Host only: no GPU is touched.
+ * The kind is chosen by the path's extension, .ply / .spz in any letter case (GaussianFileReader.ReadFile); any other is GS_ERR_INVALID_ASSET.
+ * offsets[]: where in a vertex row each float property lies, in bytes: x y z, f_dc_0..2, opacity, scale_0..2, rot_0..3, f_rest_0..44 -- the 59 the
+ * importer reads -- then nx ny nz, which it does not; -1 = absent (a f_rest_k then reads as 0).  The file's own order: properties may come in any
+ * order with foreign ones between them.  An SPZ has stride 0 and every offset -1. */
+#define GS_SPLAT_FILE_PLY 1u
+#define GS_SPLAT_FILE_SPZ 2u
+typedef struct gs_splat_file gs_splat_file;
+typedef struct gs_splat_file_info {
+    uint32_t kind;          /* GS_SPLAT_FILE_PLY / GS_SPLAT_FILE_SPZ */
+    uint32_t splat_count;
+    uint32_t stride;        /* PLY: bytes per vertex row */
+    uint32_t sh_level;      /* SPZ: 0..3 */
+    uint32_t fract_bits;    /* SPZ: 0..24 */
+    uint32_t reserved;
+    uint64_t body_bytes;    /* what goes to the GPU: PLY splat_count x stride; SPZ the header + the six columns of the gunzipped stream */
+    int32_t offsets[62];
+} gs_splat_file_info;
+int32_t gs_splat_file_open(const char* path, gs_splat_file** out, gs_splat_file_info* info /* may be NULL */);
+int32_t gs_splat_file_close(gs_splat_file* file);
+/* The file's bytes to the GPU and from there to a new asset owned by ctx, with the rows / columns themselves as the importer's source: the asset --
+ * five blobs and bounds -- that gs_import_encode_to_asset makes of gs_ply_open / gs_spz_open + gs_ply_arrays of the same file, byte for byte, under
+ * that function's premises.  formats->linearize must be the kind's value, 1 for a PLY and 0 for an SPZ.
+ * A PLY's rows go to one transient device buffer of body_bytes through two pinned slices of slice_bytes (0 = 64 MiB; never more than the body
+ * needs), filled alternately: the file is read into one while the other's copy is in flight, so the host holds two slices whatever the file's
+ * size.  An SPZ's gunzipped stream is uploaded as it is.  A file that ends early is gs_ply_open's "fewer data bytes" error.
+ * The handle may be imported any number of times.  BLOCKS; runs on the context's stream after gs_context_synchronize.
+ * Refused with GS_ERR_INVALID_ARGUMENT, *out NULL and nothing left allocated: a NULL ctx, file, formats or out; a handle that is not open; a
+ * linearize of the other kind; morton > 1; slice_bytes in 1..4095; whatever gs_import_blob_sizes refuses. */
+int32_t gs_import_file_to_asset(gs_context* ctx, gs_splat_file* file, const gs_import_formats* formats, uint32_t slice_bytes, gs_asset** out,
+                                float bounds_min[3], float bounds_max[3]);
+
 /* ---- stand-alone sorter: GpuSorting (GpuSorting.cs) ----------------------------------------------- */
 /* SupportResources.Load(count) :48-63 */
 int32_t gs_sorter_create(gs_context* ctx, uint32_t max_count, gs_sorter** out);

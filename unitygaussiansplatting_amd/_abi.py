@@ -75,6 +75,18 @@ class gs_import_formats(C.Structure):
                 ("linearize", C.c_uint32), ("morton", C.c_uint32)]
 
 
+GS_SPLAT_FILE_PLY = 1
+GS_SPLAT_FILE_SPZ = 2
+# gs_splat_file_info.offsets by name: the 59 float properties the importer reads, then the normals
+PLY_OFFSET_NAMES = (["x", "y", "z", "f_dc_0", "f_dc_1", "f_dc_2", "opacity", "scale_0", "scale_1", "scale_2", "rot_0", "rot_1", "rot_2", "rot_3"]
+                    + [f"f_rest_{k}" for k in range(45)] + ["nx", "ny", "nz"])
+
+
+class gs_splat_file_info(C.Structure):   # what gs_splat_file_open found in the file
+    _fields_ = [("kind", C.c_uint32), ("splat_count", C.c_uint32), ("stride", C.c_uint32), ("sh_level", C.c_uint32), ("fract_bits", C.c_uint32),
+                ("reserved", C.c_uint32), ("body_bytes", C.c_uint64), ("offsets", C.c_int32 * 62)]
+
+
 class gs_frame_stats(C.Structure):
     _fields_ = [("tile_pairs", C.c_uint64), ("pair_capacity", C.c_uint64), ("visible_splats", C.c_uint32),
                 ("tiles_x", C.c_uint32), ("tiles_y", C.c_uint32), ("sort_error", C.c_uint32), ("tile_w", C.c_uint32), ("tile_h", C.c_uint32),

@@ -7,7 +7,7 @@ import ctypes as C
 import os
 
 from ._abi import (gs_asset_desc, gs_copy_params, gs_cutout, gs_edit_info, gs_export_params, gs_frame_params, gs_frame_stats, gs_import_formats, gs_import_input,
-                   gs_stage_times)
+                   gs_splat_file_info, gs_stage_times)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GSPLAT_LIB") or os.path.join(_HERE, "libgsplat_hip.so")   # GSPLAT_LIB: A/B a variant build
@@ -125,6 +125,9 @@ SIGNATURES = {
     "gs_spz_open": (C.c_int32, [C.c_char_p, _PP, C.POINTER(C.c_uint32)]),
     "gs_ply_arrays": (C.c_int32, [_P, C.POINTER(gs_import_input)]),
     "gs_ply_close": (C.c_int32, [_P]),
+    "gs_splat_file_open": (C.c_int32, [C.c_char_p, _PP, C.POINTER(gs_splat_file_info)]),
+    "gs_splat_file_close": (C.c_int32, [_P]),
+    "gs_import_file_to_asset": (C.c_int32, [_P, _P, C.POINTER(gs_import_formats), C.c_uint32, _PP, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "gs_sorter_create": (C.c_int32, [_P, C.c_uint32, _PP]),
     "gs_sorter_destroy": (C.c_int32, [_P]),
     "gs_sorter_dispatch": (C.c_int32, [_P, _P, _P, C.c_uint32, C.c_uint32]),

@@ -620,6 +620,35 @@ def CreateGpuAssetFromSplats(raw, quality: str = "Medium", *, formatPos=None, fo
     return GpuAsset(context, h, n, (fmt.pos_format, fmt.scale_format, fmt.color_format, fmt.sh_format), tuple(bmin), tuple(bmax))
 
 
+def CreateGpuAssetFromFile(path: str, quality: str = "Medium", *, formatPos=None, formatScale=None, formatColor=None, formatSH=None,
+                           morton: bool = True, slice_bytes: int = 0, context):
+    """A .ply / .spz file straight into a renderer.GpuAsset on the context's GPU (gs_splat_file_open + gs_import_file_to_asset, csrc/gs_bake.hip):
+    the file's own bytes are the importer's source -- a PLY's vertex rows as they lie in the file, uploaded through two pinned slices of slice_bytes
+    (0 = 64 MiB), an SPZ's gunzipped columns -- and the six arrays of InputSplatData are never built.  The asset holds the bytes
+    CreateGpuAssetFromSplats makes of ReadPLYNative / ReadSPZNative of the same file (PLY data is linearised, SPZ data already is).  A file either
+    reader refuses raises the same GsError.  Blocks."""
+    import ctypes as C
+    from . import _lib
+    from ._abi import GS_SPLAT_FILE_PLY, gs_import_formats, gs_splat_file_info
+    from .renderer import GpuAsset
+    fp, fs, fc, fsh = QUALITY[quality]
+    fp = VectorFormat(fp if formatPos is None else formatPos)
+    fs = VectorFormat(fs if formatScale is None else formatScale)
+    fc = ColorFormat(fc if formatColor is None else formatColor)
+    fsh = SHFormat(fsh if formatSH is None else formatSH)
+    l = _lib.lib()
+    f, info = C.c_void_p(), gs_splat_file_info()
+    _lib.check(l.gs_splat_file_open(path.encode("utf-8"), C.byref(f), C.byref(info)), "gs_splat_file_open")
+    try:
+        fmt = gs_import_formats(int(fp), int(fs), int(fc), int(fsh), 1 if info.kind == GS_SPLAT_FILE_PLY else 0, int(bool(morton)))
+        h = C.c_void_p()
+        bmin, bmax = (C.c_float * 3)(), (C.c_float * 3)()
+        _lib.check(l.gs_import_file_to_asset(context._h, f, C.byref(fmt), int(slice_bytes), C.byref(h), bmin, bmax), "gs_import_file_to_asset")
+    finally:
+        l.gs_splat_file_close(f)
+    return GpuAsset(context, h, info.splat_count, (fmt.pos_format, fmt.scale_format, fmt.color_format, fmt.sh_format), tuple(bmin), tuple(bmax))
+
+
 def AssignClusters(x, means, context=None) -> np.ndarray:
     """Index of the nearest of `means` [K,45] for every row of `x` [N,45] (fp32 in, distances in float64 as ClusterSHs' assign; first
     minimum) through gs_import_assign_clusters: the native host loop, or with context = a renderer.GpuContext the HIP kernel of

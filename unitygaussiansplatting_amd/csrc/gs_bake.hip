@@ -29,9 +29,14 @@
 // host's), linearised on the fly by gsm::ImportRecord -- and step 1 is then only the bounds: every input splat is alive.  That route accepts a BC7
 // colour target: bake_encode_kernel<Src, true> compresses a chunk's 16 x 16 tile in place as sixteen mode-6 blocks, sixteen lanes (one DPP row) per
 // block, and writes the texture's tiles behind the last chunk as the encoding of an all-zero block.  The bake itself still refuses BC7.
+//
+// gs_import_file_to_asset is that import straight from a file: two more sources, BakePlyRowsSource and BakeSpzSource, read a
+// PLY's vertex rows as they lie in the file and an SPZ's gunzipped columns from one transient device buffer (gsm::PlyRowRecord / gsm::SpzRecord: the
+// host readers' transpose, linearise and unpack per splat), so that the six arrays are never built; a PLY's rows get there through two pinned slices.
 #include <new>
 
 #include "gs_common.h"
+#include "gs_splat_file.h"
 
 namespace gs {
 
@@ -67,6 +72,18 @@ struct BakeArraySource {
     gsm::ImportSrc in; uint32_t linearize;
     __device__ __forceinline__ gsm::V3 position(uint32_t j) const { return { in.pos[(size_t)j * 3u], in.pos[(size_t)j * 3u + 1u], in.pos[(size_t)j * 3u + 2u] }; }
     __device__ __forceinline__ void record(uint32_t j, gsm::BakeRec& rec) const { gsm::ImportRecord(in, j, linearize, rec); }
+};
+// A file's own bytes in device memory (gs_import_file_to_asset): BakePlyRowsSource, vertex row j of a PLY as it lies in the file, through the table
+// of property offsets; BakeSpzSource, point j of an SPZ's gunzipped columns.  What the host readers do to build the six arrays happens per splat here
+struct BakePlyRowsSource {
+    gsm::PlyRowSrc s;
+    __device__ __forceinline__ gsm::V3 position(uint32_t j) const { return gsm::PlyRowPosition(s, j); }
+    __device__ __forceinline__ void record(uint32_t j, gsm::BakeRec& rec) const { gsm::PlyRowRecord(s, j, rec); }
+};
+struct BakeSpzSource {
+    gsm::SpzSrc s;
+    __device__ __forceinline__ gsm::V3 position(uint32_t j) const { return gsm::SpzPosition(s, j); }
+    __device__ __forceinline__ void record(uint32_t j, gsm::BakeRec& rec) const { gsm::SpzRecord(s, j, rec); }
 };
 
 // alive[base[chunk] + rank] = idx for the alive splats of source chunk blockIdx.x; partial[chunk][0..2 / 3..5] = min / max of their positions
@@ -110,6 +127,33 @@ __global__ __launch_bounds__(256) void bake_array_bounds_kernel(const float* __r
     __syncthreads();
     if (threadIdx.x < 3u) partial[blockIdx.x * 6u + threadIdx.x] = fminf(fminf(s_red[0][threadIdx.x], s_red[1][threadIdx.x]), fminf(s_red[2][threadIdx.x], s_red[3][threadIdx.x]));
     else if (threadIdx.x < 6u) partial[blockIdx.x * 6u + threadIdx.x] = fmaxf(fmaxf(s_red[0][threadIdx.x], s_red[1][threadIdx.x]), fmaxf(s_red[2][threadIdx.x], s_red[3][threadIdx.x]));
+}
+
+// the same partials for any source whose every splat is alive: the pre-pass as a template over Src::position
+template <class Src>
+__global__ __launch_bounds__(256) void bake_source_bounds_kernel(Src src, uint32_t n, float* __restrict__ partial) {
+    __shared__ float s_red[4][6];
+    const uint32_t idx = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const bool mine = idx < n;
+    const float inf = gsm::u2f(0x7f800000u);
+    const gsm::V3 pos = mine ? src.position(idx) : gsm::V3{ 0.0f, 0.0f, 0.0f };
+    const float p[3] = { pos.x, pos.y, pos.z };
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float mn = wave_min(mine ? p[c] : inf), mx = wave_max(mine ? p[c] : -inf);
+        if (lane == 0u) { s_red[wave][c] = mn; s_red[wave][3 + c] = mx; }
+    }
+    __syncthreads();
+    if (threadIdx.x < 3u) partial[blockIdx.x * 6u + threadIdx.x] = fminf(fminf(s_red[0][threadIdx.x], s_red[1][threadIdx.x]), fminf(s_red[2][threadIdx.x], s_red[3][threadIdx.x]));
+    else if (threadIdx.x < 6u) partial[blockIdx.x * 6u + threadIdx.x] = fmaxf(fmaxf(s_red[0][threadIdx.x], s_red[1][threadIdx.x]), fmaxf(s_red[2][threadIdx.x], s_red[3][threadIdx.x]));
+}
+// the pre-pass of a source: the six arrays keep the kernel over their positions array as it is
+static void bake_launch_source_bounds(hipStream_t st, const BakeArraySource& src, uint32_t n, float* partial) {
+    hipLaunchKernelGGL(bake_array_bounds_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, src.in.pos, n, partial);
+}
+template <class Src>
+static void bake_launch_source_bounds(hipStream_t st, const Src& src, uint32_t n, float* partial) {
+    hipLaunchKernelGGL(bake_source_bounds_kernel<Src>, dim3((n + 255u) / 256u), dim3(256), 0, st, src, n, partial);
 }
 
 // bounds[0..2 / 3..5] = min / max over the partials; one workgroup
@@ -513,6 +557,40 @@ static int32_t bake_impl(gs_renderer* r, const gs_import_formats* f, gs_asset** 
     return GS_OK;
 }
 
+// What every import does once its source lies in device memory: the per-workgroup bounds partials + the bake's fold, steps 2 and 3 as the bake runs
+// them, bake_finish.  Whatever fails, the stream is drained before this returns: the caller's upload may still be in flight.  ev: null, or six events
+// -- 3 after the bounds, 4 / 5 by bake_enqueue_from
+template <class Src>
+static int32_t import_from_source(gs_context* ctx, const Src& src, const gs_import_formats* f, uint32_t total, const uint64_t need[5], BakeRun& run, gs_asset** out,
+                                  float bounds_min[3], float bounds_max[3], Event* ev, const hipEvent_t* cev) {
+    hipStream_t st = ctx->stream;
+    const uint32_t blocks = (total + 255u) / 256u;
+    {
+        const int32_t rcAlloc = [&]() -> int32_t { GS_HIP(run.partial.alloc((size_t)blocks * 6 * 4)); return bake_run_alloc(ctx, f, run, total); }();
+        if (rcAlloc != GS_OK) { (void)hipStreamSynchronize(st); return rcAlloc; }       // (the uploads may still be in flight)
+    }
+    gs_asset* a = nullptr;
+    {
+        const int32_t rcAsset = bake_asset_alloc(ctx, need, &a);
+        if (rcAsset != GS_OK) { (void)hipStreamSynchronize(st); return rcAsset; }
+    }
+    int32_t rc = [&]() -> int32_t {
+        bake_launch_source_bounds(st, src, total, run.partial.get());
+        hipLaunchKernelGGL(bake_bounds_kernel, dim3(1), dim3(kBakeReduceThreads), 0, st, (const float*)run.partial.get(), blocks, run.bounds.get());
+        GS_HIP(hipGetLastError());
+        if (ev) GS_HIP(hipEventRecord(ev[3], st));
+        return bake_enqueue_from(ctx, src, f, run, total, bake_dst_of(a, total, f), need[2], ev, cev);
+    }();
+    float hostBounds[6] = { 0, 0, 0, 0, 0, 0 };
+    GS_TRY(bake_finish(ctx, rc, run, f, a, total, hostBounds));
+    for (int c = 0; c < 3; ++c) {
+        if (bounds_min) bounds_min[c] = hostBounds[c];
+        if (bounds_max) bounds_max[c] = hostBounds[3 + c];
+    }
+    *out = a;
+    return GS_OK;
+}
+
 // gs_import_encode_to_asset: the importer's pipeline with the six raw arrays as the source.  memory_kind 0 copies them into transient device buffers
 // (N x 236 bytes) first; then per-workgroup bounds partials + the bake's fold, and steps 2 and 3 as the bake runs them.  One stream; everything
 // transient is freed when the call returns.  ev: null, or six events -- 0 / 1 around the upload, 3 after the bounds, 4 / 5 by bake_enqueue_from
@@ -542,31 +620,99 @@ static int32_t import_impl(gs_context* ctx, const gs_import_input* in, uint32_t 
         for (int k = 0; k < 6; ++k) arrays[k] = up[k].get();
     }
     if (ev) GS_HIP(hipEventRecord(ev[1], st));
-    const uint32_t blocks = (total + 255u) / 256u;
-    {
-        const int32_t rcAlloc = [&]() -> int32_t { GS_HIP(run.partial.alloc((size_t)blocks * 6 * 4)); return bake_run_alloc(ctx, f, run, total); }();
-        if (rcAlloc != GS_OK) { (void)hipStreamSynchronize(st); return rcAlloc; }       // (the uploads may still be in flight)
-    }
-    gs_asset* a = nullptr;
-    {
-        const int32_t rcAsset = bake_asset_alloc(ctx, need, &a);
-        if (rcAsset != GS_OK) { (void)hipStreamSynchronize(st); return rcAsset; }
-    }
     const BakeArraySource src = { { arrays[0], arrays[1], arrays[2], arrays[3], arrays[4], arrays[5] }, f->linearize };
-    int32_t rc = [&]() -> int32_t {
-        hipLaunchKernelGGL(bake_array_bounds_kernel, dim3(blocks), dim3(256), 0, st, arrays[0], total, run.partial.get());
-        hipLaunchKernelGGL(bake_bounds_kernel, dim3(1), dim3(kBakeReduceThreads), 0, st, (const float*)run.partial.get(), blocks, run.bounds.get());
-        GS_HIP(hipGetLastError());
-        if (ev) GS_HIP(hipEventRecord(ev[3], st));
-        return bake_enqueue_from(ctx, src, f, run, total, bake_dst_of(a, total, f), need[2], ev, cev);
-    }();
-    float hostBounds[6] = { 0, 0, 0, 0, 0, 0 };
-    GS_TRY(bake_finish(ctx, rc, run, f, a, total, hostBounds));
-    for (int c = 0; c < 3; ++c) {
-        if (bounds_min) bounds_min[c] = hostBounds[c];
-        if (bounds_max) bounds_max[c] = hostBounds[3 + c];
+    return import_from_source(ctx, src, f, total, need, run, out, bounds_min, bounds_max, ev, cev);
+}
+
+// the pinned slice of a PLY upload when the caller names none, and the smallest one it may name
+constexpr size_t kFileSliceDefault = (size_t)64 << 20, kFileSliceMin = 4096;
+
+// A PLY's vertex rows from the file's stream to dev[0, bytes) through two pinned slices, filled alternately: fread into one while the other's copy is
+// in flight; the slice's event says when it may be refilled.  Whatever happens, the stream is drained before the slices are freed
+static int32_t upload_ply_rows(hipStream_t st, gs_splat_file* file, uint8_t* dev, size_t bytes, size_t slice) {
+    if (fseeko(file->f, file->bodyAt, SEEK_SET) != 0) return fail(GS_ERR_INVALID_ASSET, "PLY read error: the file cannot be positioned at its vertex rows");
+    PinnedBuf<uint8_t> pin[2];
+    Event refill[2];
+    for (int k = 0; k < 2; ++k) {
+        GS_HIP(pin[k].alloc(slice, hipHostMallocDefault));
+        GS_HIP(refill[k].create(hipEventDisableTiming));
     }
-    *out = a;
+    int32_t rc = GS_OK;
+    size_t done = 0;
+    for (uint32_t turn = 0; done < bytes && rc == GS_OK; ++turn) {
+        const int k = (int)(turn & 1u);
+        const size_t want = bytes - done < slice ? bytes - done : slice;
+        hipError_t he = turn >= 2u ? hipEventSynchronize(refill[k]) : hipSuccess;       // the copy out of this slice two turns ago
+        if (he == hipSuccess) {
+            if (fread(pin[k].get(), 1, want, file->f) != want) { rc = fail(GS_ERR_INVALID_ASSET, "PLY read error: fewer data bytes than the header announces"); break; }
+            he = hipMemcpyAsync(dev + done, pin[k].get(), want, hipMemcpyHostToDevice, st);
+        }
+        if (he == hipSuccess) he = hipEventRecord(refill[k], st);
+        if (he != hipSuccess) rc = fail_hip(he, "import: upload the vertex rows", __FILE__, __LINE__);
+        done += want;
+    }
+    (void)hipStreamSynchronize(st);                                 // before the slices are freed
+    return rc;
+}
+
+// gs_import_file_to_asset: the importer's pipeline with the file's own bytes as the source.  The body goes to one transient device buffer (a PLY's
+// rows through upload_ply_rows, an SPZ's gunzipped stream as it is), then import_from_source with BakePlyRowsSource / BakeSpzSource.  One stream;
+// everything transient is freed when the call returns.  ev: null, or six events -- 0 / 1 around the upload, the rest as in import_impl
+static int32_t import_file_impl(gs_context* ctx, gs_splat_file* file, const gs_import_formats* f, uint32_t slice_bytes, gs_asset** out, float bounds_min[3],
+                                float bounds_max[3], Event* ev = nullptr, const hipEvent_t* cev = nullptr) {
+    if (out) *out = nullptr;
+    if (!ctx || !file || !f || !out) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
+    if (!splat_file_is_open(file)) return fail(GS_ERR_INVALID_ARGUMENT, "not an open splat file handle");
+    const gs_splat_file_info& fi = file->info;
+    const bool ply = fi.kind == GS_SPLAT_FILE_PLY;
+    if (f->linearize != (ply ? 1u : 0u)) return fail(GS_ERR_INVALID_ARGUMENT, "import: linearize must be 1 for a PLY file and 0 for an SPZ file");
+    if (f->morton > 1) return fail(GS_ERR_INVALID_ARGUMENT, "import: morton must be 0 or 1");
+    if (slice_bytes != 0u && slice_bytes < kFileSliceMin) return fail(GS_ERR_INVALID_ARGUMENT, "import: slice_bytes must be 0 or at least 4096");
+    const uint32_t total = fi.splat_count;
+    uint64_t need[5];
+    GS_TRY(gs_import_blob_sizes(total, f, need));               // (an enum out of range, a Cluster* target with too few splats)
+    GS_HIP(hipSetDevice(ctx->device));
+    GS_TRY(gs_context_synchronize(ctx));                        // the sorts need the GPU the way the bake's do
+    hipStream_t st = ctx->stream;
+    BakeRun run;
+    DevBuf<uint8_t> body;
+    const size_t bytes = (size_t)fi.body_bytes;
+    GS_HIP(body.alloc(bytes));
+    if (ev) GS_HIP(hipEventRecord(ev[0], st));
+    if (ply) {
+        size_t slice = slice_bytes ? (size_t)slice_bytes : kFileSliceDefault;
+        const size_t whole = (bytes + kFileSliceMin - 1) / kFileSliceMin * kFileSliceMin;      // no slice larger than the body needs
+        if (slice > whole) slice = whole;
+        GS_TRY(upload_ply_rows(st, file, body.get(), bytes, slice));
+    } else {
+        const hipError_t he = hipMemcpyAsync(body.get(), file->raw.data(), bytes, hipMemcpyHostToDevice, st);
+        if (he != hipSuccess) { (void)hipStreamSynchronize(st); return fail_hip(he, "import: upload", __FILE__, __LINE__); }
+    }
+    if (ev) {
+        const hipError_t he = hipEventRecord(ev[1], st);
+        if (he != hipSuccess) { (void)hipStreamSynchronize(st); return fail_hip(he, "import: event", __FILE__, __LINE__); }
+    }
+    if (ply) {
+        BakePlyRowsSource src;
+        src.s.rows = body.get(); src.s.stride = fi.stride;
+        for (int k = 0; k < gsm::kPlyOffsets; ++k) src.s.off[k] = fi.offsets[k];
+        gsm::PlyRowLayout(src.s);                                   // dword loads where everything is aligned, the INRIA layout's merged ones where it is that
+        return import_from_source(ctx, src, f, total, need, run, out, bounds_min, bounds_max, ev, cev);
+    }
+    const BakeSpzSource src = { { body.get(), total, fi.sh_level == 1u ? 3u : (fi.sh_level == 2u ? 8u : (fi.sh_level == 3u ? 15u : 0u)), fi.fract_bits } };
+    return import_from_source(ctx, src, f, total, need, run, out, bounds_min, bounds_max, ev, cev);
+}
+
+// the events of a finished import as the five stage times the timing scripts report
+static int32_t import_stage_times(const gs_import_formats* formats, const Event* ev, const hipEvent_t* cev, float ms[5]) {
+    const bool palette = formats->sh_format > GS_SH_NORM6;
+    GS_HIP(hipEventElapsedTime(&ms[0], ev[0], ev[1]));
+    GS_HIP(hipEventElapsedTime(&ms[1], ev[1], ev[3]));
+    GS_HIP(hipEventElapsedTime(&ms[2], ev[3], ev[4]));
+    ms[3] = 0.0f;
+    if (palette) GS_HIP(hipEventElapsedTime(&ms[3], cev[0], cev[10]));
+    if (palette) GS_HIP(hipEventElapsedTime(&ms[4], cev[10], cev[11]));
+    else GS_HIP(hipEventElapsedTime(&ms[4], ev[4], ev[5]));
     return GS_OK;
 }
 
@@ -583,6 +729,11 @@ int32_t gs_renderer_edit_bake_asset(gs_renderer* r, const gs_import_formats* for
 int32_t gs_import_encode_to_asset(gs_context* ctx, const gs_import_input* in, uint32_t memory_kind, const gs_import_formats* formats, gs_asset** out,
                                   float bounds_min[3], float bounds_max[3]) {
     return import_impl(ctx, in, memory_kind, formats, out, bounds_min, bounds_max);
+}
+
+int32_t gs_import_file_to_asset(gs_context* ctx, gs_splat_file* file, const gs_import_formats* formats, uint32_t slice_bytes, gs_asset** out,
+                                float bounds_min[3], float bounds_max[3]) {
+    return import_file_impl(ctx, file, formats, slice_bytes, out, bounds_min, bounds_max);
 }
 
 int32_t gs_asset_download_blobs(const gs_asset* asset, void* const blobs[5], const uint64_t sizes[5]) {
@@ -647,15 +798,23 @@ __attribute__((visibility("default"))) int32_t gs_import_gpu_stage_times_for_scr
     gs_asset* a = nullptr;
     GS_TRY(import_impl(ctx, in, memory_kind, formats, &a, nullptr, nullptr, ev, cev));
     (void)gs_asset_destroy(a);
-    const bool palette = formats->sh_format > GS_SH_NORM6;
-    GS_HIP(hipEventElapsedTime(&ms[0], ev[0], ev[1]));
-    GS_HIP(hipEventElapsedTime(&ms[1], ev[1], ev[3]));
-    GS_HIP(hipEventElapsedTime(&ms[2], ev[3], ev[4]));
-    ms[3] = 0.0f;
-    if (palette) GS_HIP(hipEventElapsedTime(&ms[3], cev[0], cev[10]));
-    if (palette) GS_HIP(hipEventElapsedTime(&ms[4], cev[10], cev[11]));
-    else GS_HIP(hipEventElapsedTime(&ms[4], ev[4], ev[5]));
-    return GS_OK;
+    return import_stage_times(formats, ev, cev, ms);
+}
+
+// The same for scripts/import_file_timing.py: one whole gs_import_file_to_asset whose asset is destroyed again; ms[0] is then the upload of the file's
+// bytes, for a PLY with the reads of the file it overlaps.
+__attribute__((visibility("default"))) int32_t gs_import_file_stage_times_for_scripts(gs_context* ctx, gs_splat_file* file, const gs_import_formats* formats,
+                                                                                      uint32_t slice_bytes, float ms[5]) {
+    if (!ctx || !file || !formats || !ms) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
+    GS_HIP(hipSetDevice(ctx->device));
+    Event ev[6], cevOwned[12];
+    hipEvent_t cev[12];
+    for (Event& e : ev) GS_HIP(e.create(hipEventDefault));
+    for (int k = 0; k < 12; ++k) { GS_HIP(cevOwned[k].create(hipEventDefault)); cev[k] = cevOwned[k]; }
+    gs_asset* a = nullptr;
+    GS_TRY(import_file_impl(ctx, file, formats, slice_bytes, &a, nullptr, nullptr, ev, cev));
+    (void)gs_asset_destroy(a);
+    return import_stage_times(formats, ev, cev, ms);
 }
 
 } // extern "C"

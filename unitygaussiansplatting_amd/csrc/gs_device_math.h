@@ -1625,6 +1625,114 @@ GS_HD void ImportRecord(const ImportSrc& in, uint32_t i, uint32_t linearize, Bak
     for (int k = 0; k < 45; ++k) o.sh[k] = sh[k];
 }
 
+// ---- import from a file's own bytes (gs_import_file_to_asset; kernels in gs_bake.hip): the readers of gs_import.cpp restated per splat, so that
+// the six arrays are never built.  Host and device from one text, as above -----------------------------------------------------------------------
+// The vertex rows of a binary little-endian PLY as they lie in the file: row i at rows + i * stride, and where in a row each float property lies.
+// off[]: x y z, f_dc_0..2, opacity, scale_0..2, rot_0..3, f_rest_0..44 (the 59 the importer reads), then nx ny nz (which it does not); -1 = the file
+// has no float property of that name.  aligned: rows, stride and every offset that is read are multiples of 4 -- a field is then one dword load.
+// inria: aligned, and the 59 offsets are those of the INRIA layout (x y z nx ny nz f_dc_0..2 f_rest_0..44 opacity scale_0..2 rot_0..3, what every
+// trainer writes): the offsets are then compile-time constants, and the loads of neighbouring floats merge into wide ones as those of the six
+// arrays do.  PlyRowLayout sets both
+constexpr int kPlyOffsets = 62, kPlyOffsetsRead = 59;
+constexpr int kPlyOffPos = 0, kPlyOffDc = 3, kPlyOffOpacity = 6, kPlyOffScale = 7, kPlyOffRot = 10, kPlyOffRest = 14, kPlyOffNormal = 59;
+struct PlyRowSrc { const uint8_t* rows; uint32_t stride; uint32_t aligned, inria; int32_t off[kPlyOffsets]; };
+// which float of an INRIA row entry k of the table is
+GS_HD constexpr int PlyInriaFloat(int k) { return k < 3 ? k : (k < 6 ? k + 3 : (k == 6 ? 54 : (k < 14 ? k + 48 : k - 5))); }
+GS_HD void PlyRowLayout(PlyRowSrc& s) {
+    uint32_t low = s.stride | (uint32_t)(uintptr_t)s.rows;
+    bool inria = true;
+    for (int k = 0; k < kPlyOffsetsRead; ++k) {
+        if (s.off[k] >= 0) low |= (uint32_t)s.off[k];
+        inria = inria && s.off[k] == 4 * PlyInriaFloat(k);
+    }
+    s.aligned = (low & 3u) == 0u ? 1u : 0u;
+    s.inria = s.aligned && inria ? 1u : 0u;
+}
+// the float property `k` of the row at `row`: 0 when absent (gs_ply_open's ld); else one dword, or four bytes assembled -- a row of odd stride
+// starts at any address
+GS_HD float PlyRowField(const PlyRowSrc& s, const uint8_t* row, int k) {
+    const int32_t o = s.off[k];
+    if (o < 0) return 0.0f;
+    const uint8_t* p = row + o;
+    if (s.aligned) return u2f(*(const uint32_t*)p);
+    return u2f((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24));
+}
+GS_HD V3 PlyRowPosition(const PlyRowSrc& s, uint32_t i) {
+    const uint8_t* row = s.rows + (uint64_t)i * s.stride;
+    if (s.inria) { const float* r = (const float*)row; return { r[0], r[1], r[2] }; }
+    return { PlyRowField(s, row, kPlyOffPos), PlyRowField(s, row, kPlyOffPos + 1), PlyRowField(s, row, kPlyOffPos + 2) };
+}
+// row i as the record the Bake* functions consume: the 59 floats in the table's order, gs_ply_open's transpose (ReorderSHs: sh[j * 3 + c] =
+// f_rest[c * 15 + j]), then ImportRecord with linearize = 1
+GS_HD void PlyRowRecord(const PlyRowSrc& s, uint32_t i, BakeRec& o) {
+    const uint8_t* row = s.rows + (uint64_t)i * s.stride;
+    float f[kPlyOffsetsRead];
+    if (s.inria) {
+        const float* r = (const float*)row;
+#pragma unroll
+        for (int k = 0; k < kPlyOffsetsRead; ++k) f[k] = r[PlyInriaFloat(k)];
+    } else {
+#pragma unroll
+        for (int k = 0; k < kPlyOffsetsRead; ++k) f[k] = PlyRowField(s, row, k);
+    }
+    o.pos = { f[kPlyOffPos], f[kPlyOffPos + 1], f[kPlyOffPos + 2] };
+    V3 dc0 = { f[kPlyOffDc], f[kPlyOffDc + 1], f[kPlyOffDc + 2] };
+    o.scale = { f[kPlyOffScale], f[kPlyOffScale + 1], f[kPlyOffScale + 2] };
+    float opacity = f[kPlyOffOpacity];
+    V4 rot = { f[kPlyOffRot], f[kPlyOffRot + 1], f[kPlyOffRot + 2], f[kPlyOffRot + 3] };
+    ImportLinearize(dc0, o.scale, opacity, rot);
+    o.rot = BakeQ(rot.x, 1023.5f) | (BakeQ(rot.y, 1023.5f) << 10) | (BakeQ(rot.z, 1023.5f) << 20) | (BakeQ(rot.w, 3.5f) << 30);
+    o.col = { dc0.x, dc0.y, dc0.z, opacity };
+#pragma unroll
+    for (int j = 0; j < 15; ++j) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o.sh[j * 3 + c] = f[kPlyOffRest + c * 15 + j];
+    }
+}
+
+// The gunzipped stream of an SPZ file (SPZFileReader.cs:26-198): the 16-byte header, then for all n points the columns positions (3 x 24-bit fixed
+// point), alphas, colours (3 bytes), scales (3), rotations (3), SH (shCoeffs x 3).  Header and sizes are checked by the host before a source is made
+struct SpzSrc { const uint8_t* base; uint32_t n, shCoeffs, fractBits; };
+GS_HD float SpzPositionComponent(const uint8_t* q, float fractScale) {
+    int32_t fx = (int32_t)q[0] | ((int32_t)q[1] << 8) | ((int32_t)q[2] << 16);
+    if (fx & 0x800000) fx |= (int32_t)0xff000000;                 // sign extension
+    return (float)fx * fractScale;
+}
+GS_HD V3 SpzPosition(const SpzSrc& s, uint32_t i) {
+    const float fractScale = 1.0f / (float)(1 << s.fractBits);
+    const uint8_t* q = s.base + 16u + (uint64_t)i * 9u;
+    return { SpzPositionComponent(q, fractScale), SpzPositionComponent(q + 3, fractScale), SpzPositionComponent(q + 6, fractScale) };
+}
+GS_HD float SpzScale(uint8_t b) { return fabsf(ImportExpDet((float)b / 16.0f - 10.0f)); }                        // LinearScale
+GS_HD float SpzColor(uint8_t b) { return (((float)b / 255.0f - 0.5f) / 0.15f) * 0.2820948f + 0.5f; }             // SH0ToColor
+// point i as the record the Bake* functions consume: spz_open_impl's per-splat loop (UnpackDataJob :141-205), operation for operation, then what
+// ImportRecord does with linearize = 0.  The SH quirk is kept: fifteen coefficients from i * 3 * shCoeffs whatever the level, bytes past the array
+// reading as 128
+GS_HD void SpzRecord(const SpzSrc& s, uint32_t i, BakeRec& o) {
+    const uint64_t N = s.n, i3 = (uint64_t)i * 3u;
+    const uint8_t* alpha = s.base + 16u + N * 9u;
+    const uint8_t* col = alpha + N;
+    const uint8_t* scale = col + N * 3u;
+    const uint8_t* rotb = scale + N * 3u;
+    const uint8_t* sh = rotb + N * 3u;
+    o.pos = SpzPosition(s, i);
+    o.scale = { SpzScale(scale[i3]), SpzScale(scale[i3 + 1]), SpzScale(scale[i3 + 2]) };
+    o.col = { SpzColor(col[i3]), SpzColor(col[i3 + 1]), SpzColor(col[i3 + 2]), (float)alpha[i] / 255.0f };
+    const float qx = (float)rotb[i3] * (1.0f / 127.5f) - 1.0f, qy = (float)rotb[i3 + 1] * (1.0f / 127.5f) - 1.0f, qz = (float)rotb[i3 + 2] * (1.0f / 127.5f) - 1.0f;
+    const float sq = (qx * qx + qy * qy) + qz * qz;
+    const float qw = sqrtf(fmaxf(0.0f, 1.0f - sq));
+    const float inv = 1.0f / sqrtf(((qx * qx + qy * qy) + qz * qz) + qw * qw);            // math.normalize
+    const V4 rot = PackSmallest3Rotation({ qx * inv, qy * inv, qz * inv, qw * inv });
+    o.rot = BakeQ(rot.x, 1023.5f) | (BakeQ(rot.y, 1023.5f) << 10) | (BakeQ(rot.z, 1023.5f) << 20) | (BakeQ(rot.w, 3.5f) << 30);
+    const uint64_t shLen = N * 3u * s.shCoeffs, first = i3 * s.shCoeffs;
+#pragma unroll
+    for (int k = 0; k < 45; ++k) {
+        const uint64_t at = first + (uint64_t)k;
+        const float bv = at < shLen ? (float)sh[at] : 128.0f;
+        o.sh[k] = (bv - 128.0f) / 128.0f;
+    }
+}
+
 // ---- BC7 mode-6 colour blocks (bc7_encode_mode6 of gs_import.cpp, operation for operation): the colour texture of the VeryLow preset ------------
 // Three steps, so that one thread can own a block (BC7EncodeMode6) or sixteen lanes can, each with its texel: the per-block endpoints from
 // the channel minima / maxima, the per-texel index, the per-block packing of the sixteen indices.

@@ -11,6 +11,7 @@
 // gs_import_encode_on / gs_import_assign_clusters with a context): the same operations in the same order, the same bytes.
 // gs_import_cluster_shs exposes cluster_shs below as it is, and with a context runs the whole of it on the GPU instead (gs_cluster.hip).
 // The whole of import_encode_impl on the GPU, to a device-resident asset holding these bytes, is gs_import_encode_to_asset (gs_bake.hip).
+// gs_splat_file_open, at the end, is the readers' checks without their arrays: the handle gs_import_file_to_asset (gs_bake.hip) imports from.
 // Arithmetic is plain IEEE fp32, one rounding per operation (-ffp-contract=off), and the two transcendental steps are
 // written out (exp as Cephes-style range reduction + polynomial, x^(1/8) as three correctly rounded square roots) so that
 // the bytes are a function of this source only: unitygaussiansplatting_amd/creator.py performs the same operations with
@@ -23,7 +24,9 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <cctype>
 #include <limits>
+#include <memory>
 #include <new>
 #include <numeric>
 #include <exception>
@@ -35,6 +38,7 @@
 
 #include "../../include/gsplat_c.h"
 #include "gs_device_math.h"     // gsm::shClusterCount: the one format -> table size mapping, shared with the bake
+#include "gs_splat_file.h"
 
 namespace gs {
 int32_t fail(int32_t code, const char* what);
@@ -563,6 +567,41 @@ static bool read_line(FILE* f, std::string& line) {        // PLYFileReader.Read
     return any;
 }
 
+// The header of a PLY as PLYFileReader.ReadHeaderImpl scans it, with the reader's quirks: a property of a type it does not know adds no bytes, the
+// first float property of a name wins, a line's trailing CR is dropped.  Then the checks both entries make on it, in this order.  f is left at the
+// first vertex row; on failure the caller closes it
+struct PlyHeader {
+    struct Attr { std::string name; int type; int offset; };                    // type: 1 float, 2 double, 3 uchar, 0 none
+    std::vector<Attr> attrs;
+    long long count = 0;
+    int stride = 0;
+    int find(const std::string& nm) const { for (auto& at : attrs) if (at.name == nm && at.type == 1) return at.offset; return -1; }
+};
+static int32_t ply_read_header(FILE* f, PlyHeader& h) {
+    bool le = false;
+    std::string line;
+    for (int li = 0; li < 9000; ++li) {
+        if (!read_line(f, line) || line == "end_header" || line.empty()) break;
+        std::vector<std::string> tok;
+        size_t a = 0;
+        for (;;) { const size_t b = line.find(' ', a); tok.push_back(line.substr(a, b == std::string::npos ? b : b - a)); if (b == std::string::npos) break; a = b + 1; }
+        if (tok.size() == 3 && tok[0] == "format" && tok[1] == "binary_little_endian" && tok[2] == "1.0") le = true;
+        if (tok.size() == 3 && tok[0] == "element" && tok[1] == "vertex") h.count = atoll(tok[2].c_str());
+        if (tok.size() == 3 && tok[0] == "property") {
+            const int type = tok[1] == "float" ? 1 : (tok[1] == "double" ? 2 : (tok[1] == "uchar" ? 3 : 0));
+            h.attrs.push_back({ tok[2], type, h.stride });
+            h.stride += type == 1 ? 4 : (type == 2 ? 8 : (type == 3 ? 1 : 0));
+        }
+    }
+    if (!le) return gs::fail(GS_ERR_INVALID_ASSET, "PLY not supported: needs to be binary, little endian PLY format");
+    if (h.count <= 0 || h.count > (1ll << 30) || h.stride <= 0) return gs::fail(GS_ERR_INVALID_ASSET, "PLY has no vertices");
+    const char* required[] = { "x", "y", "z", "f_dc_0", "f_dc_1", "f_dc_2", "opacity", "scale_0", "scale_1", "scale_2", "rot_0", "rot_1", "rot_2", "rot_3" };
+    for (const char* r : required)
+        if (h.find(r) < 0) return gs::fail(GS_ERR_INVALID_ASSET, "PLY file is probably not a Gaussian Splat file (a required float property is missing)");
+    return GS_OK;
+}
+static const char* const kPlyShortBody = "PLY read error: fewer data bytes than the header announces";
+
 static int32_t ply_open_impl(const char* path, gs_ply** out, uint32_t* splat_count);
 
 int32_t gs_ply_open(const char* path, gs_ply** out, uint32_t* splat_count) {
@@ -576,31 +615,11 @@ static int32_t ply_open_impl(const char* path, gs_ply** out, uint32_t* splat_cou
     *out = nullptr;
     FILE* f = fopen(path, "rb");
     if (!f) return gs::fail(GS_ERR_INVALID_ASSET, "PLY file cannot be opened");
-    struct Attr { std::string name; int type; int offset; };                    // type: 1 float, 2 double, 3 uchar, 0 none
-    std::vector<Attr> attrs;
-    long long count = 0;
-    int stride = 0;
-    bool le = false;
-    std::string line;
-    for (int li = 0; li < 9000; ++li) {
-        if (!read_line(f, line) || line == "end_header" || line.empty()) break;
-        std::vector<std::string> tok;
-        size_t a = 0;
-        for (;;) { const size_t b = line.find(' ', a); tok.push_back(line.substr(a, b == std::string::npos ? b : b - a)); if (b == std::string::npos) break; a = b + 1; }
-        if (tok.size() == 3 && tok[0] == "format" && tok[1] == "binary_little_endian" && tok[2] == "1.0") le = true;
-        if (tok.size() == 3 && tok[0] == "element" && tok[1] == "vertex") count = atoll(tok[2].c_str());
-        if (tok.size() == 3 && tok[0] == "property") {
-            const int type = tok[1] == "float" ? 1 : (tok[1] == "double" ? 2 : (tok[1] == "uchar" ? 3 : 0));
-            attrs.push_back({ tok[2], type, stride });
-            stride += type == 1 ? 4 : (type == 2 ? 8 : (type == 3 ? 1 : 0));
-        }
-    }
-    if (!le) { fclose(f); return gs::fail(GS_ERR_INVALID_ASSET, "PLY not supported: needs to be binary, little endian PLY format"); }
-    if (count <= 0 || count > (1ll << 30) || stride <= 0) { fclose(f); return gs::fail(GS_ERR_INVALID_ASSET, "PLY has no vertices"); }
-    auto find = [&](const std::string& nm) { for (auto& at : attrs) if (at.name == nm && at.type == 1) return at.offset; return -1; };
-    const char* required[] = { "x", "y", "z", "f_dc_0", "f_dc_1", "f_dc_2", "opacity", "scale_0", "scale_1", "scale_2", "rot_0", "rot_1", "rot_2", "rot_3" };
-    for (const char* r : required)
-        if (find(r) < 0) { fclose(f); return gs::fail(GS_ERR_INVALID_ASSET, "PLY file is probably not a Gaussian Splat file (a required float property is missing)"); }
+    PlyHeader hdr;
+    { const int32_t hrc = ply_read_header(f, hdr); if (hrc != GS_OK) { fclose(f); return hrc; } }
+    const long long count = hdr.count;
+    const int stride = hdr.stride;
+    auto find = [&](const std::string& nm) { return hdr.find(nm); };
     gs_ply* p = new (std::nothrow) gs_ply();
     if (!p) { fclose(f); return gs::fail(GS_ERR_OUT_OF_MEMORY, "host allocation"); }
     std::vector<uint8_t> body;
@@ -612,7 +631,7 @@ static int32_t ply_open_impl(const char* path, gs_ply** out, uint32_t* splat_cou
     } catch (...) { fclose(f); delete p; return gs::fail(GS_ERR_OUT_OF_MEMORY, "host allocation"); }
     const size_t got = fread(body.data(), 1, body.size(), f);
     fclose(f);
-    if (got != body.size()) { delete p; return gs::fail(GS_ERR_INVALID_ASSET, "PLY read error: fewer data bytes than the header announces"); }
+    if (got != body.size()) { delete p; return gs::fail(GS_ERR_INVALID_ASSET, kPlyShortBody); }
     const int ox[3] = { find("x"), find("y"), find("z") }, od[3] = { find("f_dc_0"), find("f_dc_1"), find("f_dc_2") };
     const int os[3] = { find("scale_0"), find("scale_1"), find("scale_2") }, orr[4] = { find("rot_0"), find("rot_1"), find("rot_2"), find("rot_3") };
     const int oo = find("opacity");
@@ -668,12 +687,11 @@ static bool gunzip_file(FILE* f, std::vector<uint8_t>& out, size_t limit) {
     return true;
 }
 
-static int32_t spz_open_impl(const char* path, gs_ply** out, uint32_t* splat_count) {
-    if (!path || !out) return gs::fail(GS_ERR_INVALID_ARGUMENT, "null argument");
-    *out = nullptr;
+// The file gunzipped into `raw`, with every check of SPZFileReader.ReadFile (:66-139) on the header and on the stream's length, in its order
+struct SpzHeader { size_t n = 0; int shLevel = 0, fractBits = 0, shCoeffs = 0; size_t end = 0; };     // end: the header + the six columns, in bytes
+static int32_t spz_read_stream(const char* path, std::vector<uint8_t>& raw, SpzHeader& hd) {
     FILE* f = fopen(path, "rb");
     if (!f) return gs::fail(GS_ERR_INVALID_ASSET, "SPZ file cannot be opened");
-    std::vector<uint8_t> raw;
     const bool ok = gunzip_file(f, raw, (size_t)10'000'000 * 64 + 64);
     fclose(f);
     if (!ok) return gs::fail(GS_ERR_INVALID_ASSET, "SPZ read error: not a gzip stream");
@@ -687,10 +705,23 @@ static int32_t spz_open_impl(const char* path, gs_ply** out, uint32_t* splat_cou
     if (n < 1 || n > 10'000'000) return gs::fail(GS_ERR_INVALID_ASSET, "SPZ read error, out of range splat count");     // 10M hardcoded in SPZ code
     if (shLevel < 0 || shLevel > 3) return gs::fail(GS_ERR_INVALID_ASSET, "SPZ read error, out of range SH level");
     if (fractBits < 0 || fractBits > 24) return gs::fail(GS_ERR_INVALID_ASSET, "SPZ read error, out of range fractional bits");
-    const int shCoeffs = shLevel == 1 ? 3 : (shLevel == 2 ? 8 : (shLevel == 3 ? 15 : 0));
-    const size_t N = (size_t)n;
-    const size_t oPos = 16, oAlpha = oPos + N * 9, oCol = oAlpha + N, oScale = oCol + N * 3, oRot = oScale + N * 3, oSh = oRot + N * 3, end = oSh + N * 3 * shCoeffs;
-    if (raw.size() < end) return gs::fail(GS_ERR_INVALID_ASSET, "SPZ read error, file smaller than it should be");
+    hd.n = (size_t)n; hd.shLevel = shLevel; hd.fractBits = fractBits;
+    hd.shCoeffs = shLevel == 1 ? 3 : (shLevel == 2 ? 8 : (shLevel == 3 ? 15 : 0));
+    hd.end = 16 + hd.n * 9 + hd.n + hd.n * 3 * 3 + hd.n * 3 * (size_t)hd.shCoeffs;
+    if (raw.size() < hd.end) return gs::fail(GS_ERR_INVALID_ASSET, "SPZ read error, file smaller than it should be");
+    return GS_OK;
+}
+
+static int32_t spz_open_impl(const char* path, gs_ply** out, uint32_t* splat_count) {
+    if (!path || !out) return gs::fail(GS_ERR_INVALID_ARGUMENT, "null argument");
+    *out = nullptr;
+    std::vector<uint8_t> raw;
+    SpzHeader hd;
+    { const int32_t hrc = spz_read_stream(path, raw, hd); if (hrc != GS_OK) return hrc; }
+    const int64_t n = (int64_t)hd.n;
+    const int shCoeffs = hd.shCoeffs, fractBits = hd.fractBits;
+    const size_t N = hd.n;
+    const size_t oPos = 16, oAlpha = oPos + N * 9, oCol = oAlpha + N, oScale = oCol + N * 3, oRot = oScale + N * 3, oSh = oRot + N * 3;
     gs_ply* p = new (std::nothrow) gs_ply();
     if (!p) return gs::fail(GS_ERR_OUT_OF_MEMORY, "host allocation");
     try {
@@ -754,3 +785,82 @@ int32_t gs_ply_close(gs_ply* ply) {
 }
 
 } // extern "C"
+
+// ---- a file as the GPU import's source (gs_import_file_to_asset, gs_bake.hip): the readers' checks without their arrays ------------------------
+// The handles that are open, so that a closed one is refused, not dereferenced
+static std::mutex g_splatFilesMu;
+static std::vector<const gs_splat_file*> g_splatFiles;
+
+bool gs::splat_file_is_open(const gs_splat_file* file) {
+    std::lock_guard<std::mutex> g(g_splatFilesMu);
+    return file && std::find(g_splatFiles.begin(), g_splatFiles.end(), file) != g_splatFiles.end();
+}
+
+static bool has_extension(const std::string& path, const char* ext) {            // EndsWith(ext, ignoreCase) of GaussianFileReader.ReadFile
+    if (path.size() < 4) return false;
+    for (int k = 0; k < 4; ++k) if (std::tolower((unsigned char)path[path.size() - 4 + k]) != ext[k]) return false;
+    return true;
+}
+
+static int32_t splat_file_open_impl(const char* path, gs_splat_file** out, gs_splat_file_info* info) {
+    if (!path || !out) return gs::fail(GS_ERR_INVALID_ARGUMENT, "null argument");
+    *out = nullptr;
+    const bool ply = has_extension(path, ".ply");
+    if (!ply && !has_extension(path, ".spz")) return gs::fail(GS_ERR_INVALID_ASSET, "file is not a supported format (.ply or .spz)");
+    std::unique_ptr<gs_splat_file> file(new gs_splat_file());
+    gs_splat_file_info& fi = file->info;
+    for (int32_t& o : fi.offsets) o = -1;
+    if (ply) {
+        file->f = fopen(path, "rb");
+        if (!file->f) return gs::fail(GS_ERR_INVALID_ASSET, "PLY file cannot be opened");
+        PlyHeader hdr;
+        { const int32_t hrc = ply_read_header(file->f, hdr); if (hrc != GS_OK) return hrc; }
+        fi.kind = GS_SPLAT_FILE_PLY;
+        fi.splat_count = (uint32_t)hdr.count;
+        fi.stride = (uint32_t)hdr.stride;
+        fi.body_bytes = (uint64_t)hdr.count * (uint64_t)hdr.stride;
+        static const char* const kNames[14] = { "x", "y", "z", "f_dc_0", "f_dc_1", "f_dc_2", "opacity", "scale_0", "scale_1", "scale_2", "rot_0", "rot_1", "rot_2", "rot_3" };
+        for (int k = 0; k < 14; ++k) fi.offsets[k] = hdr.find(kNames[k]);
+        for (int k = 0; k < 45; ++k) fi.offsets[gsm::kPlyOffRest + k] = hdr.find("f_rest_" + std::to_string(k));
+        for (int k = 0; k < 3; ++k) fi.offsets[gsm::kPlyOffNormal + k] = hdr.find(k == 0 ? "nx" : (k == 1 ? "ny" : "nz"));
+        // the rows must all be there: what the reader finds out when its fread comes back short
+        file->bodyAt = ftello(file->f);
+        if (file->bodyAt < 0 || fseeko(file->f, 0, SEEK_END) != 0) return gs::fail(GS_ERR_INVALID_ASSET, "PLY file cannot be measured");
+        const long long size = ftello(file->f);
+        if (size < 0 || (uint64_t)(size - file->bodyAt) < fi.body_bytes) return gs::fail(GS_ERR_INVALID_ASSET, kPlyShortBody);
+        if (fseeko(file->f, file->bodyAt, SEEK_SET) != 0) return gs::fail(GS_ERR_INVALID_ASSET, "PLY file cannot be measured");
+    } else {
+        SpzHeader hd;
+        { const int32_t hrc = spz_read_stream(path, file->raw, hd); if (hrc != GS_OK) return hrc; }
+        fi.kind = GS_SPLAT_FILE_SPZ;
+        fi.splat_count = (uint32_t)hd.n;
+        fi.sh_level = (uint32_t)hd.shLevel;
+        fi.fract_bits = (uint32_t)hd.fractBits;
+        fi.body_bytes = hd.end;
+    }
+    if (info) *info = fi;
+    {
+        std::lock_guard<std::mutex> g(g_splatFilesMu);
+        g_splatFiles.push_back(file.get());
+    }
+    *out = file.release();
+    return GS_OK;
+}
+
+int32_t gs_splat_file_open(const char* path, gs_splat_file** out, gs_splat_file_info* info) {
+    try { return splat_file_open_impl(path, out, info); }
+    catch (const std::bad_alloc&) { return gs::fail(GS_ERR_OUT_OF_MEMORY, "host allocation"); }
+    catch (...) { return gs::fail(GS_ERR_INVALID_ASSET, "unexpected failure while reading the file"); }
+}
+
+int32_t gs_splat_file_close(gs_splat_file* file) {
+    if (!file) return GS_OK;
+    {
+        std::lock_guard<std::mutex> g(g_splatFilesMu);
+        const auto at = std::find(g_splatFiles.begin(), g_splatFiles.end(), file);
+        if (at == g_splatFiles.end()) return gs::fail(GS_ERR_INVALID_ARGUMENT, "not an open splat file handle");
+        g_splatFiles.erase(at);
+    }
+    delete file;
+    return GS_OK;
+}

@@ -178,6 +178,17 @@ namespace GaussianSplatting.Runtime
         [DllImport(Lib)] public static extern int gs_spz_open([MarshalAs(UnmanagedType.LPStr)] string path, out IntPtr ply, out uint splatCount);
         [DllImport(Lib)] public static extern int gs_ply_arrays(IntPtr ply, out ImportInput arrays);
         [DllImport(Lib)] public static extern int gs_ply_close(IntPtr ply);
+        // a .ply / .spz file straight into a device asset: the file's own bytes are the GPU importer's source (kind: 1 PLY, 2 SPZ)
+        [StructLayout(LayoutKind.Sequential)]
+        public struct SplatFileInfo
+        {
+            public uint kind, splatCount, stride, shLevel, fractBits, reserved;
+            public ulong bodyBytes;
+            [MarshalAs(UnmanagedType.ByValArray, SizeConst = 62)] public int[] offsets;
+        }
+        [DllImport(Lib)] public static extern int gs_splat_file_open([MarshalAs(UnmanagedType.LPStr)] string path, out IntPtr file, out SplatFileInfo info);
+        [DllImport(Lib)] public static extern int gs_splat_file_close(IntPtr file);
+        [DllImport(Lib)] public static extern int gs_import_file_to_asset(IntPtr ctx, IntPtr file, ref ImportFormats formats, uint sliceBytes, out IntPtr asset, [Out] float[] boundsMin3, [Out] float[] boundsMax3);
 
         [DllImport(Lib)] public static extern int gs_sorter_create(IntPtr ctx, uint maxCount, out IntPtr sorter);
         [DllImport(Lib)] public static extern int gs_sorter_destroy(IntPtr sorter);
