@@ -399,6 +399,30 @@ int32_t gs_renderer_edit_export_alive(gs_renderer* r, const gs_export_params* p,
 /* ExportPlyFile: the reference's header + the alive records.  On an error the partially written file is removed. */
 int32_t gs_renderer_edit_export_ply(gs_renderer* r, const gs_export_params* p, const char* path, uint32_t* alive);
 
+/* ---- export to SPZ (no counterpart in the reference, which only reads the format: SPZFileReader.cs:26-198)  (additions to ABI 9) ----
+ * The alive splats as an SPZ version 2 file, 64 bytes per splat before gzip at SH level 3: the inverse of what gs_spz_open /
+ * gs_splat_file_open read, packed on the GPU column by column from the same records the PLY export writes (after bake_transform), except
+ * alpha, which is the decoded linear opacity x 255.  DESIGN.md section 4.13 states every byte operation by operation (fp32, round to
+ * nearest even, clamped; SH codes are plain roundings).  The body is the gunzipped stream: a 16-byte header (magic, version 2, count,
+ * sh_level | fract_bits << 8), then the columns positions (n x 9), alpha (n), colour (n x 3), scale (n x 3), rotation (n x 3),
+ * SH (n x 3 x {0, 3, 8, 15}).  Both calls read the current deleted bits and cutout list, run on the context's stream and BLOCK.  The
+ * columns reach the host through two pinned slices of slice_bytes that fill alternately; the file call deflates each slice as it
+ * arrives (gzip wrapper) and removes a partially written file on any error.  Refused with GS_ERR_INVALID_ARGUMENT, nothing written:
+ * a NULL r, p or s; a lane; sh_level > 3; fract_bits > 24 other than GS_SPZ_FRACT_AUTO; compression_level outside -1..9; slice_bytes
+ * 1..4095; a too-small capacity_bytes; no alive splat, or more than 10,000,000 (the readers refuse both). */
+#define GS_SPZ_FRACT_AUTO 0xffffffffu
+typedef struct gs_spz_params {
+    uint32_t sh_level;                  /* 0..3: 0, 3, 8 or 15 SH coefficients per splat */
+    uint32_t fract_bits;                /* 0..24 fractional bits of the 24-bit positions, or GS_SPZ_FRACT_AUTO: the largest value up
+                                         * to 12 at which the largest |coordinate| of the exported positions still fits */
+    int32_t compression_level;          /* -1..9, handed to zlib as given (the file call only) */
+    uint32_t slice_bytes;               /* 0 = 64 MiB; else at least 4096 */
+} gs_spz_params;
+/* the gunzipped stream (header + six columns) of the alive splats to host memory; out may be NULL to get the sizes alone */
+int32_t gs_renderer_edit_export_spz_body(gs_renderer* r, const gs_export_params* p, const gs_spz_params* s, void* out, size_t capacity_bytes,
+                                         uint64_t* body_bytes, uint32_t* alive, uint32_t* fract_bits_used);
+int32_t gs_renderer_edit_export_spz(gs_renderer* r, const gs_export_params* p, const gs_spz_params* s, const char* path, uint32_t* alive);
+
 /* ---- merge: EditSetSplatCount / EditCopySplatsInto / EditCopySplats (GaussianSplatRenderer.cs:960-1075), CSCopySplats
  * (SplatUtilities.compute:675-758); the editor's MergeSplatObjects (GaussianSplatRendererEditor.cs:213-235) is host code over the two
  * (additions to ABI 9) ----

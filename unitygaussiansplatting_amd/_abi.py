@@ -61,6 +61,13 @@ class gs_export_params(C.Structure):     # what CSExportData reads of its dispat
                 ("bake_transform", C.c_uint32)]
 
 
+GS_SPZ_FRACT_AUTO = 0xffffffff
+
+
+class gs_spz_params(C.Structure):        # gs_renderer_edit_export_spz / _spz_body
+    _fields_ = [("sh_level", C.c_uint32), ("fract_bits", C.c_uint32), ("compression_level", C.c_int32), ("slice_bytes", C.c_uint32)]
+
+
 class gs_copy_params(C.Structure):       # what CSCopySplats reads of its dispatch (gs_renderer_edit_set_splat_count / _copy_splats_into)
     _fields_ = [("matrix", C.c_float * 16), ("rotation", C.c_float * 4), ("scale", C.c_float * 3)]
 

@@ -7,7 +7,7 @@ import ctypes as C
 import os
 
 from ._abi import (gs_asset_desc, gs_copy_params, gs_cutout, gs_edit_info, gs_export_params, gs_frame_params, gs_frame_stats, gs_import_formats, gs_import_input,
-                   gs_splat_file_info, gs_stage_times)
+                   gs_splat_file_info, gs_spz_params, gs_stage_times)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GSPLAT_LIB") or os.path.join(_HERE, "libgsplat_hip.so")   # GSPLAT_LIB: A/B a variant build
@@ -74,6 +74,9 @@ SIGNATURES = {
     "gs_renderer_edit_export_data": (C.c_int32, [_P, C.POINTER(gs_export_params), _P, C.c_size_t, C.c_int32]),
     "gs_renderer_edit_export_alive": (C.c_int32, [_P, C.POINTER(gs_export_params), _P, C.c_size_t, C.POINTER(C.c_uint32)]),
     "gs_renderer_edit_export_ply": (C.c_int32, [_P, C.POINTER(gs_export_params), C.c_char_p, C.POINTER(C.c_uint32)]),
+    "gs_renderer_edit_export_spz_body": (C.c_int32, [_P, C.POINTER(gs_export_params), C.POINTER(gs_spz_params), _P, C.c_size_t, C.POINTER(C.c_uint64),
+                                                     C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "gs_renderer_edit_export_spz": (C.c_int32, [_P, C.POINTER(gs_export_params), C.POINTER(gs_spz_params), C.c_char_p, C.POINTER(C.c_uint32)]),
     "gs_renderer_splat_count": (C.c_int32, [_P, C.POINTER(C.c_uint32)]),
     "gs_renderer_edit_set_splat_count": (C.c_int32, [_P, C.c_uint32, C.POINTER(gs_copy_params)]),
     "gs_renderer_edit_copy_splats_into": (C.c_int32, [_P, _P, C.POINTER(gs_copy_params), C.c_uint32, C.c_uint32, C.c_uint32]),

@@ -86,9 +86,10 @@ struct BakeSpzSource {
     __device__ __forceinline__ void record(uint32_t j, gsm::BakeRec& rec) const { gsm::SpzRecord(s, j, rec); }
 };
 
-// alive[base[chunk] + rank] = idx for the alive splats of source chunk blockIdx.x; partial[chunk][0..2 / 3..5] = min / max of their positions
-__global__ __launch_bounds__(256) void bake_alive_kernel(gsm::AssetView a, gsm::EditView e, const uint32_t* __restrict__ base, uint32_t* __restrict__ alive,
-                                                         float* __restrict__ partial) {
+// alive[base[chunk] + rank] = idx for the alive splats of source chunk blockIdx.x; partial[chunk][0..2 / 3..5] = min / max of their positions -- as
+// stored, or (X.through: the SPZ export's bounds) through the matrix a baked export moves them by
+__global__ __launch_bounds__(256) void bake_alive_kernel(gsm::AssetView a, gsm::EditView e, AliveXform X, const uint32_t* __restrict__ base,
+                                                         uint32_t* __restrict__ alive, float* __restrict__ partial) {
     __shared__ uint32_t s_cnt[4];
     __shared__ float s_red[4][6];
     const uint32_t idx = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -98,7 +99,11 @@ __global__ __launch_bounds__(256) void bake_alive_kernel(gsm::AssetView a, gsm::
     const uint32_t slot = (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
     if (lane == 0u) s_cnt[wave] = (uint32_t)__popcll(bal);
     const float inf = gsm::u2f(0x7f800000u);
-    const float p[3] = { pos.x, pos.y, pos.z };
+    float p[3] = { pos.x, pos.y, pos.z };
+    if (X.through != 0u) {                                         // BakeSplatTransform's position
+#pragma unroll
+        for (int c = 0; c < 3; ++c) p[c] = gsm::mrow(X.m, c, pos.x, pos.y, pos.z);
+    }
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const float mn = wave_min(mine ? p[c] : inf), mx = wave_max(mine ? p[c] : -inf);
@@ -177,6 +182,16 @@ __global__ __launch_bounds__(kBakeReduceThreads) void bake_bounds_kernel(const f
         for (uint32_t w = 1; w < kBakeReduceThreads / 64; ++w) r = t < 3u ? fminf(r, s_red[w][t]) : fmaxf(r, s_red[w][t]);
         bounds[t] = r;
     }
+}
+
+// step 1's second half on st, after enqueue_alive_counts: the alive list, the per-chunk partials and their fold (the bake's, and the SPZ export's in
+// gs_export.hip)
+int32_t enqueue_alive_list(hipStream_t st, const gsm::AssetView& a, const gsm::EditView& e, const AliveXform& X, uint32_t chunks, const uint32_t* base,
+                           uint32_t* alive, float* partial, float* bounds) {
+    hipLaunchKernelGGL(bake_alive_kernel, dim3(chunks), dim3(256), 0, st, a, e, X, base, alive, partial);
+    hipLaunchKernelGGL(bake_bounds_kernel, dim3(1), dim3(kBakeReduceThreads), 0, st, (const float*)partial, chunks, bounds);
+    GS_HIP(hipGetLastError());
+    return GS_OK;
 }
 
 // the Morton code of the source's splat j as two sort keys, and the identity payload
@@ -449,9 +464,7 @@ static int32_t bake_enqueue(gs_renderer* r, const gs_import_formats* f, BakeRun&
     GS_TRY(bake_run_alloc(ctx, f, run, total));
     const BakeRendererSource src = { asset_view(r), run.alive.get() };
     if (ev) GS_HIP(hipEventRecord(ev[2], st));
-    hipLaunchKernelGGL(bake_alive_kernel, dim3(chunks), dim3(256), 0, st, src.a, edit_view(r), (const uint32_t*)run.base.get(), run.alive.get(), run.partial.get());
-    hipLaunchKernelGGL(bake_bounds_kernel, dim3(1), dim3(kBakeReduceThreads), 0, st, (const float*)run.partial.get(), chunks, run.bounds.get());
-    GS_HIP(hipGetLastError());
+    GS_TRY(enqueue_alive_list(st, src.a, edit_view(r), AliveXform{}, chunks, run.base.get(), run.alive.get(), run.partial.get(), run.bounds.get()));
     if (ev) GS_HIP(hipEventRecord(ev[3], st));
     return bake_enqueue_from(ctx, src, f, run, total, d, colorBytes, ev, cev);
 }

@@ -491,6 +491,12 @@ __device__ __forceinline__ bool export_alive(const gsm::AssetView& a, const gsm:
 }
 // export_count_kernel + export_scan_kernel on st: counts[c] = alive splats of chunk c, base[0 .. chunks] = their exclusive prefix and the total
 int32_t enqueue_alive_counts(hipStream_t st, const gsm::AssetView& a, const gsm::EditView& e, uint32_t chunks, uint32_t* counts, uint32_t* base);
+// bake_alive_kernel + bake_bounds_kernel on st (gs_bake.hip), after enqueue_alive_counts: alive[j] = source index of the j-th alive splat (total + 16
+// words), partial = chunks x 6 floats, bounds[0..2 / 3..5] = min / max of the alive positions -- as stored, or with X.through != 0 moved through the
+// rows 0..2 of X.m first (what a baked export does to them)
+struct AliveXform { uint32_t through = 0; float m[12] = {}; };
+int32_t enqueue_alive_list(hipStream_t st, const gsm::AssetView& a, const gsm::EditView& e, const AliveXform& X, uint32_t chunks, const uint32_t* base,
+                           uint32_t* alive, float* partial, float* bounds);
 // the Cluster* SH palette on device pointers (gs_cluster.hip): what one run of the Lloyd loop holds besides the points, the means and the indices
 struct ClusterRun {
     DevBuf<float> sub;                      // the stride-sampled training subset (only when n > 200,000)

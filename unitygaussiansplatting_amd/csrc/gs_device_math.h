@@ -1381,7 +1381,9 @@ GS_HD void BakeSplatTransform(SplatFull& s, const float* m, const float* rot, co
 // The body of CSExportData (SplatUtilities.compute:616-673) for one splat: rec = the 62 floats of ExportSplatData = InputSplatData
 // (pos, nor, dc0, 15 R + 15 G + 15 B SH coefficients, opacity, scale, rot wxyz).  pos = LoadSplatPosChunk(a, idx, ci) and cut = IsSplatCut(pos)
 // come from the caller, which needs them before it decides whether the splat is exported at all.
-GS_HD void ExportSplat(const AssetView& a, const ExportXform& X, uint32_t idx, uint32_t ci, const V3& pos, bool cut, float* rec) {
+// ExportSplatLinear also hands out the decoded linear opacity, the value the logit of rec[54] is taken of (the SPZ writer's alpha: no log between
+// the asset and its byte).
+GS_HD void ExportSplatLinear(const AssetView& a, const ExportXform& X, uint32_t idx, uint32_t ci, const V3& pos, bool cut, float* rec, float& opacity) {
     SplatFull s;
     LoadSplatDataFull(a, idx, ci, pos, s);
     if (X.bake != 0u) BakeSplatTransform(s, X.o2w, X.rot, X.scale, X.sh);
@@ -1394,7 +1396,83 @@ GS_HD void ExportSplat(const AssetView& a, const ExportXform& X, uint32_t idx, u
     rec[54] = LogDetFull(s.opacity / fmaxf(1.0f - s.opacity, 1.0e-6f));                 // InvSigmoid
     rec[55] = LogDetFull(s.scale.x); rec[56] = LogDetFull(s.scale.y); rec[57] = LogDetFull(s.scale.z);
     rec[58] = s.rot.w; rec[59] = s.rot.x; rec[60] = s.rot.y; rec[61] = s.rot.z;
+    opacity = s.opacity;
 }
+GS_HD void ExportSplat(const AssetView& a, const ExportXform& X, uint32_t idx, uint32_t ci, const V3& pos, bool cut, float* rec) {
+    float opacity;
+    ExportSplatLinear(a, X, idx, ci, pos, cut, rec, opacity);
+}
+
+// ---- export to SPZ: the inverse of SpzRecord / spz_read_stream (below; SPZFileReader.cs:26-198), column by column (kernels in gs_export.hip) ----
+// Every byte is a function of this text: fp32 operations, each product and each sum rounded on its own, rintf (ties to even) to an integer, and
+// no NaN ever converted.  The SH codes are plain roundings: the bucket snapping of the format's original packer is not restated.
+constexpr uint32_t kSpzMagic = 0x5053474eu;                        // "NGSP"
+constexpr uint32_t kSpzMaxSplats = 10000000u;                      // the readers' limit (SPZFileReader.cs:72)
+constexpr uint32_t kSpzFractAuto = 0xffffffffu;
+constexpr uint32_t kSpzColumns = 6u;
+GS_HD uint32_t SpzShCoeffs(uint32_t level) { return level == 1u ? 3u : (level == 2u ? 8u : (level == 3u ? 15u : 0u)); }
+// bytes per splat of column c: positions, alpha, colour, scale, rotation, SH
+GS_HD uint32_t SpzColumnWidth(uint32_t c, uint32_t shCoeffs) { return c == 0u ? 9u : (c == 1u ? 1u : (c == 5u ? 3u * shCoeffs : 3u)); }
+GS_HD uint32_t SpzCode8(float t) {
+    if (!(t >= 0.0f)) return 0u;                                   // NaN, -inf, every negative
+    if (t > 255.0f) return 255u;
+    return (uint32_t)rintf(t);
+}
+// one coordinate as 24-bit two's complement fixed point with fractBits (0..24) fractional bits
+GS_HD uint32_t SpzPackCoordinate(float p, uint32_t fractBits) {
+    const float q = rintf(p * (float)(1u << fractBits));          // the scaling by a power of two is exact
+    if (!(q == q)) return 0u;
+    if (q < -8388608.0f) return 0x800000u;
+    if (q > 8388607.0f) return 0x7fffffu;
+    return (uint32_t)(int32_t)q & 0xffffffu;
+}
+// the automatic fractBits for bounds = min xyz / max xyz of the exported positions: the largest f <= 12 at which the largest |coordinate| still fits
+GS_HD uint32_t SpzAutoFractBits(const float* bounds) {
+    float m = 0.0f;
+    for (int k = 0; k < 6; ++k) m = fmaxf(m, fabsf(bounds[k]));
+    for (uint32_t f = 12u; f > 0u; --f)
+        if (rintf(m * (float)(1u << f)) <= 8388607.0f) return f;
+    return 0u;
+}
+GS_HD void SpzPackPosition(const float* rec, uint32_t fractBits, uint8_t* out9) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const uint32_t q = SpzPackCoordinate(rec[c], fractBits);
+        out9[c * 3] = (uint8_t)q; out9[c * 3 + 1] = (uint8_t)(q >> 8); out9[c * 3 + 2] = (uint8_t)(q >> 16);
+    }
+}
+GS_HD uint8_t SpzPackAlpha(float linearOpacity) { return (uint8_t)SpzCode8(linearOpacity * 255.0f); }
+GS_HD uint8_t SpzPackColor(float dc0) { return (uint8_t)SpzCode8(((dc0 * 0.15f) + 0.5f) * 255.0f); }
+GS_HD uint8_t SpzPackScale(float logScale) { return (uint8_t)SpzCode8((logScale + 10.0f) * 16.0f); }
+GS_HD uint8_t SpzPackSH(float c) { return (uint8_t)SpzCode8((c * 128.0f) + 128.0f); }
+// w, x, y, z of the record -> the x, y, z bytes of the unit quaternion with w >= 0
+GS_HD void SpzPackRotation(float w, float x, float y, float z, uint8_t* out3) {
+    const float l2 = ((x * x + y * y) + z * z) + w * w;
+    const float inv = 1.0f / sqrtf(l2);
+    float c[3] = { x * inv, y * inv, z * inv };
+    if (w < 0.0f) { c[0] = -c[0]; c[1] = -c[1]; c[2] = -c[2]; }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out3[k] = (uint8_t)SpzCode8((c[k] * 127.5f) + 127.5f);
+}
+// One splat into its place in each of the six columns: rec = the 62 floats of ExportSplatLinear, linearOpacity its second output.  The SH column takes
+// the first shCoeffs coefficients as [coefficient][r, g, b]; the record holds them channel-major
+GS_HD void SpzPackSplat(const float* rec, float linearOpacity, uint32_t fractBits, uint32_t shCoeffs, uint8_t* pos9, uint8_t* alpha1, uint8_t* col3,
+                        uint8_t* scale3, uint8_t* rot3, uint8_t* sh) {
+    SpzPackPosition(rec, fractBits, pos9);
+    alpha1[0] = SpzPackAlpha(linearOpacity);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { col3[c] = SpzPackColor(rec[6 + c]); scale3[c] = SpzPackScale(rec[55 + c]); }
+    SpzPackRotation(rec[58], rec[59], rec[60], rec[61], rot3);
+#pragma unroll
+    for (uint32_t j = 0; j < 15u; ++j) {
+        if (j < shCoeffs) {
+#pragma unroll
+            for (uint32_t c = 0; c < 3u; ++c) sh[j * 3u + c] = SpzPackSH(rec[9u + c * 15u + j]);
+        }
+    }
+}
+// the 16 bytes in front of the columns
+GS_HD void SpzHeaderWords(uint32_t n, uint32_t shLevel, uint32_t fractBits, uint32_t* w) { w[0] = kSpzMagic; w[1] = 2u; w[2] = n; w[3] = shLevel | (fractBits << 8); }
 
 // ---- merge: CSCopySplats (SplatUtilities.compute:675-758; kernel in gs_copy.hip) ----------------------------------------------------
 // what the kernel reads of its dispatch: _CopyTransformMatrix (rows 0..2), _CopyTransformRotation (xyzw), _CopyTransformScale, and the band

@@ -21,7 +21,10 @@
 // every wave keeps 31 x 512-byte stores in flight does not need more waves to cover the write latency.  -DGS_EXPORT_DIRECT builds the variant in which
 // every lane stores its own record (scripts/export_timing.py times one against the other).
 #include <errno.h>
+#include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
+#include <zlib.h>
 #include <new>
 #include <string>
 
@@ -218,6 +221,213 @@ static int32_t export_begin(gs_renderer* r, const gs_export_params* p, bool comp
     return run.prepare();
 }
 
+// ---- SPZ: the alive splats as the six byte columns of an SPZ version 2 stream ----------------------------------------
+// After export_count / export_scan, the bake's alive list (enqueue_alive_list, gs_bake.hip: alive[j] = source index of the j-th alive splat) with its
+// bounds taken of the positions AS EXPORTED (through the matrix when the transform is baked: the automatic fract_bits follows from them; the host
+// derives it from the six floats), then one plain launch that waits on no other workgroup:
+//   export_spz         256 threads per 256 destination ranks: lane j decodes alive[256 b + j] (LoadSplatDataFull + the ExportSplat body) and packs.
+// Each column has a 16-byte aligned region of its own in one transient buffer, padded past its end.  The 64 ranks of a wave own 64 x {9, 1, 3, 3,
+// 3, 3k} bytes of each column -- every one a multiple of 4 at a multiple-of-4 offset -- so a wave stages its bytes in LDS (64 x 64 B = 4 KB, 16 KB per
+// workgroup: occupancy is not LDS-bound) and writes each column's range with contiguous dword stores.  No two waves store to the same dword: only
+// the last wave with any rank below n rounds its byte count up, into the region's padding, and the lanes of ranks >= n stage zeros there.  Those
+// lanes read neither alive[] nor the asset, and every lane of the workgroup reaches the barrier.
+struct SpzColumns { uint8_t* col[gsm::kSpzColumns]; };
+
+__global__ __launch_bounds__(256) void export_spz_kernel(gsm::AssetView a, gsm::ExportXform X, const uint32_t* __restrict__ alive, uint32_t n, uint32_t fractBits,
+                                                         uint32_t shCoeffs, SpzColumns out) {
+    // per wave: positions 576, alpha 64, colour / scale / rotation 192 each, SH 2880 bytes -- 4096, each part at a multiple of 4
+    constexpr uint32_t kAt[gsm::kSpzColumns] = { 0u, 576u, 640u, 832u, 1024u, 1216u };
+    __shared__ __attribute__((aligned(16))) uint8_t s_col[4][4096];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t waveFirst = blockIdx.x * 256u + wave * 64u, rank = waveFirst + lane;
+    uint8_t* s = s_col[wave];
+    const uint32_t shWidth = 3u * shCoeffs;
+    if (rank < n) {
+        const uint32_t src = alive[rank], ci = src >> 8;
+        float rec[kRecFloats], opacity;
+        gsm::ExportSplatLinear(a, X, src, ci, gsm::LoadSplatPosChunk(a, src, ci), false, rec, opacity);
+        gsm::SpzPackSplat(rec, opacity, fractBits, shCoeffs, s + kAt[0] + lane * 9u, s + kAt[1] + lane, s + kAt[2] + lane * 3u, s + kAt[3] + lane * 3u,
+                          s + kAt[4] + lane * 3u, s + kAt[5] + lane * shWidth);
+    } else {                                                       // what the last wave's rounding up carries into the padding
+        for (uint32_t k = 0; k < 9u; ++k) s[kAt[0] + lane * 9u + k] = 0u;
+        s[kAt[1] + lane] = 0u;
+        for (uint32_t k = 0; k < 3u; ++k) { s[kAt[2] + lane * 3u + k] = 0u; s[kAt[3] + lane * 3u + k] = 0u; s[kAt[4] + lane * 3u + k] = 0u; }
+        for (uint32_t k = 0; k < shWidth; ++k) s[kAt[5] + lane * shWidth + k] = 0u;
+    }
+    __syncthreads();
+    if (waveFirst >= n) return;                                    // (after the barrier: a wave without a rank writes nothing)
+    const uint32_t count = n - waveFirst < 64u ? n - waveFirst : 64u;
+#pragma unroll
+    for (uint32_t c = 0; c < gsm::kSpzColumns; ++c) {
+        const uint32_t w = gsm::SpzColumnWidth(c, shCoeffs);
+        const uint32_t dwords = (count * w + 3u) / 4u;             // <= 16 w: inside the wave's 64 w staged bytes, and inside the region's padding
+        uint32_t* dst = (uint32_t*)(out.col[c] + (size_t)waveFirst * w);
+        const uint32_t* from = (const uint32_t*)(s + kAt[c]);
+        for (uint32_t i = lane; i < dwords; i += 64u) dst[i] = from[i];
+    }
+}
+
+// bytes of column c's region in the transient buffer: n x width, a dword of padding, rounded up to 16
+static size_t spz_region_bytes(uint32_t n, uint32_t width) { return (((size_t)n * width + 4u) + 15u) / 16u * 16u; }
+
+// One SPZ export: the alive list and the bounds, fract_bits, the pack, then the columns to the host slice by slice.  ev: null, or six events
+// (scripts/export_spz_timing.py): before / after the count + scan, the alive list + bounds, the pack
+struct SpzRun {
+    gs_renderer* r = nullptr;
+    gsm::ExportXform X;
+    gs_spz_params s;
+    uint32_t chunks = 0, total = 0, fract = 0, shCoeffs = 0;
+    DevBuf<uint32_t> counts, base, alive;
+    DevBuf<float> partial, bounds;
+    DevBuf<uint8_t> cols;
+    size_t off[gsm::kSpzColumns] = {}, bytes[gsm::kSpzColumns] = {};
+
+    uint64_t body_bytes() const { return spz_body_bytes(total, s.sh_level); }
+
+    int32_t prepare(Event* ev = nullptr) {
+        hipStream_t st = r->ctx->stream;
+        shCoeffs = gsm::SpzShCoeffs(s.sh_level);
+        chunks = (r->n + 255u) / 256u;
+        if (chunks == 0u) return fail(GS_ERR_INVALID_ARGUMENT, spz_alive_refusal(0));
+        GS_HIP(counts.alloc((size_t)chunks * 4));
+        GS_HIP(base.alloc(((size_t)chunks + 1) * 4));
+        if (ev) GS_HIP(hipEventRecord(ev[0], st));
+        GS_TRY(enqueue_alive_counts(st, asset_view(r), edit_view(r), chunks, counts.get(), base.get()));
+        if (ev) GS_HIP(hipEventRecord(ev[1], st));
+        {
+            const hipError_t he = hipMemcpyAsync(&total, base.get() + chunks, 4, hipMemcpyDeviceToHost, st);
+            const hipError_t hs = hipStreamSynchronize(st);        // nothing in flight outlives the buffers
+            GS_HIP(he);
+            GS_HIP(hs);
+        }
+        if (const char* why = spz_alive_refusal(total)) return fail(GS_ERR_INVALID_ARGUMENT, why);
+        GS_HIP(alive.alloc(((size_t)total + 16) * 4));
+        GS_HIP(partial.alloc((size_t)chunks * 6 * 4));
+        GS_HIP(bounds.alloc(6 * 4));
+        AliveXform B;
+        B.through = X.bake;
+        memcpy(B.m, X.o2w, sizeof(B.m));
+        float hostBounds[6] = { 0, 0, 0, 0, 0, 0 };
+        if (ev) GS_HIP(hipEventRecord(ev[2], st));
+        const int32_t rc = enqueue_alive_list(st, asset_view(r), edit_view(r), B, chunks, base.get(), alive.get(), partial.get(), bounds.get());
+        hipError_t he = hipSuccess;
+        if (rc == GS_OK && ev) he = hipEventRecord(ev[3], st);
+        if (rc == GS_OK && he == hipSuccess) he = hipMemcpyAsync(hostBounds, bounds.get(), sizeof(hostBounds), hipMemcpyDeviceToHost, st);
+        const hipError_t hs = hipStreamSynchronize(st);            // whatever failed: nothing in flight outlives the buffers
+        GS_TRY(rc);
+        GS_HIP(he);
+        GS_HIP(hs);
+        fract = s.fract_bits == GS_SPZ_FRACT_AUTO ? gsm::SpzAutoFractBits(hostBounds) : s.fract_bits;
+        return GS_OK;
+    }
+
+    // the six columns into the transient buffer; the caller drains the stream (stream() does) before `cols` goes away
+    int32_t pack(Event* ev = nullptr) {
+        hipStream_t st = r->ctx->stream;
+        size_t at = 0;
+        for (uint32_t c = 0; c < gsm::kSpzColumns; ++c) {
+            const uint32_t w = gsm::SpzColumnWidth(c, shCoeffs);
+            off[c] = at; bytes[c] = (size_t)total * w;
+            at += spz_region_bytes(total, w);
+        }
+        GS_HIP(cols.alloc(at));
+        SpzColumns out;
+        for (uint32_t c = 0; c < gsm::kSpzColumns; ++c) out.col[c] = cols.get() + off[c];
+        if (ev) GS_HIP(hipEventRecord(ev[4], st));
+        hipLaunchKernelGGL(export_spz_kernel, dim3((total + 255u) / 256u), dim3(256), 0, st, asset_view(r), X, (const uint32_t*)alive.get(), total, fract, shCoeffs, out);
+        GS_HIP(hipGetLastError());
+        if (ev) GS_HIP(hipEventRecord(ev[5], st));
+        return GS_OK;
+    }
+
+    // header, then column by column through two pinned slices that fill alternately: the next slice's copy is in flight while the sink has this one.
+    // sink(data, bytes) != 0 stops the run with GS_ERR_INVALID_ARGUMENT (its own detail set).  The host never holds the body.
+    template <class Sink> int32_t stream(Sink&& sink) {
+        hipStream_t st = r->ctx->stream;
+        int32_t rc = pack();
+        size_t slice = s.slice_bytes ? (size_t)s.slice_bytes : (size_t)kSpzSliceDefault, largest = 0;
+        for (size_t b : bytes) largest = b > largest ? b : largest;
+        const size_t whole = (largest + kSpzSliceMin - 1) / kSpzSliceMin * kSpzSliceMin;      // no slice larger than a column needs
+        if (slice > whole) slice = whole;
+        PinnedBuf<uint8_t> pin[2];
+        Event ev[2];
+        for (int k = 0; k < 2 && rc == GS_OK; ++k) {
+            hipError_t he = pin[k].alloc(slice, hipHostMallocDefault);
+            if (he == hipSuccess) he = ev[k].create(hipEventDisableTiming);
+            if (he != hipSuccess) rc = fail_hip(he, "export: pinned slice", __FILE__, __LINE__);
+        }
+        if (rc == GS_OK) {
+            uint32_t head[4];
+            gsm::SpzHeaderWords(total, s.sh_level, fract, head);
+            if (sink((const uint8_t*)head, sizeof(head)) != 0) rc = GS_ERR_INVALID_ARGUMENT;
+        }
+        int pending = -1, cur = 0;
+        size_t pendingBytes = 0, at = 0;
+        uint32_t c = 0;
+        while (rc == GS_OK) {
+            while (c < gsm::kSpzColumns && at >= bytes[c]) { ++c; at = 0; }
+            const bool have = c < gsm::kSpzColumns;
+            size_t len = 0;
+            if (have) {
+                len = bytes[c] - at < slice ? bytes[c] - at : slice;
+                hipError_t he = hipMemcpyAsync(pin[cur].get(), cols.get() + off[c] + at, len, hipMemcpyDeviceToHost, st);
+                if (he == hipSuccess) he = hipEventRecord(ev[cur], st);
+                if (he != hipSuccess) { rc = fail_hip(he, "export slice", __FILE__, __LINE__); break; }
+                at += len;
+            }
+            if (pending >= 0) {                                    // the slice before this one: consumed while this one's copy runs
+                const hipError_t he = hipEventSynchronize(ev[pending]);
+                if (he != hipSuccess) { rc = fail_hip(he, "hipEventSynchronize", __FILE__, __LINE__); break; }
+                if (sink(pin[pending].get(), pendingBytes) != 0) { rc = GS_ERR_INVALID_ARGUMENT; break; }
+                pending = -1;
+            }
+            if (!have) break;
+            pending = cur; pendingBytes = len; cur ^= 1;
+        }
+        const hipError_t hs = hipStreamSynchronize(st);            // nothing in flight may outlive the buffers
+        if (rc == GS_OK && hs != hipSuccess) rc = fail_hip(hs, "export", __FILE__, __LINE__);
+        return rc;
+    }
+};
+
+static int32_t spz_begin(gs_renderer* r, const gs_export_params* p, const gs_spz_params* s, SpzRun& run, Event* ev = nullptr) {
+    if (!r || !p || !s) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
+    if (r->laneOf) return fail(GS_ERR_INVALID_ARGUMENT, "a lane holds no edit state: export its owner");
+    if (const char* why = spz_params_refusal(*s)) return fail(GS_ERR_INVALID_ARGUMENT, why);
+    GS_HIP(hipSetDevice(r->ctx->device));
+    run.r = r; run.s = *s;
+    run.X = export_xform_of(*p);
+    return run.prepare(ev);
+}
+
+// the gzip stream of a file being written: deflate with the gzip wrapper, the output through one fixed buffer
+struct GzWriter {
+    FILE* f = nullptr;
+    z_stream z;
+    bool live = false;
+    uint8_t buf[1 << 16];
+    ~GzWriter() { if (live) (void)deflateEnd(&z); }
+    int begin(FILE* file, int level) {
+        f = file;
+        memset(&z, 0, sizeof(z));
+        if (deflateInit2(&z, level, Z_DEFLATED, 16 + MAX_WBITS, 8, Z_DEFAULT_STRATEGY) != Z_OK) return 1;
+        live = true;
+        return 0;
+    }
+    // 0, 1 = deflate failed, 2 = fwrite failed (errno)
+    int write(const uint8_t* data, size_t n, int flush) {
+        z.next_in = (Bytef*)data; z.avail_in = (uInt)n;            // (a slice is at most 4 GiB - 1: slice_bytes is 32 bits)
+        for (;;) {
+            z.next_out = buf; z.avail_out = (uInt)sizeof(buf);
+            const int rc = deflate(&z, flush);
+            if (rc != Z_OK && rc != Z_STREAM_END && rc != Z_BUF_ERROR) return 1;
+            const size_t have = sizeof(buf) - z.avail_out;
+            if (have && fwrite(buf, 1, have, f) != have) return 2;
+            if (flush == Z_FINISH ? rc == Z_STREAM_END : (z.avail_in == 0 && z.avail_out != 0)) return 0;
+        }
+    }
+};
+
 } // namespace gs
 
 using namespace gs;
@@ -317,7 +527,77 @@ static int32_t export_kernel_times_impl(gs_renderer* r, const gs_export_params* 
     return GS_OK;
 }
 
+static int32_t export_spz_body_impl(gs_renderer* r, const gs_export_params* p, const gs_spz_params* s, void* out, size_t capacity_bytes, uint64_t* body_bytes,
+                                    uint32_t* alive, uint32_t* fract_bits_used) {
+    SpzRun run;
+    GS_TRY(spz_begin(r, p, s, run));
+    if (out && capacity_bytes < run.body_bytes()) return fail(GS_ERR_INVALID_ARGUMENT, "export: the buffer is smaller than the SPZ body");
+    if (body_bytes) *body_bytes = run.body_bytes();
+    if (alive) *alive = run.total;
+    if (fract_bits_used) *fract_bits_used = run.fract;
+    if (!out) return GS_OK;
+    uint8_t* dst = (uint8_t*)out;
+    return run.stream([&](const uint8_t* data, size_t n) { memcpy(dst, data, n); dst += n; return 0; });
+}
+
+static int32_t export_spz_impl(gs_renderer* r, const gs_export_params* p, const gs_spz_params* s, const char* path, uint32_t* alive) {
+    if (!path) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
+    SpzRun run;
+    GS_TRY(spz_begin(r, p, s, run));                               // every refusal comes before the file exists
+    FILE* f = fopen(path, "wb");
+    if (!f) { set_error_detail("export: cannot create %s: %s", path, strerror(errno)); return GS_ERR_INVALID_ARGUMENT; }
+    int32_t rc = GS_OK;
+    {
+        GzWriter gz;
+        auto put = [&](const uint8_t* data, size_t n, int flush) {
+            const int e = gz.write(data, n, flush);
+            if (e == 1) set_error_detail("export: deflate failed for %s", path);
+            if (e == 2) set_error_detail("export: writing %s failed: %s", path, strerror(errno));
+            return e;
+        };
+        if (gz.begin(f, s->compression_level) != 0) rc = fail(GS_ERR_OUT_OF_MEMORY, "export: deflateInit2 failed");
+        if (rc == GS_OK) rc = run.stream([&](const uint8_t* data, size_t n) { return put(data, n, Z_NO_FLUSH); });
+        if (rc == GS_OK && put(nullptr, 0, Z_FINISH) != 0) rc = GS_ERR_INVALID_ARGUMENT;
+    }
+    if (fclose(f) != 0 && rc == GS_OK) { set_error_detail("export: closing %s failed: %s", path, strerror(errno)); rc = GS_ERR_INVALID_ARGUMENT; }
+    if (rc != GS_OK) { remove(path); return rc; }                  // no partially written file is left behind
+    if (alive) *alive = run.total;
+    return GS_OK;
+}
+
+// The SPZ export's kernels once, timed by events: ms[0] export_count + export_scan, ms[1] the alive list + the bounds, ms[2] export_spz
+static int32_t export_spz_kernel_times_impl(gs_renderer* r, const gs_export_params* p, const gs_spz_params* s, float ms[3], uint32_t* alive, uint64_t* body_bytes) {
+    if (!ms) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
+    Event ev[6];
+    for (Event& e : ev) GS_HIP(e.create(hipEventDefault));
+    SpzRun run;
+    GS_TRY(spz_begin(r, p, s, run, ev));
+    const int32_t rc = run.pack(ev);
+    const hipError_t hs = hipStreamSynchronize(r->ctx->stream);   // whatever failed: nothing in flight outlives the events and the buffers
+    GS_TRY(rc);
+    GS_HIP(hs);
+    for (int k = 0; k < 3; ++k) GS_HIP(hipEventElapsedTime(&ms[k], ev[2 * k], ev[2 * k + 1]));
+    if (alive) *alive = run.total;
+    if (body_bytes) *body_bytes = run.body_bytes();
+    return GS_OK;
+}
+
 extern "C" {
+
+int32_t gs_renderer_edit_export_spz_body(gs_renderer* r, const gs_export_params* p, const gs_spz_params* s, void* out, size_t capacity_bytes, uint64_t* body_bytes,
+                                         uint32_t* alive, uint32_t* fract_bits_used) {
+    return export_guarded([&] { return export_spz_body_impl(r, p, s, out, capacity_bytes, body_bytes, alive, fract_bits_used); });
+}
+
+int32_t gs_renderer_edit_export_spz(gs_renderer* r, const gs_export_params* p, const gs_spz_params* s, const char* path, uint32_t* alive) {
+    return export_guarded([&] { return export_spz_impl(r, p, s, path, alive); });
+}
+
+// A measurement aid of scripts/export_spz_timing.py, which binds it itself: not declared in gsplat_c.h, not part of the ABI
+__attribute__((visibility("default"))) int32_t gs_export_spz_kernel_times_for_scripts(gs_renderer* r, const gs_export_params* p, const gs_spz_params* s, float ms[3],
+                                                                                    uint32_t* alive, uint64_t* body_bytes) {
+    return export_guarded([&] { return export_spz_kernel_times_impl(r, p, s, ms, alive, body_bytes); });
+}
 
 int32_t gs_renderer_edit_export_data(gs_renderer* r, const gs_export_params* p, void* out, size_t bytes, int32_t memory_kind) {
     return export_guarded([&] { return export_data_impl(r, p, out, bytes, memory_kind); });

@@ -42,6 +42,24 @@ inline gsm::ExportXform export_xform_of(const gs_export_params& p) {
     return X;
 }
 
+// The SPZ export's argument checks, host logic alone (so a host harness holds them without a device).  Each returns what is wrong, or null.
+// spz_params_refusal: before anything is launched; spz_alive_refusal: once the alive count is known -- a file the readers refuse is not written
+constexpr uint32_t kSpzSliceDefault = 64u << 20, kSpzSliceMin = 4096u;
+inline const char* spz_params_refusal(const gs_spz_params& s) {
+    if (s.sh_level > 3u) return "export: sh_level must be 0..3";
+    if (s.fract_bits > 24u && s.fract_bits != GS_SPZ_FRACT_AUTO) return "export: fract_bits must be 0..24 or GS_SPZ_FRACT_AUTO";
+    if (s.compression_level < -1 || s.compression_level > 9) return "export: compression_level must be -1..9";
+    if (s.slice_bytes != 0u && s.slice_bytes < kSpzSliceMin) return "export: slice_bytes must be 0 or at least 4096";
+    return nullptr;
+}
+inline const char* spz_alive_refusal(uint64_t alive) {
+    if (alive == 0u) return "export: no alive splat (an SPZ file holds at least one)";
+    if (alive > gsm::kSpzMaxSplats) return "export: more than 10,000,000 alive splats (the SPZ readers' limit)";
+    return nullptr;
+}
+// bytes of the gunzipped stream of n splats: the header and the six columns
+inline uint64_t spz_body_bytes(uint64_t n, uint32_t shLevel) { return 16u + n * (19u + 3u * gsm::SpzShCoeffs(shLevel)); }
+
 // what CSSelectionUpdate reads of a frame, and _SelectionRect
 inline gsm::EditSelect edit_select_of(const gs_frame_params& p, const float rect[4]) {
     gsm::EditSelect S;

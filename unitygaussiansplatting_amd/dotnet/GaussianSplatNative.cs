@@ -116,6 +116,12 @@ namespace GaussianSplatting.Runtime
         [DllImport(Lib)] public static extern int gs_renderer_edit_export_data(IntPtr renderer, ref ExportParams p, IntPtr dst, UIntPtr bytes, int memoryKind);
         [DllImport(Lib)] public static extern int gs_renderer_edit_export_alive(IntPtr renderer, ref ExportParams p, IntPtr dst, UIntPtr capacityRecords, out uint alive);
         [DllImport(Lib)] public static extern int gs_renderer_edit_export_ply(IntPtr renderer, ref ExportParams p, [MarshalAs(UnmanagedType.LPStr)] string path, out uint alive);
+        // export to SPZ: the gunzipped stream (header + six columns) to host memory, or the gzip file; fractBits 0..24 or SpzFractAuto, level -1..9
+        public const uint SpzFractAuto = 0xffffffffu;
+        [StructLayout(LayoutKind.Sequential)]
+        public struct SpzParams { public uint shLevel; public uint fractBits; public int compressionLevel; public uint sliceBytes; }
+        [DllImport(Lib)] public static extern int gs_renderer_edit_export_spz_body(IntPtr renderer, ref ExportParams p, ref SpzParams s, IntPtr dst, UIntPtr capacityBytes, out ulong bodyBytes, out uint alive, out uint fractBitsUsed);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_export_spz(IntPtr renderer, ref ExportParams p, ref SpzParams s, [MarshalAs(UnmanagedType.LPStr)] string path, out uint alive);
         // merge (EditSetSplatCount / EditCopySplatsInto, GaussianSplatRenderer.cs:960-1075; MergeSplatObjects, GaussianSplatRendererEditor.cs:213-235)
         [StructLayout(LayoutKind.Sequential)]
         public unsafe struct CopyParams { public fixed float matrix[16]; public fixed float rotation[4]; public fixed float scale[3]; }

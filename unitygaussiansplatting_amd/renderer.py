@@ -18,8 +18,8 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from ._abi import (GS_ERR_PAIR_OVERFLOW, GS_SORT_FULL, GS_SORT_VISIBLE, VIEW_DTYPE, gs_copy_params, gs_edit_info, gs_export_params, gs_frame_params, gs_frame_stats,
-                   gs_import_formats, gs_stage_times, make_asset_desc)
+from ._abi import (GS_ERR_PAIR_OVERFLOW, GS_SORT_FULL, GS_SORT_VISIBLE, GS_SPZ_FRACT_AUTO, VIEW_DTYPE, gs_copy_params, gs_edit_info, gs_export_params, gs_frame_params, gs_frame_stats,
+                   gs_import_formats, gs_spz_params, gs_stage_times, make_asset_desc)
 from ._lib import GsError, check
 from .asset import CalcTextureSize, ColorFormat, GaussianSplatAsset, SHFormat, VectorFormat, kCurrentVersion, kMaxSplats
 from .camera import Camera, Transform, frame_params, mat_mul, matrix_rotation_scale, sort_matrix
@@ -696,6 +696,35 @@ class GaussianSplatRenderer:
         p = self.ExportParams(bakeTransform)
         alive = C.c_uint32(0)
         check(_lib.lib().gs_renderer_edit_export_ply(self._r_h, C.byref(p), os.fsencode(path), C.byref(alive)), "gs_renderer_edit_export_ply")
+        return int(alive.value)
+
+    # -- editing: export to SPZ (no counterpart in the reference, which only reads the format) ----------------------------------------
+    @staticmethod
+    def SpzParams(shLevel: int = 3, fractBits=None, level: int = -1, sliceBytes: int = 0) -> gs_spz_params:
+        """fractBits None = automatic: the largest value up to 12 at which the largest exported |coordinate| still fits 24 bits"""
+        s = gs_spz_params()
+        s.sh_level, s.fract_bits = int(shLevel), GS_SPZ_FRACT_AUTO if fractBits is None else int(fractBits)
+        s.compression_level, s.slice_bytes = int(level), int(sliceBytes)
+        return s
+
+    def ExportSpzBody(self, bakeTransform: bool = False, shLevel: int = 3, fractBits=None, sliceBytes: int = 0):
+        """The gunzipped SPZ stream (16-byte header + six columns) of the splats that are neither deleted nor cut:
+        (np.uint8 array, alive, fract_bits used).  Blocks."""
+        self.UpdateCutoutsBuffer()
+        p, s = self.ExportParams(bakeTransform), self.SpzParams(shLevel, fractBits, -1, sliceBytes)
+        size, alive, fract = C.c_uint64(0), C.c_uint32(0), C.c_uint32(0)
+        fn = _lib.lib().gs_renderer_edit_export_spz_body
+        check(fn(self._r_h, C.byref(p), C.byref(s), None, 0, C.byref(size), C.byref(alive), C.byref(fract)), "gs_renderer_edit_export_spz_body")
+        out = np.zeros(size.value, np.uint8)
+        check(fn(self._r_h, C.byref(p), C.byref(s), out.ctypes.data, out.nbytes, C.byref(size), C.byref(alive), C.byref(fract)), "gs_renderer_edit_export_spz_body")
+        return out, int(alive.value), int(fract.value)
+
+    def ExportSpzFile(self, path: str, bakeTransform: bool = False, shLevel: int = 3, fractBits=None, level: int = -1, sliceBytes: int = 0) -> int:
+        """Writes the alive splats as an SPZ file (gzip level -1..9) that ReadSPZ / CreateGpuAssetFromFile read back; returns their number.  Blocks."""
+        self.UpdateCutoutsBuffer()
+        p, s = self.ExportParams(bakeTransform), self.SpzParams(shLevel, fractBits, level, sliceBytes)
+        alive = C.c_uint32(0)
+        check(_lib.lib().gs_renderer_edit_export_spz(self._r_h, C.byref(p), C.byref(s), os.fsencode(path), C.byref(alive)), "gs_renderer_edit_export_spz")
         return int(alive.value)
 
     # -- editing: bake (no counterpart in the reference, whose way back is ExportPlyFile + the importer) -------------------------------
