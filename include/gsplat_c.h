@@ -534,6 +534,39 @@ int32_t gs_target_device_ptr(gs_target* t, void** rgba16f_dev, void** resolved_r
 int32_t gs_target_set_profiling(gs_target* t, int32_t enabled);
 int32_t gs_target_resolve_time(gs_target* t, float* mean_ms, int32_t* count);
 
+/* ---- pick output: per-pixel surface depth and splat id from the blend  (additions to ABI 9) ------------------------
+ * The reference draws the splats with ZWrite Off: nothing after the draw knows where the splat surface is.  With pick output on, the splat
+ * blend also leaves one 16-byte record per pixel of the target.  The ACCUMULATED ALPHA of a pixel is the blend's own accumulator (the fp16
+ * alpha after every ROP step in exact mode, the fp32 one in fast mode); a pixel is CROSSED by the first live fragment whose blend takes it
+ * from < threshold to >= threshold; the record holds that fragment's splat index in the asset, that splat's view depth clip.w (the bits
+ * gs_renderer_calc_view culled and drew it with) and the tag of the renderer that drew it.  A pixel never crossed holds
+ * { +inf, 0xFFFFFFFF, 0, 0 }.  gs_target_clear resets every record (folded into the next draw like the pixel clear).  A draw into a target
+ * that already holds pixels starts from the stored alpha: it leaves an existing record alone and writes a pixel's record only if it is the
+ * draw that crosses it, so several renderers (distinct tags) can share one target.  Pixels are the same bits with pick output on or off.
+ * Only GS_RENDER_SPLATS draws write records: gs_renderer_draw in a debug render mode into a target with pick output on returns
+ * GS_ERR_INVALID_ARGUMENT. */
+typedef struct gs_pick_record {
+    float depth;        /* view depth (clip.w) of the crossing splat; +inf = none */
+    uint32_t splat;     /* its index in the asset; 0xFFFFFFFF = none */
+    uint32_t tag;       /* gs_renderer_set_pick_tag of the renderer that drew it */
+    uint32_t zero;
+} gs_pick_record;
+/* enabled != 0: allocates the records (all "none") and sets the threshold, 0 < threshold <= 1 (else GS_ERR_INVALID_ARGUMENT, nothing changed);
+ * a target that is already on only takes the new threshold.  0: frees them.  A target of a context with lanes
+ * (gs_renderer_set_frames_in_flight) doubles the records exactly as it doubles its pixels. */
+int32_t gs_target_set_pick_output(gs_target* t, int32_t enabled, float threshold);
+int32_t gs_target_download_pick(gs_target* t, void* out, size_t bytes);   /* exactly W*H*16 B, row 0 = top; blocks */
+int32_t gs_target_pick_at(gs_target* t, uint32_t x, uint32_t y, gs_pick_record* record_out);   /* one record; blocks; x >= W or y >= H: invalid argument */
+/* the device pointer of the records (W*H x 16 B); marks the target exposed, as gs_target_device_ptr does */
+int32_t gs_target_pick_device_ptr(gs_target* t, void** pick_dev);
+/* the tag this renderer's draws write (default 0); a plain setting, shared by the lanes of gs_renderer_set_frames_in_flight */
+int32_t gs_renderer_set_pick_tag(gs_renderer* r, uint32_t tag);
+/* Select what one SEES: for every pixel of the inclusive rectangle (x0, y0) .. (x1, y1) (pixels, y down, clipped to the target) whose record
+ * carries this renderer's tag and a splat < N that is neither deleted nor cut by the renderer's current cutouts, set that splat's bit in
+ * `selected` (subtract != 0: clear it).  A click is a 1x1 rectangle.  Asynchronous on the context's stream, ordered after the target's last
+ * use; gs_renderer_edit_info then reports the new counts and bounds.  x0 > x1 or y0 > y1, or a target without pick output: invalid argument. */
+int32_t gs_renderer_edit_select_surface(gs_renderer* r, gs_target* t, int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t subtract);
+
 /* ---- native importer (host code; no GPU needed, one optional GPU stage): GaussianSplatAssetCreator.CreateAsset minus the Unity asset database -- */
 /* InputSplatData (GaussianFileReader.cs:17-26) as separate arrays, in the PLY domain after ReorderSHs: */
 typedef struct gs_import_input {

@@ -18,4 +18,4 @@ for f in files:
         else:
             cur[k] = v
         if k == "LDS Size [bytes/block]" or k.startswith("LDS Size"):
-            print(f"{cur['name'][:40]:40s} vgpr {cur.get('VGPRs','?'):>4s} agpr {cur.get('AGPRs','?'):>3s} sgpr {cur.get('TotalSGPRs','?'):>4s} scratch {cur.get('ScratchSize [bytes/lane]','?'):>4s} occ {cur.get('Occupancy [waves/SIMD]','?'):>2s} lds {v}")
+            print(f"{cur['name'][:48]:48s} vgpr {cur.get('VGPRs','?'):>4s} agpr {cur.get('AGPRs','?'):>3s} sgpr {cur.get('TotalSGPRs','?'):>4s} scratch {cur.get('ScratchSize [bytes/lane]','?'):>4s} occ {cur.get('Occupancy [waves/SIMD]','?'):>2s} lds {v}")

@@ -53,6 +53,14 @@ class gs_edit_info(C.Structure):         # m_GpuEditCountsBounds decoded (gs_ren
                 ("bounds_min", C.c_float * 3), ("bounds_max", C.c_float * 3)]
 
 
+class gs_pick_record(C.Structure):       # one pixel of a target's pick output (gs_target_set_pick_output): 16 bytes
+    _fields_ = [("depth", C.c_float), ("splat", C.c_uint32), ("tag", C.c_uint32), ("zero", C.c_uint32)]
+
+
+GS_PICK_NO_SPLAT = 0xFFFFFFFF
+# gs_target_download_pick as a structured numpy array
+PICK_DTYPE = [("depth", "<f4"), ("splat", "<u4"), ("tag", "<u4"), ("zero", "<u4")]
+
 GS_EXPORT_RECORD_BYTES = 248
 
 

@@ -7,7 +7,7 @@ import ctypes as C
 import os
 
 from ._abi import (gs_asset_desc, gs_copy_params, gs_cutout, gs_edit_info, gs_export_params, gs_frame_params, gs_frame_stats, gs_import_formats, gs_import_input,
-                   gs_splat_file_info, gs_spz_params, gs_stage_times)
+                   gs_pick_record, gs_splat_file_info, gs_spz_params, gs_stage_times)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GSPLAT_LIB") or os.path.join(_HERE, "libgsplat_hip.so")   # GSPLAT_LIB: A/B a variant build
@@ -114,6 +114,12 @@ SIGNATURES = {
     "gs_target_device_ptr": (C.c_int32, [_P, _PP, _PP]),
     "gs_target_set_profiling": (C.c_int32, [_P, C.c_int32]),
     "gs_target_resolve_time": (C.c_int32, [_P, C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
+    "gs_target_set_pick_output": (C.c_int32, [_P, C.c_int32, C.c_float]),
+    "gs_target_download_pick": (C.c_int32, [_P, _P, C.c_size_t]),
+    "gs_target_pick_at": (C.c_int32, [_P, C.c_uint32, C.c_uint32, C.POINTER(gs_pick_record)]),
+    "gs_target_pick_device_ptr": (C.c_int32, [_P, _PP]),
+    "gs_renderer_set_pick_tag": (C.c_int32, [_P, C.c_uint32]),
+    "gs_renderer_edit_select_surface": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "gs_import_blob_sizes": (C.c_int32, [C.c_uint32, C.POINTER(gs_import_formats), C.c_uint64 * 5]),
     "gs_import_encode": (C.c_int32, [C.POINTER(gs_import_input), C.POINTER(gs_import_formats), C.c_void_p * 5, C.c_uint64 * 5,
                                       C.POINTER(C.c_float), C.POINTER(C.c_float)]),

@@ -559,6 +559,8 @@ int32_t gs_renderer_draw(gs_renderer* r, const gs_frame_params* p, gs_target* rt
     if ((uint32_t)p->screen_w != rt->width || (uint32_t)p->screen_h != rt->height) return fail(GS_ERR_INVALID_ARGUMENT, "screen_w/h do not match the target");
     GS_TRY(bind_device(r->ctx));
     const int mode = settings(r).renderMode;
+    // the box blend and the debug-point kernels write no pick records: a frame whose records would be stale is refused, not drawn
+    if (mode != GS_RENDER_SPLATS && rt->pick) return fail(GS_ERR_INVALID_ARGUMENT, "gs_renderer_draw: a debug render mode cannot draw into a target with pick output on");
     if (mode == GS_RENDER_DEBUG_POINTS || mode == GS_RENDER_DEBUG_POINT_INDICES) return enqueue_debug_points(r, p, rt);
     GS_TRY(maybe_grow_pairs(r));
     if (mode == GS_RENDER_DEBUG_BOXES) return enqueue_debug_boxes(r, p, rt, false);
@@ -640,6 +642,13 @@ int32_t gs_renderer_set_render_mode(gs_renderer* r, int32_t mode, float point_di
 int32_t gs_renderer_set_blend_mode(gs_renderer* r, int32_t mode) {
     if (!r || (mode != 0 && mode != 1)) return fail(GS_ERR_INVALID_ARGUMENT, "blend mode must be 0 or 1");
     r->set.blendMode = mode;
+    return GS_OK;
+}
+
+int32_t gs_renderer_set_pick_tag(gs_renderer* r, uint32_t tag) {
+    if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
+    if (r->laneOf) return fail(GS_ERR_INVALID_ARGUMENT, "a lane draws with its owner's settings: set its owner");
+    r->set.pickTag = tag;                                        // (a plain setting: the lanes read it through gs::settings)
     return GS_OK;
 }
 
@@ -990,7 +999,12 @@ int32_t gs_target_clear(gs_target* t) {
             GS_TRY(bind_device(t->ctx));
             GS_HIP(t->rgba16fAlt.alloc((size_t)t->width * t->height * 8));
         }
+        if (t->pick && !t->pickAlt) {                   // (the pending clear fills it: no record of it is read before)
+            GS_TRY(bind_device(t->ctx));
+            GS_HIP(t->pickAlt.alloc((size_t)t->width * t->height * sizeof(PickRecord)));
+        }
         std::swap(t->rgba16f, t->rgba16fAlt);
+        std::swap(t->pick, t->pickAlt);
         std::swap(t->evLastUse, t->evLastUseAlt);
         std::swap(t->lastUseValid, t->lastUseValidAlt);
     }
@@ -1066,6 +1080,54 @@ int32_t gs_target_device_ptr(gs_target* t, void** rgba16f_dev, void** resolved_d
     t->exposed = true;                      // (lanes: from now on a draw into this target waits for everything the context's stream holds)
     if (rgba16f_dev) *rgba16f_dev = t->rgba16f;
     if (resolved_dev) *resolved_dev = t->resolved;
+    return GS_OK;
+}
+
+// ---- pick output -----------------------------------------------------------------
+int32_t gs_target_set_pick_output(gs_target* t, int32_t enabled, float threshold) {
+    if (!t) return fail(GS_ERR_INVALID_ARGUMENT, "target is null");
+    if (enabled && !(threshold > 0.0f && threshold <= 1.0f)) return fail(GS_ERR_INVALID_ARGUMENT, "pick threshold must be in (0, 1]");
+    GS_TRY(bind_device(t->ctx));
+    if (!enabled) {
+        if (t->pick || t->pickAlt) {
+            GS_HIP(hipStreamSynchronize(t->ctx->stream));       // (a lane's blend into the target is joined into this stream by its draw)
+            t->pick.reset(); t->pickAlt.reset();
+        }
+        return GS_OK;
+    }
+    if (!t->pick) {
+        DevBuf<PickRecord> rec;
+        GS_HIP(rec.alloc((size_t)t->width * t->height * sizeof(PickRecord)));
+        GS_TRY(enqueue_pick_fill(t, rec));
+        t->pick = std::move(rec);
+        GS_TRY(target_touched(t, t->ctx->stream));
+    }
+    t->pickTau = threshold;
+    return GS_OK;
+}
+
+int32_t gs_target_download_pick(gs_target* t, void* out, size_t bytes) {
+    if (!t || !out) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
+    if (!t->pick) return fail(GS_ERR_INVALID_ARGUMENT, "the target has no pick output (gs_target_set_pick_output)");
+    if (bytes != (size_t)t->width * t->height * sizeof(PickRecord)) return fail(GS_ERR_INVALID_ARGUMENT, "pick download: bytes must be width * height * 16");
+    GS_TRY(flush_clear(t));
+    return download(t->ctx, out, t->pick, bytes);
+}
+
+int32_t gs_target_pick_at(gs_target* t, uint32_t x, uint32_t y, gs_pick_record* record_out) {
+    if (!t || !record_out) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
+    if (!t->pick) return fail(GS_ERR_INVALID_ARGUMENT, "the target has no pick output (gs_target_set_pick_output)");
+    if (x >= t->width || y >= t->height) return fail(GS_ERR_INVALID_ARGUMENT, "pick_at: pixel outside the target");
+    GS_TRY(flush_clear(t));
+    return download(t->ctx, record_out, t->pick + ((size_t)y * t->width + x), sizeof(PickRecord));
+}
+
+int32_t gs_target_pick_device_ptr(gs_target* t, void** pick_dev) {
+    if (!t || !pick_dev) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
+    if (!t->pick) return fail(GS_ERR_INVALID_ARGUMENT, "the target has no pick output (gs_target_set_pick_output)");
+    GS_TRY(flush_clear(t));                 // the caller is about to read the memory directly
+    t->exposed = true;                      // (no more flips: the pointer stays put; lanes wait for everything the context's stream holds)
+    *pick_dev = t->pick.get();
     return GS_OK;
 }
 

@@ -144,6 +144,20 @@ enum TieBase { TB_INDEX = 0,      // base = identity: the splat index
                TB_RANK = 1,       // base = gs_renderer::order: rank[splat] (its inverse, gs_renderer::visBaseRank)
                TB_POSITION = 2 }; // the input is a stable sort OF the base: the position inside the run (consolidation over all N)
 
+// One pixel of a target's pick output (gs_pick_record of the C ABI): the splat whose blend took the pixel's accumulated alpha from < tau to >= tau, its view
+// depth clip.w (splat_depth_kernel's bits) and the tag of the renderer that drew it; { +inf, 0xFFFFFFFF, 0, 0 } = never crossed
+struct alignas(16) PickRecord { float depth; uint32_t splat, tag, zero; };
+static_assert(sizeof(PickRecord) == 16 && sizeof(PickRecord) == sizeof(gs_pick_record), "PickRecord is 16 B");
+constexpr uint32_t kPickNoSplat = 0xFFFFFFFFu;
+// what a blend with pick output needs besides the pixels (a kernel argument; all zero for the other instantiations, which never read it)
+struct PickOut {
+    PickRecord* rec;        // the target's records
+    float tau;              // the threshold, as the fp32 accumulator of fast mode compares it
+    uint32_t tauHalfHi;     // ... and for exact mode: the smallest fp16 >= tau, << 16 (alpha is the high half of the accumulator's second dword)
+    uint32_t tag;           // the drawing renderer's tag
+    uint32_t noDepth;       // the target has no depth attachment: the scene-depth test of the depth-carrying form is off
+};
+
 // The two words every workgroup hits with an atomic (ticket, visible) sit in their own 128-B lines: same-address
 // atomics serialise in one L2 channel (~11 ns each), so they must not also queue behind each other.
 struct BinControl {
@@ -233,6 +247,11 @@ struct gs_target {
     gs::Event evLastUseAlt;
     bool lastUseValidAlt = false;
     bool exposed = false;                   // gs_target_device_ptr handed the memory out: the host's own work on the context's stream may touch it (and the pointer stays put)
+    // optional pick output (gs_target_set_pick_output): one gs::PickRecord per pixel, written by the splat blend for the pixel
+    // whose accumulated alpha it takes across pickTau.  Doubled with the pixels (pickAlt follows rgba16fAlt through gs_target_clear's flip).
+    gs::DevBuf<gs::PickRecord> pick;        // W*H records, or null (pick output off)
+    gs::DevBuf<gs::PickRecord> pickAlt;     // the other buffer's, allocated at the first flip
+    float pickTau = 0.5f;                   // 0 < tau <= 1
 };
 
 namespace gs {
@@ -248,6 +267,7 @@ struct RendererSettings {
     uint32_t tileOverrideWL = 0, tileOverrideHL = 0;   // gs_renderer_set_tile_shape: log2 tile width / height, 0 = automatic
     int visHistLimit = kVisHistory;         // rows kept before the base is consolidated (gs_renderer_set_sort_history_limit; GSPLAT_VIS_HISTORY)
     bool selectionHighlight = false;        // gs_renderer_set_selection_highlight: splat frames draw the selection as the reference does (gs::edit_view)
+    uint32_t pickTag = 0;                   // gs_renderer_set_pick_tag: what this renderer's draws write into the pick records they own
 };
 } // namespace gs
 
@@ -272,7 +292,7 @@ struct gs_renderer {
     gs::DevBuf<gs::SplatRec> recs;          // N x 32 B, indexed by splat (written by calc_view)
     gs::DevBuf<gsm::BoxRec> boxRecs;        // N x 64 B, debug box modes only (allocated on first use)
     gs::DevBuf<uint32_t> chunkOrder;        // identity order of the chunks (DebugChunkBounds draws them in index order)
-    gs::DevBuf<float> recW;                 // N x 4 B: clip.w of the visible splats, filled by the draw only when the target has a depth attachment
+    gs::DevBuf<float> recW;                 // N x 4 B: clip.w of the visible splats, filled by the draw only when the target has a depth attachment or pick output
     gs::DevBuf<uint2> rects;                // N x 8 B: x = x0 | y0 << 16, y = (x1 + 1) | (y1 + 1) << 16, pixels (0 = culled): gsm::PackPixelRect
     gs::DevBuf<unsigned long long> visMask; // ceil(N/64) x 8 B: bit s = splat s reaches at least one tile (written by calc_view); + ceil(N/64) B per-wave flags (wave_flags_of)
     // edit state read by calc_view (m_GpuEditDeleted / m_GpuEditCutouts, GaussianSplatRenderer.cs:266,269)
@@ -431,6 +451,7 @@ int32_t enqueue_debug_points(gs_renderer* r, const gs_frame_params* p, gs_target
 int32_t enqueue_debug_boxes(gs_renderer* r, const gs_frame_params* p, gs_target* rt, bool chunks);   // RenderMode.DebugBoxes / DebugChunkBounds
 int32_t enqueue_resolve(gs_target* t, const float bg[4], bool want8);
 int32_t flush_clear(gs_target* t);          // perform a pending gs_target_clear now
+int32_t enqueue_pick_fill(gs_target* t, PickRecord* rec);   // every record of a target's pick buffer := "none", on the context's stream
 // edit (gs_edit.hip)
 void edit_free(gs_renderer* r);             // the selection buffers and the mouse-down copies (not deletedBits, not the private blobs)
 int32_t edit_ensure(gs_renderer* r);        // EnsureEditingBuffers: the zeroed selection buffers, made once

@@ -732,6 +732,14 @@ struct EditSelect {
     float rect[4];
 };
 
+// gs_renderer_edit_select_surface: the inclusive pixel rectangle clipped to the target (w = 0: nothing left), the renderer's tag and the operation
+struct PickSelect {
+    uint32_t x0, y0, w, h;          // clipped rectangle, pixels
+    uint32_t stride;                // the target's width: records per row
+    uint32_t tag;
+    uint32_t subtract;
+};
+
 // CSSelectionUpdate's test of one splat (SplatUtilities.compute:400-416): does the rectangle select it?  World and clip position
 // are CalcViewGeom's expressions, so the clip position has the bits of the view record's pos.  Every comparison is the
 // reference's, literally: a NaN w is not "behind", and a NaN pixel position is outside no edge of the rectangle, so it is a hit.

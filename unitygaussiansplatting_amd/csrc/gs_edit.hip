@@ -175,6 +175,24 @@ __global__ __launch_bounds__(256) void edit_transform_kernel(uint8_t* __restrict
     }
 }
 
+// gs_renderer_edit_select_surface: one thread per pixel of the clipped rectangle.  A record counts if it carries the renderer's tag and a splat < N that
+// is neither deleted nor cut (the test every kernel above makes); many pixels name the same splat and a word's splats lie anywhere in the rectangle,
+// so -- unlike the kernels above, where a wave owns its words -- the bit is set or cleared with an atomic (the reference's InterlockedOr / And).
+__global__ __launch_bounds__(256) void edit_select_surface_kernel(gsm::AssetView a, gsm::EditView e, gsm::PickSelect S, const PickRecord* __restrict__ rec,
+                                                                  uint32_t* __restrict__ sel) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= S.w * S.h) return;
+    const uint32_t x = S.x0 + i % S.w, y = S.y0 + i / S.w;
+    const PickRecord pr = rec[(size_t)y * S.stride + x];
+    if (pr.tag != S.tag || pr.splat >= a.n) return;
+    const uint32_t idx = pr.splat;
+    if (e.deletedBits && ((e.deletedBits[idx >> 5] >> (idx & 31u)) & 1u)) return;
+    const gsm::V3 pos = gsm::LoadSplatPosChunk(a, idx, idx >> 8);
+    if (gsm::IsSplatCut(e, pos.x, pos.y, pos.z)) return;
+    if (S.subtract) atomicAnd(sel + (idx >> 5), ~(1u << (idx & 31u)));
+    else atomicOr(sel + (idx >> 5), 1u << (idx & 31u));
+}
+
 // EnsureEditingBuffers (GaussianSplatRenderer.cs:767-786) without the deleted buffer, which is made when a delete first needs it
 int32_t edit_ensure(gs_renderer* r) {
     if (r->laneOf) return fail(GS_ERR_INVALID_ARGUMENT, "a lane holds no selection: edit its owner");
@@ -363,6 +381,25 @@ int32_t gs_renderer_edit_update_selection(gs_renderer* r, const gs_frame_params*
                        (const uint32_t*)r->editSelectedMouseDown, r->editSelected, (uint32_t)bit_words(r->n), subtract ? 0u : 1u);
     GS_HIP(hipGetLastError());
     return edit_selected_to_lanes(r);
+}
+
+int32_t gs_renderer_edit_select_surface(gs_renderer* r, gs_target* t, int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t subtract) {
+    if (!r || !t) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
+    if (t->ctx != r->ctx) return fail(GS_ERR_INVALID_ARGUMENT, "target belongs to another context");
+    if (!t->pick) return fail(GS_ERR_INVALID_ARGUMENT, "the target has no pick output (gs_target_set_pick_output)");
+    if (x0 > x1 || y0 > y1) return fail(GS_ERR_INVALID_ARGUMENT, "select_surface: empty rectangle");
+    GS_TRY(edit_ensure(r));
+    GS_TRY(flush_clear(t));                                        // a cleared target that nothing has drawn into holds no record
+    // the records' last writer: a lane's blend is joined into the context's stream by its draw, so the stream already orders this kernel after it
+    const gsm::PickSelect S = pick_select_of(x0, y0, x1, y1, t->width, t->height, r->set.pickTag, subtract);
+    if (S.w && S.h) {
+        const uint32_t pixels = S.w * S.h;
+        hipLaunchKernelGGL(edit_select_surface_kernel, dim3((pixels + 255u) / 256u), dim3(256), 0, r->ctx->stream, asset_view(r), edit_view(r), S,
+                           (const PickRecord*)t->pick.get(), r->editSelected.get());
+        GS_HIP(hipGetLastError());
+        GS_TRY(target_touched(t, r->ctx->stream));
+    }
+    return edit_selected_to_lanes(r);                              // (counts and bounds: gs_renderer_edit_info computes them when asked, as after every selection call)
 }
 
 int32_t gs_renderer_edit_delete_selected(gs_renderer* r) {

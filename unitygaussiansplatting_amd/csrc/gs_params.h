@@ -70,6 +70,19 @@ inline gsm::EditSelect edit_select_of(const gs_frame_params& p, const float rect
     return S;
 }
 
+// gs_renderer_edit_select_surface: (x0, y0) .. (x1, y1) inclusive, y down, clipped to a width x height target; w = h = 0 when nothing is left
+// (the caller has refused x0 > x1 and y0 > y1)
+inline gsm::PickSelect pick_select_of(int32_t x0, int32_t y0, int32_t x1, int32_t y1, uint32_t width, uint32_t height, uint32_t tag, int32_t subtract) {
+    gsm::PickSelect S;
+    memset(&S, 0, sizeof(S));
+    S.stride = width; S.tag = tag; S.subtract = subtract ? 1u : 0u;
+    const int64_t cx0 = x0 < 0 ? 0 : x0, cy0 = y0 < 0 ? 0 : y0;
+    const int64_t cx1 = x1 >= (int64_t)width ? (int64_t)width - 1 : x1, cy1 = y1 >= (int64_t)height ? (int64_t)height - 1 : y1;
+    if (cx0 > cx1 || cy0 > cy1) return S;
+    S.x0 = (uint32_t)cx0; S.y0 = (uint32_t)cy0; S.w = (uint32_t)(cx1 - cx0 + 1); S.h = (uint32_t)(cy1 - cy0 + 1);
+    return S;
+}
+
 // the three transforms: zeros, then _SelectionCenter and the two matrices (rotate, scale; center = null: translate, which reads neither) and the
 // first deltaFloats of _SelectionDelta (3: translate, scale) / _SelectionDeltaRot (4: rotate)
 inline gsm::EditXform edit_xform_of(const float* center, const float* o2w, const float* w2o, const float* delta, int deltaFloats) {

@@ -17,7 +17,9 @@
 //                  The tile's list is streamed in batches of one record per thread staged in LDS (software-pipelined loads); each
 //                  wave culls the batch against its quadrant (bounding box + separating-axis test) with a ballot and walks
 //                  only the survivors, reading the record with wave-uniform LDS loads, blending front-to-back in registers.
-//                  It also performs a pending gs_target_clear (it writes every pixel of the target).
+//                  It also performs a pending gs_target_clear (it writes every pixel of the target).  On a target with pick output
+//                  (gs_target_set_pick_output) it also leaves, per pixel, the splat that took the accumulated alpha across the
+//                  target's threshold, its view depth and the renderer's tag (the PICK instantiations).
 // Semantics (DESIGN.md "compositor semantics") are those of the reference rasteriser: oriented quad |q|<=2,
 // alpha = saturate(exp(-|q|^2) * a), discard < 1/255, dst = src*(1-dst.a) + dst, fp16 rounding per blend.
 #include "gs_common.h"
@@ -857,6 +859,8 @@ template <> struct PixelAcc<0> {
     // src = (pr, pg, pb, pa) already premultiplied, fp32 (the box fragment shader's output)
     __device__ __forceinline__ void blend_src(float pr, float pg, float pb, float pa) { const float t = mix_one_minus_hi(ba); mix_blend4(rg, ba, pr, pg, pb, pa, t); }
     __device__ __forceinline__ bool finished() const { return (ba >> 16) == 0x3c00u; }      // A == 1.0: further blends add exactly 0
+    // pick output: A >= tau.  A is never negative, so fp16 order is the order of the bits, and with A in the high half one unsigned compare of the dword
+    __device__ __forceinline__ bool reached(const PickOut& pk) const { return ba >= pk.tauHalfHi; }
     __device__ __forceinline__ bool saturated() const { return false; }
     __device__ __forceinline__ uint2 pack() const { return make_uint2(rg, ba); }
 };
@@ -873,6 +877,7 @@ template <> struct PixelAcc<1> {
     __device__ __forceinline__ void blend_src(float pr, float pg, float pb, float pa) { const float t = 1.0f - a; r = fmaf(pr, t, r); g = fmaf(pg, t, g); b = fmaf(pb, t, b); a = fmaf(pa, t, a); }
     __device__ __forceinline__ bool finished() const { return (1.0f - a) < (1.0f / 4096.0f); }
     __device__ __forceinline__ bool saturated() const { return (1.0f - a) < (1.0f / 4096.0f); }
+    __device__ __forceinline__ bool reached(const PickOut& pk) const { return a >= pk.tau; }
     __device__ __forceinline__ uint2 pack() const {
         uint2 o;
         o.x = gsm::f32tof16(r) | (gsm::f32tof16(g) << 16);
@@ -923,14 +928,21 @@ __device__ unsigned long long g_blendTl[8192 * 8];
 // (RenderGaussianSplats.shader:87-101; gsm::DecideSelected): from the same q, power, y2 and v_exp_f32 result as the plain path, premultiplied in fp32
 // and blended through blend_src.  A survivor's record is an LDS broadcast, so the test is wave-uniform: a scalar branch.  Early termination,
 // finished() / saturated() and the depth test apply unchanged.  HL = false is the kernel as it was: frames without highlight launch it.
-template <int MODE, bool DEPTH, int TWL, int THL, bool HL>
+// PICK: the target has pick output (gs_target_set_pick_output).  The splat index travels beside r0 / r1 through the staging
+// pipeline into s_p[], the view depth into s_e[].w as for DEPTH (PICK is only instantiated over DEPTH = true; pk.noDepth switches the scene-depth
+// test off when the target has no attachment).  After every live blend a lane compares its accumulator with tau and keeps the staging slot of the
+// first fragment that reaches it (slots grow along the walk: a min); the slot is turned into (depth, splat) before the batch's staging is overwritten,
+// which is also before a wave that has just finished its quadrant leaves.  One 16-byte store per lane at the end, only by the draw that crossed the
+// pixel (or that performs the pending clear).  PICK = false is the kernel as it was.
+template <int MODE, bool DEPTH, int TWL, int THL, bool HL, bool PICK>
 __global__ __launch_bounds__(64 << (TWL + THL - 6)) void blend_kernel(const uint32_t* __restrict__ pairVals, const uint32_t* __restrict__ tileStart,
                                                     const uint32_t* __restrict__ tileEnd, const uint32_t* __restrict__ tileOrder,
                                                     uint32_t* __restrict__ tileCost, const SplatRec* __restrict__ recs,
                                                     uint16_t* __restrict__ rt, RasterConsts rc, int dstIsZero,
                                                     const float* __restrict__ recW, const float* __restrict__ sceneDepth,
                                                     const BinControl* __restrict__ binCtl, const uint32_t* __restrict__ pairSortError,
-                                                    FrameReport* __restrict__ report) {
+                                                    FrameReport* __restrict__ report, PickOut pk) {
+    static_assert(!PICK || DEPTH, "pick output is built over the depth-carrying form");
     constexpr int TW = 1 << TWL, TH = 1 << THL;                   // tile, pixels
     constexpr int NWX = TW / 8, NW = NWX * (TH / 8);              // waves: one per 8x8 quadrant
     constexpr int NT = 64 * NW;                                   // threads = pixels of the tile = records per batch
@@ -940,6 +952,8 @@ __global__ __launch_bounds__(64 << (TWL + THL - 6)) void blend_kernel(const uint
     __shared__ float4 s_e[NT];       // half extents of the footprint's bounding box, pixels; r^2 = ln(255 a) with slack
     __shared__ int s_done;
     __shared__ uint32_t s_cost;
+    uint32_t* s_p = nullptr;         // PICK: the staged records' splat indices
+    if constexpr (PICK) { __shared__ uint32_t s_pick[NT]; s_p = s_pick; }
     uint32_t survWalked = 0;                                      // survivors this wave walked (wave-uniform)
 
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -967,6 +981,7 @@ __global__ __launch_bounds__(64 << (TWL + THL - 6)) void blend_kernel(const uint
         if (threadIdx.x == 0 && blockIdx.x < 8192u) { unsigned long long* q = g_blendTl + blockIdx.x * 8u; q[0] = tl0; q[1] = wall_clock64(); q[2] = 0; q[3] = 0; q[4] = 0; q[5] = tile; q[6] = 0; }
 #endif
         if (dstIsZero && inside) *dst = make_uint2(0u, 0u);    // ... or cleared here, when this draw also performs the pending clear
+        if (PICK && dstIsZero && inside) pk.rec[(size_t)py * rc.width + (size_t)px] = PickRecord{ __builtin_inff(), kPickNoSplat, 0u, 0u };
         return;
     }
     uint32_t batchesWalked = 0;
@@ -977,8 +992,16 @@ __global__ __launch_bounds__(64 << (TWL + THL - 6)) void blend_kernel(const uint
 
     PixelAcc<MODE> acc;
     float sceneZ = 0.0f;
-    if (DEPTH) sceneZ = inside ? sceneDepth[(size_t)py * rc.width + (size_t)px] : 0.0f;
+    const bool noDepth = PICK && pk.noDepth != 0u;                // (uniform)
+    if (DEPTH) sceneZ = (inside && !noDepth) ? sceneDepth[(size_t)py * rc.width + (size_t)px] : 0.0f;
     acc.load((inside && !dstIsZero) ? *dst : make_uint2(0u, 0u));
+    // PICK: the staging slot of the fragment that crossed tau in the batch being walked; kPickOpen = not crossed yet, -1 = crossed (by an earlier
+    // batch, or by whatever the target held before this draw: then the record is not this draw's to write)
+    constexpr int kPickOpen = 0x7fffffff;
+    int pickSlot = kPickOpen;
+    float pickDepth = 0.0f;
+    uint32_t pickSplat = kPickNoSplat;                            // != kPickNoSplat: this draw crossed the pixel
+    if (PICK) pickSlot = acc.reached(pk) ? -1 : kPickOpen;
     if (tid == 0) s_done = 0;
     if (tid == 0) s_cost = 0u;
     bool waveDone = false;
@@ -990,11 +1013,13 @@ __global__ __launch_bounds__(64 << (TWL + THL - 6)) void blend_kernel(const uint
     const uint32_t lastPair = end - 1u;
     float4 r0, r1;
     float rw = 0.0f;                                              // DEPTH: the record's view depth
+    uint32_t rs = 0u;                                             // PICK: the record's splat index
     {
         const uint32_t s0 = pairVals[min(start + (uint32_t)tid, lastPair)];
         const float4* rp = (const float4*)(recs + s0);
         r0 = rp[0]; r1 = rp[1];                                   // cx cy a1x a1y | a2x a2y c0 c1
         if (DEPTH) rw = recW[s0];
+        if (PICK) rs = s0;
     }
     uint32_t sidxNext = pairVals[min(start + (uint32_t)NT + (uint32_t)tid, lastPair)];
     for (uint32_t bs = start; bs < end; bs += (uint32_t)NT) {
@@ -1016,11 +1041,13 @@ __global__ __launch_bounds__(64 << (TWL + THL - 6)) void blend_kernel(const uint
             s_a[tid] = make_float4(r0.x, r0.y, r0.z * inv1, r1.x * inv2);
             s_b[tid] = make_uint4(gsm::f2u(r0.w * inv1), gsm::f2u(r1.y * inv2), gsm::f2u(r1.z), gsm::f2u(r1.w));
             s_e[tid] = make_float4(fminf(exr, exe) + 0.02f, fminf(eyr, eye) + 0.02f, r2, rw);
+            if (PICK) s_p[tid] = rs;
         }
         {
             const float4* rp = (const float4*)(recs + sidxNext);
             r0 = rp[0]; r1 = rp[1];
             if (DEPTH) rw = recW[sidxNext];
+            if (PICK) rs = sidxNext;
             sidxNext = pairVals[min(bs + 2u * (uint32_t)NT + (uint32_t)tid, lastPair)];
         }
         __syncthreads();
@@ -1056,7 +1083,7 @@ __global__ __launch_bounds__(64 << (TWL + THL - 6)) void blend_kernel(const uint
                         bool ring, liveS;
                         const float alphaS = gsm::DecideSelected(__builtin_amdgcn_exp2f(y2), y2, ring, liveS);
                         liveS = liveS && inQuadS;
-                        if (DEPTH) liveS = liveS && (s_e[rec].w <= sceneZ);
+                        if (DEPTH) liveS = liveS && (noDepth || s_e[rec].w <= sceneZ);
                         if (MODE == 1) liveS = liveS && !acc.saturated();
 #ifdef GS_BLEND_STATS
                         { const unsigned long long lv = __ballot(liveS); GS_STAT(4, __popcll(lv)); }
@@ -1065,6 +1092,7 @@ __global__ __launch_bounds__(64 << (TWL + THL - 6)) void blend_kernel(const uint
                             float cr = ring ? 1.0f : half_hi(B4.z), cg = ring ? 0.0f : half_lo(B4.z), cb = ring ? 1.0f : half_hi(B4.w);
                             cr = fmaf(0.5f, 1.0f - cr, cr); cg = fmaf(0.5f, 0.0f - cg, cg); cb = fmaf(0.5f, 1.0f - cb, cb);      // lerp(rgb, (1, 0, 1), 0.5)
                             acc.blend_src(cr * alphaS, cg * alphaS, cb * alphaS, alphaS);
+                            if (PICK) pickSlot = min(pickSlot, acc.reached(pk) ? (int)rec : kPickOpen);
                         }
                         return;
                     }
@@ -1085,12 +1113,15 @@ __global__ __launch_bounds__(64 << (TWL + THL - 6)) void blend_kernel(const uint
                     } else {
                         live = (inQuad & (int)(alpha >= 1.0f / 255.0f)) != 0;
                     }
-                    if (DEPTH) live = live && (s_e[rec].w <= sceneZ);                  // ZTest LEqual on the quad's (single) depth
+                    if (DEPTH) live = live && (noDepth || s_e[rec].w <= sceneZ);       // ZTest LEqual on the quad's (single) depth
                     if (MODE == 1) live = live && !acc.saturated();
 #ifdef GS_BLEND_STATS
                     { const unsigned long long lv = __ballot(live); GS_STAT(4, __popcll(lv)); }
 #endif
-                    if (live) acc.blend(B4.z, B4.w, alpha);
+                    if (live) {
+                        acc.blend(B4.z, B4.w, alpha);
+                        if (PICK) pickSlot = min(pickSlot, acc.reached(pk) ? (int)rec : kPickOpen);      // one compare, one select (+ the min that keeps the first)
+                    }
                 };
 #ifdef GS_BLEND_PREFETCH
                 // the survivors' records one ahead: the ds_reads of the next survivor are issued before this one's arithmetic, so a wave that has its SIMD
@@ -1138,9 +1169,16 @@ __global__ __launch_bounds__(64 << (TWL + THL - 6)) void blend_kernel(const uint
                     break;
                 }
             }
+            // PICK: this batch's staging is overwritten after the next barrier; a wave that has just finished passes here before it stops walking
+            if (PICK && pickSlot >= 0 && pickSlot != kPickOpen) { pickDepth = s_e[pickSlot].w; pickSplat = s_p[pickSlot]; pickSlot = -1; }
         }
     }
     if (inside) *dst = acc.pack();
+    if (PICK && inside) {
+        PickRecord* pr = pk.rec + ((size_t)py * rc.width + (size_t)px);
+        if (pickSplat != kPickNoSplat) *pr = PickRecord{ pickDepth, pickSplat, pk.tag, 0u };
+        else if (dstIsZero) *pr = PickRecord{ __builtin_inff(), kPickNoSplat, 0u, 0u };
+    }
     // next frame's scheduling hint (tile_order_body), 1 .. 254: the tile's critical chain -- the most survivors one of its waves
     // walked -- plus NT / 8 per batch (its ballots: 32 for the 256-record batches of a 16x16 tile), in units of 4.  (Batches alone: +2 % at
     // C2 / C3 -- survivors per batch vary tenfold between tiles; the measured duration of the tile schedules worse than either, 0.189 vs
@@ -1161,7 +1199,7 @@ __global__ __launch_bounds__(64 << (TWL + THL - 6)) void blend_kernel(const uint
 }
 
 // View depth (centerClipPos.w, SplatUtilities.compute:199-200) of every visible splat, for the scene-depth test of the blend:
-// only launched by a draw whose target has a depth attachment, so the default path neither computes nor stores it.  Same
+// only launched by a draw whose target has a depth attachment or pick output (whose records carry it), so the default path neither computes nor stores it.  Same
 // operations as CalcViewGeom, hence the same bits as the w the splat was culled and drawn with.
 __global__ __launch_bounds__(256) void splat_depth_kernel(gsm::AssetView a, gsm::FrameConsts P, const uint32_t* __restrict__ visMask32, float* __restrict__ recW) {
     const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
@@ -1169,6 +1207,12 @@ __global__ __launch_bounds__(256) void splat_depth_kernel(gsm::AssetView a, gsm:
     const gsm::V3 pos = gsm::LoadSplatPosChunk(a, idx, blockIdx.x);
     const float wx = gsm::mrow(P.o2w, 0, pos.x, pos.y, pos.z), wy = gsm::mrow(P.o2w, 1, pos.x, pos.y, pos.z), wz = gsm::mrow(P.o2w, 2, pos.x, pos.y, pos.z);
     recW[idx] = gsm::mrow(P.vp, 3, wx, wy, wz);
+}
+
+// every pick record := "none" (gs_target_set_pick_output, and a gs_target_clear that no draw folds in)
+__global__ __launch_bounds__(256) void pick_fill_kernel(PickRecord* __restrict__ rec, uint32_t numPix) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < numPix) rec[i] = PickRecord{ __builtin_inff(), kPickNoSplat, 0u, 0u };
 }
 
 // RenderMode.DebugBoxes / DebugChunkBounds (GaussianDebugRenderBoxes.shader; GaussianSplatRenderer.cs:126-131,156-166): one
@@ -1627,19 +1671,28 @@ int32_t enqueue_draw(gs_renderer* r, const gs_frame_params* p, gs_target* rt) {
         if (rt->exposed || borrowedDepth) GS_TRY(signal_to(rt->ctx, st));
         else if (rt->lastUseValid) GS_HIP(hipStreamWaitEvent(st, rt->evLastUse, 0));
     }
-    if (rt->sceneDepth) {
+    if (rt->sceneDepth || rt->pick) {                           // recW: the scene-depth test's operand, and the depth a pick record carries
         gsm::FrameConsts fc;
         flatten_params(p, fc);
         hipLaunchKernelGGL(splat_depth_kernel, dim3(div_up(r->n, 256)), dim3(256), 0, st, asset_view(r), fc, (const uint32_t*)r->visMask.get(), r->recW);
     }
     // the records carry the selection's marks iff this frame's calc_view ran with the selected bits: then, and only then, the highlight build
-#define GS_LAUNCH_BLEND_K(M, D, WL, HL, SEL) hipLaunchKernelGGL((blend_kernel<M, D, WL, HL, SEL>), dim3(numTiles), dim3(64u << (WL + HL - 6)), 0, st, r->pairVals, tileStart, tileEnd, \
+    // pick output: the twelve PICK instantiations are all of the depth-carrying form; a target without attachment runs them with the test off (pk.noDepth)
+    PickOut pk{};
+    if (rt->pick) {
+        const float tau = rt->pickTau;
+        uint32_t th = gsm::f32tof16(tau);                        // the smallest fp16 >= tau
+        if (gsm::f16tof32(th) < tau) ++th;
+        pk.rec = rt->pick; pk.tau = tau; pk.tauHalfHi = th << 16; pk.tag = settings(r).pickTag; pk.noDepth = rt->sceneDepth ? 0u : 1u;
+    }
+#define GS_LAUNCH_BLEND_K(M, D, WL, HL, SEL, PK) hipLaunchKernelGGL((blend_kernel<M, D, WL, HL, SEL, PK>), dim3(numTiles), dim3(64u << (WL + HL - 6)), 0, st, r->pairVals, tileStart, tileEnd, \
                                              tileOrder, ds.costWrite, r->recs, rt->rgba16f, rc, dstIsZero, r->recW, rt->sceneDepth, \
-                                             ds.binCtl, ds.pairSortError, r->hostReport.device())
-#define GS_LAUNCH_BLEND_S(M, D, WL, HL) do { if (r->viewHighlight) GS_LAUNCH_BLEND_K(M, D, WL, HL, true); else GS_LAUNCH_BLEND_K(M, D, WL, HL, false); } while (0)
-#define GS_LAUNCH_BLEND(M, D) do { if (twl == 4u) GS_LAUNCH_BLEND_S(M, D, 4, 4); else if (thl == 4u) GS_LAUNCH_BLEND_S(M, D, 5, 4); else GS_LAUNCH_BLEND_S(M, D, 5, 5); } while (0)
-    if (rt->sceneDepth) { if (settings(r).blendMode == 0) GS_LAUNCH_BLEND(0, true); else GS_LAUNCH_BLEND(1, true); }
-    else { if (settings(r).blendMode == 0) GS_LAUNCH_BLEND(0, false); else GS_LAUNCH_BLEND(1, false); }
+                                             ds.binCtl, ds.pairSortError, r->hostReport.device(), pk)
+#define GS_LAUNCH_BLEND_S(M, D, WL, HL, PK) do { if (r->viewHighlight) GS_LAUNCH_BLEND_K(M, D, WL, HL, true, PK); else GS_LAUNCH_BLEND_K(M, D, WL, HL, false, PK); } while (0)
+#define GS_LAUNCH_BLEND(M, D, PK) do { if (twl == 4u) GS_LAUNCH_BLEND_S(M, D, 4, 4, PK); else if (thl == 4u) GS_LAUNCH_BLEND_S(M, D, 5, 4, PK); else GS_LAUNCH_BLEND_S(M, D, 5, 5, PK); } while (0)
+    if (rt->pick) { if (settings(r).blendMode == 0) GS_LAUNCH_BLEND(0, true, true); else GS_LAUNCH_BLEND(1, true, true); }
+    else if (rt->sceneDepth) { if (settings(r).blendMode == 0) GS_LAUNCH_BLEND(0, true, false); else GS_LAUNCH_BLEND(1, true, false); }
+    else { if (settings(r).blendMode == 0) GS_LAUNCH_BLEND(0, false, false); else GS_LAUNCH_BLEND(1, false, false); }
 #undef GS_LAUNCH_BLEND
 #undef GS_LAUNCH_BLEND_S
 #undef GS_LAUNCH_BLEND_K
@@ -1727,8 +1780,16 @@ int32_t flush_clear(gs_target* t) {
     if (!t->clearPending) return GS_OK;
     GS_HIP(hipSetDevice(t->ctx->device));
     GS_HIP(hipMemsetAsync(t->rgba16f, 0, (size_t)t->width * t->height * 8, t->ctx->stream));
+    if (t->pick) GS_TRY(enqueue_pick_fill(t, t->pick));         // the records go with the pixels
     t->clearPending = false;
     return target_touched(t, t->ctx->stream);
+}
+
+int32_t enqueue_pick_fill(gs_target* t, PickRecord* rec) {
+    const uint32_t numPix = t->width * t->height;
+    hipLaunchKernelGGL(pick_fill_kernel, dim3(div_up(numPix, 256)), dim3(256), 0, t->ctx->stream, rec, numPix);
+    GS_HIP(hipGetLastError());
+    return GS_OK;
 }
 
 int32_t target_touched(gs_target* t, hipStream_t st) {

@@ -164,6 +164,14 @@ namespace GaussianSplatting.Runtime
         [DllImport(Lib)] public static extern int gs_target_device_ptr(IntPtr target, out IntPtr rgba16fDev, out IntPtr resolvedDev);
         [DllImport(Lib)] public static extern int gs_target_set_profiling(IntPtr target, int enabled);
         [DllImport(Lib)] public static extern int gs_target_resolve_time(IntPtr target, out float meanMs, out int count);
+        // pick output: one GsPickRecord per pixel from the splat blend -- the splat that took the pixel's accumulated alpha across the threshold, its view depth, the drawing renderer's tag
+        [StructLayout(LayoutKind.Sequential)] public struct GsPickRecord { public float depth; public uint splat; public uint tag; public uint zero; }   // none: +inf, 0xFFFFFFFF, 0, 0
+        [DllImport(Lib)] public static extern int gs_target_set_pick_output(IntPtr target, int enabled, float threshold);
+        [DllImport(Lib)] public static extern int gs_target_download_pick(IntPtr target, IntPtr dstRecords, UIntPtr bytes);
+        [DllImport(Lib)] public static extern int gs_target_pick_at(IntPtr target, uint x, uint y, out GsPickRecord record);
+        [DllImport(Lib)] public static extern int gs_target_pick_device_ptr(IntPtr target, out IntPtr pickDev);
+        [DllImport(Lib)] public static extern int gs_renderer_set_pick_tag(IntPtr renderer, uint tag);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_select_surface(IntPtr renderer, IntPtr target, int x0, int y0, int x1, int y1, int subtract);
 
         // native importer (host code): GaussianSplatAssetCreator.CreateAsset without the asset database
         [StructLayout(LayoutKind.Sequential)]

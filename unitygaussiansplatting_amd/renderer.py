@@ -18,8 +18,8 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from ._abi import (GS_ERR_PAIR_OVERFLOW, GS_SORT_FULL, GS_SORT_VISIBLE, GS_SPZ_FRACT_AUTO, VIEW_DTYPE, gs_copy_params, gs_edit_info, gs_export_params, gs_frame_params, gs_frame_stats,
-                   gs_import_formats, gs_spz_params, gs_stage_times, make_asset_desc)
+from ._abi import (GS_ERR_INVALID_ARGUMENT, GS_ERR_PAIR_OVERFLOW, GS_SORT_FULL, GS_SORT_VISIBLE, GS_SPZ_FRACT_AUTO, PICK_DTYPE, VIEW_DTYPE, gs_copy_params, gs_edit_info,
+                   gs_export_params, gs_frame_params, gs_frame_stats, gs_import_formats, gs_pick_record, gs_spz_params, gs_stage_times, make_asset_desc)
 from ._lib import GsError, check
 from .asset import CalcTextureSize, ColorFormat, GaussianSplatAsset, SHFormat, VectorFormat, kCurrentVersion, kMaxSplats
 from .camera import Camera, Transform, frame_params, mat_mul, matrix_rotation_scale, sort_matrix
@@ -153,6 +153,25 @@ class RenderTarget:
         out = np.empty((self.height, self.width, 4), np.uint16)
         check(_lib.lib().gs_target_download(self._h, out.ctypes.data, out.nbytes), "gs_target_download")
         return out
+
+    def SetPickOutput(self, enabled: bool, threshold: float = 0.5) -> None:
+        """True: splat draws also leave one record per pixel -- the splat whose blend took the pixel's accumulated alpha across `threshold`
+        (0 < threshold <= 1), its view depth and the drawing renderer's tag (gs_target_set_pick_output).  False: frees the records."""
+        check(_lib.lib().gs_target_set_pick_output(self._h, int(bool(enabled)), float(threshold)), "gs_target_set_pick_output")
+
+    def DownloadPick(self) -> np.ndarray:
+        """H x W structured array (depth f4, splat u4, tag u4, zero u4), row 0 = top; a pixel never crossed is (+inf, 0xFFFFFFFF, 0, 0).  Blocks."""
+        out = np.empty((self.height, self.width), np.dtype(PICK_DTYPE))
+        check(_lib.lib().gs_target_download_pick(self._h, out.ctypes.data, out.nbytes), "gs_target_download_pick")
+        return out
+
+    def PickAt(self, x: int, y: int) -> Tuple[float, int, int]:
+        """(depth, splat, tag) of pixel (x, y), y down; splat = 0xFFFFFFFF and depth = +inf where no splat crossed the threshold.  Blocks."""
+        if x < 0 or y < 0:
+            raise GsError(GS_ERR_INVALID_ARGUMENT, "gs_target_pick_at", "pixel outside the target")
+        rec = gs_pick_record()
+        check(_lib.lib().gs_target_pick_at(self._h, int(x), int(y), C.byref(rec)), "gs_target_pick_at")
+        return rec.depth, rec.splat, rec.tag
 
     def Resolve(self, background=(0.0, 0.0, 0.0, 0.0), want8: bool = True):
         """GaussianComposite.shader onto a constant background: (linear RGBA float32, sRGB RGBA8)."""
@@ -290,6 +309,7 @@ class GaussianSplatRenderer:
         self.sortMode = SortMode.Visible if os.environ.get("GSPLAT_SORT_MODE", "") == "visible" else SortMode.Full
         self.framesInFlight = max(1, int(os.environ.get("GSPLAT_FRAMES_IN_FLIGHT", "1") or 1))     # SetFramesInFlight
         self.selectionHighlight = False           # SetSelectionHighlight
+        self.pickTag = 0                          # SetPickTag
         self._asset_h = C.c_void_p()
         self._r_h = C.c_void_p()
         self._keep: list = []
@@ -348,6 +368,8 @@ class GaussianSplatRenderer:
             check(_lib.lib().gs_renderer_set_frames_in_flight(self._r_h, int(self.framesInFlight)), "gs_renderer_set_frames_in_flight")
         if self.selectionHighlight:
             check(_lib.lib().gs_renderer_set_selection_highlight(self._r_h, 1), "gs_renderer_set_selection_highlight")
+        if self.pickTag:
+            check(_lib.lib().gs_renderer_set_pick_tag(self._r_h, self.pickTag), "gs_renderer_set_pick_tag")
 
     def ShareResourcesOf(self, other: "GaussianSplatRenderer") -> None:
         """A second renderer over the SAME device blobs as `other` (no copy; `other` must outlive this one), on this renderer's own context =
@@ -375,6 +397,8 @@ class GaussianSplatRenderer:
             check(_lib.lib().gs_renderer_set_frames_in_flight(self._r_h, int(self.framesInFlight)), "gs_renderer_set_frames_in_flight")
         if self.selectionHighlight:
             check(_lib.lib().gs_renderer_set_selection_highlight(self._r_h, 1), "gs_renderer_set_selection_highlight")
+        if self.pickTag:
+            check(_lib.lib().gs_renderer_set_pick_tag(self._r_h, self.pickTag), "gs_renderer_set_pick_tag")
 
     def DisposeResourcesForAsset(self) -> None:     # :527-565
         l = _lib.lib()
@@ -500,6 +524,17 @@ class GaussianSplatRenderer:
         p = self.FrameParams(cam)
         rect = np.array([rectMin[0], rectMax[1], rectMax[0], rectMin[1]], np.float32)       # :835
         check(_lib.lib().gs_renderer_edit_update_selection(self._r_h, C.byref(p), _fptr(rect), int(bool(subtract))), "gs_renderer_edit_update_selection")
+        self.UpdateEditCountsAndBounds()
+
+    def EditSelectSurface(self, target: "RenderTarget", rect, subtract: bool = False) -> None:
+        """Select what one SEES: rect = (x0, y0, x1, y1), inclusive pixels, y down, clipped to the target (a click: x0 == x1, y0 == y1).  Every pixel whose
+        pick record carries this renderer's tag names a splat; those that are neither deleted nor cut are added to the selection, or with subtract
+        removed from it (gs_renderer_edit_select_surface).  The target needs SetPickOutput(True) and a splat frame drawn into it."""
+        if not self.EnsureEditingBuffers():
+            return
+        self.UpdateCutoutsBuffer()
+        x0, y0, x1, y1 = (int(v) for v in rect)
+        check(_lib.lib().gs_renderer_edit_select_surface(self._r_h, target._h, x0, y0, x1, y1, int(bool(subtract))), "gs_renderer_edit_select_surface")
         self.UpdateEditCountsAndBounds()
 
     def EditDeleteSelected(self) -> None:           # :896-904
@@ -796,6 +831,13 @@ class GaussianSplatRenderer:
         self.selectionHighlight = bool(enabled)
         if self._r_h:
             check(_lib.lib().gs_renderer_set_selection_highlight(self._r_h, int(self.selectionHighlight)), "gs_renderer_set_selection_highlight")
+
+    def SetPickTag(self, tag: int) -> None:
+        """What this renderer's draws write into the pick records they own (default 0): several renderers that share one target tell their
+        records apart by it, and EditSelectSurface only considers the renderer's own (gs_renderer_set_pick_tag)."""
+        self.pickTag = int(tag) & 0xFFFFFFFF
+        if self._r_h:
+            check(_lib.lib().gs_renderer_set_pick_tag(self._r_h, self.pickTag), "gs_renderer_set_pick_tag")
 
     def SetFramesInFlight(self, frames: int) -> None:
         """Frames (or the views of a batch of cameras) in flight INSIDE the library, behind this one renderer: `frames` lanes on streams of their own, dealt
