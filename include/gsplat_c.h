@@ -333,7 +333,7 @@ int32_t gs_renderer_edit_info(gs_renderer* r, gs_edit_info* out);
 int32_t gs_renderer_edit_upload_selected_bits(gs_renderer* r, const uint32_t* words, size_t word_count);
 /* ceil(N/32) words each; any may be NULL; a buffer that does not exist reads as zeros; blocks */
 int32_t gs_renderer_edit_download_bits(gs_renderer* r, uint32_t* selected, uint32_t* selected_mouse_down, uint32_t* deleted, size_t word_count);
-int32_t gs_renderer_edit_release(gs_renderer* r);                   /* frees selected + mouse-down (bits, pos, other); deleted bits and moved splats stay */
+int32_t gs_renderer_edit_release(gs_renderer* r);                   /* frees selected + mouse-down (bits, pos, other, sh); deleted bits and moved splats stay */
 /* The reference's highlight of the selection (RenderGaussianSplats.shader:63-73,87-101; _SplatBitsValid, GaussianSplatRenderer.cs:518-520)
  * (addition to ABI 9).  enabled != 0: every GS_RENDER_SPLATS frame whose gs_renderer_calc_view runs while the edit buffers exist draws the splats
  * selected at that call as the reference does: tinted magenta (rgb = lerp(rgb, (1, 0, 1), 0.5)), with raised opacity (alpha = saturate(e + 0.3)
@@ -357,7 +357,8 @@ int32_t gs_renderer_set_selection_highlight(gs_renderer* r, int32_t enabled);
  * asset with GS_VECTOR_FLOAT32 positions, rotation words only in a chunk-less asset with fp32 scales and fp32 SH; where no gate passes a call
  * returns GS_OK and changes nothing.  Rotate reads pos and other from their mouse-down copies, scale reads pos from its copy, both write
  * the current blobs; translate reads and writes the current positions.  Rotate without both store calls (scale: without the pos one) is
- * GS_ERR_INVALID_ARGUMENT.  SHs are not rotated and splat scales not scaled (the reference's own TODOs).  Arithmetic: DESIGN.md section 4.7;
+ * GS_ERR_INVALID_ARGUMENT.  SHs are not rotated and splat scales not scaled (the reference's own TODOs) unless
+ * gs_renderer_edit_set_rigid_transforms (below) is on.  Arithmetic: DESIGN.md section 4.7;
  * one deviation -- the fields of a re-encoded rotation word are clamped to their ranges, which only matters for a delta quaternion that is
  * not of unit length.  Asynchronous on the context's stream and ordered against sorts, GS_SORT_VISIBLE's history (the order buffer as the
  * reference holds it at the call becomes the new base) and frames in flight (a frame already dealt to a lane finishes with the old
@@ -370,6 +371,29 @@ int32_t gs_renderer_edit_rotate_selection(gs_renderer* r, const float center[3],
                                           const float world_to_local[16], const float rotation_xyzw[4]);   /* :856-874 */
 int32_t gs_renderer_edit_scale_selection(gs_renderer* r, const float center[3], const float local_to_world[16],
                                          const float world_to_local[16], const float scale[3]);            /* :877-894 */
+/* Rigid rotate and scale (additions to ABI 9).  Off by default: every call above is then what it is without these two.
+ * enabled != 0: a rotated selection turns as one object and a uniformly scaled one grows as one -- what the reference's three @TODOs leave out.
+ * The format gates stay the reference's: positions as above; rotation word, scale and SH are written only in a chunk-less asset with fp32 scales
+ * and fp32 SH; where no gate passes a call returns GS_OK and launches nothing.
+ *   rotate   positions as above.  With L = W2O3 . R(delta) . O2W3 the linear part of the position map (delta normalised; all in fp64, rounded to
+ *            fp32 once), every selected splat's rotation word becomes QuatMul(q_L, rot) re-encoded and its 15 SH coefficients go through the band
+ *            matrices of L -- the arithmetic of the merge and the baked export, from the mouse-down state.  q_L and the bands are taken from L
+ *            with its rows normalised, the reference's answer for a matrix that is not a pure rotation.  Of a 192-byte SH record the first 180
+ *            bytes are rewritten.  Needs all three store calls, a delta of finite non-zero norm and a local_to_world without a zero or
+ *            non-finite row: otherwise GS_ERR_INVALID_ARGUMENT (checked before the gates).  The first such call makes the SH blob private.
+ *   scale    positions as above.  If the three components of `scale` are equal as floats (s s s: the uniform handle) the three fp32 scales of
+ *            every selected splat become their mouse-down values times |s| -- 12 bytes of the other record; this needs the `other` store call
+ *            (else GS_ERR_INVALID_ARGUMENT).  A non-uniform scale leaves splat sizes alone, as the reference does: the image of a rotated
+ *            ellipsoid under an anisotropic scale is not an ellipsoid with the same axes, and finding its axes takes an eigen-decomposition per
+ *            splat -- not done.  s < 0 multiplies by |s| and does not touch the SH (the odd bands would change sign) -- not done either.
+ *   translate is unchanged.
+ * A plain setting: kept by gs_renderer_edit_set_splat_count, read by the lanes of gs_renderer_set_frames_in_flight through their owner.
+ * gs_renderer_edit_store_sh_mouse_down is the third mouse-down copy: the renderer's CURRENT SH blob, device to device on the context's stream,
+ * allocated only where the rotation gate passes; that it was called is remembered either way.  gs_renderer_edit_release frees it, a resize drops
+ * it (with the other two), a lane handle is GS_ERR_INVALID_ARGUMENT.  Memory: the copy and the private SH blob are 192 bytes per splat EACH --
+ * about 2.4 GB together for a 6.1 M-splat VeryHigh asset -- and exist only on a renderer that stored / rotated with the setting on. */
+int32_t gs_renderer_edit_set_rigid_transforms(gs_renderer* r, int32_t enabled);
+int32_t gs_renderer_edit_store_sh_mouse_down(gs_renderer* r);
 /* the renderer's CURRENT pos / other blobs (the private copy if there is one, else the asset's); either may be NULL; blocks */
 int32_t gs_renderer_edit_download_pos_other(gs_renderer* r, void* pos, size_t pos_bytes, void* other, size_t other_bytes);
 

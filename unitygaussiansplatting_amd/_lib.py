@@ -67,6 +67,8 @@ SIGNATURES = {
     "gs_renderer_set_selection_highlight": (C.c_int32, [_P, C.c_int32]),
     "gs_renderer_edit_store_pos_mouse_down": (C.c_int32, [_P]),
     "gs_renderer_edit_store_other_mouse_down": (C.c_int32, [_P]),
+    "gs_renderer_edit_set_rigid_transforms": (C.c_int32, [_P, C.c_int32]),
+    "gs_renderer_edit_store_sh_mouse_down": (C.c_int32, [_P]),
     "gs_renderer_edit_translate_selection": (C.c_int32, [_P, C.POINTER(C.c_float)]),
     "gs_renderer_edit_rotate_selection": (C.c_int32, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "gs_renderer_edit_scale_selection": (C.c_int32, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),

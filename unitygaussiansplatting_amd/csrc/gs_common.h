@@ -268,6 +268,7 @@ struct RendererSettings {
     int visHistLimit = kVisHistory;         // rows kept before the base is consolidated (gs_renderer_set_sort_history_limit; GSPLAT_VIS_HISTORY)
     bool selectionHighlight = false;        // gs_renderer_set_selection_highlight: splat frames draw the selection as the reference does (gs::edit_view)
     uint32_t pickTag = 0;                   // gs_renderer_set_pick_tag: what this renderer's draws write into the pick records they own
+    bool rigidTransforms = false;           // gs_renderer_edit_set_rigid_transforms: rotate / scale of the selection also turn orientation and SH, scale splat sizes
 };
 } // namespace gs
 
@@ -320,7 +321,8 @@ struct gs_renderer {
     uint64_t privBytes[4] = {0, 0, 0, 0};   // bytes of each private blob while it exists: gs::blob_bytes
     gs::DevBuf<uint8_t> editPosMouseDown;   // m_GpuEditPosMouseDown: made only when the position gate can pass
     gs::DevBuf<uint8_t> editOtherMouseDown; // m_GpuEditOtherMouseDown: ... the rotation gate
-    bool editPosStored = false, editOtherStored = false;   // EditStorePosMouseDown / EditStoreOtherMouseDown have run since the last release
+    gs::DevBuf<uint8_t> editSHMouseDown;    // gs_renderer_edit_store_sh_mouse_down: N x 192 B, made only when the rotation gate can pass (read by the rigid rotate)
+    bool editPosStored = false, editOtherStored = false, editSHStored = false;   // the three mouse-down store calls have run since the last release / resize
     bool movedSinceView = false;            // the splats were moved after the last calc_view: lastParams no longer reproduce the view buffer
     float viewW = 0.f, viewH = 0.f, viewNear = 0.f, viewFar = 0.f;   // what the last calc_view was run with
     bool viewValid = false;

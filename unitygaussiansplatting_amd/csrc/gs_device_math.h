@@ -766,7 +766,8 @@ GS_HD void EditSplatBounds(const V3& pos, uint32_t lo[3], uint32_t hi[3]) {
 // CSTranslateSelection / CSRotateSelection / CSScaleSelection for one selected splat (SplatUtilities.compute:425-521).  What the three
 // read of their dispatch: _SelectionCenter, _MatrixObjectToWorld and _MatrixWorldToObject (rows 0..2), and _SelectionDelta (xyz; translate,
 // scale) or _SelectionDeltaRot (xyzw; rotate).  mul(M, float4(p, 1)) is mrow's fmaf chain, as everywhere; every other operation rounds once,
-// in the order of the reference's text.  SHs are not rotated and a splat's own scale is not scaled: the reference's @TODOs, kept.
+// in the order of the reference's text.  SHs are not rotated and a splat's own scale is not scaled: the reference's @TODOs, kept unless the
+// renderer's rigid-transform setting is on (EditRigid*, below BakeSplatTransform).
 struct EditXform { float center[3]; float o2w[12]; float w2o[12]; float delta[4]; };
 GS_HD V3 EditTranslatePos(const EditXform& X, const V3& pos) { return { pos.x + X.delta[0], pos.y + X.delta[1], pos.z + X.delta[2] }; }
 GS_HD V3 EditRotatePos(const EditXform& X, const V3& mouseDown) {
@@ -1338,13 +1339,17 @@ GS_HD void SHRotBand(const float (*r1)[3], const float* prev, int l, float* out)
             out[(m + l) * (2 * l + 1) + (n + l)] = s.any ? s.acc : 0.0f;
         }
 }
-GS_HD void CalcSHRot(const float* o2w, SHRot& R) {                 // o2w: _MatrixObjectToWorld, rows of 4
-    float m[3][3];
+// CalcSHRotMatrix (SplatUtilities.compute:588-609): the rows of the 3x3 part, each divided by its length
+GS_HD void SHRotMatrix(const float* o2w, float (*m)[3]) {          // o2w: _MatrixObjectToWorld, rows of 4
     for (int r = 0; r < 3; ++r) {
         const float x = o2w[r * 4], y = o2w[r * 4 + 1], z = o2w[r * 4 + 2];
         const float inv = 1.0f / sqrtf((x * x + y * y) + z * z);
         m[r][0] = x * inv; m[r][1] = y * inv; m[r][2] = z * inv;
     }
+}
+GS_HD void CalcSHRot(const float* o2w, SHRot& R) {
+    float m[3][3];
+    SHRotMatrix(o2w, m);
     // band 1: rows / columns in the order y, z, x of the real harmonics, with the basis' signs
     R.sh1[0][0] = m[1][1]; R.sh1[0][1] = -m[1][2]; R.sh1[0][2] = m[1][0];
     R.sh1[1][0] = -m[2][1]; R.sh1[1][1] = m[2][2]; R.sh1[1][2] = -m[2][0];
@@ -1366,6 +1371,15 @@ GS_HD V3 SHDotRow(const V3* v, const float* f, int n) {
 
 // The transform CSExportData bakes (SplatUtilities.compute:627-643) and CSCopySplats applies (:699-712), the same text in both: position through the
 // matrix (m: rows 0..2), the axis flips of a negative scale, QuatMul(rot, .), scale *= |scale|, RotateSH with the band matrices of the matrix.
+// The three pieces after the flips stand on their own: the rigid rotate / scale of the selection (EditRigid*, above the kernels of gs_edit.hip)
+// applies them to the mouse-down state of a selected splat, so that an edited splat and a merged one are the same arithmetic.
+GS_HD V4 BakeQuat(const float* rot, const V4& q) { return QuatMul({ rot[0], rot[1], rot[2], rot[3] }, q); }
+GS_HD V3 BakeScale(const V3& s, const float* scale) { return { s.x * fabsf(scale[0]), s.y * fabsf(scale[1]), s.z * fabsf(scale[2]) }; }
+// one band of RotateSH (SphericalHarmonics.hlsl:24-210): N = 3, 5, 7 coefficients in, as many out
+template <int N> GS_HD void RotateSHBand(const V3* in, const float (*f)[N], V3* out) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) out[k] = SHDotRow(in, f[k], N);
+}
 GS_HD void BakeSplatTransform(SplatFull& s, const float* m, const float* rot, const float* scale, const SHRot& sh) {
     const V3 pos = s.pos;
     s.pos = { mrow(m, 0, pos.x, pos.y, pos.z), mrow(m, 1, pos.x, pos.y, pos.z), mrow(m, 2, pos.x, pos.y, pos.z) };
@@ -1373,17 +1387,43 @@ GS_HD void BakeSplatTransform(SplatFull& s, const float* m, const float* rot, co
     if (scale[0] < 0.0f) { s.rot.y = -s.rot.y; s.rot.z = -s.rot.z; }
     if (scale[1] < 0.0f) { s.rot.x = -s.rot.x; s.rot.z = -s.rot.z; }
     if (scale[2] < 0.0f) { s.rot.x = -s.rot.x; s.rot.y = -s.rot.y; }
-    s.rot = QuatMul({ rot[0], rot[1], rot[2], rot[3] }, s.rot);
-    s.scale.x *= fabsf(scale[0]); s.scale.y *= fabsf(scale[1]); s.scale.z *= fabsf(scale[2]);
+    s.rot = BakeQuat(rot, s.rot);
+    s.scale = BakeScale(s.scale, scale);
     V3 out[15];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) out[k] = SHDotRow(s.sh, sh.sh1[k], 3);
-#pragma unroll
-    for (int k = 0; k < 5; ++k) out[3 + k] = SHDotRow(s.sh + 3, sh.sh2[k], 5);
-#pragma unroll
-    for (int k = 0; k < 7; ++k) out[8 + k] = SHDotRow(s.sh + 8, sh.sh3[k], 7);
+    RotateSHBand<3>(s.sh, sh.sh1, out);
+    RotateSHBand<5>(s.sh + 3, sh.sh2, out + 3);
+    RotateSHBand<7>(s.sh + 8, sh.sh3, out + 8);
 #pragma unroll
     for (int k = 0; k < 15; ++k) s.sh[k] = out[k];
+}
+
+// ---- rigid rotate / scale of the selection (gs_renderer_edit_set_rigid_transforms; kernels in gs_edit.hip) --------
+// What the reference's three @TODOs leave out, for one selected splat, from its mouse-down state.  q: the quaternion of the linear part L of the
+// position map, sh: the band matrices of L, both made once per call on the host (gs::edit_rigid_of, gs_params.h); s: the uniform scale factor.
+struct EditRigid { float q[4]; float s; SHRot sh; };
+// the rotation word: QuatMul(q_L, rot) -- the side BakeSplatTransform multiplies on, not CSRotateSelection's
+GS_HD uint32_t EditRigidRotateWord(const EditRigid& G, uint32_t mouseDown) {
+    return EncodeQuatToNorm10(PackSmallest3Rotation(BakeQuat(G.q, DecodeRotation(mouseDown))));
+}
+// the three fp32 scales: each times |s|, one product
+GS_HD V3 EditRigidScale(const EditRigid& G, const V3& mouseDown) {
+    const float s3[3] = { G.s, G.s, G.s };
+    return BakeScale(mouseDown, s3);
+}
+// one band of an fp32 SH record (floats, 3 per coefficient; first = 0, 3, 8), read from the mouse-down record and written to the current one
+template <int N> GS_HD void EditRigidSHBand(const float* src, float* dst, const float (*f)[N], int first) {
+    V3 in[N], out[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) in[k] = { src[3 * (first + k)], src[3 * (first + k) + 1], src[3 * (first + k) + 2] };
+    RotateSHBand<N>(in, f, out);
+#pragma unroll
+    for (int k = 0; k < N; ++k) { dst[3 * (first + k)] = out[k].x; dst[3 * (first + k) + 1] = out[k].y; dst[3 * (first + k) + 2] = out[k].z; }
+}
+// the 45 coefficients of a record: 180 of its 192 bytes; the last 12 are not touched (the copy kernel's rule)
+GS_HD void EditRigidRotateSH(const EditRigid& G, const float* src, float* dst) {
+    EditRigidSHBand<3>(src, dst, G.sh.sh1, 0);
+    EditRigidSHBand<5>(src, dst, G.sh.sh2, 3);
+    EditRigidSHBand<7>(src, dst, G.sh.sh3, 8);
 }
 
 // The body of CSExportData (SplatUtilities.compute:616-673) for one splat: rec = the 62 floats of ExportSplatData = InputSplatData

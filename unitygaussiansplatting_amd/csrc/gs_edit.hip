@@ -10,7 +10,9 @@
 //   CSTranslateSelection / CSRotateSelection / CSScaleSelection  :425-521  the selected splats' positions (and rotation words) rewritten
 // The last three are the only kernels that write splat data.  The asset's blobs are shared between contexts, lanes and replicas and stay
 // immutable: the first transform whose format gate can pass gives the renderer a private copy of the pos and / or other blob (copy-on-write,
-// gs::asset_view), and from then on every kernel of this renderer and of its lanes reads that copy.  CSExportData only reads: gs_export.hip.
+// gs::asset_view), and from then on every kernel of this renderer and of its lanes reads that copy.  With gs_renderer_edit_set_rigid_transforms on,
+// rotate and uniform scale also do what the reference's three @TODOs leave out -- orientation on the right side, SH rotated, splat sizes scaled -- and
+// the SH blob becomes private the same way (the RIGID instantiations below).  CSExportData only reads: gs_export.hip.
 // CSCopySplats / EditSetSplatCount / EditCopySplatsInto -- the merge -- are gs_copy.hip.  The highlight of selected splats
 // (RenderGaussianSplats.shader:63-73,87-101) is drawn by calc_view and the blend (gs_view.hip, gs_raster.hip) when
 // gs_renderer_set_selection_highlight is on; what this file does for it is keep the lanes' copies of the selection in step
@@ -154,10 +156,23 @@ __global__ __launch_bounds__(256) void edit_update_data_kernel(gsm::AssetView a,
 // last word say.  A wave whose two words are zero -- most waves under a rectangle selection -- leaves before it touches pos / other.  Only selected
 // lanes load and store, and of a 16-byte other record only the rotation word is rewritten.  pos / other: the renderer's private blobs (null = that
 // gate failed); posMD / otherMD: the mouse-down copies rotate and scale read.
+//
+// RIGID (gs_renderer_edit_set_rigid_transforms): the instantiations that also do what the reference's @TODOs leave out, from
+// the mouse-down state like everything else here.  Rotate: the rotation word is QuatMul(q_L, rot) re-encoded and the 45 SH coefficients of the splat's
+// 192-byte record go through the band matrices of L -- BakeSplatTransform's own pieces (gsm::EditRigid*), read from shMD and written to sh, the last
+// 12 bytes of the record left alone.  Scale (launched for a uniform delta only): the three fp32 scales of the other record become |s| times the
+// mouse-down ones; 12 bytes written.  One thread per splat, band by band: a band's 3 / 5 / 7 coefficients are loaded, multiplied out and stored before
+// the next band is touched, so at most 21 + 21 coefficient registers are live and nothing spills (the resource table of section 4.15).  The band
+// matrices travel by value in G, as they do into the copy kernel.  With RIGID = false the argument is an empty struct and the kernel is the text it was.
 enum { kEditTranslate = 0, kEditRotate = 1, kEditScale = 2 };
-template <int OP>
+struct EditNoRigid {};
+struct EditRigidArgs { uint8_t* sh; const uint8_t* shMD; gsm::EditRigid G; };
+template <bool RIGID> struct EditRigidArg { typedef EditNoRigid type; };
+template <> struct EditRigidArg<true> { typedef EditRigidArgs type; };
+template <int OP, bool RIGID = false>
 __global__ __launch_bounds__(256) void edit_transform_kernel(uint8_t* __restrict__ pos, uint8_t* __restrict__ other, const uint8_t* __restrict__ posMD,
-                                                             const uint8_t* __restrict__ otherMD, const uint32_t* __restrict__ sel, uint32_t n, gsm::EditXform X) {
+                                                             const uint8_t* __restrict__ otherMD, const uint32_t* __restrict__ sel, uint32_t n, gsm::EditXform X,
+                                                             typename EditRigidArg<RIGID>::type A) {
     const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
     const uint32_t word = idx < n ? sel[idx >> 5] : 0u;            // idx < n: the word exists
     if (__ballot(word != 0u) == 0ull) return;
@@ -169,9 +184,22 @@ __global__ __launch_bounds__(256) void edit_transform_kernel(uint8_t* __restrict
         const gsm::V3 q = OP == kEditTranslate ? gsm::EditTranslatePos(X, p) : (OP == kEditRotate ? gsm::EditRotatePos(X, p) : gsm::EditScalePos(X, p));
         dst[0] = q.x; dst[1] = q.y; dst[2] = q.z;
     }
-    if (OP == kEditRotate && other) {
-        const uint32_t enc = *(const uint32_t*)(otherMD + (size_t)idx * 16u);
-        *(uint32_t*)(other + (size_t)idx * 16u) = gsm::EditRotateWord(X, enc);
+    if constexpr (!RIGID) {
+        if (OP == kEditRotate && other) {
+            const uint32_t enc = *(const uint32_t*)(otherMD + (size_t)idx * 16u);
+            *(uint32_t*)(other + (size_t)idx * 16u) = gsm::EditRotateWord(X, enc);
+        }
+    } else if (other) {                                            // (other, sh and the three mouse-down copies exist together: the rotation gate)
+        if (OP == kEditRotate) {
+            const uint32_t enc = *(const uint32_t*)(otherMD + (size_t)idx * 16u);
+            *(uint32_t*)(other + (size_t)idx * 16u) = gsm::EditRigidRotateWord(A.G, enc);
+            gsm::EditRigidRotateSH(A.G, (const float*)(A.shMD + (size_t)idx * 192u), (float*)(A.sh + (size_t)idx * 192u));
+        } else if (OP == kEditScale) {
+            const float* src = (const float*)(otherMD + (size_t)idx * 16u + 4u);
+            float* dst = (float*)(other + (size_t)idx * 16u + 4u);
+            const gsm::V3 sc = gsm::EditRigidScale(A.G, { src[0], src[1], src[2] });
+            dst[0] = sc.x; dst[1] = sc.y; dst[2] = sc.z;
+        }
     }
 }
 
@@ -220,8 +248,8 @@ int32_t ensure_deleted_bits(gs_renderer* r, hipStream_t st) {
 
 void edit_free(gs_renderer* r) {
     r->editSelected.reset(); r->editSelectedMouseDown.reset(); r->editCountsBounds.reset();
-    r->editPosMouseDown.reset(); r->editOtherMouseDown.reset();
-    r->editPosStored = r->editOtherStored = false;
+    r->editPosMouseDown.reset(); r->editOtherMouseDown.reset(); r->editSHMouseDown.reset();
+    r->editPosStored = r->editOtherStored = r->editSHStored = false;
 }
 
 static inline uint32_t splat_grid(const gs_renderer* r) { return (r->n + 255u) / 256u; }
@@ -261,8 +289,8 @@ int32_t edit_selected_to_lanes(gs_renderer* r) {
 // positions, rotation words only in a chunk-less asset with fp32 scales and fp32 SH (so an other record is 4 + 12 bytes).
 static inline bool edit_pos_gate(const gs_renderer* r) { const gsm::AssetView& a = r->asset->view; return a.chunkCount == 0 && a.posFmt == 0; }
 static inline bool edit_rot_gate(const gs_renderer* r) { const gsm::AssetView& a = r->asset->view; return a.chunkCount == 0 && a.scaleFmt == 0 && a.shFmt == 0; }
-// what a transform may touch of blob k (0 pos, 1 other): whole records only
-static inline size_t edit_blob_bytes(const gs_renderer* r, int k) { return (size_t)r->n * (k == 0 ? 12u : 16u); }
+// what a transform may touch of blob k (0 pos, 1 other, 3 sh): whole records only
+static inline size_t edit_blob_bytes(const gs_renderer* r, int k) { return (size_t)r->n * (k == 0 ? 12u : (k == 1 ? 16u : 192u)); }
 
 // copy-on-write: the private copy of blob k (0 pos, 1 other, 2 color, 3 sh), made on the context's stream the first time a transform or a copy
 // is about to write it.  Padded like an owned upload of the asset (the dword stitching of LoadUInt may touch the dword after the last record).
@@ -278,16 +306,17 @@ int32_t edit_make_private(gs_renderer* r, int k) {
     return GS_OK;
 }
 
-// EditStorePosMouseDown / EditStoreOtherMouseDown: the copy is only made where a kernel can read it (the blob's gate)
+// EditStorePosMouseDown / EditStoreOtherMouseDown, and the third copy the rigid rotate reads (k = 3, the SH blob: with fp32 SH -- the rotation
+// gate -- a record is 192 bytes): the copy is only made where a kernel can read it (the blob's gate)
 static int32_t edit_store_mouse_down(gs_renderer* r, int k) {
     if (r->laneOf) return fail(GS_ERR_INVALID_ARGUMENT, "a lane holds no edit state: edit its owner");
     GS_HIP(hipSetDevice(r->ctx->device));
     if (k == 0 ? edit_pos_gate(r) : edit_rot_gate(r)) {
-        DevBuf<uint8_t>& md = k == 0 ? r->editPosMouseDown : r->editOtherMouseDown;
+        DevBuf<uint8_t>& md = k == 0 ? r->editPosMouseDown : (k == 1 ? r->editOtherMouseDown : r->editSHMouseDown);
         if (!md) GS_HIP(md.alloc(edit_blob_bytes(r, k)));
         GS_HIP(hipMemcpyAsync(md, blob_ptr(r, k), edit_blob_bytes(r, k), hipMemcpyDeviceToDevice, r->ctx->stream));
     }
-    (k == 0 ? r->editPosStored : r->editOtherStored) = true;
+    (k == 0 ? r->editPosStored : (k == 1 ? r->editOtherStored : r->editSHStored)) = true;
     return GS_OK;
 }
 
@@ -318,20 +347,28 @@ int32_t edit_after_move(gs_renderer* r) {
 //     order is the new base with an empty history -- from here on the reference, too, stably sorts that buffer by keys of the new positions;
 //   - lanes read the owner's private blobs in place: the context's stream waits for what each lane has been dealt (those frames finish with the old
 //     positions), the kernel runs, and every lane's stream waits for it.  signal_to only; mirror_bits_to_lanes turned round.
-static int32_t edit_transform(gs_renderer* r, int op, const gsm::EditXform& X) {
-    const bool doPos = edit_pos_gate(r), doRot = op == kEditRotate && edit_rot_gate(r);
+// G: null = the reference's kernels; else the rigid form (the setting is on; for a scale: and the delta is uniform).
+static int32_t edit_transform(gs_renderer* r, int op, const gsm::EditXform& X, const gsm::EditRigid* G = nullptr) {
+    const bool doPos = edit_pos_gate(r), doRot = (op == kEditRotate || (G && op == kEditScale)) && edit_rot_gate(r);
     if (!doPos && !doRot) return GS_OK;                            // neither gate: the reference's kernel writes nothing
+    const bool doSH = doRot && G && op == kEditRotate;
     GS_TRY(edit_before_move(r));
     if (doPos) GS_TRY(edit_make_private(r, 0));
     if (doRot) GS_TRY(edit_make_private(r, 1));
+    if (doSH) GS_TRY(edit_make_private(r, 3));
     uint8_t* pos = doPos ? r->priv[0].get() : nullptr;
     uint8_t* other = doRot ? r->priv[1].get() : nullptr;
     const uint8_t* posMD = r->editPosMouseDown, * otherMD = r->editOtherMouseDown;
     const uint32_t* sel = r->editSelected;
     const dim3 grid(splat_grid(r)), block(256);
-    if (op == kEditTranslate) hipLaunchKernelGGL(edit_transform_kernel<kEditTranslate>, grid, block, 0, r->ctx->stream, pos, other, posMD, otherMD, sel, r->n, X);
-    else if (op == kEditRotate) hipLaunchKernelGGL(edit_transform_kernel<kEditRotate>, grid, block, 0, r->ctx->stream, pos, other, posMD, otherMD, sel, r->n, X);
-    else hipLaunchKernelGGL(edit_transform_kernel<kEditScale>, grid, block, 0, r->ctx->stream, pos, other, posMD, otherMD, sel, r->n, X);
+    const EditNoRigid none;
+    if (G) {
+        const EditRigidArgs A = { doSH ? r->priv[3].get() : nullptr, r->editSHMouseDown.get(), *G };
+        if (op == kEditRotate) hipLaunchKernelGGL((edit_transform_kernel<kEditRotate, true>), grid, block, 0, r->ctx->stream, pos, other, posMD, otherMD, sel, r->n, X, A);
+        else hipLaunchKernelGGL((edit_transform_kernel<kEditScale, true>), grid, block, 0, r->ctx->stream, pos, other, posMD, otherMD, sel, r->n, X, A);
+    } else if (op == kEditTranslate) hipLaunchKernelGGL(edit_transform_kernel<kEditTranslate>, grid, block, 0, r->ctx->stream, pos, other, posMD, otherMD, sel, r->n, X, none);
+    else if (op == kEditRotate) hipLaunchKernelGGL(edit_transform_kernel<kEditRotate>, grid, block, 0, r->ctx->stream, pos, other, posMD, otherMD, sel, r->n, X, none);
+    else hipLaunchKernelGGL(edit_transform_kernel<kEditScale>, grid, block, 0, r->ctx->stream, pos, other, posMD, otherMD, sel, r->n, X, none);
     GS_HIP(hipGetLastError());
     return edit_after_move(r);
 }
@@ -468,6 +505,18 @@ int32_t gs_renderer_edit_store_other_mouse_down(gs_renderer* r) {
     return edit_store_mouse_down(r, 1);
 }
 
+int32_t gs_renderer_edit_store_sh_mouse_down(gs_renderer* r) {
+    if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
+    return edit_store_mouse_down(r, 3);
+}
+
+int32_t gs_renderer_edit_set_rigid_transforms(gs_renderer* r, int32_t enabled) {
+    if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
+    if (r->laneOf) return fail(GS_ERR_INVALID_ARGUMENT, "a lane has no settings of its own: set its owner's");
+    r->set.rigidTransforms = enabled != 0;
+    return GS_OK;
+}
+
 int32_t gs_renderer_edit_translate_selection(gs_renderer* r, const float delta[3]) {
     if (!r || !delta) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
     GS_TRY(edit_ensure(r));
@@ -480,7 +529,13 @@ int32_t gs_renderer_edit_rotate_selection(gs_renderer* r, const float center[3],
     GS_TRY(edit_ensure(r));
     if (!r->editPosStored || !r->editOtherStored)                  // "should have captured initial state" (:859)
         return fail(GS_ERR_INVALID_ARGUMENT, "rotate: the mouse-down copies of pos and other have not been stored");
-    return edit_transform(r, kEditRotate, edit_xform_of(center, local_to_world, world_to_local, rotation_xyzw, 4));
+    const gsm::EditXform X = edit_xform_of(center, local_to_world, world_to_local, rotation_xyzw, 4);
+    if (!r->set.rigidTransforms) return edit_transform(r, kEditRotate, X);
+    if (!r->editSHStored) return fail(GS_ERR_INVALID_ARGUMENT, "rigid rotate: the mouse-down copy of sh has not been stored");
+    gsm::EditRigid G;
+    float L[12];
+    if (const char* why = edit_rigid_rotate_of(local_to_world, world_to_local, rotation_xyzw, G, L)) return fail(GS_ERR_INVALID_ARGUMENT, why);
+    return edit_transform(r, kEditRotate, X, &G);
 }
 
 int32_t gs_renderer_edit_scale_selection(gs_renderer* r, const float center[3], const float local_to_world[16], const float world_to_local[16],
@@ -488,7 +543,11 @@ int32_t gs_renderer_edit_scale_selection(gs_renderer* r, const float center[3], 
     if (!r || !center || !local_to_world || !world_to_local || !scale) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
     GS_TRY(edit_ensure(r));
     if (!r->editPosStored) return fail(GS_ERR_INVALID_ARGUMENT, "scale: the mouse-down copy of pos has not been stored");      // :880
-    return edit_transform(r, kEditScale, edit_xform_of(center, local_to_world, world_to_local, scale, 3));
+    const gsm::EditXform X = edit_xform_of(center, local_to_world, world_to_local, scale, 3);
+    if (!r->set.rigidTransforms || !edit_rigid_scale_uniform(scale)) return edit_transform(r, kEditScale, X);
+    if (!r->editOtherStored) return fail(GS_ERR_INVALID_ARGUMENT, "rigid scale: the mouse-down copy of other has not been stored");
+    const gsm::EditRigid G = edit_rigid_scale_of(scale);
+    return edit_transform(r, kEditScale, X, &G);
 }
 
 int32_t gs_renderer_edit_download_pos_other(gs_renderer* r, void* pos, size_t pos_bytes, void* other, size_t other_bytes) {
@@ -503,7 +562,7 @@ int32_t gs_renderer_edit_download_pos_other(gs_renderer* r, void* pos, size_t po
 
 int32_t gs_renderer_edit_release(gs_renderer* r) {
     if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
-    if (!r->editSelected && !r->editPosStored && !r->editOtherStored) return GS_OK;
+    if (!r->editSelected && !r->editPosStored && !r->editOtherStored && !r->editSHStored) return GS_OK;
     GS_HIP(hipSetDevice(r->ctx->device));
     GS_HIP(hipStreamSynchronize(r->ctx->stream));
     for (gs_renderer* L : r->lanes) {                              // no edit buffers, nothing to highlight: the lanes' copies go once their frames have read them

@@ -105,6 +105,9 @@ namespace GaussianSplatting.Runtime
         // moving the selection (copy-on-write of the renderer's pos / other blobs); matrices row-major, quaternion x y z w
         [DllImport(Lib)] public static extern int gs_renderer_edit_store_pos_mouse_down(IntPtr renderer);
         [DllImport(Lib)] public static extern int gs_renderer_edit_store_other_mouse_down(IntPtr renderer);
+        // rigid rotate / scale (off by default): orientation and SH follow a rotation, splat sizes a uniform scale; the third mouse-down copy
+        [DllImport(Lib)] public static extern int gs_renderer_edit_set_rigid_transforms(IntPtr renderer, int enabled);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_store_sh_mouse_down(IntPtr renderer);
         [DllImport(Lib)] public static extern int gs_renderer_edit_translate_selection(IntPtr renderer, float[] delta3);
         [DllImport(Lib)] public static extern int gs_renderer_edit_rotate_selection(IntPtr renderer, float[] center3, float[] localToWorld16, float[] worldToLocal16, float[] rotationXyzw4);
         [DllImport(Lib)] public static extern int gs_renderer_edit_scale_selection(IntPtr renderer, float[] center3, float[] localToWorld16, float[] worldToLocal16, float[] scale3);

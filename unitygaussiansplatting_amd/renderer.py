@@ -310,6 +310,7 @@ class GaussianSplatRenderer:
         self.framesInFlight = max(1, int(os.environ.get("GSPLAT_FRAMES_IN_FLIGHT", "1") or 1))     # SetFramesInFlight
         self.selectionHighlight = False           # SetSelectionHighlight
         self.pickTag = 0                          # SetPickTag
+        self.rigidTransforms = False              # EditSetRigidTransforms
         self._asset_h = C.c_void_p()
         self._r_h = C.c_void_p()
         self._keep: list = []
@@ -322,6 +323,7 @@ class GaussianSplatRenderer:
         self.m_GpuEditSelected = False            # the native renderer's edit buffers exist (EnsureEditingBuffers)
         self.m_GpuEditPosMouseDown = False        # EditStorePosMouseDown / EditStoreOtherMouseDown have run (:794-809)
         self.m_GpuEditOtherMouseDown = False
+        self.m_GpuEditSHMouseDown = False         # EditStoreSHMouseDown has run (the third copy, read by a rigid rotate)
         self.editSelectedSplats = 0
         self.editDeletedSplats = 0
         self.editCutSplats = 0
@@ -370,6 +372,8 @@ class GaussianSplatRenderer:
             check(_lib.lib().gs_renderer_set_selection_highlight(self._r_h, 1), "gs_renderer_set_selection_highlight")
         if self.pickTag:
             check(_lib.lib().gs_renderer_set_pick_tag(self._r_h, self.pickTag), "gs_renderer_set_pick_tag")
+        if self.rigidTransforms:
+            check(_lib.lib().gs_renderer_edit_set_rigid_transforms(self._r_h, 1), "gs_renderer_edit_set_rigid_transforms")
 
     def ShareResourcesOf(self, other: "GaussianSplatRenderer") -> None:
         """A second renderer over the SAME device blobs as `other` (no copy; `other` must outlive this one), on this renderer's own context =
@@ -399,13 +403,15 @@ class GaussianSplatRenderer:
             check(_lib.lib().gs_renderer_set_selection_highlight(self._r_h, 1), "gs_renderer_set_selection_highlight")
         if self.pickTag:
             check(_lib.lib().gs_renderer_set_pick_tag(self._r_h, self.pickTag), "gs_renderer_set_pick_tag")
+        if self.rigidTransforms:
+            check(_lib.lib().gs_renderer_edit_set_rigid_transforms(self._r_h, 1), "gs_renderer_edit_set_rigid_transforms")
 
     def DisposeResourcesForAsset(self) -> None:     # :527-565
         l = _lib.lib()
         if self._r_h:
-            if self.m_GpuEditSelected or self.m_GpuEditPosMouseDown or self.m_GpuEditOtherMouseDown:
+            if self.m_GpuEditSelected or self.m_GpuEditPosMouseDown or self.m_GpuEditOtherMouseDown or self.m_GpuEditSHMouseDown:
                 l.gs_renderer_edit_release(self._r_h)   # DisposeBuffer(ref m_GpuEditSelected) ..., :547-553
-            self.m_GpuEditSelected = self.m_GpuEditPosMouseDown = self.m_GpuEditOtherMouseDown = False
+            self.m_GpuEditSelected = self.m_GpuEditPosMouseDown = self.m_GpuEditOtherMouseDown = self.m_GpuEditSHMouseDown = False
             self.editModified = False
             l.gs_renderer_destroy(self._r_h)
             self._r_h = C.c_void_p()
@@ -589,6 +595,20 @@ class GaussianSplatRenderer:
         check(_lib.lib().gs_renderer_edit_store_other_mouse_down(self._r_h), "gs_renderer_edit_store_other_mouse_down")
         self.m_GpuEditOtherMouseDown = True
 
+    def EditStoreSHMouseDown(self) -> None:
+        """The third mouse-down copy: the renderer's current SH blob (gs_renderer_edit_store_sh_mouse_down), read by a rotate while
+        EditSetRigidTransforms is on.  192 bytes per splat where the asset passes the rotation gate, nothing elsewhere."""
+        check(_lib.lib().gs_renderer_edit_store_sh_mouse_down(self._r_h), "gs_renderer_edit_store_sh_mouse_down")
+        self.m_GpuEditSHMouseDown = True
+
+    def EditSetRigidTransforms(self, enabled: bool) -> None:
+        """True: EditRotateSelection also turns every selected splat's orientation and SH with the object and EditScaleSelection with a uniform
+        scale (s, s, s) also multiplies the splats' own sizes by |s| -- what the reference's @TODOs leave out (gs_renderer_edit_set_rigid_transforms;
+        DESIGN.md section 4.15).  False (default): the reference's kernels word for word."""
+        self.rigidTransforms = bool(enabled)
+        if self._r_h:
+            check(_lib.lib().gs_renderer_edit_set_rigid_transforms(self._r_h, int(self.rigidTransforms)), "gs_renderer_edit_set_rigid_transforms")
+
     def EditTranslateSelection(self, localSpacePosDelta) -> None:      # :842-854
         if not self.EnsureEditingBuffers():
             return
@@ -603,6 +623,8 @@ class GaussianSplatRenderer:
             return
         if not self.m_GpuEditPosMouseDown or not self.m_GpuEditOtherMouseDown:
             return                                  # should have captured initial state
+        if self.rigidTransforms and not self.m_GpuEditSHMouseDown:
+            return                                  # ... all three of them
         c = np.ascontiguousarray(localSpaceCenter, np.float32).reshape(3)
         l2w = np.ascontiguousarray(localToWorld, np.float32).reshape(16)
         w2l = np.ascontiguousarray(worldToLocal, np.float32).reshape(16)
@@ -620,6 +642,8 @@ class GaussianSplatRenderer:
         l2w = np.ascontiguousarray(localToWorld, np.float32).reshape(16)
         w2l = np.ascontiguousarray(worldToLocal, np.float32).reshape(16)
         v = np.ascontiguousarray(scale, np.float32).reshape(3)
+        if self.rigidTransforms and v[0] == v[1] == v[2] and not self.m_GpuEditOtherMouseDown:
+            return                                  # the uniform handle scales the splats' own sizes from their mouse-down values
         check(_lib.lib().gs_renderer_edit_scale_selection(self._r_h, _fptr(c), _fptr(l2w), _fptr(w2l), _fptr(v)), "gs_renderer_edit_scale_selection")
         self.UpdateEditCountsAndBounds()
         self.editModified = True
@@ -663,7 +687,7 @@ class GaussianSplatRenderer:
             return
         self.UpdateCutoutsBuffer()                  # SetAssetDataOnCS, :507
         check(_lib.lib().gs_renderer_edit_set_splat_count(self._r_h, newSplatCount, None), "gs_renderer_edit_set_splat_count")
-        self.m_GpuEditPosMouseDown = self.m_GpuEditOtherMouseDown = False      # DisposeBuffer(ref m_GpuEditPosMouseDown) ..., :1026-1027
+        self.m_GpuEditPosMouseDown = self.m_GpuEditOtherMouseDown = self.m_GpuEditSHMouseDown = False      # DisposeBuffer(ref m_GpuEditPosMouseDown) ..., :1026-1027
         self.m_SplatCount = self._native_splat_count()
         self.m_Resized = True
         self.editModified = True
