@@ -483,6 +483,60 @@ int32_t gs_renderer_edit_copy_splats_into(gs_renderer* src, gs_renderer* dst, co
 int32_t gs_renderer_edit_download_splat_data(gs_renderer* r, void* pos, size_t pos_bytes, void* other, size_t other_bytes,
                                              void* color, size_t color_bytes, void* sh, size_t sh_bytes);
 
+/* ---- undo and redo of the edit state: a sparse journal kept on the GPU (no counterpart in the reference, which has no undo:
+ * docs/splat-editing.md)  (additions to ABI 9) ----
+ * Off by default: a renderer that never calls gs_renderer_edit_history_enable allocates nothing, launches nothing new and behaves as without
+ * these calls.  gs_renderer_edit_history_enable(r, max_bytes): max_bytes > 0 switches the history on (or changes the budget of one that is
+ * on, evicting the oldest entries that no longer fit); 0 switches it off and frees every entry.
+ * gs_renderer_edit_checkpoint(r, what) is called BEFORE a gesture, where the reference's tools call EditStore*MouseDown, and captures what
+ * the gesture may change:
+ *   GS_HIST_SELECTION / GS_HIST_DELETED   the bit buffer, whole: whatever changes it before the next checkpoint is undone,
+ *                                         gs_renderer_edit_upload_selected_bits and gs_renderer_set_deleted_bits included;
+ *   GS_HIST_POS / OTHER / SH              the 12 / 16 / 192-byte records of the splats selected AT THE CALL (index < N: the tail bits select-all
+ *                                         sets are never gathered), in index order, with their index list;
+ *   GS_HIST_TRANSFORM                     POS | OTHER, and SH iff gs_renderer_edit_set_rigid_transforms is on.
+ * The format gates are the transforms': POS only in a chunk-less asset with fp32 positions, OTHER and SH only in a chunk-less asset with fp32
+ * scales and fp32 SH.  A flag whose gate fails is dropped silently (top_what reports what was kept); if nothing is left the call returns GS_OK
+ * and pushes nothing.  The call BLOCKS: one 4-byte readback of the selected count sizes the entry, and everything is allocated before the
+ * stack changes.  A checkpoint drops all redo entries.  If the entry does not fit into the budget the oldest entries are evicted until it does
+ * (`evicted` counts them); an entry that alone exceeds max_bytes: GS_ERR_OUT_OF_MEMORY, history and renderer unchanged.
+ * An entry costs 4 ceil(N/32) bytes per captured bit buffer + k x (4 + 12 + 16 + 192) bytes for k journalled splats (less without a kind).
+ * gs_renderer_edit_undo / _redo are one operation: the entry's contents are SWAPPED with the renderer's current state -- bit buffers word for
+ * word, records through the index list -- so the entry then holds the state it replaced; undo moves it to the redo side, redo moves it back.
+ * Both are asynchronous on the context's stream and ordered like the call they undo: a record swap like a transform (sorts on the second
+ * queue, GS_SORT_VISIBLE's base and history, frames in flight; gs_renderer_download_view needs a new gs_renderer_calc_view afterwards), a swap
+ * of the deleted / selected bits like a delete / a selection call (the lanes' copies follow).  Buffers that were released in between
+ * (gs_renderer_edit_release, gs_renderer_set_deleted_bits(NULL)) are made again, zeroed, first.  A blob the renderer has no private copy of at
+ * that time cannot have been written since the checkpoint and is skipped.  With nothing to undo / redo: GS_OK, nothing done.
+ * CONTRACT FOR RECORDS: an entry restores exactly the splats that were selected at its checkpoint.  While the history is on, every call that
+ * changes journalable state -- every selection call, delete, the bit uploads, the three transforms, gs_renderer_edit_copy_splats_into on its
+ * destination -- drops the redo entries first (host bookkeeping, no kernel).  gs_renderer_edit_set_splat_count and
+ * gs_renderer_edit_copy_splats_into clear the WHOLE history of the renderer they resize / write into (the copy writes index ranges, not the
+ * selection); the switch, the budget and the counters survive a resize.  uncovered_transforms counts the transforms issued while there is
+ * nothing to undo, while the entry an undo would apply captured no records, or after the selection may have changed since that entry (judged
+ * by any selection-changing call, an undo / redo of GS_HIST_SELECTION included: conservative, a pure subtraction counts too) -- gestures an
+ * undo would not fully take back.  gs_renderer_edit_release keeps the history.  The mouse-down copies are not touched by any of this.
+ * A lane handle, a NULL argument, `what` zero or with unknown bits, and checkpoint / undo / redo while the history is off:
+ * GS_ERR_INVALID_ARGUMENT, nothing changed. */
+#define GS_HIST_SELECTION 1u            /* editSelected, all ceil(N/32) words */
+#define GS_HIST_DELETED   2u            /* deletedBits, all words (absent buffer = zeros) */
+#define GS_HIST_POS       4u            /* 12-byte positions of the splats selected now */
+#define GS_HIST_OTHER     8u            /* 16-byte other records of the same splats */
+#define GS_HIST_SH        16u           /* 192-byte SH records of the same splats */
+#define GS_HIST_TRANSFORM 0x80000000u   /* POS|OTHER, plus SH iff rigid transforms are on */
+typedef struct gs_edit_history_info {
+    uint32_t enabled, undo_depth, redo_depth, top_what;  /* top_what: flags actually captured by the entry an undo would apply */
+    uint64_t bytes, max_bytes;                           /* device bytes held by all entries; the budget */
+    uint64_t top_bytes; uint32_t top_splats;             /* of the entry an undo would apply (0 if none) */
+    uint32_t evicted, uncovered_transforms;              /* counters since enable */
+} gs_edit_history_info;
+int32_t gs_renderer_edit_history_enable(gs_renderer* r, uint64_t max_bytes);  /* 0 = disable and free */
+int32_t gs_renderer_edit_checkpoint(gs_renderer* r, uint32_t what);
+int32_t gs_renderer_edit_undo(gs_renderer* r);
+int32_t gs_renderer_edit_redo(gs_renderer* r);
+int32_t gs_renderer_edit_history_clear(gs_renderer* r);
+int32_t gs_renderer_edit_history_info(const gs_renderer* r, gs_edit_history_info* out);
+
 /* m_RenderMode + m_PointDisplaySize (GaussianSplatRenderer.cs:241-242; material choice :126-131).  DebugPoints / DebugPointIndices
  * (GaussianDebugRenderPoints.shader) draw every splat as an opaque screen-space square of `point_display_size` pixels, nearest
  * wins (ZWrite On), colour = saturate(DC colour) or an index code; gs_renderer_draw then neither needs gs_renderer_sort nor

@@ -80,6 +80,20 @@ class gs_copy_params(C.Structure):       # what CSCopySplats reads of its dispat
     _fields_ = [("matrix", C.c_float * 16), ("rotation", C.c_float * 4), ("scale", C.c_float * 3)]
 
 
+GS_HIST_SELECTION = 1
+GS_HIST_DELETED = 2
+GS_HIST_POS = 4
+GS_HIST_OTHER = 8
+GS_HIST_SH = 16
+GS_HIST_TRANSFORM = 0x80000000
+
+
+class gs_edit_history_info(C.Structure):     # gs_renderer_edit_history_info
+    _fields_ = [("enabled", C.c_uint32), ("undo_depth", C.c_uint32), ("redo_depth", C.c_uint32), ("top_what", C.c_uint32),
+                ("bytes", C.c_uint64), ("max_bytes", C.c_uint64), ("top_bytes", C.c_uint64), ("top_splats", C.c_uint32),
+                ("evicted", C.c_uint32), ("uncovered_transforms", C.c_uint32)]
+
+
 class gs_import_input(C.Structure):
     _fields_ = [("splat_count", C.c_uint32), ("pos", C.c_void_p), ("dc0", C.c_void_p), ("sh", C.c_void_p),
                 ("opacity", C.c_void_p), ("scale", C.c_void_p), ("rot", C.c_void_p)]

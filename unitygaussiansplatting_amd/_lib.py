@@ -6,7 +6,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-from ._abi import (gs_asset_desc, gs_copy_params, gs_cutout, gs_edit_info, gs_export_params, gs_frame_params, gs_frame_stats, gs_import_formats, gs_import_input,
+from ._abi import (gs_asset_desc, gs_copy_params, gs_cutout, gs_edit_history_info, gs_edit_info, gs_export_params, gs_frame_params, gs_frame_stats, gs_import_formats, gs_import_input,
                    gs_pick_record, gs_splat_file_info, gs_spz_params, gs_stage_times)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -83,6 +83,12 @@ SIGNATURES = {
     "gs_renderer_edit_set_splat_count": (C.c_int32, [_P, C.c_uint32, C.POINTER(gs_copy_params)]),
     "gs_renderer_edit_copy_splats_into": (C.c_int32, [_P, _P, C.POINTER(gs_copy_params), C.c_uint32, C.c_uint32, C.c_uint32]),
     "gs_renderer_edit_download_splat_data": (C.c_int32, [_P, _P, C.c_size_t, _P, C.c_size_t, _P, C.c_size_t, _P, C.c_size_t]),
+    "gs_renderer_edit_history_enable": (C.c_int32, [_P, C.c_uint64]),
+    "gs_renderer_edit_checkpoint": (C.c_int32, [_P, C.c_uint32]),
+    "gs_renderer_edit_undo": (C.c_int32, [_P]),
+    "gs_renderer_edit_redo": (C.c_int32, [_P]),
+    "gs_renderer_edit_history_clear": (C.c_int32, [_P]),
+    "gs_renderer_edit_history_info": (C.c_int32, [_P, C.POINTER(gs_edit_history_info)]),
     "gs_renderer_set_view_buffer_mode": (C.c_int32, [_P, C.c_int32]),
     "gs_renderer_set_blend_mode": (C.c_int32, [_P, C.c_int32]),
     "gs_renderer_set_render_mode": (C.c_int32, [_P, C.c_int32, C.c_float]),

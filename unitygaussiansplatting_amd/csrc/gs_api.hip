@@ -612,6 +612,7 @@ int32_t gs_renderer_set_deleted_bits(gs_renderer* r, const uint32_t* words, size
     if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
     GS_TRY(bind_device(r->ctx));
     const size_t need = bit_words(r->n);
+    hist_mutated(r, false);                                 // (on a lane: its history is off)
     if (!words) {                                           // _SplatBitsValid = 0
         if (r->deletedBits) { GS_HIP(hipStreamSynchronize(r->ctx->stream)); r->deletedBits.reset(); }
         for (gs_renderer* L : r->lanes) GS_TRY(gs_renderer_set_deleted_bits(L, nullptr, 0));

@@ -270,6 +270,29 @@ struct RendererSettings {
     uint32_t pickTag = 0;                   // gs_renderer_set_pick_tag: what this renderer's draws write into the pick records they own
     bool rigidTransforms = false;           // gs_renderer_edit_set_rigid_transforms: rotate / scale of the selection also turn orientation and SH, scale splat sizes
 };
+
+// ---- the edit history (gs_renderer_edit_history_enable; gs_edit.hip) ----
+// One entry = what one gs_renderer_edit_checkpoint captured: the two bit buffers whole, and the records of the k splats selected then (index < N, in
+// index order) with their index list.  Undo / redo SWAP an entry's contents with the renderer's state, so an entry is always "the other state".
+struct EditHistEntry {
+    uint32_t what = 0;                      // GS_HIST_* actually captured (gates applied, GS_HIST_TRANSFORM resolved)
+    uint32_t k = 0;                         // journalled splats
+    uint64_t bytes = 0;                     // device bytes of the buffers below
+    uint64_t selGen = 0;                    // EditHistory::selGen at the checkpoint: still equal = the selection is the one the records were gathered for
+    DevBuf<uint32_t> sel, del, idx;         // ceil(N/32) words each / k indices
+    DevBuf<uint8_t> pos, other, sh;         // k x 12 / 16 / 192 bytes
+};
+struct EditHistory {
+    bool enabled = false;
+    uint64_t maxBytes = 0, bytes = 0;       // the budget; bytes of undo + redo
+    std::vector<EditHistEntry> undo, redo;  // back() = the entry the next undo / redo applies
+    // entries dropped by a call that may not wait (a mutating edit call drops the redo side): an undo's swap may still be reading them on the stream, so they
+    // are only released where the stream is known to have drained -- the next checkpoint, clear, disable, or the renderer's end
+    std::vector<EditHistEntry> dead;
+    uint32_t evicted = 0, uncovered = 0;
+    uint64_t selGen = 0;                    // bumped by every call that may change the selection
+    DevBuf<uint32_t> counts, base;          // per 256-splat block: selected splats, and their exclusive prefix (+ the total); made by enable
+};
 } // namespace gs
 
 // A plain-value setting goes into gs::RendererSettings, and nothing else needs doing.
@@ -391,6 +414,8 @@ struct gs_renderer {
     std::vector<gs_renderer*> lanes;
     int laneCur = -1;                       // the lane of the frame in progress (-1: none yet)
     gs_renderer* laneOf = nullptr;          // a lane's owner
+    // ---- the edit history (gs_renderer_edit_history_enable; gs_edit.hip) ----
+    gs::EditHistory hist;                   // undo / redo of the edit state: off (and empty) unless gs_renderer_edit_history_enable was called; the owner's only
 };
 
 namespace gs {
@@ -461,6 +486,14 @@ int32_t edit_make_private(gs_renderer* r, int k);   // copy-on-write of blob k (
 int32_t edit_deleted_to_lanes(gs_renderer* r);      // the lanes' copies of the deleted bits follow the owner's, stream-ordered (mirror_bits_to_lanes)
 int32_t edit_selected_to_lanes(gs_renderer* r);     // ... and, while the highlight is on, their copies of the selection
 int32_t ensure_deleted_bits(gs_renderer* r, hipStream_t st);   // a renderer without a deleted buffer gets one, zero-filled on st
+// the edit history's hooks (host bookkeeping only, nothing is launched; all of them do nothing while the history is off):
+void hist_mutated(gs_renderer* r, bool selection);   // a call is about to change journalable state: the redo side goes; selection: the selection may change
+void hist_transform(gs_renderer* r);                 // ... a transform: hist_mutated + the uncovered_transforms count
+int32_t hist_clear(gs_renderer* r);                  // every entry released (waits for the stream first)
+void hist_forget(gs_renderer* r);                    // ... without waiting: every entry dropped now, its memory released at the next call of the history's that waits
+void hist_carry(gs_renderer* to, const gs_renderer* from);   // a resize: the switch, the budget and the counters move on to the new state, the entries do not
+// gs_export.hip: base[i] = counts[0] + .. + counts[i - 1] for i in [0, n] on st (export_scan_kernel, one workgroup)
+int32_t enqueue_scan(hipStream_t st, const uint32_t* counts, uint32_t* base, uint32_t n);
 // what brackets a kernel that rewrites positions (the transforms, the merge): ordering against sorts, GS_SORT_VISIBLE's history and the lanes
 int32_t edit_before_move(gs_renderer* r);
 int32_t edit_after_move(gs_renderer* r);

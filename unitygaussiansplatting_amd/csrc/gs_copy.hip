@@ -161,6 +161,7 @@ static int32_t set_splat_count_impl(gs_renderer* r, uint32_t newN, const gs_copy
     rc = gs_renderer_set_frames_in_flight(r, 1);
     if (rc != GS_OK) { (void)gs_renderer_destroy(f); return rc; }
     std::swap(*r, *f);
+    hist_carry(r, f);                                              // the edit history's entries go with the old state; its switch, budget and counters stay
     (void)gs_renderer_destroy(f);
     if (lanes > 1) GS_TRY(gs_renderer_set_frames_in_flight(r, lanes));
     return GS_OK;
@@ -174,6 +175,7 @@ static int32_t copy_splats_into_impl(gs_renderer* src, gs_renderer* dst, const g
     if (!copy_dst_gate(dst)) return fail(GS_ERR_INVALID_ARGUMENT, "copy_splats_into: the destination must be chunk-less with fp32 pos / scale / sh and Float32x4 colour");
     if (copy_clamp(src->n, dst->n, srcStart, dstStart, count) == 0u) return GS_OK;
     GS_HIP(hipSetDevice(dst->ctx->device));
+    hist_forget(dst);                                              // the copy writes index ranges, not the selection: nothing of it is journalled
     const gsm::CopyXform X = copy_xform_of(p);
     hipStream_t st = dst->ctx->stream;
     GS_TRY(edit_before_move(dst));                                 // positions change: the transform's ordering (gs_edit.hip)

@@ -1999,4 +1999,41 @@ GS_HD void BakeEncodeChunkSerial(BakeRec* rec, uint32_t cnt, uint32_t first, con
     }
 }
 
+// ---- the edit history's compaction (gs_renderer_edit_checkpoint; kernels in gs_edit.hip) ----------------------------
+// A checkpoint journals the records of the splats selected NOW, in index order: splat s of 256-splat block b goes to journal slot
+// base[b] + HistRank(m, s & 255), base = the exclusive prefix of HistBlockCount over the blocks.  Bits of the last word at indices >= n (select-all
+// and invert set them) name no splat and are masked off first.
+constexpr uint32_t kHistBlock = 256;                               // splats per block: eight selection words
+// selection word `w` (splats 32 w .. 32 w + 31) of a renderer of n splats without the bits at indices >= n
+GS_HD uint32_t HistMaskedWord(uint32_t word, uint32_t w, uint32_t n) {
+    const uint32_t first = w * 32u;
+    if (first >= n) return 0u;
+    const uint32_t left = n - first;
+    return left >= 32u ? word : (word & ((1u << left) - 1u));
+}
+// the eight masked words of block b (a word index >= nWords reads as zero)
+GS_HD void HistBlockWords(const uint32_t* sel, uint32_t nWords, uint32_t n, uint32_t b, uint32_t m[8]) {
+#pragma unroll
+    for (uint32_t j = 0; j < 8u; ++j) {
+        const uint32_t w = b * 8u + j;
+        m[j] = w < nWords ? HistMaskedWord(sel[w], w, n) : 0u;
+    }
+}
+// selected splats of the block
+GS_HD uint32_t HistBlockCount(const uint32_t m[8]) {
+    uint32_t c = 0u;
+#pragma unroll
+    for (uint32_t j = 0; j < 8u; ++j) c += (uint32_t)__builtin_popcount(m[j]);
+    return c;
+}
+// selected splats of the block below splat t (0 .. 255) of it: the splat's journal slot inside the block if it is selected itself
+GS_HD uint32_t HistRank(const uint32_t m[8], uint32_t t) {
+    const uint32_t wj = t >> 5, below = (1u << (t & 31u)) - 1u;
+    uint32_t r = 0u;
+#pragma unroll
+    for (uint32_t j = 0; j < 8u; ++j)                              // (no m[wj]: a register array is never indexed by a variable)
+        r += (uint32_t)__builtin_popcount(m[j] & (j < wj ? ~0u : (j == wj ? below : 0u)));
+    return r;
+}
+
 } // namespace gsm

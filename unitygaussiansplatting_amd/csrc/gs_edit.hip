@@ -12,7 +12,9 @@
 // immutable: the first transform whose format gate can pass gives the renderer a private copy of the pos and / or other blob (copy-on-write,
 // gs::asset_view), and from then on every kernel of this renderer and of its lanes reads that copy.  With gs_renderer_edit_set_rigid_transforms on,
 // rotate and uniform scale also do what the reference's three @TODOs leave out -- orientation on the right side, SH rotated, splat sizes scaled -- and
-// the SH blob becomes private the same way (the RIGID instantiations below).  CSExportData only reads: gs_export.hip.
+// the SH blob becomes private the same way (the RIGID instantiations below).  Undo and redo of all of this, which the
+// reference does not have, is the edit history: a journal of the bit buffers and of the selected splats' records (hist_*).
+// CSExportData only reads: gs_export.hip.
 // CSCopySplats / EditSetSplatCount / EditCopySplatsInto -- the merge -- are gs_copy.hip.  The highlight of selected splats
 // (RenderGaussianSplats.shader:63-73,87-101) is drawn by calc_view and the blend (gs_view.hip, gs_raster.hip) when
 // gs_renderer_set_selection_highlight is on; what this file does for it is keep the lanes' copies of the selection in step
@@ -221,6 +223,106 @@ __global__ __launch_bounds__(256) void edit_select_surface_kernel(gsm::AssetView
     else atomicOr(sel + (idx >> 5), 1u << (idx & 31u));
 }
 
+// ---- the edit history's kernels (gs_renderer_edit_checkpoint / _undo / _redo) -------------------------------------
+// A checkpoint compacts the records of the selected splats into per-kind contiguous journal arrays: count, scan (export_scan_kernel), gather.  The
+// shape of this file -- one thread per splat, 256-thread workgroups = one 256-splat block, a wave owns two selection words -- and the arithmetic
+// (masked words, block count, rank) is gsm::Hist*, which the host harness runs too.  No atomics, no workgroup waits on another, no scratch.
+
+// counts[b] = selected splats of block b with index < n.  Eight words and eight popcounts per block are one lane's work, so a thread takes a BLOCK (a
+// workgroup per block would idle 255 of its lanes): neighbouring threads read neighbouring 32-byte runs of words.
+__global__ __launch_bounds__(256) void hist_count_kernel(const uint32_t* __restrict__ sel, uint32_t nWords, uint32_t n, uint32_t blocks, uint32_t* __restrict__ counts) {
+    const uint32_t b = blockIdx.x * 256u + threadIdx.x;
+    if (b >= blocks) return;
+    uint32_t m[8];
+    gsm::HistBlockWords(sel, nWords, n, b, m);
+    counts[b] = gsm::HistBlockCount(m);
+}
+
+struct HistJournal { uint32_t* idx; uint8_t* pos; uint8_t* other; uint8_t* sh; };      // k indices; k x 12 / 16 / 192 bytes (null = that kind is not captured)
+
+// Journal slot of a selected splat = base[block] + its rank inside the block, which every wave works out for itself from the block's eight words (uniform
+// loads): no wave waits for another's count.  pos / other go out per lane -- the slots of a wave's selected lanes are consecutive, so the stores of one
+// instruction cover one contiguous range.  An SH record is 192 bytes: a lane copying its own record would put neighbouring lanes 192 bytes apart on both
+// sides (the shape DESIGN.md section 4.8 measured slower), so a wave stages its selected INDICES in LDS (256 bytes; the rows themselves need not pass
+// through LDS) and then moves the c records as c x 12 dwordx4 items, lanes striding over the items: the journal side is one contiguous, 16-byte aligned
+// range, the blob side contiguous per record.  A wave whose two words are zero touches no blob.
+__global__ __launch_bounds__(256) void hist_gather_kernel(const uint8_t* __restrict__ pos, const uint8_t* __restrict__ other, const uint8_t* __restrict__ sh,
+                                                          const uint32_t* __restrict__ sel, uint32_t nWords, uint32_t n, const uint32_t* __restrict__ base,
+                                                          HistJournal J) {
+    __shared__ uint32_t s_idx[4][64];
+    const uint32_t t = threadIdx.x, idx = blockIdx.x * 256u + t, lane = t & 63u, wave = t >> 6;
+    uint32_t m[8];
+    gsm::HistBlockWords(sel, nWords, n, blockIdx.x, m);
+    const uint32_t w0 = wave == 0u ? m[0] : (wave == 1u ? m[2] : (wave == 2u ? m[4] : m[6]));
+    const uint32_t w1 = wave == 0u ? m[1] : (wave == 1u ? m[3] : (wave == 2u ? m[5] : m[7]));
+    if ((w0 | w1) == 0u) return;                                   // wave-uniform; no barrier below
+    const uint32_t blockBase = base[blockIdx.x];
+    const uint32_t waveFirst = blockBase + gsm::HistRank(m, wave * 64u);       // slot of the wave's first selected splat
+    const bool mine = (((lane < 32u ? w0 : w1) >> (lane & 31u)) & 1u) != 0u;   // (masked: idx < n)
+    if (mine) {
+        const uint32_t slot = blockBase + gsm::HistRank(m, t);
+        J.idx[slot] = idx;
+        s_idx[wave][slot - waveFirst] = idx;
+        if (J.pos) {
+            const uint32_t* s = (const uint32_t*)(pos + (size_t)idx * 12u);
+            uint32_t* d = (uint32_t*)(J.pos + (size_t)slot * 12u);
+            d[0] = s[0]; d[1] = s[1]; d[2] = s[2];
+        }
+        if (J.other) *(uint4*)(J.other + (size_t)slot * 16u) = *(const uint4*)(other + (size_t)idx * 16u);
+    }
+    if (!J.sh) return;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");         // s_idx[wave] is this wave's own and the LDS operations of one wave complete in order:
+    __builtin_amdgcn_wave_barrier();                               // nothing to wait for, the compiler only has to keep the stores above the loads
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const uint32_t c = (uint32_t)(__popc(w0) + __popc(w1));
+    uint4* dst = (uint4*)(J.sh + (size_t)waveFirst * 192u);
+    for (uint32_t i = lane; i < c * 12u; i += 64u) {
+        const uint32_t rec = i / 12u, q = i - rec * 12u;
+        dst[i] = *(const uint4*)(sh + (size_t)s_idx[wave][rec] * 192u + q * 16u);
+    }
+}
+
+// undo / redo: the journalled records change places with the renderer's.  The indices are distinct, so no two threads touch one record.  One thread per
+// item for pos (three dwords) and other (one dwordx4 each way) ...
+__global__ __launch_bounds__(256) void hist_swap_records_kernel(const uint32_t* __restrict__ idx, uint32_t k, uint8_t* __restrict__ pos, uint8_t* __restrict__ posJ,
+                                                                uint8_t* __restrict__ other, uint8_t* __restrict__ otherJ) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= k) return;
+    const uint32_t s = idx[i];
+    if (pos) {
+        uint32_t* a = (uint32_t*)(pos + (size_t)s * 12u);
+        uint32_t* b = (uint32_t*)(posJ + (size_t)i * 12u);
+        const uint32_t a0 = a[0], a1 = a[1], a2 = a[2], b0 = b[0], b1 = b[1], b2 = b[2];
+        a[0] = b0; a[1] = b1; a[2] = b2;
+        b[0] = a0; b[1] = a1; b[2] = a2;
+    }
+    if (other) {
+        uint4* a = (uint4*)(other + (size_t)s * 16u);
+        uint4* b = (uint4*)(otherJ + (size_t)i * 16u);
+        const uint4 va = *a, vb = *b;
+        *a = vb; *b = va;
+    }
+}
+
+// ... and twelve lanes per item for SH, 16 bytes each: the journal side fully contiguous, the blob side contiguous per record
+__global__ __launch_bounds__(256) void hist_swap_sh_kernel(const uint32_t* __restrict__ idx, uint32_t k, uint8_t* __restrict__ sh, uint8_t* __restrict__ shJ) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256ull + threadIdx.x;
+    if (i >= (unsigned long long)k * 12ull) return;
+    const uint32_t rec = (uint32_t)(i / 12ull), q = (uint32_t)(i - (unsigned long long)rec * 12ull);
+    uint4* a = (uint4*)(sh + (size_t)idx[rec] * 192u + q * 16u);
+    uint4* b = (uint4*)(shJ + (size_t)i * 16u);
+    const uint4 va = *a, vb = *b;
+    *a = vb; *b = va;
+}
+
+// a bit buffer and its journalled copy, word for word
+__global__ __launch_bounds__(256) void hist_swap_words_kernel(uint32_t* __restrict__ a, uint32_t* __restrict__ b, uint32_t nWords) {
+    const uint32_t w = blockIdx.x * 256u + threadIdx.x;
+    if (w >= nWords) return;
+    const uint32_t va = a[w], vb = b[w];
+    a[w] = vb; b[w] = va;
+}
+
 // EnsureEditingBuffers (GaussianSplatRenderer.cs:767-786) without the deleted buffer, which is made when a delete first needs it
 int32_t edit_ensure(gs_renderer* r) {
     if (r->laneOf) return fail(GS_ERR_INVALID_ARGUMENT, "a lane holds no selection: edit its owner");
@@ -349,6 +451,7 @@ int32_t edit_after_move(gs_renderer* r) {
 //     positions), the kernel runs, and every lane's stream waits for it.  signal_to only; mirror_bits_to_lanes turned round.
 // G: null = the reference's kernels; else the rigid form (the setting is on; for a scale: and the delta is uniform).
 static int32_t edit_transform(gs_renderer* r, int op, const gsm::EditXform& X, const gsm::EditRigid* G = nullptr) {
+    hist_transform(r);
     const bool doPos = edit_pos_gate(r), doRot = (op == kEditRotate || (G && op == kEditScale)) && edit_rot_gate(r);
     if (!doPos && !doRot) return GS_OK;                            // neither gate: the reference's kernel writes nothing
     const bool doSH = doRot && G && op == kEditRotate;
@@ -373,6 +476,190 @@ static int32_t edit_transform(gs_renderer* r, int op, const gsm::EditXform& X, c
     return edit_after_move(r);
 }
 
+// ---- the edit history -----------------------------------------------------------------------------------------------------------------------
+constexpr uint32_t kHistBits = GS_HIST_SELECTION | GS_HIST_DELETED;
+constexpr uint32_t kHistRecords = GS_HIST_POS | GS_HIST_OTHER | GS_HIST_SH;
+
+// entries leave a stack without a wait: they move to `dead` (no host memory for that: the stream is drained instead and they are released here)
+static void hist_retire(gs_renderer* r, std::vector<EditHistEntry>& v) {
+    EditHistory& h = r->hist;
+    for (const EditHistEntry& e : v) h.bytes -= e.bytes;
+    try {
+        h.dead.reserve(h.dead.size() + v.size());
+        for (EditHistEntry& e : v) h.dead.push_back(std::move(e));
+    } catch (const std::bad_alloc&) {
+        (void)hipStreamSynchronize(r->ctx->stream);
+    }
+    v.clear();
+}
+static void hist_drop_redo(gs_renderer* r) { if (!r->hist.redo.empty()) hist_retire(r, r->hist.redo); }
+
+void hist_mutated(gs_renderer* r, bool selection) {
+    EditHistory& h = r->hist;
+    if (!h.enabled) return;
+    hist_drop_redo(r);
+    if (selection) ++h.selGen;
+}
+
+void hist_transform(gs_renderer* r) {
+    EditHistory& h = r->hist;
+    if (!h.enabled) return;
+    hist_drop_redo(r);
+    if (h.undo.empty() || !(h.undo.back().what & kHistRecords) || h.undo.back().selGen != h.selGen) ++h.uncovered;
+}
+
+void hist_forget(gs_renderer* r) {
+    EditHistory& h = r->hist;
+    if (!h.enabled) return;
+    hist_drop_redo(r);
+    hist_retire(r, h.undo);
+    ++h.selGen;
+}
+
+// the stream has drained: nothing reads a dropped entry any more
+static void hist_bury(EditHistory& h) { h.dead.clear(); }
+
+int32_t hist_clear(gs_renderer* r) {
+    EditHistory& h = r->hist;
+    if (h.undo.empty() && h.redo.empty() && h.dead.empty()) return GS_OK;
+    GS_HIP(hipSetDevice(r->ctx->device));
+    GS_HIP(hipStreamSynchronize(r->ctx->stream));                  // an undo's swap may still be running
+    h.undo.clear(); h.redo.clear(); h.dead.clear();
+    h.bytes = 0;
+    return GS_OK;
+}
+
+static int32_t hist_alloc_scratch(gs_renderer* r) {
+    const size_t blocks = ((size_t)r->n + 255) / 256;
+    DevBuf<uint32_t> counts, base;
+    if (counts.alloc(blocks * 4) != hipSuccess || base.alloc((blocks + 1) * 4) != hipSuccess) return fail(GS_ERR_OUT_OF_MEMORY, "edit history: out of device memory");
+    r->hist.counts = std::move(counts); r->hist.base = std::move(base);
+    return GS_OK;
+}
+
+void hist_carry(gs_renderer* to, const gs_renderer* from) {
+    const EditHistory& f = from->hist;
+    if (!f.enabled) return;
+    if (hist_alloc_scratch(to) != GS_OK) return;                   // (no memory for two small arrays: the new state starts with the history off)
+    EditHistory& t = to->hist;
+    t.enabled = true; t.maxBytes = f.maxBytes; t.evicted = f.evicted; t.uncovered = f.uncovered; t.selGen = f.selGen + 1;
+}
+
+// evict the oldest entries until `extra` more bytes fit (the caller has checked that extra alone does, and has drained the stream: they are released here)
+static void hist_evict_for(EditHistory& h, uint64_t extra) {
+    size_t gone = 0;
+    while (gone < h.undo.size() && h.bytes + extra > h.maxBytes) { h.bytes -= h.undo[gone].bytes; ++gone; ++h.evicted; }
+    h.undo.erase(h.undo.begin(), h.undo.begin() + (ptrdiff_t)gone);
+}
+
+static int32_t hist_checkpoint(gs_renderer* r, uint32_t what) {
+    EditHistory& h = r->hist;
+    hipStream_t st = r->ctx->stream;
+    GS_HIP(hipSetDevice(r->ctx->device));
+    if (what & GS_HIST_TRANSFORM) what = (what & ~GS_HIST_TRANSFORM) | GS_HIST_POS | GS_HIST_OTHER | (r->set.rigidTransforms ? GS_HIST_SH : 0u);
+    if (!edit_pos_gate(r)) what &= ~GS_HIST_POS;
+    if (!edit_rot_gate(r)) what &= ~(GS_HIST_OTHER | GS_HIST_SH);
+    if (!what) return GS_OK;
+    const uint32_t nWords = (uint32_t)bit_words(r->n), blocks = splat_grid(r);
+    const uint64_t bitBytes = (uint64_t)nWords * 4;
+    if (what & (GS_HIST_SELECTION | kHistRecords)) GS_TRY(edit_ensure(r));
+    // the count: one 4-byte readback, which also drains the stream -- whatever the dropped entries were still read by has finished
+    uint32_t k = 0;
+    if (what & kHistRecords) {
+        hipLaunchKernelGGL(hist_count_kernel, dim3((blocks + 255u) / 256u), dim3(256), 0, st, (const uint32_t*)r->editSelected, nWords, r->n, blocks, h.counts.get());
+        GS_HIP(hipGetLastError());
+        GS_TRY(enqueue_scan(st, h.counts, h.base, blocks));
+        GS_HIP(hipMemcpyAsync(&k, h.base + blocks, 4, hipMemcpyDeviceToHost, st));
+    }
+    GS_HIP(hipStreamSynchronize(st));
+    hist_bury(h);
+    EditHistEntry e;
+    e.what = what; e.k = k; e.selGen = h.selGen;
+    const uint64_t perSplat = 4u + ((what & GS_HIST_POS) ? 12u : 0u) + ((what & GS_HIST_OTHER) ? 16u : 0u) + ((what & GS_HIST_SH) ? 192u : 0u);
+    e.bytes = ((what & GS_HIST_SELECTION) ? bitBytes : 0) + ((what & GS_HIST_DELETED) ? bitBytes : 0) + ((what & kHistRecords) ? perSplat * k : 0);
+    if (e.bytes > h.maxBytes) return fail(GS_ERR_OUT_OF_MEMORY, "edit checkpoint: the entry alone exceeds the history's budget");
+    // everything is allocated before the stack changes.  The kernels read other / sh records as dwordx4: an asset blob the host lent at an odd address
+    // becomes private (hipMalloc's alignment) first
+    bool ok = true;
+    if (what & GS_HIST_SELECTION) ok = ok && e.sel.alloc(bitBytes) == hipSuccess;
+    if (what & GS_HIST_DELETED) ok = ok && e.del.alloc(bitBytes) == hipSuccess;
+    if (k) {
+        ok = ok && e.idx.alloc((size_t)k * 4) == hipSuccess;
+        if (what & GS_HIST_POS) ok = ok && e.pos.alloc((size_t)k * 12) == hipSuccess;
+        if (what & GS_HIST_OTHER) ok = ok && e.other.alloc((size_t)k * 16) == hipSuccess;
+        if (what & GS_HIST_SH) ok = ok && e.sh.alloc((size_t)k * 192) == hipSuccess;
+    }
+    if (!ok) { (void)hipGetLastError(); return fail(GS_ERR_OUT_OF_MEMORY, "edit checkpoint: out of device memory"); }
+    if (k) {
+        if ((what & GS_HIST_OTHER) && ((uintptr_t)blob_ptr(r, 1) & 15u)) GS_TRY(edit_make_private(r, 1));
+        if ((what & GS_HIST_SH) && ((uintptr_t)blob_ptr(r, 3) & 15u)) GS_TRY(edit_make_private(r, 3));
+    }
+    try { h.undo.reserve(h.undo.size() + 1); }
+    catch (const std::bad_alloc&) { return fail(GS_ERR_OUT_OF_MEMORY, "edit checkpoint: out of host memory"); }
+    // the captures, on the stream
+    if (what & GS_HIST_SELECTION) GS_HIP(hipMemcpyAsync(e.sel, r->editSelected, bitBytes, hipMemcpyDeviceToDevice, st));
+    if (what & GS_HIST_DELETED) {
+        if (r->deletedBits) GS_HIP(hipMemcpyAsync(e.del, r->deletedBits, bitBytes, hipMemcpyDeviceToDevice, st));
+        else GS_HIP(hipMemsetAsync(e.del, 0, bitBytes, st));      // a buffer that does not exist reads as zeros
+    }
+    if (k) {
+        const HistJournal J = { e.idx, e.pos, e.other, e.sh };
+        hipLaunchKernelGGL(hist_gather_kernel, dim3(blocks), dim3(256), 0, st, blob_ptr(r, 0), blob_ptr(r, 1), blob_ptr(r, 3), (const uint32_t*)r->editSelected,
+                           nWords, r->n, (const uint32_t*)h.base, J);
+        GS_HIP(hipGetLastError());
+    }
+    hist_drop_redo(r);
+    hist_evict_for(h, e.bytes);
+    h.bytes += e.bytes;
+    h.undo.push_back(std::move(e));
+    hist_bury(h);                                                  // nothing enqueued since the stream drained reads a dropped or evicted entry
+    return GS_OK;
+}
+
+// undo (from = undo side) and redo (from = redo side): the top entry of `from` changes places with the renderer's state and moves to `to`
+static int32_t hist_apply(gs_renderer* r, std::vector<EditHistEntry>& from, std::vector<EditHistEntry>& to) {
+    if (from.empty()) return GS_OK;
+    GS_HIP(hipSetDevice(r->ctx->device));
+    try { to.reserve(to.size() + 1); } catch (const std::bad_alloc&) { return fail(GS_ERR_OUT_OF_MEMORY, "edit history: out of host memory"); }
+    EditHistEntry& e = from.back();
+    hipStream_t st = r->ctx->stream;
+    const uint32_t nWords = (uint32_t)bit_words(r->n);
+    // records: a blob without a private copy has not been written since the checkpoint (only a resize drops private copies, and it clears the history)
+    uint8_t* pos = (e.what & GS_HIST_POS) && e.k ? r->priv[0].get() : nullptr;
+    uint8_t* other = (e.what & GS_HIST_OTHER) && e.k ? r->priv[1].get() : nullptr;
+    uint8_t* sh = (e.what & GS_HIST_SH) && e.k ? r->priv[3].get() : nullptr;
+    if (pos || other || sh) {
+        GS_TRY(edit_before_move(r));
+        if (pos || other) hipLaunchKernelGGL(hist_swap_records_kernel, dim3((e.k + 255u) / 256u), dim3(256), 0, st, (const uint32_t*)e.idx, e.k, pos, e.pos.get(), other, e.other.get());
+        if (sh) hipLaunchKernelGGL(hist_swap_sh_kernel, dim3((uint32_t)(((uint64_t)e.k * 12u + 255u) / 256u)), dim3(256), 0, st, (const uint32_t*)e.idx, e.k, sh, e.sh.get());
+        GS_HIP(hipGetLastError());
+        GS_TRY(edit_after_move(r));
+    }
+    if (e.what & GS_HIST_DELETED) {
+        GS_TRY(ensure_deleted_bits(r, st));
+        hipLaunchKernelGGL(hist_swap_words_kernel, dim3(word_grid(r)), dim3(256), 0, st, r->deletedBits.get(), e.del.get(), nWords);
+        GS_HIP(hipGetLastError());
+        GS_TRY(edit_deleted_to_lanes(r));
+    }
+    if (e.what & GS_HIST_SELECTION) {
+        GS_TRY(edit_ensure(r));
+        hipLaunchKernelGGL(hist_swap_words_kernel, dim3(word_grid(r)), dim3(256), 0, st, r->editSelected.get(), e.sel.get(), nWords);
+        GS_HIP(hipGetLastError());
+        ++r->hist.selGen;
+        GS_TRY(edit_selected_to_lanes(r));
+    }
+    to.push_back(std::move(e));
+    from.pop_back();
+    return GS_OK;
+}
+
+static int32_t hist_usable(const gs_renderer* r, bool needOn) {
+    if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
+    if (r->laneOf) return fail(GS_ERR_INVALID_ARGUMENT, "a lane holds no edit state: edit its owner");
+    if (needOn && !r->hist.enabled) return fail(GS_ERR_INVALID_ARGUMENT, "the edit history is off (gs_renderer_edit_history_enable)");
+    return GS_OK;
+}
+
 } // namespace gs
 
 using namespace gs;
@@ -382,6 +669,7 @@ extern "C" {
 int32_t gs_renderer_edit_select_all(gs_renderer* r) {
     if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
     GS_TRY(edit_ensure(r));
+    hist_mutated(r, true);
     hipLaunchKernelGGL(edit_select_all_kernel, dim3(splat_grid(r)), dim3(256), 0, r->ctx->stream, asset_view(r), edit_view(r), r->editSelected,
                        (uint32_t)bit_words(r->n), 0u);
     GS_HIP(hipGetLastError());
@@ -391,6 +679,7 @@ int32_t gs_renderer_edit_select_all(gs_renderer* r) {
 int32_t gs_renderer_edit_invert_selection(gs_renderer* r) {
     if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
     GS_TRY(edit_ensure(r));
+    hist_mutated(r, true);
     hipLaunchKernelGGL(edit_select_all_kernel, dim3(splat_grid(r)), dim3(256), 0, r->ctx->stream, asset_view(r), edit_view(r), r->editSelected,
                        (uint32_t)bit_words(r->n), 1u);
     GS_HIP(hipGetLastError());
@@ -400,6 +689,7 @@ int32_t gs_renderer_edit_invert_selection(gs_renderer* r) {
 int32_t gs_renderer_edit_deselect_all(gs_renderer* r) {
     if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
     GS_TRY(edit_ensure(r));
+    hist_mutated(r, true);
     GS_HIP(hipMemsetAsync(r->editSelected, 0, bit_words(r->n) * 4, r->ctx->stream));          // CSClearBuffer
     return edit_selected_to_lanes(r);
 }
@@ -414,6 +704,7 @@ int32_t gs_renderer_edit_store_selection(gs_renderer* r) {
 int32_t gs_renderer_edit_update_selection(gs_renderer* r, const gs_frame_params* p, const float selection_rect[4], int32_t subtract) {
     if (!r || !p || !selection_rect) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
     GS_TRY(edit_ensure(r));
+    hist_mutated(r, true);
     hipLaunchKernelGGL(edit_selection_update_kernel, dim3(splat_grid(r)), dim3(256), 0, r->ctx->stream, asset_view(r), edit_view(r), edit_select_of(*p, selection_rect),
                        (const uint32_t*)r->editSelectedMouseDown, r->editSelected, (uint32_t)bit_words(r->n), subtract ? 0u : 1u);
     GS_HIP(hipGetLastError());
@@ -426,6 +717,7 @@ int32_t gs_renderer_edit_select_surface(gs_renderer* r, gs_target* t, int32_t x0
     if (!t->pick) return fail(GS_ERR_INVALID_ARGUMENT, "the target has no pick output (gs_target_set_pick_output)");
     if (x0 > x1 || y0 > y1) return fail(GS_ERR_INVALID_ARGUMENT, "select_surface: empty rectangle");
     GS_TRY(edit_ensure(r));
+    hist_mutated(r, true);
     GS_TRY(flush_clear(t));                                        // a cleared target that nothing has drawn into holds no record
     // the records' last writer: a lane's blend is joined into the context's stream by its draw, so the stream already orders this kernel after it
     const gsm::PickSelect S = pick_select_of(x0, y0, x1, y1, t->width, t->height, r->set.pickTag, subtract);
@@ -443,6 +735,7 @@ int32_t gs_renderer_edit_delete_selected(gs_renderer* r) {
     if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
     GS_TRY(edit_ensure(r));
     GS_TRY(ensure_deleted_bits(r, r->ctx->stream));
+    hist_mutated(r, true);                                         // (the delete clears the selection)
     hipLaunchKernelGGL(edit_delete_kernel, dim3(word_grid(r)), dim3(256), 0, r->ctx->stream, r->deletedBits, r->editSelected, (uint32_t)bit_words(r->n));
     GS_HIP(hipGetLastError());
     GS_TRY(edit_deleted_to_lanes(r));
@@ -474,6 +767,7 @@ int32_t gs_renderer_edit_upload_selected_bits(gs_renderer* r, const uint32_t* wo
     if (!r || !words) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
     if (word_count != bit_words(r->n)) return fail(GS_ERR_INVALID_ARGUMENT, "selected bits: word_count must be ceil(splat_count / 32)");
     GS_TRY(edit_ensure(r));
+    hist_mutated(r, true);
     GS_HIP(hipMemcpyAsync(r->editSelected, words, word_count * 4, hipMemcpyHostToDevice, r->ctx->stream));
     GS_HIP(hipStreamSynchronize(r->ctx->stream));                  // `words` is only read during the call
     return edit_selected_to_lanes(r);
@@ -571,6 +865,65 @@ int32_t gs_renderer_edit_release(gs_renderer* r) {
         L->laneSelected.reset();
     }
     edit_free(r);
+    return GS_OK;
+}
+
+int32_t gs_renderer_edit_history_enable(gs_renderer* r, uint64_t max_bytes) {
+    GS_TRY(hist_usable(r, false));
+    EditHistory& h = r->hist;
+    if (max_bytes == 0) {
+        GS_TRY(hist_clear(r));
+        if (h.enabled) { GS_HIP(hipSetDevice(r->ctx->device)); GS_HIP(hipStreamSynchronize(r->ctx->stream)); }   // (a checkpoint's count may be the last thing enqueued)
+        h.counts.reset(); h.base.reset();
+        h.enabled = false; h.maxBytes = 0; h.evicted = h.uncovered = 0; h.selGen = 0;
+        return GS_OK;
+    }
+    GS_HIP(hipSetDevice(r->ctx->device));
+    if (!h.enabled) {
+        GS_TRY(hist_alloc_scratch(r));
+        h.enabled = true; h.evicted = h.uncovered = 0; h.selGen = 0; h.bytes = 0;
+    }
+    h.maxBytes = max_bytes;
+    if (h.bytes > h.maxBytes) {                                    // a smaller budget: the oldest undo entries go first, then the farthest redo entries
+        GS_HIP(hipStreamSynchronize(r->ctx->stream));
+        hist_evict_for(h, 0);
+        while (!h.redo.empty() && h.bytes > h.maxBytes) { h.bytes -= h.redo.front().bytes; h.redo.erase(h.redo.begin()); ++h.evicted; }
+        hist_bury(h);
+    }
+    return GS_OK;
+}
+
+int32_t gs_renderer_edit_checkpoint(gs_renderer* r, uint32_t what) {
+    GS_TRY(hist_usable(r, true));
+    if (what == 0u || (what & ~(kHistBits | kHistRecords | GS_HIST_TRANSFORM))) return fail(GS_ERR_INVALID_ARGUMENT, "edit checkpoint: `what` is zero or has unknown bits");
+    return hist_checkpoint(r, what);
+}
+
+int32_t gs_renderer_edit_undo(gs_renderer* r) {
+    GS_TRY(hist_usable(r, true));
+    return hist_apply(r, r->hist.undo, r->hist.redo);
+}
+
+int32_t gs_renderer_edit_redo(gs_renderer* r) {
+    GS_TRY(hist_usable(r, true));
+    return hist_apply(r, r->hist.redo, r->hist.undo);
+}
+
+int32_t gs_renderer_edit_history_clear(gs_renderer* r) {
+    GS_TRY(hist_usable(r, false));
+    return hist_clear(r);
+}
+
+int32_t gs_renderer_edit_history_info(const gs_renderer* r, gs_edit_history_info* out) {
+    GS_TRY(hist_usable(r, false));
+    if (!out) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
+    memset(out, 0, sizeof(*out));
+    const EditHistory& h = r->hist;
+    out->enabled = h.enabled ? 1u : 0u;
+    out->undo_depth = (uint32_t)h.undo.size(); out->redo_depth = (uint32_t)h.redo.size();
+    out->bytes = h.bytes; out->max_bytes = h.maxBytes;
+    if (!h.undo.empty()) { out->top_what = h.undo.back().what; out->top_bytes = h.undo.back().bytes; out->top_splats = h.undo.back().k; }
+    out->evicted = h.evicted; out->uncovered_transforms = h.uncovered;
     return GS_OK;
 }
 

@@ -85,6 +85,13 @@ int32_t enqueue_alive_counts(hipStream_t st, const gsm::AssetView& a, const gsm:
     return GS_OK;
 }
 
+// the scan alone, for counts made elsewhere (the edit history's compaction, gs_edit.hip)
+int32_t enqueue_scan(hipStream_t st, const uint32_t* counts, uint32_t* base, uint32_t n) {
+    hipLaunchKernelGGL(export_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, counts, base, n);
+    GS_HIP(hipGetLastError());
+    return GS_OK;
+}
+
 // out: the records of the chunks [firstChunk, firstChunk + gridDim.x).  base == null: record idx - firstChunk * 256 for every idx < N; else record
 // base[chunk] - base[firstChunk] + rank for the alive ones.
 __global__ __launch_bounds__(256) void export_records_kernel(gsm::AssetView a, gsm::EditView e, gsm::ExportXform X, const uint32_t* __restrict__ base,

@@ -132,6 +132,16 @@ namespace GaussianSplatting.Runtime
         [DllImport(Lib)] public static extern int gs_renderer_edit_set_splat_count(IntPtr renderer, uint newCount, IntPtr copyParamsOrZero);
         [DllImport(Lib)] public static extern int gs_renderer_edit_copy_splats_into(IntPtr src, IntPtr dst, ref CopyParams p, uint srcStart, uint dstStart, uint count);
         [DllImport(Lib)] public static extern int gs_renderer_edit_download_splat_data(IntPtr renderer, IntPtr pos, UIntPtr posBytes, IntPtr other, UIntPtr otherBytes, IntPtr color, UIntPtr colorBytes, IntPtr sh, UIntPtr shBytes);
+        // undo / redo of the edit state: a checkpoint before a gesture journals the two bit buffers and the records of the selected splats; undo / redo swap them back in
+        public const uint HistSelection = 1u, HistDeleted = 2u, HistPos = 4u, HistOther = 8u, HistSH = 16u, HistTransform = 0x80000000u;
+        [StructLayout(LayoutKind.Sequential)]
+        public struct EditHistoryInfo { public uint enabled, undoDepth, redoDepth, topWhat; public ulong bytes, maxBytes, topBytes; public uint topSplats, evicted, uncoveredTransforms; }
+        [DllImport(Lib)] public static extern int gs_renderer_edit_history_enable(IntPtr renderer, ulong maxBytes);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_checkpoint(IntPtr renderer, uint what);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_undo(IntPtr renderer);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_redo(IntPtr renderer);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_history_clear(IntPtr renderer);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_history_info(IntPtr renderer, out EditHistoryInfo info);
         [DllImport(Lib)] public static extern int gs_renderer_set_view_buffer_mode(IntPtr renderer, int everyFrame);
         [DllImport(Lib)] public static extern int gs_renderer_set_blend_mode(IntPtr renderer, int mode);
         [DllImport(Lib)] public static extern int gs_renderer_set_tile_shape(IntPtr renderer, uint tileW, uint tileH);

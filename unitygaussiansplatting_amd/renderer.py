@@ -18,7 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from ._abi import (GS_ERR_INVALID_ARGUMENT, GS_ERR_PAIR_OVERFLOW, GS_SORT_FULL, GS_SORT_VISIBLE, GS_SPZ_FRACT_AUTO, PICK_DTYPE, VIEW_DTYPE, gs_copy_params, gs_edit_info,
+from ._abi import (GS_ERR_INVALID_ARGUMENT, GS_ERR_PAIR_OVERFLOW, GS_SORT_FULL, GS_SORT_VISIBLE, GS_SPZ_FRACT_AUTO, PICK_DTYPE, VIEW_DTYPE, gs_copy_params, gs_edit_history_info, gs_edit_info,
                    gs_export_params, gs_frame_params, gs_frame_stats, gs_import_formats, gs_pick_record, gs_spz_params, gs_stage_times, make_asset_desc)
 from ._lib import GsError, check
 from .asset import CalcTextureSize, ColorFormat, GaussianSplatAsset, SHFormat, VectorFormat, kCurrentVersion, kMaxSplats
@@ -55,6 +55,15 @@ class RenderMode(enum.IntEnum):          # GaussianSplatRenderer.RenderMode (:21
 class SortMode(enum.IntEnum):            # gs_sort_mode: what SortPoints sorts (no counterpart in the reference, whose sort precedes its cull)
     Full = GS_SORT_FULL                  # all N splats, every SortPoints, like GaussianSplatRenderer.SortPoints (:612-639)
     Visible = GS_SORT_VISIBLE            # cull first: only the splats CalcViewData found visible, inside Draw
+
+
+class EditHistoryFlags(enum.IntFlag):    # GS_HIST_*: what an EditCheckpoint captures
+    Selection = 1                        # the selected bits, whole
+    Deleted = 2                          # the deleted bits, whole
+    Pos = 4                              # the records of the splats selected at the checkpoint ...
+    Other = 8
+    SH = 16
+    Transform = 0x80000000               # Pos | Other, and SH while EditSetRigidTransforms is on
 
 
 class Bounds:
@@ -648,6 +657,45 @@ class GaussianSplatRenderer:
         self.UpdateEditCountsAndBounds()
         self.editModified = True
 
+    # -- editing: undo and redo (no counterpart in the reference, which has none) ------------------
+    def EditHistoryEnable(self, maxBytes: int) -> None:
+        """Switches the edit history on with a budget of maxBytes of device memory for its entries (0: off, every entry freed).  Off by default."""
+        check(_lib.lib().gs_renderer_edit_history_enable(self._r_h, int(maxBytes)), "gs_renderer_edit_history_enable")
+
+    def EditCheckpoint(self, what=EditHistoryFlags.Selection | EditHistoryFlags.Deleted | EditHistoryFlags.Transform) -> None:
+        """Before a gesture, where the reference's tools call EditStore*MouseDown: captures the bit buffers named in `what` whole and the pos / other / SH
+        records of the splats selected NOW, which is exactly what a later EditUndo restores.  Blocks (one 4-byte readback sizes the entry)."""
+        check(_lib.lib().gs_renderer_edit_checkpoint(self._r_h, int(what)), "gs_renderer_edit_checkpoint")
+        if int(what) & ~int(EditHistoryFlags.Deleted):
+            self.m_GpuEditSelected = True           # (the native call made the edit buffers)
+
+    def _history_step(self, fn, where) -> None:
+        depth = self.EditHistoryInfo()
+        check(fn(self._r_h), where)
+        if depth.undo_depth + depth.redo_depth:
+            self.m_GpuEditSelected = True           # an entry with the selection makes released edit buffers again
+            self.UpdateEditCountsAndBounds()
+            self.editModified = True
+
+    def EditUndo(self) -> None:
+        """The entry of the last checkpoint changes places with the renderer's state (asynchronous); nothing to undo: nothing happens."""
+        self._history_step(_lib.lib().gs_renderer_edit_undo, "gs_renderer_edit_undo")
+
+    def EditRedo(self) -> None:
+        self._history_step(_lib.lib().gs_renderer_edit_redo, "gs_renderer_edit_redo")
+
+    def EditHistoryClear(self) -> None:
+        check(_lib.lib().gs_renderer_edit_history_clear(self._r_h), "gs_renderer_edit_history_clear")
+
+    def EditHistoryInfo(self) -> gs_edit_history_info:
+        info = gs_edit_history_info()
+        check(_lib.lib().gs_renderer_edit_history_info(self._r_h, C.byref(info)), "gs_renderer_edit_history_info")
+        return info
+
+    def EditGesture(self, what=EditHistoryFlags.Selection | EditHistoryFlags.Deleted | EditHistoryFlags.Transform):
+        """`with r.EditGesture(): ...` -- a checkpoint on entry, so that one EditUndo takes back everything the block did to the captured state."""
+        return _EditGesture(self, what)
+
     def _blob_sizes(self) -> Tuple[int, int, int, int]:
         """bytes of the renderer's current pos / other / color / sh blobs: the asset's until the first resize, from then on -- also back at the
         asset's own count -- those of the VeryHigh layout at splatCount (whole records only, where the importer pads its blobs)"""
@@ -982,6 +1030,18 @@ class GaussianSplatRenderer:
             self.DisposeResourcesForAsset()
         except Exception:
             pass
+
+
+class _EditGesture:
+    def __init__(self, renderer: GaussianSplatRenderer, what):
+        self.renderer, self.what = renderer, what
+
+    def __enter__(self) -> GaussianSplatRenderer:
+        self.renderer.EditCheckpoint(self.what)
+        return self.renderer
+
+    def __exit__(self, *exc) -> bool:
+        return False
 
 
 class ViewsInFlight:
