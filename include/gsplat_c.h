@@ -645,6 +645,30 @@ int32_t gs_renderer_set_pick_tag(gs_renderer* r, uint32_t tag);
  * use; gs_renderer_edit_info then reports the new counts and bounds.  x0 > x1 or y0 > y1, or a target without pick output: invalid argument. */
 int32_t gs_renderer_edit_select_surface(gs_renderer* r, gs_target* t, int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t subtract);
 
+/* ---- floaters: splats with few neighbours, counted on a grid on the GPU  (additions to ABI 9) -----------------------------
+ * The isolated splats training leaves in empty space lie in front of and behind everything: neither selection tool above reaches them.
+ * The contract, operation by operation:
+ *   ALIVE      a splat whose index is < N, that is not deleted and not cut by the renderer's current cutouts (the test of every edit call).
+ *   POSITIONS  object-space positions as the renderer decodes them, any preset; the renderer's private copy where a transform or a merge
+ *              made one.  `radius` is in that space.
+ *   N(i, j)    all in fp32, nothing fused: dx = xj - xi, dy, dz likewise; d2 = (dx dx + dy dy) + dz dz; r2 = radius radius; N holds when
+ *              d2 <= r2 (the boundary included).  Every comparison with NaN is false: a splat whose position is not finite is nobody's
+ *              neighbour and has none.
+ *   count(i)   the alive j != i for which N(i, j) holds.  Splats at identical positions are neighbours of one another.
+ * gs_renderer_edit_neighbour_counts writes min(count(i), cap) for every alive splat and 0xFFFFFFFF for every other one into counts_out
+ * (`count` words, which must be N) and changes nothing on the renderer.
+ * gs_renderer_edit_select_sparse: splat i is SPARSE if it is alive and count(i) < min_neighbours (so an alive splat with a non-finite position
+ * is sparse whenever min_neighbours > 0, and min_neighbours = 0 selects nothing).  subtract == 0: selected |= sparse; else selected &= ~sparse
+ * -- on the current selection, as gs_renderer_edit_select_surface.  No bit at or beyond N is ever set.  It makes the edit buffers if there
+ * are none, is a selection change to the edit history (undo and redo cover it) and keeps a highlighted selection's lanes in step.  The walk
+ * stops counting for a splat at min_neighbours (at cap): a dense core is cheap.
+ * Refused with GS_ERR_INVALID_ARGUMENT, nothing changed and nothing left allocated: a NULL argument, a lane, a radius that is not finite or
+ * outside [1e-15, 1e15], cap == 0, count != N.  A renderer without an alive splat is no error (all 0xFFFFFFFF; nothing selected).
+ * Both calls BLOCK, as the bake does: they wait for everything enqueued on the context (their sorts want the GPU to themselves), allocate
+ * transient buffers and free them before they return.  A sort whose bounded look-back spin expired: GS_ERR_SORT_TIMEOUT, selection unchanged. */
+int32_t gs_renderer_edit_neighbour_counts(gs_renderer* r, float radius, uint32_t cap, uint32_t* counts_out, size_t count);
+int32_t gs_renderer_edit_select_sparse(gs_renderer* r, float radius, uint32_t min_neighbours, int32_t subtract);
+
 /* ---- native importer (host code; no GPU needed, one optional GPU stage): GaussianSplatAssetCreator.CreateAsset minus the Unity asset database -- */
 /* InputSplatData (GaussianFileReader.cs:17-26) as separate arrays, in the PLY domain after ReorderSHs: */
 typedef struct gs_import_input {

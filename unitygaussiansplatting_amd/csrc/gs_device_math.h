@@ -2036,4 +2036,82 @@ GS_HD uint32_t HistRank(const uint32_t m[8], uint32_t t) {
     return r;
 }
 
+// ---- fixed-radius neighbour counts on a grid (gs_renderer_edit_neighbour_counts / _select_sparse; kernels in gs_neighbours.hip) ----
+// The predicate is fp32, operation by operation; the grid only decides which pairs are looked at, in fp64: a cell is radius (1 + 2^-10) wide, so two
+// splats the predicate joins lie at most one cell apart on every axis (the argument: section 4.17).  The listed splats -- alive, finite position -- are
+// sorted by cell key with x the lowest field: the cells (x-1 .. x+1, y, z) are one contiguous run of the sorted array, and a splat visits nine such runs.
+constexpr uint32_t kNeighbourCellMax = (1u << 21) - 1u;            // 21 bits per axis
+struct alignas(16) NeighbourRec { float x, y, z; uint32_t idx; };  // a listed splat in sorted order: its position and its index in the renderer
+
+// every comparison with NaN is false and inf - inf is NaN: a splat with a non-finite component is never listed
+GS_HD bool NeighbourFinite(V3 p) {
+    return (f2u(p.x) & 0x7f800000u) != 0x7f800000u && (f2u(p.y) & 0x7f800000u) != 0x7f800000u && (f2u(p.z) & 0x7f800000u) != 0x7f800000u;
+}
+GS_HD double NeighbourCellEdge(float radius) { return (double)radius * 1.0009765625; }      // 1 + 2^-10
+// p, origin finite, origin <= p, h > 0: the quotient is >= 0 and never NaN; the clamp is monotone
+GS_HD uint32_t NeighbourCellCoord(float p, float origin, double h) {
+    const double c = floor(((double)p - (double)origin) / h);
+    return c >= (double)kNeighbourCellMax ? kNeighbourCellMax : (c > 0.0 ? (uint32_t)c : 0u);
+}
+GS_HD unsigned long long NeighbourKey(uint32_t cx, uint32_t cy, uint32_t cz) {
+    return (unsigned long long)cx | ((unsigned long long)cy << 21) | ((unsigned long long)cz << 42);
+}
+GS_HD unsigned long long NeighbourKeyOf(V3 p, const float* origin, double h) {
+    return NeighbourKey(NeighbourCellCoord(p.x, origin[0], h), NeighbourCellCoord(p.y, origin[1], h), NeighbourCellCoord(p.z, origin[2], h));
+}
+// N(i, j): d2 = (dx dx + dy dy) + dz dz <= r2, the boundary included
+GS_HD bool NeighbourTest(const NeighbourRec& i, const NeighbourRec& j, float r2) {
+    const float dx = j.x - i.x, dy = j.y - i.y, dz = j.z - i.z;
+    const float d2 = (dx * dx + dy * dy) + dz * dz;
+    return d2 <= r2;
+}
+// the keys of the first and the last cell of the run (cx-1 .. cx+1, cy + dy, cz + dz); false: that row of cells lies outside the grid and is SKIPPED
+// (clamped, it would coincide with a row already visited and its splats would be counted twice).  On x, leaving out the cells outside is the clip.
+GS_HD bool NeighbourRun(unsigned long long key, int dy, int dz, unsigned long long& first, unsigned long long& last) {
+    const uint32_t cx = (uint32_t)key & kNeighbourCellMax, cy = (uint32_t)(key >> 21) & kNeighbourCellMax, cz = (uint32_t)(key >> 42) & kNeighbourCellMax;
+    const int y = (int)cy + dy, z = (int)cz + dz;
+    if (y < 0 || y > (int)kNeighbourCellMax || z < 0 || z > (int)kNeighbourCellMax) return false;
+    first = NeighbourKey(cx > 0u ? cx - 1u : 0u, (uint32_t)y, (uint32_t)z);
+    last = NeighbourKey(cx < kNeighbourCellMax ? cx + 1u : kNeighbourCellMax, (uint32_t)y, (uint32_t)z);
+    return true;
+}
+// first index in [lo, hi) whose key is >= k (orEqual) / > k (!orEqual); hi if there is none
+GS_HD uint32_t NeighbourBound(const unsigned long long* keys, uint32_t lo, uint32_t hi, unsigned long long k, bool orEqual) {
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        const unsigned long long v = keys[mid];
+        if (orEqual ? v < k : v <= k) lo = mid + 1u; else hi = mid;
+    }
+    return lo;
+}
+// first index in [a, m) whose key is > last, a being where the run starts: a run is a few splats long -- most are empty -- so the end is looked for
+// from a in doubling steps and only the last step is bisected (an empty run costs one load, not log2 m: the count kernel took 0.79 of its time at
+// 6.1 M splats)
+GS_HD uint32_t NeighbourRunEnd(const unsigned long long* keys, uint32_t a, uint32_t m, unsigned long long last) {
+    uint32_t lo = a, hi = a, step = 1u;
+    while (hi < m && keys[hi] <= last) { lo = hi + 1u; hi += step; step <<= 1; }       // every key below lo is <= last; keys[hi] > last, or hi >= m
+    return NeighbourBound(keys, lo, hi < m ? hi : m, last, false);
+}
+// min(count(i), limit) of the listed splat at sorted position i among the m listed ones: nine runs, each found by a binary search for its start and
+// NeighbourRunEnd and walked in order; the walk stops at `limit` and never counts the splat itself.  tests: += the predicates evaluated (a statistic)
+GS_HD uint32_t NeighbourCount(const unsigned long long* keys, const NeighbourRec* recs, uint32_t m, uint32_t i, float r2, uint32_t limit, uint32_t& tests) {
+    if (limit == 0u) return 0u;
+    const NeighbourRec me = recs[i];
+    const unsigned long long key = keys[i];
+    uint32_t count = 0u;
+    for (int dz = -1; dz <= 1; ++dz)
+        for (int dy = -1; dy <= 1; ++dy) {
+            unsigned long long first, last;
+            if (!NeighbourRun(key, dy, dz, first, last)) continue;
+            const uint32_t a = NeighbourBound(keys, 0u, m, first, true);
+            const uint32_t b = NeighbourRunEnd(keys, a, m, last);
+            for (uint32_t j = a; j < b; ++j) {
+                if (j == i) continue;
+                ++tests;
+                if (NeighbourTest(me, recs[j], r2) && ++count == limit) return count;
+            }
+        }
+    return count;
+}
+
 } // namespace gsm

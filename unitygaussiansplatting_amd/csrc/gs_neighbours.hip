@@ -1,0 +1,370 @@
+// gs_neighbours.hip -- the floater tool: for every alive splat, how many other alive splats lie within `radius` of it (gs_renderer_edit_neighbour_counts),
+// and the selection of those with fewer than `min_neighbours` (gs_renderer_edit_select_sparse).  No counterpart in the reference; the contract, the
+// grid argument and the measurements are DESIGN.md section 4.17, the arithmetic is gsm::Neighbour* (gs_device_math.h), which tests/neighbour_host_harness.cpp
+// runs on the host.
+//
+// One call, on the context's stream, everything transient and freed before it returns:
+//   1. nb_count + the scan + nb_list + nb_origin   the LIST: alive splats (index < N, not deleted, not cut -- export_alive, the test of every edit kernel)
+//                                                  whose position is finite, in index order, and the per-axis minimum of their positions, the grid's origin
+//   2. nb_keys + two stable Onesweep sorts         the 63-bit cell key of every listed splat, x lowest, sorted as the bake sorts its Morton codes: the low
+//                                                  word over 32 bits, then the gathered high word over 31
+//   3. nb_records                                  the sorted splats as 16-byte records (x, y, z, index) and their keys: what the walk streams
+//   4. nb_walk                                     one thread per listed splat in SORTED order -- the lanes of a wave then search for the same runs and walk
+//                                                  the same cache lines -- nine runs each (gsm::NeighbourCount: the start by bisection, the end by doubling
+//                                                  steps from it), stopping at the limit; one store per splat
+//   5. nb_counts_out / nb_apply                    by splat index, 256-thread workgroups like gs_edit.hip: the host's array, or the predicate as a word
+//                                                  through __ballot and a plain read-modify-write of the word a half-wave owns
+// No atomics (but the optional statistic of the timing script), no workgroup waits on another outside the sorts, no scratch, no LDS beyond the reductions'.
+#include <cmath>
+
+#include "gs_common.h"
+
+namespace gs {
+
+constexpr uint32_t kNbReduceThreads = 1024;
+constexpr uint32_t kNbNotAlive = 0xFFFFFFFFu;
+
+__device__ __forceinline__ float nb_wave_min(float v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = fminf(v, __shfl_xor(v, d));
+    return v;
+}
+
+// is splat idx listed?  (alive and every component of its position finite)
+__device__ __forceinline__ bool nb_listed(const gsm::AssetView& a, const gsm::EditView& e, uint32_t idx, uint32_t ci, gsm::V3& pos) {
+    bool cut;
+    return export_alive(a, e, idx, ci, pos, cut) && gsm::NeighbourFinite(pos);
+}
+
+// counts[c] = listed splats of chunk c
+__global__ __launch_bounds__(256) void nb_count_kernel(gsm::AssetView a, gsm::EditView e, uint32_t* __restrict__ counts) {
+    __shared__ uint32_t s_cnt[4];
+    const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
+    gsm::V3 pos;
+    const uint32_t c = (uint32_t)__popcll(__ballot(nb_listed(a, e, idx, blockIdx.x, pos)));
+    if ((threadIdx.x & 63u) == 0u) s_cnt[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0u) counts[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+}
+
+// list[base[chunk] + rank] = idx for the listed splats of chunk blockIdx.x; partial[chunk][0..2] = the minimum of their positions (+inf: none)
+__global__ __launch_bounds__(256) void nb_list_kernel(gsm::AssetView a, gsm::EditView e, const uint32_t* __restrict__ base, uint32_t* __restrict__ list,
+                                                      float* __restrict__ partial) {
+    __shared__ uint32_t s_cnt[4];
+    __shared__ float s_red[4][3];
+    const uint32_t idx = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    gsm::V3 pos;
+    const bool mine = nb_listed(a, e, idx, blockIdx.x, pos);
+    const unsigned long long bal = __ballot(mine);
+    const uint32_t slot = (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+    if (lane == 0u) s_cnt[wave] = (uint32_t)__popcll(bal);
+    const float inf = gsm::u2f(0x7f800000u);
+    const float p[3] = { pos.x, pos.y, pos.z };
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float mn = nb_wave_min(mine ? p[c] : inf);
+        if (lane == 0u) s_red[wave][c] = mn;
+    }
+    __syncthreads();
+    uint32_t first = base[blockIdx.x];
+    for (uint32_t w = 0; w < wave; ++w) first += s_cnt[w];
+    if (mine) list[first + slot] = idx;
+    if (threadIdx.x < 3u) partial[blockIdx.x * 3u + threadIdx.x] = fminf(fminf(s_red[0][threadIdx.x], s_red[1][threadIdx.x]), fminf(s_red[2][threadIdx.x], s_red[3][threadIdx.x]));
+}
+
+// origin[0..2] = the minimum over the partials; one workgroup
+__global__ __launch_bounds__(kNbReduceThreads) void nb_origin_kernel(const float* __restrict__ partial, uint32_t chunks, float* __restrict__ origin) {
+    __shared__ float s_red[kNbReduceThreads / 64][3];
+    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+    const float inf = gsm::u2f(0x7f800000u);
+    float v[3] = { inf, inf, inf };
+    for (uint32_t i = t; i < chunks; i += kNbReduceThreads) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = fminf(v[c], partial[i * 3u + c]);
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float mn = nb_wave_min(v[c]);
+        if (lane == 0u) s_red[wave][c] = mn;
+    }
+    __syncthreads();
+    if (t < 3u) {
+        float r = s_red[0][t];
+        for (uint32_t w = 1; w < kNbReduceThreads / 64; ++w) r = fminf(r, s_red[w][t]);
+        origin[t] = r;
+    }
+}
+
+// the cell key of listed splat j as two sort keys, and the identity payload
+__global__ __launch_bounds__(256) void nb_keys_kernel(gsm::AssetView a, const uint32_t* __restrict__ list, const float* __restrict__ origin, double h, uint32_t m,
+                                                      uint32_t* __restrict__ lo, uint32_t* __restrict__ hi, uint32_t* __restrict__ rank) {
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= m) return;
+    const uint32_t idx = list[j];
+    const unsigned long long key = gsm::NeighbourKeyOf(gsm::LoadSplatPosChunk(a, idx, idx >> 8), origin, h);
+    lo[j] = (uint32_t)key; hi[j] = (uint32_t)(key >> 32); rank[j] = j;
+}
+
+__global__ __launch_bounds__(256) void nb_gather_kernel(const uint32_t* __restrict__ hi, const uint32_t* __restrict__ rank, uint32_t m, uint32_t* __restrict__ out) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < m) out[i] = hi[rank[i]];
+}
+
+// sorted position i: the record and the key of the splat the two sorts put there
+__global__ __launch_bounds__(256) void nb_records_kernel(gsm::AssetView a, const uint32_t* __restrict__ list, const uint32_t* __restrict__ rank,
+                                                         const float* __restrict__ origin, double h, uint32_t m, gsm::NeighbourRec* __restrict__ recs,
+                                                         unsigned long long* __restrict__ keys) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= m) return;
+    const uint32_t idx = list[rank[i]];
+    const gsm::V3 p = gsm::LoadSplatPosChunk(a, idx, idx >> 8);
+    recs[i] = { p.x, p.y, p.z, idx };
+    keys[i] = gsm::NeighbourKeyOf(p, origin, h);
+}
+
+// counts[index of the splat at sorted position i] = min(count, limit); tests: null, or where every wave adds the predicates it evaluated
+__global__ __launch_bounds__(256) void nb_walk_kernel(const unsigned long long* __restrict__ keys, const gsm::NeighbourRec* __restrict__ recs, uint32_t m, float r2,
+                                                      uint32_t limit, uint32_t* __restrict__ counts, unsigned long long* __restrict__ tests) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    uint32_t mine = 0u;
+    if (i < m) counts[recs[i].idx] = gsm::NeighbourCount(keys, recs, m, i, r2, limit, mine);
+    if (tests) {
+        unsigned long long t = mine;
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) t += (unsigned long long)__shfl_xor((int)(uint32_t)t, d) | ((unsigned long long)__shfl_xor((int)(uint32_t)(t >> 32), d) << 32);
+        if ((threadIdx.x & 63u) == 0u && t) atomicAdd(tests, t);
+    }
+}
+
+// what the host gets: the count of an alive splat (0 for one that is not listed: its position is not finite), 0xFFFFFFFF for every other splat
+__global__ __launch_bounds__(256) void nb_counts_out_kernel(gsm::AssetView a, gsm::EditView e, uint32_t* __restrict__ counts) {
+    const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
+    if (idx >= a.n) return;
+    gsm::V3 pos; bool cut;
+    if (!export_alive(a, e, idx, blockIdx.x, pos, cut)) counts[idx] = kNbNotAlive;
+}
+
+// sparse = alive and count < minNeighbours; selected |= sparse (subtract: &= ~sparse).  The shape of gs_edit.hip: a wave owns two consecutive words
+__global__ __launch_bounds__(256) void nb_apply_kernel(gsm::AssetView a, gsm::EditView e, const uint32_t* __restrict__ counts, uint32_t minNeighbours,
+                                                       uint32_t* __restrict__ sel, uint32_t nWords, uint32_t subtract) {
+    const uint32_t idx = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u;
+    gsm::V3 pos; bool cut;
+    const bool sparse = export_alive(a, e, idx, blockIdx.x, pos, cut) && counts[idx] < minNeighbours;
+    const uint32_t word = (uint32_t)(__ballot(sparse) >> (lane & 32u));
+    const uint32_t w = idx >> 5;
+    if ((lane & 31u) == 0u && w < nWords && word) sel[w] = subtract ? (sel[w] & ~word) : (sel[w] | word);
+}
+
+// ---- host -----------------------------------------------------------------------------------------------------------------------------
+// everything a call holds: freed when it returns
+struct NeighbourRun {
+    DevBuf<uint32_t> chunkCounts, base, list, lo, hi, hi2, rank, counts;
+    DevBuf<float> partial, origin;
+    DevBuf<gsm::NeighbourRec> recs;
+    DevBuf<unsigned long long> keys, tests;
+    SortState sort;
+    DevBuf<SortControl> control;            // two blocks, one per sort: each has an error word of its own
+    uint32_t listed = 0;
+};
+
+// what scripts/neighbour_timing.py asks of a call besides its result: events around the stages (all recorded whenever the call succeeds), the
+// predicates the walk evaluated, the listed splats
+enum { kNbEvCount = 0, kNbEvScan, kNbEvList, kNbEvOrigin, kNbEvSorted, kNbEvRecords, kNbEvWalk, kNbEvApply, kNbEvDone, kNbEvents };
+struct NeighbourProbe { hipEvent_t ev[kNbEvents]; unsigned long long tests; uint32_t listed; };
+static hipError_t nb_mark(const NeighbourProbe* probe, int from, int to, hipStream_t st) {
+    if (!probe) return hipSuccess;
+    for (int k = from; k <= to; ++k) { const hipError_t e = hipEventRecord(probe->ev[k], st); if (e != hipSuccess) return e; }
+    return hipSuccess;
+}
+
+static int32_t nb_sort(gs_context* ctx, NeighbourRun& run, SortControl* control, uint32_t* keys, uint32_t m, uint32_t keyBits) {
+    const int passes = (int)((keyBits + 7u) / 8u);
+    const uint32_t lastMask = (1u << (keyBits - 8u * (uint32_t)(passes - 1))) - 1u;
+    GS_TRY(enqueue_histogram(ctx, ctx->stream, keys, m, nullptr, passes, lastMask, control, run.sort));
+    return enqueue_sort_passes(ctx, ctx->stream, run.sort, control, keys, run.rank, m, nullptr, passes, lastMask);
+}
+
+static const char* nb_radius_refusal(float radius) {
+    return (std::isfinite(radius) && radius >= 1.0e-15f && radius <= 1.0e15f) ? nullptr : "neighbours: radius must be finite and within [1e-15, 1e15]";
+}
+
+// steps 1 to 4 on the context's stream: run.counts[idx] = min(count(idx), limit) for the listed splats, 0 for every other index.  The stream has drained
+// when this returns GS_OK; the caller drains it otherwise
+static int32_t nb_enqueue(gs_renderer* r, float radius, uint32_t limit, NeighbourRun& run, const NeighbourProbe* probe) {
+    const bool stats = probe != nullptr;
+    gs_context* ctx = r->ctx;
+    hipStream_t st = ctx->stream;
+    const gsm::AssetView a = asset_view(r);
+    const gsm::EditView e = edit_view(r);
+    const uint32_t chunks = (r->n + 255u) / 256u;
+    GS_HIP(run.counts.alloc(((size_t)r->n + 16) * 4));
+    GS_HIP(hipMemsetAsync(run.counts, 0, (size_t)r->n * 4, st));
+    if (stats) {
+        GS_HIP(run.tests.alloc(8));
+        GS_HIP(hipMemsetAsync(run.tests, 0, 8, st));
+    }
+    if (r->n == 0u || limit == 0u) {
+        GS_HIP(nb_mark(probe, kNbEvCount, kNbEvWalk, st));
+        return hipStreamSynchronize(st) == hipSuccess ? GS_OK : fail(GS_ERR_HIP, "neighbours: the stream failed");
+    }
+    GS_HIP(run.chunkCounts.alloc((size_t)chunks * 4));
+    GS_HIP(run.base.alloc(((size_t)chunks + 1) * 4));
+    GS_HIP(nb_mark(probe, kNbEvCount, kNbEvCount, st));
+    hipLaunchKernelGGL(nb_count_kernel, dim3(chunks), dim3(256), 0, st, a, e, run.chunkCounts.get());
+    GS_HIP(hipGetLastError());
+    GS_TRY(enqueue_scan(st, run.chunkCounts, run.base, chunks));
+    GS_HIP(nb_mark(probe, kNbEvScan, kNbEvScan, st));
+    uint32_t m = 0;
+    GS_HIP(hipMemcpyAsync(&m, run.base.get() + chunks, 4, hipMemcpyDeviceToHost, st));
+    GS_HIP(hipStreamSynchronize(st));
+    run.listed = m;
+    if (m == 0u) {
+        GS_HIP(nb_mark(probe, kNbEvList, kNbEvWalk, st));
+        return GS_OK;
+    }
+    const uint32_t blocks = (m + 255u) / 256u;
+    GS_HIP(run.list.alloc(((size_t)m + 16) * 4));
+    GS_HIP(run.partial.alloc((size_t)chunks * 3 * 4));
+    GS_HIP(run.origin.alloc(3 * 4));
+    for (DevBuf<uint32_t>* b : { &run.lo, &run.hi, &run.hi2, &run.rank }) GS_HIP(b->alloc(((size_t)m + 16) * 4));
+    GS_HIP(run.recs.alloc((size_t)m * sizeof(gsm::NeighbourRec)));
+    GS_HIP(run.keys.alloc((size_t)m * 8));
+    GS_TRY(sort_state_create(ctx, run.sort, m, true));
+    GS_HIP(run.control.alloc(2 * sizeof(SortControl)));
+    const double h = gsm::NeighbourCellEdge(radius);
+    // 1. the list and the origin
+    GS_HIP(nb_mark(probe, kNbEvList, kNbEvList, st));
+    hipLaunchKernelGGL(nb_list_kernel, dim3(chunks), dim3(256), 0, st, a, e, (const uint32_t*)run.base.get(), run.list.get(), run.partial.get());
+    hipLaunchKernelGGL(nb_origin_kernel, dim3(1), dim3(kNbReduceThreads), 0, st, (const float*)run.partial.get(), chunks, run.origin.get());
+    GS_HIP(hipGetLastError());
+    GS_HIP(nb_mark(probe, kNbEvOrigin, kNbEvOrigin, st));
+    // 2. keys and sorts
+    hipLaunchKernelGGL(nb_keys_kernel, dim3(blocks), dim3(256), 0, st, a, (const uint32_t*)run.list.get(), (const float*)run.origin.get(), h, m, run.lo.get(), run.hi.get(),
+                       run.rank.get());
+    GS_HIP(hipGetLastError());
+    GS_TRY(nb_sort(ctx, run, run.control.get(), run.lo, m, 32u));
+    hipLaunchKernelGGL(nb_gather_kernel, dim3(blocks), dim3(256), 0, st, (const uint32_t*)run.hi.get(), (const uint32_t*)run.rank.get(), m, run.hi2.get());
+    GS_HIP(hipGetLastError());
+    GS_TRY(nb_sort(ctx, run, run.control.get() + 1, run.hi2, m, 31u));
+    GS_HIP(nb_mark(probe, kNbEvSorted, kNbEvSorted, st));
+    // 3. the records
+    hipLaunchKernelGGL(nb_records_kernel, dim3(blocks), dim3(256), 0, st, a, (const uint32_t*)run.list.get(), (const uint32_t*)run.rank.get(), (const float*)run.origin.get(),
+                       h, m, run.recs.get(), run.keys.get());
+    GS_HIP(hipGetLastError());
+    GS_HIP(nb_mark(probe, kNbEvRecords, kNbEvRecords, st));
+    // 4. the walk
+    hipLaunchKernelGGL(nb_walk_kernel, dim3(blocks), dim3(256), 0, st, (const unsigned long long*)run.keys.get(), (const gsm::NeighbourRec*)run.recs.get(), m,
+                       radius * radius, limit, run.counts.get(), stats ? run.tests.get() : (unsigned long long*)nullptr);
+    GS_HIP(hipGetLastError());
+    GS_HIP(nb_mark(probe, kNbEvWalk, kNbEvWalk, st));
+    // the sorts' error words, before anything of the renderer's is touched
+    uint32_t err[2] = { 0u, 0u };
+    GS_HIP(hipMemcpyAsync(&err[0], &run.control.get()[0].error, 4, hipMemcpyDeviceToHost, st));
+    GS_HIP(hipMemcpyAsync(&err[1], &run.control.get()[1].error, 4, hipMemcpyDeviceToHost, st));
+    GS_HIP(hipStreamSynchronize(st));
+    if (err[0] | err[1]) return fail(GS_ERR_SORT_TIMEOUT, "neighbours: a bounded look-back spin expired");
+    return GS_OK;
+}
+
+// the checks both entry points share, and what they do before the first launch: after everything already enqueued, the lanes' frames included -- the sorts
+// assume their workgroups have the GPU to themselves, as the bake's do
+static int32_t nb_begin(gs_renderer* r, float radius) {
+    if (r->laneOf) return fail(GS_ERR_INVALID_ARGUMENT, "a lane holds no edit state: edit its owner");
+    if (const char* why = nb_radius_refusal(radius)) return fail(GS_ERR_INVALID_ARGUMENT, why);
+    GS_HIP(hipSetDevice(r->ctx->device));
+    return gs_context_synchronize(r->ctx);
+}
+
+static int32_t nb_counts_impl(gs_renderer* r, float radius, uint32_t cap, uint32_t* counts_out, size_t count, NeighbourProbe* probe) {
+    if (!r || !counts_out) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
+    if (cap == 0u) return fail(GS_ERR_INVALID_ARGUMENT, "neighbour_counts: cap must be at least 1");
+    if (count != (size_t)r->n) return fail(GS_ERR_INVALID_ARGUMENT, "neighbour_counts: count must be the renderer's splat count");
+    GS_TRY(nb_begin(r, radius));
+    hipStream_t st = r->ctx->stream;
+    NeighbourRun run;
+    int32_t rc = nb_enqueue(r, radius, cap, run, probe);
+    if (rc == GS_OK) {
+        rc = [&]() -> int32_t {
+            GS_HIP(nb_mark(probe, kNbEvApply, kNbEvApply, st));
+            if (r->n) hipLaunchKernelGGL(nb_counts_out_kernel, dim3((r->n + 255u) / 256u), dim3(256), 0, st, asset_view(r), edit_view(r), run.counts.get());
+            GS_HIP(hipGetLastError());
+            GS_HIP(nb_mark(probe, kNbEvDone, kNbEvDone, st));
+            if (r->n) GS_HIP(hipMemcpyAsync(counts_out, run.counts.get(), (size_t)r->n * 4, hipMemcpyDeviceToHost, st));
+            if (probe) GS_HIP(hipMemcpyAsync(&probe->tests, run.tests.get(), 8, hipMemcpyDeviceToHost, st));
+            return GS_OK;
+        }();
+    }
+    const hipError_t hs = hipStreamSynchronize(st);                // whatever failed: nothing in flight outlives the buffers
+    if (rc == GS_OK && hs != hipSuccess) rc = fail_hip(hs, "neighbour_counts", __FILE__, __LINE__);
+    if (probe) probe->listed = run.listed;
+    return rc;
+}
+
+static int32_t nb_select_impl(gs_renderer* r, float radius, uint32_t min_neighbours, int32_t subtract, NeighbourProbe* probe) {
+    if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "renderer is null");
+    GS_TRY(nb_begin(r, radius));
+    GS_TRY(edit_ensure(r));
+    hipStream_t st = r->ctx->stream;
+    NeighbourRun run;
+    int32_t rc = nb_enqueue(r, radius, min_neighbours, run, probe);
+    if (rc == GS_OK) {
+        rc = [&]() -> int32_t {
+            hist_mutated(r, true);
+            GS_HIP(nb_mark(probe, kNbEvApply, kNbEvApply, st));
+            if (r->n && min_neighbours) {
+                hipLaunchKernelGGL(nb_apply_kernel, dim3((r->n + 255u) / 256u), dim3(256), 0, st, asset_view(r), edit_view(r), (const uint32_t*)run.counts.get(),
+                                   min_neighbours, r->editSelected.get(), (uint32_t)bit_words(r->n), subtract ? 1u : 0u);
+                GS_HIP(hipGetLastError());
+            }
+            GS_HIP(nb_mark(probe, kNbEvDone, kNbEvDone, st));
+            if (probe) GS_HIP(hipMemcpyAsync(&probe->tests, run.tests.get(), 8, hipMemcpyDeviceToHost, st));
+            return edit_selected_to_lanes(r);
+        }();
+    }
+    const hipError_t hs = hipStreamSynchronize(st);                // whatever failed: nothing in flight outlives the buffers
+    if (rc == GS_OK && hs != hipSuccess) rc = fail_hip(hs, "select_sparse", __FILE__, __LINE__);
+    if (probe) probe->listed = run.listed;
+    return rc;
+}
+
+} // namespace gs
+
+using namespace gs;
+
+extern "C" {
+
+int32_t gs_renderer_edit_neighbour_counts(gs_renderer* r, float radius, uint32_t cap, uint32_t* counts_out, size_t count) {
+    return nb_counts_impl(r, radius, cap, counts_out, count, nullptr);
+}
+
+int32_t gs_renderer_edit_select_sparse(gs_renderer* r, float radius, uint32_t min_neighbours, int32_t subtract) {
+    return nb_select_impl(r, radius, min_neighbours, subtract, nullptr);
+}
+
+// A measurement aid of scripts/neighbour_timing.py, which binds it itself: not declared in gsplat_c.h, not part of the ABI.  One whole call -- select != 0:
+// gs_renderer_edit_select_sparse(radius, limit, 0), else gs_renderer_edit_neighbour_counts(radius, limit) into counts_out (N words) -- with events
+// inside it: ms[0..4] = GPU milliseconds of the list + origin (count, scan, list, fold; the host's readback of the list's length between them not
+// included), the keys + the two sorts, the records, the walk, the last kernel; *tests = the predicates the walk evaluated; *listed = the listed splats.
+__attribute__((visibility("default"))) int32_t gs_neighbour_stage_times_for_scripts(gs_renderer* r, float radius, uint32_t limit, int32_t select, uint32_t* counts_out,
+                                                                                   float ms[5], uint64_t* tests, uint32_t* listed) {
+    if (!r || !ms || !tests || !listed) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
+    GS_HIP(hipSetDevice(r->ctx->device));
+    Event owned[kNbEvents];
+    NeighbourProbe probe = {};
+    for (int k = 0; k < kNbEvents; ++k) { GS_HIP(owned[k].create(hipEventDefault)); probe.ev[k] = owned[k]; }
+    if (select) GS_TRY(nb_select_impl(r, radius, limit, 0, &probe));
+    else GS_TRY(nb_counts_impl(r, radius, limit, counts_out, r->n, &probe));
+    float head = 0.0f;
+    GS_HIP(hipEventElapsedTime(&head, probe.ev[kNbEvCount], probe.ev[kNbEvScan]));
+    GS_HIP(hipEventElapsedTime(&ms[0], probe.ev[kNbEvList], probe.ev[kNbEvOrigin]));
+    ms[0] += head;
+    GS_HIP(hipEventElapsedTime(&ms[1], probe.ev[kNbEvOrigin], probe.ev[kNbEvSorted]));
+    GS_HIP(hipEventElapsedTime(&ms[2], probe.ev[kNbEvSorted], probe.ev[kNbEvRecords]));
+    GS_HIP(hipEventElapsedTime(&ms[3], probe.ev[kNbEvRecords], probe.ev[kNbEvWalk]));
+    GS_HIP(hipEventElapsedTime(&ms[4], probe.ev[kNbEvApply], probe.ev[kNbEvDone]));
+    *tests = probe.tests;
+    *listed = probe.listed;
+    return GS_OK;
+}
+
+} // extern "C"

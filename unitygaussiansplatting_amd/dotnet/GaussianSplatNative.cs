@@ -185,6 +185,9 @@ namespace GaussianSplatting.Runtime
         [DllImport(Lib)] public static extern int gs_target_pick_device_ptr(IntPtr target, out IntPtr pickDev);
         [DllImport(Lib)] public static extern int gs_renderer_set_pick_tag(IntPtr renderer, uint tag);
         [DllImport(Lib)] public static extern int gs_renderer_edit_select_surface(IntPtr renderer, IntPtr target, int x0, int y0, int x1, int y1, int subtract);
+        // floaters: min(count, cap) of the alive splats within radius (object space) of every alive splat, 0xFFFFFFFF for the others; and the selection of those with fewer than minNeighbours.  Both block
+        [DllImport(Lib)] public static extern int gs_renderer_edit_neighbour_counts(IntPtr renderer, float radius, uint cap, [Out] uint[] countsOut, UIntPtr count);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_select_sparse(IntPtr renderer, float radius, uint minNeighbours, int subtract);
 
         // native importer (host code): GaussianSplatAssetCreator.CreateAsset without the asset database
         [StructLayout(LayoutKind.Sequential)]

@@ -552,6 +552,24 @@ class GaussianSplatRenderer:
         check(_lib.lib().gs_renderer_edit_select_surface(self._r_h, target._h, x0, y0, x1, y1, int(bool(subtract))), "gs_renderer_edit_select_surface")
         self.UpdateEditCountsAndBounds()
 
+    def EditNeighbourCounts(self, radius: float, cap: int = 65535) -> np.ndarray:
+        """For every alive splat -- not deleted, not cut -- min(cap, the other alive splats within `radius` of it), boundary included; 0xFFFFFFFF for a
+        splat that is not alive.  `radius` is in object space, the space of the positions.  What an editor draws a histogram of before it picks the
+        threshold of EditSelectSparse (gs_renderer_edit_neighbour_counts).  Changes nothing; blocks."""
+        self.UpdateCutoutsBuffer()
+        out = np.zeros(self.m_SplatCount, np.uint32)
+        check(_lib.lib().gs_renderer_edit_neighbour_counts(self._r_h, float(radius), int(cap), out.ctypes.data, len(out)), "gs_renderer_edit_neighbour_counts")
+        return out
+
+    def EditSelectSparse(self, radius: float, minNeighbours: int, subtract: bool = False) -> None:
+        """Select the floaters: every alive splat with fewer than minNeighbours other alive splats within `radius` (object space) is added to the
+        selection, or with subtract removed from it (gs_renderer_edit_select_sparse).  Blocks."""
+        if not self.EnsureEditingBuffers():
+            return
+        self.UpdateCutoutsBuffer()
+        check(_lib.lib().gs_renderer_edit_select_sparse(self._r_h, float(radius), int(minNeighbours), int(bool(subtract))), "gs_renderer_edit_select_sparse")
+        self.UpdateEditCountsAndBounds()
+
     def EditDeleteSelected(self) -> None:           # :896-904
         if not self.EnsureEditingBuffers():
             return
