@@ -669,6 +669,31 @@ int32_t gs_renderer_edit_select_surface(gs_renderer* r, gs_target* t, int32_t x0
 int32_t gs_renderer_edit_neighbour_counts(gs_renderer* r, float radius, uint32_t cap, uint32_t* counts_out, size_t count);
 int32_t gs_renderer_edit_select_sparse(gs_renderer* r, float radius, uint32_t min_neighbours, int32_t subtract);
 
+/* ---- islands: the connected components of the neighbour graph, on the GPU  (additions to ABI 9) ---------------------------------
+ * A clump of floaters has plenty of neighbours inside itself: no min_neighbours above selects it.  It is a SMALL CONNECTED COMPONENT of
+ * the graph whose vertices are the alive splats and whose edges are N(i, j); a whole object is a large one.  ALIVE, POSITIONS, N(i, j)
+ * and the radius refusals are the floater block's, word for word; N is symmetric in fp32.
+ *   COMPONENT  a class of the transitive closure of N over the alive splats.  An alive splat whose position is not finite has no edges
+ *              and is a component of its own.
+ *   label(i)   the smallest splat index in i's component.
+ *   size(i)    the number of splats in i's component.
+ * Both are unique whatever order the GPU links in.
+ * gs_renderer_edit_components writes label(i) into labels_out and size(i) into sizes_out for every alive splat, 0xFFFFFFFF and 0 for
+ * every other one (`count` words each, which must be N; either pointer may be NULL, not both) and changes nothing on the renderer.
+ * gs_renderer_edit_select_islands: splat i is an ISLAND if it is alive and size(i) < min_size.  subtract == 0: selected |= island; else
+ * selected &= ~island -- on the current selection.  min_size 0 or 1 selects nothing and is no error (as min_neighbours == 0 above);
+ * min_size 2 sets exactly the words gs_renderer_edit_select_sparse(radius, 1) sets.
+ * gs_renderer_edit_grow_selection: a SEED is an alive splat with index < N whose selected bit is set; every alive splat of a component
+ * that holds a seed is added to the selection.  It never clears a bit and never sets one at or beyond N; an empty selection stays empty.
+ * Both selecting calls make the edit buffers if there are none, are one selection change to the edit history (undo and redo cover them)
+ * and keep a highlighted selection's lanes in step.
+ * Refused with GS_ERR_INVALID_ARGUMENT, nothing changed and nothing left allocated: a NULL renderer, both outputs NULL, a lane, a radius
+ * that is not finite or outside [1e-15, 1e15], count != N.  A renderer without an alive splat is no error.
+ * All three calls BLOCK exactly as the two above do; a sort whose bounded look-back spin expired: GS_ERR_SORT_TIMEOUT, selection unchanged. */
+int32_t gs_renderer_edit_components(gs_renderer* r, float radius, uint32_t* labels_out, uint32_t* sizes_out, size_t count);
+int32_t gs_renderer_edit_select_islands(gs_renderer* r, float radius, uint32_t min_size, int32_t subtract);
+int32_t gs_renderer_edit_grow_selection(gs_renderer* r, float radius);
+
 /* ---- native importer (host code; no GPU needed, one optional GPU stage): GaussianSplatAssetCreator.CreateAsset minus the Unity asset database -- */
 /* InputSplatData (GaussianFileReader.cs:17-26) as separate arrays, in the PLY domain after ReorderSHs: */
 typedef struct gs_import_input {

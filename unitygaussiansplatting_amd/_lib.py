@@ -130,6 +130,9 @@ SIGNATURES = {
     "gs_renderer_edit_select_surface": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "gs_renderer_edit_neighbour_counts": (C.c_int32, [_P, C.c_float, C.c_uint32, _P, C.c_size_t]),
     "gs_renderer_edit_select_sparse": (C.c_int32, [_P, C.c_float, C.c_uint32, C.c_int32]),
+    "gs_renderer_edit_components": (C.c_int32, [_P, C.c_float, _P, _P, C.c_size_t]),
+    "gs_renderer_edit_select_islands": (C.c_int32, [_P, C.c_float, C.c_uint32, C.c_int32]),
+    "gs_renderer_edit_grow_selection": (C.c_int32, [_P, C.c_float]),
     "gs_import_blob_sizes": (C.c_int32, [C.c_uint32, C.POINTER(gs_import_formats), C.c_uint64 * 5]),
     "gs_import_encode": (C.c_int32, [C.POINTER(gs_import_input), C.POINTER(gs_import_formats), C.c_void_p * 5, C.c_uint64 * 5,
                                       C.POINTER(C.c_float), C.POINTER(C.c_float)]),

@@ -2113,5 +2113,26 @@ GS_HD uint32_t NeighbourCount(const unsigned long long* keys, const NeighbourRec
         }
     return count;
 }
+// edge(j) for every sorted position j < i with N(i, j): the edges of the neighbour graph, each handed out once, at its later end (N is symmetric in
+// fp32: xj - xi is exactly -(xi - xj)).  The nine runs of NeighbourCount, rows outside the grid skipped; the sorted keys ascend, so a run that starts
+// at or beyond i holds no j < i and a run is walked up to i at most
+template <class Edge>
+GS_HD void NeighbourForEach(const unsigned long long* keys, const NeighbourRec* recs, uint32_t m, uint32_t i, float r2, Edge&& edge) {
+    const NeighbourRec me = recs[i];
+    const unsigned long long key = keys[i];
+    for (int dz = -1; dz <= 1; ++dz)
+        for (int dy = -1; dy <= 1; ++dy) {
+            unsigned long long first, last;
+            if (!NeighbourRun(key, dy, dz, first, last)) continue;
+            if (first > key) continue;                             // every key of the run is above this splat's: it lies behind i
+            const uint32_t a = NeighbourBound(keys, 0u, m, first, true);
+            if (a >= i) continue;
+            const uint32_t b = NeighbourRunEnd(keys, a, m, last);
+            for (uint32_t j = a; j < b; ++j) {
+                if (j >= i) break;
+                if (NeighbourTest(me, recs[j], r2)) edge(j);
+            }
+        }
+}
 
 } // namespace gsm

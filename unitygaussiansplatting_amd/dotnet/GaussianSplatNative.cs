@@ -188,6 +188,10 @@ namespace GaussianSplatting.Runtime
         // floaters: min(count, cap) of the alive splats within radius (object space) of every alive splat, 0xFFFFFFFF for the others; and the selection of those with fewer than minNeighbours.  Both block
         [DllImport(Lib)] public static extern int gs_renderer_edit_neighbour_counts(IntPtr renderer, float radius, uint cap, [Out] uint[] countsOut, UIntPtr count);
         [DllImport(Lib)] public static extern int gs_renderer_edit_select_sparse(IntPtr renderer, float radius, uint minNeighbours, int subtract);
+        // islands: the connected components of the neighbour graph at that radius -- per alive splat the smallest index and the size of its component (0xFFFFFFFF and 0 for the others; either array may be null); the selection of the components smaller than minSize; and the selection grown to every component that holds a selected splat.  All block
+        [DllImport(Lib)] public static extern int gs_renderer_edit_components(IntPtr renderer, float radius, [Out] uint[] labelsOut, [Out] uint[] sizesOut, UIntPtr count);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_select_islands(IntPtr renderer, float radius, uint minSize, int subtract);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_grow_selection(IntPtr renderer, float radius);
 
         // native importer (host code): GaussianSplatAssetCreator.CreateAsset without the asset database
         [StructLayout(LayoutKind.Sequential)]

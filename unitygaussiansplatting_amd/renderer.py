@@ -570,6 +570,33 @@ class GaussianSplatRenderer:
         check(_lib.lib().gs_renderer_edit_select_sparse(self._r_h, float(radius), int(minNeighbours), int(bool(subtract))), "gs_renderer_edit_select_sparse")
         self.UpdateEditCountsAndBounds()
 
+    def EditComponents(self, radius: float):
+        """The connected components of the graph that joins two alive splats within `radius` (object space) of each other: (labels, sizes), per alive
+        splat the smallest splat index of its component and the number of splats in it; 0xFFFFFFFF and 0 for a splat that is not alive
+        (gs_renderer_edit_components).  Changes nothing; blocks."""
+        self.UpdateCutoutsBuffer()
+        labels, sizes = np.zeros(self.m_SplatCount, np.uint32), np.zeros(self.m_SplatCount, np.uint32)
+        check(_lib.lib().gs_renderer_edit_components(self._r_h, float(radius), labels.ctypes.data, sizes.ctypes.data, len(labels)), "gs_renderer_edit_components")
+        return labels, sizes
+
+    def EditSelectIslands(self, radius: float, minSize: int, subtract: bool = False) -> None:
+        """Select the clumps: every alive splat whose component (EditComponents) has fewer than minSize splats is added to the selection, or with
+        subtract removed from it (gs_renderer_edit_select_islands).  Blocks."""
+        if not self.EnsureEditingBuffers():
+            return
+        self.UpdateCutoutsBuffer()
+        check(_lib.lib().gs_renderer_edit_select_islands(self._r_h, float(radius), int(minSize), int(bool(subtract))), "gs_renderer_edit_select_islands")
+        self.UpdateEditCountsAndBounds()
+
+    def EditGrowSelection(self, radius: float) -> None:
+        """Click, then grow: every alive splat connected to a selected alive splat (through splats within `radius` of each other) joins the selection
+        (gs_renderer_edit_grow_selection).  Blocks."""
+        if not self.EnsureEditingBuffers():
+            return
+        self.UpdateCutoutsBuffer()
+        check(_lib.lib().gs_renderer_edit_grow_selection(self._r_h, float(radius)), "gs_renderer_edit_grow_selection")
+        self.UpdateEditCountsAndBounds()
+
     def EditDeleteSelected(self) -> None:           # :896-904
         if not self.EnsureEditingBuffers():
             return
