@@ -694,6 +694,71 @@ int32_t gs_renderer_edit_components(gs_renderer* r, float radius, uint32_t* labe
 int32_t gs_renderer_edit_select_islands(gs_renderer* r, float radius, uint32_t min_size, int32_t subtract);
 int32_t gs_renderer_edit_grow_selection(gs_renderer* r, float radius);
 
+/* ---- select by attribute: opacity, size, position and colour ranges, and the numbers a histogram panel shows  (additions to ABI 9) ----
+ * The tools above select by where a splat is or what is seen; these select by what a splat IS.  The contract, operation by operation
+ * (DESIGN.md section 4.19); every result is an exact integer or an exact float bit pattern:
+ *   ALIVE      a splat whose index is < N, that is not deleted and not cut by the renderer's current cutouts (the floater block's definition).
+ *   FIELDS     LoadSplatData's decoded fields of the renderer's CURRENT blobs, any preset (the private copies where a transform or a merge
+ *              made them): the object-space position p; the linear scale s, after the chunk de-normalisation and the three squarings; the
+ *              linear opacity o, after InvSquareCentered01; the DC colour c, the de-normalised texel rgb.
+ *   value      fp32 throughout, nothing fused, denormals kept, every comparison with NaN false:
+ *                GS_ATTR_OPACITY    o
+ *                GS_ATTR_SCALE_MAX  fmaxf(fmaxf(s.x, s.y), s.z)      GS_ATTR_SCALE_MIN  fminf(fminf(s.x, s.y), s.z)
+ *                                   (a NaN operand is ignored; of +0 and -0 the first operand is returned)
+ *                GS_ATTR_VOLUME     (s.x * s.y) * s.z
+ *                GS_ATTR_POS_X, _Y, _Z   p.x, p.y, p.z
+ *                GS_ATTR_DIST2      dx = p.x - q.x, dy, dz likewise; (dx dx + dy dy) + dz dz -- the sphere tool, N(i, j)'s d2 form.  q = point,
+ *                                   in object space: read for this attribute only, where it must be non-NULL and finite; otherwise ignored
+ *                GS_ATTR_COLOR_R, _G, _B   c.x, c.y, c.z
+ *                GS_ATTR_LUMA       (0.299f c.x + 0.587f c.y) + 0.114f c.z: three products and two sums, each rounded
+ *              The sign and payload of a NaN value carry no meaning.
+ *   KEY        FloatToSortableUint of the value (the bits with the sign bit flipped, or all of them for a negative value): a total order, -0 before +0.
+ *   SCOPE      GS_SCOPE_ALIVE: the alive splats.  GS_SCOPE_SELECTED: those of them whose selected bit is set (index < N: the tail bits that
+ *              select-all sets beyond N never count); empty for a renderer without edit buffers.
+ * gs_renderer_edit_attribute_values writes the value's bits for every alive splat and the word 0xFFFFFFFF for every other one into values_out
+ * (`count` floats, which must be N).  Changes nothing; blocks.
+ * gs_renderer_edit_select_range: splat i is IN if it is alive and lo <= v && v <= hi.  subtract == 0: selected |= in; else selected &= ~in --
+ * on the current selection.  lo = -inf and hi = +inf are allowed; lo > hi selects nothing and is no error.  No bit at or beyond N is ever
+ * set.  It makes the edit buffers if there are none, is one selection change to the edit history (undo and redo cover it), keeps a
+ * highlighted selection's lanes in step, needs no sort and is asynchronous on the context's stream, like gs_renderer_edit_update_selection.
+ * gs_renderer_edit_attribute_stats: members = the size of the scope, nans = its members whose value is NaN, vmin / vmax = the values that
+ * are not NaN with the smallest / largest KEY; +inf / -inf if there is none.  Blocks.
+ * gs_renderer_edit_attribute_histogram: hist_out takes bins + 3 words (`count` must be that).  With w = hi - lo and s = (float) bins / w, both
+ * in fp32 and computed once: a NaN member is counted in hist[bins + 2], one with v < lo in hist[bins], one with v > hi in hist[bins + 1], every
+ * other in hist[min(bins - 1, (uint32_t) ((v - lo) * s))] -- one subtraction and one product, each rounded, then truncation.  The words sum
+ * to the scope's members.  Refused unless 1 <= bins <= 4096, lo and hi are finite, lo < hi and w and s are finite.  Blocks.
+ * gs_renderer_edit_attribute_ranks: the POPULATION is the scope's members whose value is not NaN; *population is their number.  Their KEYs
+ * sorted ascending (unique: keys alone), values_out[k] is the value at position ranks[k], the word 0xFFFFFFFF where ranks[k] >= population.
+ * rank_count <= 4096; rank_count == 0 with NULL arrays returns the population alone.  It BLOCKS exactly as the floater calls do (it waits
+ * for the context, takes transient buffers and frees them before it returns); a sort whose bounded look-back spin expired:
+ * GS_ERR_SORT_TIMEOUT, nothing written.
+ * All five are refused with GS_ERR_INVALID_ARGUMENT, nothing changed and nothing left allocated: a NULL renderer or a NULL required output,
+ * a lane, an unknown attribute or scope, a wrong count, a NaN lo or hi, a NULL or non-finite point for GS_ATTR_DIST2.  A renderer without an
+ * alive splat is no error. */
+typedef enum gs_splat_attribute {
+    GS_ATTR_OPACITY = 0,
+    GS_ATTR_SCALE_MAX = 1,
+    GS_ATTR_SCALE_MIN = 2,
+    GS_ATTR_VOLUME = 3,
+    GS_ATTR_POS_X = 4,
+    GS_ATTR_POS_Y = 5,
+    GS_ATTR_POS_Z = 6,
+    GS_ATTR_DIST2 = 7,
+    GS_ATTR_COLOR_R = 8,
+    GS_ATTR_COLOR_G = 9,
+    GS_ATTR_COLOR_B = 10,
+    GS_ATTR_LUMA = 11
+} gs_splat_attribute;
+typedef enum gs_attribute_scope { GS_SCOPE_ALIVE = 0, GS_SCOPE_SELECTED = 1 } gs_attribute_scope;
+typedef struct gs_attribute_stats { uint32_t members, nans; float vmin, vmax; } gs_attribute_stats;
+int32_t gs_renderer_edit_attribute_values(gs_renderer* r, int32_t attr, const float point[3], float* values_out, size_t count);
+int32_t gs_renderer_edit_select_range(gs_renderer* r, int32_t attr, const float point[3], float lo, float hi, int32_t subtract);
+int32_t gs_renderer_edit_attribute_stats(gs_renderer* r, int32_t attr, const float point[3], int32_t scope, gs_attribute_stats* out);
+int32_t gs_renderer_edit_attribute_histogram(gs_renderer* r, int32_t attr, const float point[3], int32_t scope, float lo, float hi, uint32_t bins,
+                                             uint32_t* hist_out, size_t count);
+int32_t gs_renderer_edit_attribute_ranks(gs_renderer* r, int32_t attr, const float point[3], int32_t scope, const uint32_t* ranks, uint32_t rank_count,
+                                         float* values_out, uint32_t* population);
+
 /* ---- native importer (host code; no GPU needed, one optional GPU stage): GaussianSplatAssetCreator.CreateAsset minus the Unity asset database -- */
 /* InputSplatData (GaussianFileReader.cs:17-26) as separate arrays, in the PLY domain after ReorderSHs: */
 typedef struct gs_import_input {

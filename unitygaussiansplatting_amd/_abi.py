@@ -58,6 +58,15 @@ class gs_pick_record(C.Structure):       # one pixel of a target's pick output (
 
 
 GS_PICK_NO_SPLAT = 0xFFFFFFFF
+
+
+class gs_attribute_stats(C.Structure):   # gs_renderer_edit_attribute_stats: the scope's size, its NaN values, the non-NaN values of smallest / largest key
+    _fields_ = [("members", C.c_uint32), ("nans", C.c_uint32), ("vmin", C.c_float), ("vmax", C.c_float)]
+
+
+GS_SCOPE_ALIVE = 0
+GS_SCOPE_SELECTED = 1
+GS_ATTR_NOT_ALIVE = 0xFFFFFFFF           # the word gs_renderer_edit_attribute_values / _ranks write where there is no value
 # gs_target_download_pick as a structured numpy array
 PICK_DTYPE = [("depth", "<f4"), ("splat", "<u4"), ("tag", "<u4"), ("zero", "<u4")]
 

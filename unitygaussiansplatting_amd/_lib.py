@@ -6,7 +6,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-from ._abi import (gs_asset_desc, gs_copy_params, gs_cutout, gs_edit_history_info, gs_edit_info, gs_export_params, gs_frame_params, gs_frame_stats, gs_import_formats, gs_import_input,
+from ._abi import (gs_asset_desc, gs_attribute_stats, gs_copy_params, gs_cutout, gs_edit_history_info, gs_edit_info, gs_export_params, gs_frame_params, gs_frame_stats, gs_import_formats, gs_import_input,
                    gs_pick_record, gs_splat_file_info, gs_spz_params, gs_stage_times)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -133,6 +133,11 @@ SIGNATURES = {
     "gs_renderer_edit_components": (C.c_int32, [_P, C.c_float, _P, _P, C.c_size_t]),
     "gs_renderer_edit_select_islands": (C.c_int32, [_P, C.c_float, C.c_uint32, C.c_int32]),
     "gs_renderer_edit_grow_selection": (C.c_int32, [_P, C.c_float]),
+    "gs_renderer_edit_attribute_values": (C.c_int32, [_P, C.c_int32, _P, _P, C.c_size_t]),
+    "gs_renderer_edit_select_range": (C.c_int32, [_P, C.c_int32, _P, C.c_float, C.c_float, C.c_int32]),
+    "gs_renderer_edit_attribute_stats": (C.c_int32, [_P, C.c_int32, _P, C.c_int32, C.POINTER(gs_attribute_stats)]),
+    "gs_renderer_edit_attribute_histogram": (C.c_int32, [_P, C.c_int32, _P, C.c_int32, C.c_float, C.c_float, C.c_uint32, _P, C.c_size_t]),
+    "gs_renderer_edit_attribute_ranks": (C.c_int32, [_P, C.c_int32, _P, C.c_int32, _P, C.c_uint32, _P, C.POINTER(C.c_uint32)]),
     "gs_import_blob_sizes": (C.c_int32, [C.c_uint32, C.POINTER(gs_import_formats), C.c_uint64 * 5]),
     "gs_import_encode": (C.c_int32, [C.POINTER(gs_import_input), C.POINTER(gs_import_formats), C.c_void_p * 5, C.c_uint64 * 5,
                                       C.POINTER(C.c_float), C.POINTER(C.c_float)]),

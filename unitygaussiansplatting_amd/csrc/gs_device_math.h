@@ -2135,4 +2135,80 @@ GS_HD void NeighbourForEach(const unsigned long long* keys, const NeighbourRec* 
         }
 }
 
+// ---- selection by attribute (gs_renderer_edit_attribute_* / _select_range; kernels in gs_attributes.hip) -----------------------
+// One fp32 value per splat from LoadSplatData's decoded fields, operation by operation, nothing fused; tests/attribute_host_harness.cpp runs every
+// function below on the host.  The attributes fall into four CLASSES by the bytes they need: a kernel is built per class and loads nothing else.
+enum { kAttrOpacity = 0, kAttrScaleMax = 1, kAttrScaleMin = 2, kAttrVolume = 3, kAttrPosX = 4, kAttrPosY = 5, kAttrPosZ = 6, kAttrDist2 = 7,
+       kAttrColorR = 8, kAttrColorG = 9, kAttrColorB = 10, kAttrLuma = 11, kAttrCount = 12 };      // gs_splat_attribute
+enum { kAttrClassPos = 0, kAttrClassScale = 1, kAttrClassOpacity = 2, kAttrClassColor = 3 };
+GS_HD int AttributeClass(int attr) {
+    return attr == kAttrOpacity ? kAttrClassOpacity : (attr <= kAttrVolume ? kAttrClassScale : (attr <= kAttrDist2 ? kAttrClassPos : kAttrClassColor));
+}
+// the partial forms of LoadSplatDataFull the classes read: the scale alone (the other blob and the chunk header; no colour texel) ...
+GS_HD V3 LoadSplatScale(const AssetView& a, uint32_t idx, uint32_t ci) {
+    uint32_t otherStride = 4 + vecStride(a.scaleFmt);
+    if (a.shFmt > 3) otherStride += 2;
+    V3 scale = LoadVec(a.other, (uint64_t)idx * otherStride + 4, a.scaleFmt);
+    if (ci < a.chunkCount) {
+        const uint8_t* c = a.chunk + (uint64_t)ci * 64;
+        scale.x = lerpf(f16tof32(ld32a(c, 40)), f16tof32(ld32a(c, 40) >> 16), scale.x);
+        scale.y = lerpf(f16tof32(ld32a(c, 44)), f16tof32(ld32a(c, 44) >> 16), scale.y);
+        scale.z = lerpf(f16tof32(ld32a(c, 48)), f16tof32(ld32a(c, 48) >> 16), scale.z);
+        scale.x *= scale.x; scale.y *= scale.y; scale.z *= scale.z;
+        scale.x *= scale.x; scale.y *= scale.y; scale.z *= scale.z;
+        scale.x *= scale.x; scale.y *= scale.y; scale.z *= scale.z;
+    }
+    return scale;
+}
+// ... and the opacity alone (the colour texel and the chunk header; neither the other blob nor SH)
+GS_HD float LoadSplatOpacity(const AssetView& a, uint32_t idx, uint32_t ci) {
+    float o = LoadColorTexel(a, idx).w;
+    if (ci < a.chunkCount) {
+        const uint8_t* c = a.chunk + (uint64_t)ci * 64;
+        o = InvSquareCentered01(lerpf(f16tof32(ld32a(c, 12)), f16tof32(ld32a(c, 12) >> 16), o));
+    }
+    return o;
+}
+// fmaxf / fminf with the one case the C standard leaves open pinned: of +0 and -0 the FIRST operand is returned.  A NaN operand is ignored; NaN if both are
+GS_HD float AttributeMax(float a, float b) { return (a >= b || b != b) ? a : b; }
+GS_HD float AttributeMin(float a, float b) { return (a <= b || b != b) ? a : b; }
+GS_HD float AttributeOfScale(int attr, V3 s) {
+    if (attr == kAttrScaleMax) return AttributeMax(AttributeMax(s.x, s.y), s.z);
+    if (attr == kAttrScaleMin) return AttributeMin(AttributeMin(s.x, s.y), s.z);
+    return (s.x * s.y) * s.z;
+}
+GS_HD float AttributeOfPos(int attr, V3 p, V3 q) {                // q: the point of kAttrDist2 (N(i, j)'s d2)
+    if (attr == kAttrPosX) return p.x;
+    if (attr == kAttrPosY) return p.y;
+    if (attr == kAttrPosZ) return p.z;
+    const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
+    return (dx * dx + dy * dy) + dz * dz;
+}
+GS_HD float AttributeOfColor(int attr, V3 c) {
+    if (attr == kAttrColorR) return c.x;
+    if (attr == kAttrColorG) return c.y;
+    if (attr == kAttrColorB) return c.z;
+    return (0.299f * c.x + 0.587f * c.y) + 0.114f * c.z;
+}
+// value(i, attr) of a splat whose position the caller has loaded (or not: only the position class reads it)
+GS_HD float AttributeValue(const AssetView& a, int attr, uint32_t idx, uint32_t ci, V3 pos, V3 q) {
+    const int cls = AttributeClass(attr);
+    if (cls == kAttrClassPos) return AttributeOfPos(attr, pos, q);
+    if (cls == kAttrClassScale) return AttributeOfScale(attr, LoadSplatScale(a, idx, ci));
+    if (cls == kAttrClassOpacity) return LoadSplatOpacity(a, idx, ci);
+    return AttributeOfColor(attr, LoadSplatBaseColor(a, idx));
+}
+GS_HD bool AttributeIsNaN(float v) { return v != v; }
+GS_HD bool AttributeInRange(float v, float lo, float hi) { return lo <= v && v <= hi; }          // false for a NaN, and for every v when lo > hi
+// the word of the bins + 3 histogram words a value is counted in: s = (float) bins / (hi - lo), computed once by the host
+GS_HD uint32_t AttributeBin(float v, float lo, float hi, float s, uint32_t bins) {
+    if (v != v) return bins + 2u;
+    if (v < lo) return bins;
+    if (v > hi) return bins + 1u;
+    const float t = (v - lo) * s;
+    const uint32_t b = (uint32_t)t;
+    return b < bins - 1u ? b : bins - 1u;
+}
+GS_HD float SortableUintToFloat(uint32_t u) { return u2f((u & 0x80000000u) ? (u ^ 0x80000000u) : ~u); }      // FloatToSortableUint's inverse
+
 } // namespace gsm

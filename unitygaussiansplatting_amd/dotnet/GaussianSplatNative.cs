@@ -192,6 +192,15 @@ namespace GaussianSplatting.Runtime
         [DllImport(Lib)] public static extern int gs_renderer_edit_components(IntPtr renderer, float radius, [Out] uint[] labelsOut, [Out] uint[] sizesOut, UIntPtr count);
         [DllImport(Lib)] public static extern int gs_renderer_edit_select_islands(IntPtr renderer, float radius, uint minSize, int subtract);
         [DllImport(Lib)] public static extern int gs_renderer_edit_grow_selection(IntPtr renderer, float radius);
+        // select by attribute: one fp32 value per alive splat from the decoded fields (0xFFFFFFFF for the others); the selection of a value range (asynchronous); the scope's size, NaN count and extreme values; a histogram of bins + 3 words (bins, below, above, NaN); order statistics of the sorted values.  point: float[3] in object space, read for Dist2 only (else null).  All but the range selection block
+        public enum SplatAttribute { Opacity = 0, ScaleMax = 1, ScaleMin = 2, Volume = 3, PosX = 4, PosY = 5, PosZ = 6, Dist2 = 7, ColorR = 8, ColorG = 9, ColorB = 10, Luma = 11 }
+        public enum AttributeScope { Alive = 0, Selected = 1 }
+        [StructLayout(LayoutKind.Sequential)] public struct GsAttributeStats { public uint members; public uint nans; public float vmin; public float vmax; }
+        [DllImport(Lib)] public static extern int gs_renderer_edit_attribute_values(IntPtr renderer, int attr, float[] point, [Out] float[] valuesOut, UIntPtr count);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_select_range(IntPtr renderer, int attr, float[] point, float lo, float hi, int subtract);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_attribute_stats(IntPtr renderer, int attr, float[] point, int scope, out GsAttributeStats stats);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_attribute_histogram(IntPtr renderer, int attr, float[] point, int scope, float lo, float hi, uint bins, [Out] uint[] histOut, UIntPtr count);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_attribute_ranks(IntPtr renderer, int attr, float[] point, int scope, uint[] ranks, uint rankCount, [Out] float[] valuesOut, out uint population);
 
         // native importer (host code): GaussianSplatAssetCreator.CreateAsset without the asset database
         [StructLayout(LayoutKind.Sequential)]

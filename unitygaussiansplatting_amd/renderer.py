@@ -18,7 +18,8 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from ._abi import (GS_ERR_INVALID_ARGUMENT, GS_ERR_PAIR_OVERFLOW, GS_SORT_FULL, GS_SORT_VISIBLE, GS_SPZ_FRACT_AUTO, PICK_DTYPE, VIEW_DTYPE, gs_copy_params, gs_edit_history_info, gs_edit_info,
+from ._abi import (GS_ERR_INVALID_ARGUMENT, GS_ERR_PAIR_OVERFLOW, GS_SCOPE_ALIVE, GS_SCOPE_SELECTED, GS_SORT_FULL, GS_SORT_VISIBLE, GS_SPZ_FRACT_AUTO, PICK_DTYPE, VIEW_DTYPE, gs_attribute_stats,
+                   gs_copy_params, gs_edit_history_info, gs_edit_info,
                    gs_export_params, gs_frame_params, gs_frame_stats, gs_import_formats, gs_pick_record, gs_spz_params, gs_stage_times, make_asset_desc)
 from ._lib import GsError, check
 from .asset import CalcTextureSize, ColorFormat, GaussianSplatAsset, SHFormat, VectorFormat, kCurrentVersion, kMaxSplats
@@ -55,6 +56,21 @@ class RenderMode(enum.IntEnum):          # GaussianSplatRenderer.RenderMode (:21
 class SortMode(enum.IntEnum):            # gs_sort_mode: what SortPoints sorts (no counterpart in the reference, whose sort precedes its cull)
     Full = GS_SORT_FULL                  # all N splats, every SortPoints, like GaussianSplatRenderer.SortPoints (:612-639)
     Visible = GS_SORT_VISIBLE            # cull first: only the splats CalcViewData found visible, inside Draw
+
+
+class SplatAttribute(enum.IntEnum):      # gs_splat_attribute: one fp32 value per splat from its decoded fields
+    Opacity = 0                          # linear opacity
+    ScaleMax = 1                         # the largest / smallest of the three linear scales
+    ScaleMin = 2
+    Volume = 3                           # their product
+    PosX = 4                             # object-space position
+    PosY = 5
+    PosZ = 6
+    Dist2 = 7                            # squared distance to `point` (object space): the sphere tool
+    ColorR = 8                           # DC colour
+    ColorG = 9
+    ColorB = 10
+    Luma = 11                            # 0.299 r + 0.587 g + 0.114 b
 
 
 class EditHistoryFlags(enum.IntFlag):    # GS_HIST_*: what an EditCheckpoint captures
@@ -596,6 +612,87 @@ class GaussianSplatRenderer:
         self.UpdateCutoutsBuffer()
         check(_lib.lib().gs_renderer_edit_grow_selection(self._r_h, float(radius)), "gs_renderer_edit_grow_selection")
         self.UpdateEditCountsAndBounds()
+
+    # -- editing: selection by attribute (no counterpart in the reference) ------------------------
+    @staticmethod
+    def _attr_point(point):
+        """(keep-alive array or None, the pointer the C call takes): `point` is read for SplatAttribute.Dist2 only"""
+        if point is None:
+            return None, None
+        a = np.ascontiguousarray(point, np.float32).reshape(3)
+        return a, a.ctypes.data
+
+    def EditAttributeValues(self, attr, point=None) -> np.ndarray:
+        """value(i, attr) of every alive splat -- not deleted, not cut -- as float32; the word 0xFFFFFFFF (a NaN) for a splat that is not alive: view
+        the result as uint32 to tell it from a value (gs_renderer_edit_attribute_values).  Changes nothing; blocks."""
+        self.UpdateCutoutsBuffer()
+        out = np.zeros(self.m_SplatCount, np.float32)
+        keep, p = self._attr_point(point)
+        check(_lib.lib().gs_renderer_edit_attribute_values(self._r_h, int(attr), p, out.ctypes.data, len(out)), "gs_renderer_edit_attribute_values")
+        return out
+
+    def EditSelectRange(self, attr, lo: float, hi: float, subtract: bool = False, point=None) -> None:
+        """Every alive splat with lo <= value <= hi is added to the selection, or with subtract removed from it; +-inf bounds are allowed, lo > hi
+        selects nothing (gs_renderer_edit_select_range)."""
+        if not self.EnsureEditingBuffers():
+            return
+        self.UpdateCutoutsBuffer()
+        keep, p = self._attr_point(point)
+        check(_lib.lib().gs_renderer_edit_select_range(self._r_h, int(attr), p, float(lo), float(hi), int(bool(subtract))), "gs_renderer_edit_select_range")
+        self.UpdateEditCountsAndBounds()
+
+    def EditAttributeStats(self, attr, selectedOnly: bool = False, point=None) -> gs_attribute_stats:
+        """members (the alive splats, or with selectedOnly the selected alive ones), nans (those whose value is NaN), vmin / vmax over the rest
+        (+inf / -inf if there is none) (gs_renderer_edit_attribute_stats).  Blocks."""
+        self.UpdateCutoutsBuffer()
+        out = gs_attribute_stats()
+        keep, p = self._attr_point(point)
+        check(_lib.lib().gs_renderer_edit_attribute_stats(self._r_h, int(attr), p, GS_SCOPE_SELECTED if selectedOnly else GS_SCOPE_ALIVE, C.byref(out)),
+              "gs_renderer_edit_attribute_stats")
+        return out
+
+    def EditAttributeHistogram(self, attr, lo: float, hi: float, bins: int, selectedOnly: bool = False, point=None):
+        """(hist[bins], below, above, nans): the members' values counted in `bins` equal bins over [lo, hi] (hi itself in the last), those below lo,
+        above hi and NaN apart (gs_renderer_edit_attribute_histogram).  Blocks."""
+        self.UpdateCutoutsBuffer()
+        out = np.zeros(int(bins) + 3, np.uint32)
+        keep, p = self._attr_point(point)
+        check(_lib.lib().gs_renderer_edit_attribute_histogram(self._r_h, int(attr), p, GS_SCOPE_SELECTED if selectedOnly else GS_SCOPE_ALIVE, float(lo), float(hi), int(bins),
+                                                              out.ctypes.data, len(out)), "gs_renderer_edit_attribute_histogram")
+        bins = int(bins)
+        return out[:bins].copy(), int(out[bins]), int(out[bins + 1]), int(out[bins + 2])
+
+    def EditAttributeRanks(self, attr, ranks, selectedOnly: bool = False, point=None):
+        """(values, population): the members whose value is not NaN, sorted ascending (-0 before +0); values[k] is the one at position ranks[k], the
+        word 0xFFFFFFFF where ranks[k] >= population.  At most 4096 ranks; none returns the population alone (gs_renderer_edit_attribute_ranks).  Blocks."""
+        self.UpdateCutoutsBuffer()
+        rk = np.ascontiguousarray(ranks, np.uint32).reshape(-1)
+        out = np.zeros(len(rk), np.float32)
+        pop = C.c_uint32(0)
+        keep, p = self._attr_point(point)
+        check(_lib.lib().gs_renderer_edit_attribute_ranks(self._r_h, int(attr), p, GS_SCOPE_SELECTED if selectedOnly else GS_SCOPE_ALIVE, rk.ctypes.data if len(rk) else None,
+                                                          len(rk), out.ctypes.data if len(rk) else None, C.byref(pop)), "gs_renderer_edit_attribute_ranks")
+        return out, int(pop.value)
+
+    def EditAttributeQuantiles(self, attr, fractions, selectedOnly: bool = False, point=None):
+        """A convenience composed of two EditAttributeRanks calls: the population from one with no ranks, then the values at rank
+        min(population - 1, floor(f * population)) (float64) for every f of `fractions`.  (values, population); an empty population gives no values."""
+        _, pop = self.EditAttributeRanks(attr, [], selectedOnly, point)
+        f = np.asarray(fractions, np.float64).reshape(-1)
+        if pop == 0:
+            return np.zeros(0, np.float32), 0
+        ranks = np.minimum(pop - 1, np.floor(f * np.float64(pop))).astype(np.uint32)
+        return self.EditAttributeRanks(attr, ranks, selectedOnly, point)[0], pop
+
+    def EditSelectTop(self, attr, fraction: float, largest: bool = True, subtract: bool = False, point=None) -> None:
+        """A convenience composed of EditAttributeQuantiles and EditSelectRange: the `fraction` of the alive splats with the largest (or smallest)
+        values -- the quantile's value, then the range from it to +inf (from -inf to it).  Ties at the threshold are all taken."""
+        q = 1.0 - float(fraction) if largest else float(fraction)
+        values, pop = self.EditAttributeQuantiles(attr, [min(max(q, 0.0), 1.0)], False, point)
+        if pop == 0:
+            return
+        t = float(values[0])
+        self.EditSelectRange(attr, t if largest else -np.inf, np.inf if largest else t, subtract, point)
 
     def EditDeleteSelected(self) -> None:           # :896-904
         if not self.EnsureEditingBuffers():
