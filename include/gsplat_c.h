@@ -759,6 +759,47 @@ int32_t gs_renderer_edit_attribute_histogram(gs_renderer* r, int32_t attr, const
 int32_t gs_renderer_edit_attribute_ranks(gs_renderer* r, int32_t attr, const float point[3], int32_t scope, const uint32_t* ranks, uint32_t rank_count,
                                          float* values_out, uint32_t* population);
 
+/* ---- lasso, polygon and brush: selecting through a screen mask  (additions to ABI 9) ---------------------------------------------------
+ * A MASK is one bit per pixel of a W x H screen, 1 <= W, H <= 65535, owned by a context.  Row 0 = top, y down, x right: the convention of the
+ * pick records.  A row is ceil(W/32) words; bit x & 31 of word x >> 5 is pixel x; the bits beyond W in a row's last word are zero after every
+ * call.  Every call that changes a mask -- clear, upload, the drawing calls -- and the two selecting calls are asynchronous on the context's
+ * stream, and a caller's array is only read during the call (it is copied); the download blocks.  word_count is H * ceil(W/32), exactly.
+ * The contract of the two drawing calls, operation by operation.  All arithmetic is fp32 and every + - x / rounds
+ * once; the centre of pixel (x, y) is c = ((float)x + 0.5f, (float)y + 0.5f).  `xy` is a host array of pixel coordinates in the mask's frame
+ * (x0 y0 x1 y1 ...), copied by the call.  subtract == 0: the covered pixels are set; else they are cleared.
+ *   POLYGON  3 <= vertices <= 65536; edge i runs from vertex i to vertex (i + 1) mod V; the lasso is filled by the even-odd rule.  On the row
+ *            with yc = y + 0.5f the edge (a -> b) CROSSES iff (a.y <= yc) != (b.y <= yc); its crossing abscissa is
+ *            xs = a.x + ((yc - a.y) * (b.x - a.x)) / (b.y - a.y); a crossing toggles every pixel of the row with c.x < xs; a pixel is covered
+ *            iff it was toggled an odd number of times.  A vertex on a row's centre line belongs to the half plane above it, and a horizontal
+ *            edge never crosses.
+ *   STROKE   1 <= points <= 65536, 0 < radius <= 65536: the round-capped polyline through the points, one point being a disc.  For a segment
+ *            (a -> b), a == b for a single point:  d = b - a, e = c - a, len2 = d.x d.x + d.y d.y;  t = 0 if len2 == 0, else
+ *            min(max((e.x d.x + e.y d.y) / len2, 0), 1);  q = e - t d (the product rounds, then the difference);  d2 = q.x q.x + q.y q.y.
+ *            The pixel is covered iff d2 <= radius radius for any segment.
+ * Refused with GS_ERR_INVALID_ARGUMENT and nothing changed: a NULL argument, a coordinate that is NaN, infinite or beyond 65536 in magnitude,
+ * a count outside the limits above, a radius that is not in (0, 65536], a wrong word_count. */
+typedef struct gs_mask gs_mask;
+int32_t gs_mask_create(gs_context* ctx, uint32_t width, uint32_t height, gs_mask** out);      /* every bit zero */
+int32_t gs_mask_destroy(gs_mask* m);
+int32_t gs_mask_clear(gs_mask* m);
+int32_t gs_mask_upload(gs_mask* m, const uint32_t* words, size_t word_count);                 /* bits beyond W are masked off */
+int32_t gs_mask_download(gs_mask* m, uint32_t* words, size_t word_count);                     /* blocks */
+int32_t gs_mask_fill_polygon(gs_mask* m, const float* xy, uint32_t vertices, int32_t subtract);
+int32_t gs_mask_stroke(gs_mask* m, const float* xy, uint32_t points, float radius, int32_t subtract);
+/* The lasso counterpart of gs_renderer_edit_update_selection, with the same gesture contract: selected = the mouse-down copy, plus (subtract != 0:
+ * minus) the splats the mask hits, every word written once; the host calls gs_renderer_edit_store_selection at mouse-down and this on every
+ * mouse move.  The test of one splat is the rectangle tool's up to its pixel position (not cut, clip w > 0, px and py from the same
+ * expressions, py counting up from the bottom edge); then it is a hit iff px >= 0 && px < W && py >= 0 && py < H and bit
+ * ((uint)px, H - 1 - (uint)py) of the mask is set.  A splat whose pixel position is NaN therefore hits NOTHING: deliberately not the quirk of
+ * the rectangle tool, where such a splat is inside every rectangle.  Deleted bits play no part, as there.
+ * Refused with GS_ERR_INVALID_ARGUMENT, nothing changed and no edit buffers made: a NULL argument, p->screen_w != (float)W or
+ * p->screen_h != (float)H, a mask of another context. */
+int32_t gs_renderer_edit_update_selection_mask(gs_renderer* r, const gs_frame_params* p, gs_mask* m, int32_t subtract);
+/* gs_renderer_edit_select_surface over every pixel whose mask bit is set, in place of a rectangle: the same record test (tag, splat < N, not
+ * deleted, not cut), on the current selection, ordered after the target's last use.  The mask must have the target's size and context; a
+ * target without pick output is refused as there. */
+int32_t gs_renderer_edit_select_surface_mask(gs_renderer* r, gs_target* t, gs_mask* m, int32_t subtract);
+
 /* ---- native importer (host code; no GPU needed, one optional GPU stage): GaussianSplatAssetCreator.CreateAsset minus the Unity asset database -- */
 /* InputSplatData (GaussianFileReader.cs:17-26) as separate arrays, in the PLY domain after ReorderSHs: */
 typedef struct gs_import_input {

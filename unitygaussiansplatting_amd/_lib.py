@@ -138,6 +138,15 @@ SIGNATURES = {
     "gs_renderer_edit_attribute_stats": (C.c_int32, [_P, C.c_int32, _P, C.c_int32, C.POINTER(gs_attribute_stats)]),
     "gs_renderer_edit_attribute_histogram": (C.c_int32, [_P, C.c_int32, _P, C.c_int32, C.c_float, C.c_float, C.c_uint32, _P, C.c_size_t]),
     "gs_renderer_edit_attribute_ranks": (C.c_int32, [_P, C.c_int32, _P, C.c_int32, _P, C.c_uint32, _P, C.POINTER(C.c_uint32)]),
+    "gs_mask_create": (C.c_int32, [_P, C.c_uint32, C.c_uint32, _PP]),
+    "gs_mask_destroy": (C.c_int32, [_P]),
+    "gs_mask_clear": (C.c_int32, [_P]),
+    "gs_mask_upload": (C.c_int32, [_P, _P, C.c_size_t]),
+    "gs_mask_download": (C.c_int32, [_P, _P, C.c_size_t]),
+    "gs_mask_fill_polygon": (C.c_int32, [_P, C.POINTER(C.c_float), C.c_uint32, C.c_int32]),
+    "gs_mask_stroke": (C.c_int32, [_P, C.POINTER(C.c_float), C.c_uint32, C.c_float, C.c_int32]),
+    "gs_renderer_edit_update_selection_mask": (C.c_int32, [_P, C.POINTER(gs_frame_params), _P, C.c_int32]),
+    "gs_renderer_edit_select_surface_mask": (C.c_int32, [_P, _P, _P, C.c_int32]),
     "gs_import_blob_sizes": (C.c_int32, [C.c_uint32, C.POINTER(gs_import_formats), C.c_uint64 * 5]),
     "gs_import_encode": (C.c_int32, [C.POINTER(gs_import_input), C.POINTER(gs_import_formats), C.c_void_p * 5, C.c_uint64 * 5,
                                       C.POINTER(C.c_float), C.POINTER(C.c_float)]),

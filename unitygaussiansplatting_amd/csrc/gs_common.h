@@ -254,6 +254,23 @@ struct gs_target {
     float pickTau = 0.5f;                   // 0 < tau <= 1
 };
 
+// A screen mask (gs_mask_*; gs_mask.hip): one bit per pixel, H rows of ceil(W/32) words, row 0 = top.  The outline or stroke of a
+// drawing call travels through a pinned shadow copy, as a renderer's cutouts do: the caller's array is only read during the call and the upload is
+// stream-ordered behind the kernel that still reads the previous one.
+struct gs_mask {
+    gs_context* ctx = nullptr;
+    uint32_t width = 0, height = 0, rowWords = 0;
+    gs::DevBuf<uint32_t> words;             // height x rowWords
+    gs::DevBuf<float> xy;                   // the current outline / stroke, xyCap points
+    gs::PinnedBuf<float> xyHost;
+    gs::Event xyCopied;
+    bool xyCopyPending = false;
+    uint32_t xyCap = 0;
+    gs::PinnedBuf<uint32_t> wordsHost;      // gs_mask_upload's shadow of the same kind, made by the first upload: height x rowWords
+    gs::Event wordsCopied;
+    bool wordsCopyPending = false;
+};
+
 namespace gs {
 // The plain values a host sets on a renderer and expects to keep.  One copy, the owner's: a lane reads its owner's through gs::settings(), a resize
 // copies the struct.  renderMode and pointDisplaySize are safe to read from the owner too: lanes draw only while the owner's mode is GS_RENDER_SPLATS

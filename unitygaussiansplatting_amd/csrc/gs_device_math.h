@@ -743,15 +743,82 @@ struct PickSelect {
 // CSSelectionUpdate's test of one splat (SplatUtilities.compute:400-416): does the rectangle select it?  World and clip position
 // are CalcViewGeom's expressions, so the clip position has the bits of the view record's pos.  Every comparison is the
 // reference's, literally: a NaN w is not "behind", and a NaN pixel position is outside no edge of the rectangle, so it is a hit.
-GS_HD bool EditSelectionHit(const EditSelect& S, const EditView& E, const V3& pos) {
+// the part of the test that both screen tools share: false = cut or behind the camera, else the pixel position (y up from the bottom edge)
+GS_HD bool EditSelectionPixel(const EditSelect& S, const EditView& E, const V3& pos, float& px, float& py) {
     if (IsSplatCut(E, pos.x, pos.y, pos.z)) return false;
     const float wx = mrow(S.o2w, 0, pos.x, pos.y, pos.z), wy = mrow(S.o2w, 1, pos.x, pos.y, pos.z), wz = mrow(S.o2w, 2, pos.x, pos.y, pos.z);
     const float cx = mrow(S.vp, 0, wx, wy, wz), cy = mrow(S.vp, 1, wx, wy, wz), cw = mrow(S.vp, 3, wx, wy, wz);
     if (cw <= 0.0f) return false;                                  // behindCam
-    const float px = ((cx / cw) * 0.5f + 0.5f) * S.screenW;        // (centerClipPos.y *= -1 first, :406)
-    const float py = (((-cy) / cw) * -0.5f + 0.5f) * S.screenH;
+    px = ((cx / cw) * 0.5f + 0.5f) * S.screenW;                    // (centerClipPos.y *= -1 first, :406)
+    py = (((-cy) / cw) * -0.5f + 0.5f) * S.screenH;
+    return true;
+}
+GS_HD bool EditSelectionHit(const EditSelect& S, const EditView& E, const V3& pos) {
+    float px, py;
+    if (!EditSelectionPixel(S, E, pos, px, py)) return false;
     if (px < S.rect[0] || px > S.rect[2] || py < S.rect[1] || py > S.rect[3]) return false;
     return true;
+}
+
+// ---- the screen mask (gs_mask; kernels in gs_mask.hip and gs_edit.hip) ----
+// One bit per pixel of a W x H screen, row 0 = top: a row is ceil(W/32) words, bit x & 31 of word x >> 5 is pixel x, the bits beyond W are zero.
+// Everything below is fp32 and rounds once per operation; the centre of pixel (x, y) is ((float)x + 0.5f, (float)y + 0.5f), exact for x, y < 65536.
+constexpr float kMaskCoordMax = 65536.0f;                          // |coordinate| and radius limit of the drawing calls
+constexpr uint32_t kMaskMaxPoints = 65536u;
+struct MaskView { const uint32_t* words; uint32_t w, h, rowWords; };
+GS_HD uint32_t MaskRowWords(uint32_t w) { return (w + 31u) >> 5; }
+GS_HD uint32_t MaskTailBits(uint32_t w) { return (w & 31u) ? (1u << (w & 31u)) - 1u : 0xFFFFFFFFu; }    // the valid bits of a row's last word
+GS_HD bool MaskCoordOk(float v) { return fabsf(v) <= kMaskCoordMax; }                                    // false for NaN and the infinities
+GS_HD bool MaskBit(const MaskView& M, uint32_t x, uint32_t y) { return ((M.words[(size_t)y * M.rowWords + (x >> 5)] >> (x & 31u)) & 1u) != 0u; }
+
+// the lasso counterpart of the rectangle comparison: px, py as EditSelectionPixel leaves them (py up from the bottom edge).  A NaN fails every comparison.
+GS_HD bool MaskPixelHit(const MaskView& M, float px, float py) {
+    if (!(px >= 0.0f && px < (float)M.w && py >= 0.0f && py < (float)M.h)) return false;
+    return MaskBit(M, (uint32_t)px, M.h - 1u - (uint32_t)py);
+}
+GS_HD bool EditSelectionMaskHit(const EditSelect& S, const EditView& E, const MaskView& M, const V3& pos) {
+    float px, py;
+    if (!EditSelectionPixel(S, E, pos, px, py)) return false;
+    return MaskPixelHit(M, px, py);
+}
+
+// polygon, even-odd: on the row with centre yc an edge (a -> b) crosses iff exactly one end is at or above the centre line ...
+GS_HD bool MaskEdgeCrosses(float ay, float by, float yc) { return (ay <= yc) != (by <= yc); }
+// ... at this abscissa (by != ay for a crossing edge, and |yc - ay| <= |by - ay|: finite under the coordinate limit), and toggles every pixel with xc < xs
+GS_HD float MaskEdgeCrossX(float ax, float ay, float bx, float by, float yc) { return ax + ((yc - ay) * (bx - ax)) / (by - ay); }
+// k = the number of pixels x in [0, W) with (float)x + 0.5f < xs, for EVERY float xs.  The predicate is monotone in x, so the toggled pixels are 0 .. k-1.
+//   not (xs > 0.5): no pixel (x + 0.5 >= 0.5 >= xs; a NaN compares false everywhere).   xs >= W: all of them (x + 0.5 <= W - 0.5 < xs).
+//   else f = floor(xs) is an integer in [0, W), exact: pixels x < f have x + 0.5 <= f - 0.5 < xs, pixels x > f have x + 0.5 >= f + 1.5 > xs, and
+//   pixel f is decided by the comparison itself, f + 0.5 being exact below 2^23.
+GS_HD uint32_t MaskBoundaryCount(float xs, uint32_t w) {
+    if (!(xs > 0.5f)) return 0u;
+    if (xs >= (float)w) return w;
+    const float f = floorf(xs);
+    return (uint32_t)f + ((f + 0.5f < xs) ? 1u : 0u);
+}
+
+// stroke: is the pixel centre (cx, cy) within `r2 = radius * radius` of the segment (a -> b)?  a == b is a disc
+GS_HD bool MaskSegmentCovers(float ax, float ay, float bx, float by, float cx, float cy, float r2) {
+    const float dx = bx - ax, dy = by - ay, ex = cx - ax, ey = cy - ay;
+    const float len2 = dx * dx + dy * dy;
+    float t = 0.0f;
+    if (len2 != 0.0f) t = fminf(fmaxf((ex * dx + ey * dy) / len2, 0.0f), 1.0f);
+    const float tx = t * dx, ty = t * dy;
+    const float qx = ex - tx, qy = ey - ty;
+    const float d2 = qx * qx + qy * qy;
+    return d2 <= r2;
+}
+// The conservative pixel box of a segment, clipped to the screen: every pixel MaskSegmentCovers accepts lies in [x0, x1] x [y0, y1] (x0 > x1 or y0 > y1:
+// none on screen).  R = radius + 1: a covered centre is within radius + 2^-4 of the true segment (DESIGN.md section 4.20 has the rounding argument), and
+// the box's own three roundings move an edge by less than 2^-5.  Pixel x can only be covered if lo <= x + 0.5 <= hi, so x in [floor(lo), floor(hi)].
+struct MaskBox { int32_t x0, y0, x1, y1; };
+GS_HD MaskBox MaskSegmentBox(float ax, float ay, float bx, float by, float radius, uint32_t w, uint32_t h) {
+    const float R = radius + 1.0f;
+    const float lox = fminf(ax, bx) - R, hix = fmaxf(ax, bx) + R, loy = fminf(ay, by) - R, hiy = fmaxf(ay, by) + R;
+    MaskBox B;
+    B.x0 = (int32_t)fmaxf(floorf(lox), 0.0f); B.x1 = (int32_t)fminf(floorf(hix), (float)w - 1.0f);
+    B.y0 = (int32_t)fmaxf(floorf(loy), 0.0f); B.y1 = (int32_t)fminf(floorf(hiy), (float)h - 1.0f);
+    return B;
 }
 
 // CSUpdateEditData's bounds of one selected splat (SplatUtilities.compute:279-296), as the sortable uints the kernel's

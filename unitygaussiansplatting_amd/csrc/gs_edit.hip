@@ -76,6 +76,21 @@ __global__ __launch_bounds__(256) void edit_selection_update_kernel(gsm::AssetVi
     }
 }
 
+// gs_renderer_edit_update_selection_mask: the kernel above with the rectangle comparison replaced by the screen mask's bit under the splat's pixel
+// (gsm::EditSelectionMaskHit).  The mask is at most 512 MB and typically under 1 MB: its words are read through the cache, one per hit candidate.
+__global__ __launch_bounds__(256) void edit_selection_update_mask_kernel(gsm::AssetView a, gsm::EditView e, gsm::EditSelect S, gsm::MaskView M,
+                                                                         const uint32_t* __restrict__ mouseDown, uint32_t* __restrict__ sel, uint32_t nWords, uint32_t add) {
+    const uint32_t idx = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u;
+    bool hit = false;
+    if (idx < a.n) hit = gsm::EditSelectionMaskHit(S, e, M, gsm::LoadSplatPosChunk(a, idx, blockIdx.x));
+    const uint32_t hitw = ballot_word(__ballot(hit), lane);
+    const uint32_t w = idx >> 5;
+    if ((lane & 31u) == 0u && w < nWords) {
+        const uint32_t v = mouseDown[w];
+        sel[w] = add ? (v | hitw) : (v & ~hitw);
+    }
+}
+
 // CSOrBuffers (deleted |= selected) + CSClearBuffer (selected = 0): EditDeleteSelected
 __global__ __launch_bounds__(256) void edit_delete_kernel(uint32_t* __restrict__ deleted, uint32_t* __restrict__ sel, uint32_t nWords) {
     const uint32_t w = blockIdx.x * 256u + threadIdx.x;
@@ -208,12 +223,8 @@ __global__ __launch_bounds__(256) void edit_transform_kernel(uint8_t* __restrict
 // gs_renderer_edit_select_surface: one thread per pixel of the clipped rectangle.  A record counts if it carries the renderer's tag and a splat < N that
 // is neither deleted nor cut (the test every kernel above makes); many pixels name the same splat and a word's splats lie anywhere in the rectangle,
 // so -- unlike the kernels above, where a wave owns its words -- the bit is set or cleared with an atomic (the reference's InterlockedOr / And).
-__global__ __launch_bounds__(256) void edit_select_surface_kernel(gsm::AssetView a, gsm::EditView e, gsm::PickSelect S, const PickRecord* __restrict__ rec,
-                                                                  uint32_t* __restrict__ sel) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= S.w * S.h) return;
-    const uint32_t x = S.x0 + i % S.w, y = S.y0 + i / S.w;
-    const PickRecord pr = rec[(size_t)y * S.stride + x];
+__device__ __forceinline__ void edit_select_record(const gsm::AssetView& a, const gsm::EditView& e, const gsm::PickSelect& S, const PickRecord pr,
+                                                   uint32_t* __restrict__ sel) {
     if (pr.tag != S.tag || pr.splat >= a.n) return;
     const uint32_t idx = pr.splat;
     if (e.deletedBits && ((e.deletedBits[idx >> 5] >> (idx & 31u)) & 1u)) return;
@@ -221,6 +232,25 @@ __global__ __launch_bounds__(256) void edit_select_surface_kernel(gsm::AssetView
     if (gsm::IsSplatCut(e, pos.x, pos.y, pos.z)) return;
     if (S.subtract) atomicAnd(sel + (idx >> 5), ~(1u << (idx & 31u)));
     else atomicOr(sel + (idx >> 5), 1u << (idx & 31u));
+}
+
+__global__ __launch_bounds__(256) void edit_select_surface_kernel(gsm::AssetView a, gsm::EditView e, gsm::PickSelect S, const PickRecord* __restrict__ rec,
+                                                                  uint32_t* __restrict__ sel) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= S.w * S.h) return;
+    const uint32_t x = S.x0 + i % S.w, y = S.y0 + i / S.w;
+    edit_select_record(a, e, S, rec[(size_t)y * S.stride + x], sel);
+}
+
+// gs_renderer_edit_select_surface_mask: the same over the pixels whose mask bit is set.  S is the whole target (x0 = y0 = 0, w x h = the mask's size): one
+// thread per pixel, 32 neighbouring lanes read one mask word, and only a pixel inside the lasso reads its record.
+__global__ __launch_bounds__(256) void edit_select_surface_mask_kernel(gsm::AssetView a, gsm::EditView e, gsm::PickSelect S, gsm::MaskView M,
+                                                                       const PickRecord* __restrict__ rec, uint32_t* __restrict__ sel) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;            // < 2^32: both sides are at most 65535
+    if (i >= S.w * S.h) return;
+    const uint32_t x = i % S.w, y = i / S.w;
+    if (!gsm::MaskBit(M, x, y)) return;
+    edit_select_record(a, e, S, rec[(size_t)y * S.stride + x], sel);
 }
 
 // ---- the edit history's kernels (gs_renderer_edit_checkpoint / _undo / _redo) -------------------------------------
@@ -729,6 +759,39 @@ int32_t gs_renderer_edit_select_surface(gs_renderer* r, gs_target* t, int32_t x0
         GS_TRY(target_touched(t, r->ctx->stream));
     }
     return edit_selected_to_lanes(r);                              // (counts and bounds: gs_renderer_edit_info computes them when asked, as after every selection call)
+}
+
+int32_t gs_renderer_edit_update_selection_mask(gs_renderer* r, const gs_frame_params* p, gs_mask* m, int32_t subtract) {
+    if (!r || !p || !m) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
+    if (m->ctx != r->ctx) return fail(GS_ERR_INVALID_ARGUMENT, "mask belongs to another context");
+    if (p->screen_w != (float)m->width || p->screen_h != (float)m->height) return fail(GS_ERR_INVALID_ARGUMENT, "update_selection_mask: the mask is not of the frame's screen size");
+    GS_TRY(edit_ensure(r));
+    hist_mutated(r, true);
+    const float noRect[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
+    const gsm::MaskView M = { m->words.get(), m->width, m->height, m->rowWords };
+    hipLaunchKernelGGL(edit_selection_update_mask_kernel, dim3(splat_grid(r)), dim3(256), 0, r->ctx->stream, asset_view(r), edit_view(r), edit_select_of(*p, noRect), M,
+                       (const uint32_t*)r->editSelectedMouseDown, r->editSelected.get(), (uint32_t)bit_words(r->n), subtract ? 0u : 1u);
+    GS_HIP(hipGetLastError());
+    return edit_selected_to_lanes(r);
+}
+
+int32_t gs_renderer_edit_select_surface_mask(gs_renderer* r, gs_target* t, gs_mask* m, int32_t subtract) {
+    if (!r || !t || !m) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
+    if (t->ctx != r->ctx) return fail(GS_ERR_INVALID_ARGUMENT, "target belongs to another context");
+    if (m->ctx != r->ctx) return fail(GS_ERR_INVALID_ARGUMENT, "mask belongs to another context");
+    if (!t->pick) return fail(GS_ERR_INVALID_ARGUMENT, "the target has no pick output (gs_target_set_pick_output)");
+    if (m->width != t->width || m->height != t->height) return fail(GS_ERR_INVALID_ARGUMENT, "select_surface_mask: the mask is not of the target's size");
+    GS_TRY(edit_ensure(r));
+    hist_mutated(r, true);
+    GS_TRY(flush_clear(t));                                        // a cleared target that nothing has drawn into holds no record
+    const gsm::PickSelect S = pick_select_of(0, 0, (int32_t)t->width - 1, (int32_t)t->height - 1, t->width, t->height, r->set.pickTag, subtract);
+    const gsm::MaskView M = { m->words.get(), m->width, m->height, m->rowWords };
+    const uint32_t pixels = S.w * S.h;
+    hipLaunchKernelGGL(edit_select_surface_mask_kernel, dim3((pixels + 255u) / 256u), dim3(256), 0, r->ctx->stream, asset_view(r), edit_view(r), S, M,
+                       (const PickRecord*)t->pick.get(), r->editSelected.get());
+    GS_HIP(hipGetLastError());
+    GS_TRY(target_touched(t, r->ctx->stream));
+    return edit_selected_to_lanes(r);
 }
 
 int32_t gs_renderer_edit_delete_selected(gs_renderer* r) {

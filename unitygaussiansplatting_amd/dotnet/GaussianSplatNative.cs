@@ -201,6 +201,16 @@ namespace GaussianSplatting.Runtime
         [DllImport(Lib)] public static extern int gs_renderer_edit_attribute_stats(IntPtr renderer, int attr, float[] point, int scope, out GsAttributeStats stats);
         [DllImport(Lib)] public static extern int gs_renderer_edit_attribute_histogram(IntPtr renderer, int attr, float[] point, int scope, float lo, float hi, uint bins, [Out] uint[] histOut, UIntPtr count);
         [DllImport(Lib)] public static extern int gs_renderer_edit_attribute_ranks(IntPtr renderer, int attr, float[] point, int scope, uint[] ranks, uint rankCount, [Out] float[] valuesOut, out uint population);
+        // lasso, polygon and brush: a screen mask of one bit per pixel (row 0 = top; a row is ceil(W/32) words, bit x & 31 of word x >> 5), filled on the GPU by the even-odd rule or by a round-capped polyline; xy = x0 y0 x1 y1 ... in pixels.  The selection through it: the gesture contract of gs_renderer_edit_update_selection (a splat whose pixel position is NaN hits nothing), and gs_renderer_edit_select_surface over the pixels whose bit is set.  The download blocks
+        [DllImport(Lib)] public static extern int gs_mask_create(IntPtr ctx, uint width, uint height, out IntPtr mask);
+        [DllImport(Lib)] public static extern int gs_mask_destroy(IntPtr mask);
+        [DllImport(Lib)] public static extern int gs_mask_clear(IntPtr mask);
+        [DllImport(Lib)] public static extern int gs_mask_upload(IntPtr mask, uint[] words, UIntPtr wordCount);
+        [DllImport(Lib)] public static extern int gs_mask_download(IntPtr mask, [Out] uint[] words, UIntPtr wordCount);
+        [DllImport(Lib)] public static extern int gs_mask_fill_polygon(IntPtr mask, float[] xy, uint vertices, int subtract);
+        [DllImport(Lib)] public static extern int gs_mask_stroke(IntPtr mask, float[] xy, uint points, float radius, int subtract);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_update_selection_mask(IntPtr renderer, ref FrameParams p, IntPtr mask, int subtract);
+        [DllImport(Lib)] public static extern int gs_renderer_edit_select_surface_mask(IntPtr renderer, IntPtr target, IntPtr mask, int subtract);
 
         // native importer (host code): GaussianSplatAssetCreator.CreateAsset without the asset database
         [StructLayout(LayoutKind.Sequential)]

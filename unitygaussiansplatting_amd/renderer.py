@@ -132,6 +132,10 @@ class GpuContext:
         """Run SortPoints concurrently with CalcViewData on the context's second queue (default off: no gain on MI355X)."""
         check(_lib.lib().gs_context_set_overlap(self._h, int(bool(enabled))), "gs_context_set_overlap")
 
+    def CreateScreenMask(self, width: int, height: int) -> "ScreenMask":
+        """A zeroed screen mask of this context: what FillPolygon / Stroke draw into and EditUpdateSelectionMask / EditSelectSurfaceMask select through."""
+        return ScreenMask(self, width, height)
+
     def DeviceInfo(self) -> Tuple[str, int, int]:
         name = C.create_string_buffer(256)
         cus = C.c_int32()
@@ -222,6 +226,73 @@ class RenderTarget:
     def Dispose(self) -> None:
         if self._h:
             _lib.lib().gs_target_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.Dispose()
+        except Exception:
+            pass
+
+
+class ScreenMask:
+    """One bit per pixel of a width x height screen, filled on the GPU: what the lasso, the polygon and the brush draw and the renderer selects through
+    (gs_mask).  Row 0 = top, y down, x right, as the pick records; points are pixel coordinates in that frame."""
+
+    def __init__(self, ctx: GpuContext, width: int, height: int):
+        self.ctx, self.width, self.height = ctx, int(width), int(height)
+        self.rowWords = (self.width + 31) // 32
+        self._h = C.c_void_p()
+        check(_lib.lib().gs_mask_create(ctx._h, self.width, self.height, C.byref(self._h)), "gs_mask_create")
+        ctx._adopt(self)
+
+    @staticmethod
+    def _points(points) -> np.ndarray:
+        p = np.ascontiguousarray(points, np.float32)
+        if p.ndim != 2 or p.shape[1] != 2:
+            raise GsError(GS_ERR_INVALID_ARGUMENT, "ScreenMask", "points must be an n x 2 array of pixel coordinates")
+        return p
+
+    def Clear(self) -> None:
+        check(_lib.lib().gs_mask_clear(self._h), "gs_mask_clear")
+
+    def FillPolygon(self, points, subtract: bool = False) -> None:
+        """Fill the closed outline through `points` (3 .. 65536 vertices) by the even-odd rule: the covered pixels are set, or with subtract cleared."""
+        p = self._points(points)
+        check(_lib.lib().gs_mask_fill_polygon(self._h, _fptr(p), len(p), int(bool(subtract))), "gs_mask_fill_polygon")
+
+    def Stroke(self, points, radius: float, subtract: bool = False) -> None:
+        """Draw the brush: the round-capped polyline through `points` (1 .. 65536; one point is a disc) with that radius, 0 < radius <= 65536."""
+        p = self._points(points)
+        check(_lib.lib().gs_mask_stroke(self._h, _fptr(p), len(p), float(radius), int(bool(subtract))), "gs_mask_stroke")
+
+    def UploadWords(self, words: np.ndarray) -> None:
+        w = np.ascontiguousarray(words, np.uint32).reshape(-1)
+        check(_lib.lib().gs_mask_upload(self._h, w.ctypes.data, len(w)), "gs_mask_upload")
+
+    def DownloadWords(self) -> np.ndarray:
+        """height x ceil(width / 32) words, bit x & 31 of word x >> 5 = pixel x.  Blocks."""
+        out = np.empty((self.height, self.rowWords), np.uint32)
+        check(_lib.lib().gs_mask_download(self._h, out.ctypes.data, out.size), "gs_mask_download")
+        return out
+
+    def Upload(self, mask: np.ndarray) -> None:
+        """mask: height x width booleans"""
+        m = np.asarray(mask, bool)
+        if m.shape != (self.height, self.width):
+            raise GsError(GS_ERR_INVALID_ARGUMENT, "ScreenMask.Upload", "the array must be height x width")
+        padded = np.zeros((self.height, self.rowWords * 32), np.uint8)
+        padded[:, :self.width] = m
+        self.UploadWords(np.packbits(padded, axis=1, bitorder="little").view(np.uint32))
+
+    def Download(self) -> np.ndarray:
+        """height x width booleans.  Blocks."""
+        bits = np.unpackbits(self.DownloadWords().view(np.uint8), axis=1, bitorder="little")
+        return bits[:, :self.width].astype(bool)
+
+    def Dispose(self) -> None:
+        if self._h:
+            _lib.lib().gs_mask_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -567,6 +638,53 @@ class GaussianSplatRenderer:
         x0, y0, x1, y1 = (int(v) for v in rect)
         check(_lib.lib().gs_renderer_edit_select_surface(self._r_h, target._h, x0, y0, x1, y1, int(bool(subtract))), "gs_renderer_edit_select_surface")
         self.UpdateEditCountsAndBounds()
+
+    def EditUpdateSelectionMask(self, params, mask: "ScreenMask", subtract: bool = False) -> None:
+        """The lasso counterpart of EditUpdateSelection: selected = the mouse-down copy plus (subtract: minus) every splat whose centre lands on a set
+        pixel of `mask` (gs_renderer_edit_update_selection_mask).  params: a camera, or the gs_frame_params of one; its screen must be the mask's size.
+        EditStoreSelectionMouseDown at mouse-down, this on every mouse move."""
+        if not self.HasValidAsset or not self.HasValidRenderSetup:
+            return
+        self.UpdateCutoutsBuffer()
+        p = params if isinstance(params, gs_frame_params) else self.FrameParams(params)
+        check(_lib.lib().gs_renderer_edit_update_selection_mask(self._r_h, C.byref(p), mask._h, int(bool(subtract))), "gs_renderer_edit_update_selection_mask")
+        self.m_GpuEditSelected = True               # (a refused call made no edit buffers)
+        self.UpdateEditCountsAndBounds()
+
+    def EditSelectSurfaceMask(self, target: "RenderTarget", mask: "ScreenMask", subtract: bool = False) -> None:
+        """EditSelectSurface over every pixel whose bit in `mask` is set, in place of a rectangle (gs_renderer_edit_select_surface_mask); the mask
+        must have the target's size."""
+        if not self.HasValidAsset or not self.HasValidRenderSetup:
+            return
+        self.UpdateCutoutsBuffer()
+        check(_lib.lib().gs_renderer_edit_select_surface_mask(self._r_h, target._h, mask._h, int(bool(subtract))), "gs_renderer_edit_select_surface_mask")
+        self.m_GpuEditSelected = True
+        self.UpdateEditCountsAndBounds()
+
+    def _gesture_mask(self, p: gs_frame_params) -> "ScreenMask":
+        w, h = int(p.screen_w), int(p.screen_h)
+        m = getattr(self, "_screen_mask", None)
+        if m is None or not m._h or (m.width, m.height) != (w, h):
+            if m is not None:
+                m.Dispose()
+            m = self._screen_mask = ScreenMask(self.ctx, w, h)
+        return m
+
+    def EditSelectPolygon(self, params, points, subtract: bool = False) -> None:
+        """The lasso / polygon tool in one call: a cached mask of the screen's size is cleared, filled with the outline and selected through."""
+        p = params if isinstance(params, gs_frame_params) else self.FrameParams(params)
+        m = self._gesture_mask(p)
+        m.Clear()
+        m.FillPolygon(points)
+        self.EditUpdateSelectionMask(p, m, subtract)
+
+    def EditSelectBrush(self, params, points, radius: float, subtract: bool = False) -> None:
+        """The brush tool in one call: the cached mask is cleared, the stroke drawn and selected through."""
+        p = params if isinstance(params, gs_frame_params) else self.FrameParams(params)
+        m = self._gesture_mask(p)
+        m.Clear()
+        m.Stroke(points, radius)
+        self.EditUpdateSelectionMask(p, m, subtract)
 
     def EditNeighbourCounts(self, radius: float, cap: int = 65535) -> np.ndarray:
         """For every alive splat -- not deleted, not cut -- min(cap, the other alive splats within `radius` of it), boundary included; 0xFFFFFFFF for a
