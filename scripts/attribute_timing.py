@@ -3,7 +3,7 @@
 VeryHigh renderer:
 
   - gs_renderer_edit_select_range and gs_renderer_edit_attribute_stats per attribute class (position, scale, opacity, colour), with the bytes each must
-    read and the resulting GB/s; in the same run the alive count of the export (export_count_kernel and its scan over the chunks) over the same
+    read and the resulting GB/s; in the same run the alive count of the export (alive_count_kernel and its scan over the chunks) over the same
     renderer as the floor: it reads positions, deleted words and cutouts only
   - gs_renderer_edit_attribute_histogram at 64, 256 and 4096 bins on three value distributions -- the scene's own opacity, uniform, all equal (the last
     two: the VeryHigh asset with its opacity texels rewritten) -- in each of the contention variants the kernel has: plain LDS atomics, the wave

@@ -2,7 +2,7 @@
 (creator.CreateAssetFromSplatsNative): the five blobs over gs_import_blob_sizes bytes byte for byte, the bounds bit for bit, the splat count -- no
 tolerance anywhere.  tests/test_gpu_import_asset.py holds the presets on friendly input; here the device compile of gs_device_math.h meets arguments at
 and beyond the edges of exp / sigmoid / normalize / BakeQ / BakeNorm, a chunk constant in every column, more than 262,144 splats (the second round of
-bake_bounds_kernel's fold, three look-back groups in both Onesweep sorts, for the import and for the bake), Morton codes with one word constant, the
+bounds_fold_kernel's fold, three look-back groups in both Onesweep sorts, for the import and for the bake), Morton codes with one word constant, the
 whole BC7 block set through the DPP row reductions, and device arrays that are views into larger allocations.  Every input meets the premises of
 DESIGN.md section 4.11 by construction, and they are asserted on every input; the host pipeline is held to the same inputs on the CPU by
 tests/test_import_gpu_model.py."""
@@ -138,7 +138,7 @@ def test_past_262144_splats(gpu_ctx, formats, morton):
 
 
 def test_bake_past_262144_source_splats(gpu_ctx):
-    """bake_alive_kernel over 1,028 source chunks and the same fold: a VeryHigh renderer over the big input, every third splat deleted but for the six
+    """alive_list_kernel over 1,028 source chunks and the same fold: a VeryHigh renderer over the big input, every third splat deleted but for the six
     planted extremes, baked to Medium"""
     raw = big_input()
     asset = creator.CreateAssetFromSplatsNative(raw, "VeryHigh", morton=False)

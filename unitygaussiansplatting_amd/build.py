@@ -8,8 +8,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgsplat_hip.so")
-SOURCES = ["gs_api.hip", "gs_sort.hip", "gs_vissort.hip", "gs_view.hip", "gs_edit.hip", "gs_mask.hip", "gs_neighbours.hip", "gs_attributes.hip", "gs_export.hip", "gs_copy.hip", "gs_bake.hip", "gs_raster.hip", "gs_comm.hip", "gs_cluster.hip", "gs_import.cpp"]
-HEADERS = ["gs_common.h", "gs_device_math.h", "gs_handles.h", "gs_params.h", "gs_splat_file.h", os.path.join("..", "..", "include", "gsplat_c.h")]
+SOURCES = ["gs_api.hip", "gs_sort.hip", "gs_vissort.hip", "gs_view.hip", "gs_edit.hip", "gs_mask.hip", "gs_neighbours.hip", "gs_attributes.hip", "gs_compact.hip", "gs_export.hip", "gs_copy.hip", "gs_bake.hip", "gs_raster.hip", "gs_comm.hip", "gs_cluster.hip", "gs_import.cpp"]
+HEADERS = ["gs_common.h", "gs_block.h", "gs_device_math.h", "gs_handles.h", "gs_params.h", "gs_splat_file.h", os.path.join("..", "..", "include", "gsplat_c.h")]
 # -ffp-contract=off: the kernels' arithmetic is written with explicit fmaf(); nothing else may fuse, so that
 # results match the oracle's canonical arithmetic bit for bit.
 # -fno-slp-vectorize: v_pk_*_f32 is no faster than two scalar VALU ops on gfx950 and the packing costs v_movs (and hides

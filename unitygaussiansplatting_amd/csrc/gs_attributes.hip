@@ -18,7 +18,8 @@
 // texel, never `other` or SH; scale reads `other`, never the colour texture; the position is read by its own class and, by the others, only while
 // cutouts exist (the cut test needs it).
 //   attr_values      the value's bits by splat index, 0xFFFFFFFF for a splat that is not alive
-//   attr_select      the chunk's eight selection words from ballots, written whole with |= or &= ~: a chunk owns its words, no atomics
+//   attr_select      the chunk's eight selection words from ballots, written whole with |= or &= ~ (selection_apply, gs_block.h): a chunk owns its
+//                    words, no atomics
 //   attr_stats       per thread the counts and the min / max KEY over its chunks, a wave reduction, one set of global atomics per workgroup into
 //                    one of 32 rows the host folds
 //   attr_hist        LDS counters (bins + 3 words, at most 4099), one LDS atomic per member (section 4.19: the contention variants that were measured
@@ -29,6 +30,7 @@
 #include <cmath>
 
 #include "gs_common.h"
+#include "gs_block.h"
 
 namespace gs {
 
@@ -48,8 +50,8 @@ template <int CLS>
 __device__ __forceinline__ bool attr_member(const gsm::AssetView& a, const gsm::EditView& e, const AttrArgs& A, uint32_t idx, uint32_t ci, float& v) {
     v = 0.0f;
     if (idx >= a.n) return false;
-    if (e.deletedBits && ((e.deletedBits[idx >> 5] >> (idx & 31u)) & 1u)) return false;
-    if (A.scope && !(A.sel && ((A.sel[idx >> 5] >> (idx & 31u)) & 1u))) return false;
+    if (e.deletedBits && bit_set(e.deletedBits, idx)) return false;
+    if (A.scope && !(A.sel && bit_set(A.sel, idx))) return false;
     gsm::V3 pos = { 0.0f, 0.0f, 0.0f };
     if (CLS == gsm::kAttrClassPos || e.cutoutCount) {              // (wave-uniform) without cutouts nothing is cut and only the position class needs p
         pos = gsm::LoadSplatPosChunk(a, idx, ci);
@@ -80,10 +82,7 @@ __global__ __launch_bounds__(256) void attr_select_kernel(gsm::AssetView a, gsm:
     for (uint32_t ci = blockIdx.x; ci < chunks; ci += gridDim.x) {
         const uint32_t idx = ci * 256u + threadIdx.x;
         float v;
-        const bool in = attr_member<CLS>(a, e, A, idx, ci, v) && gsm::AttributeInRange(v, lo, hi);
-        const uint32_t word = (uint32_t)(__ballot(in) >> (lane & 32u));
-        const uint32_t w = idx >> 5;
-        if ((lane & 31u) == 0u && w < nWords && word) sel[w] = subtract ? (sel[w] & ~word) : (sel[w] | word);
+        selection_apply(attr_member<CLS>(a, e, A, idx, ci, v) && gsm::AttributeInRange(v, lo, hi), idx, lane, sel, nWords, subtract);
     }
 }
 
@@ -214,11 +213,6 @@ __global__ __launch_bounds__(256) void attr_gather_kernel(const uint32_t* __rest
 // recorded whenever the call succeeds; the histogram's contention variant (-1: the library's choice; else attr_hist_variant's bits)
 enum { kAttrEvStart = 0, kAttrEvEnd, kAttrEvSortStart, kAttrEvSortEnd, kAttrEvents };
 struct AttrProbe { hipEvent_t ev[kAttrEvents]; int variant; };
-static hipError_t attr_mark(const AttrProbe* probe, int from, int to, hipStream_t st) {
-    if (!probe) return hipSuccess;
-    for (int k = from; k <= to; ++k) { const hipError_t e = hipEventRecord(probe->ev[k], st); if (e != hipSuccess) return e; }
-    return hipSuccess;
-}
 
 // the refusals every entry point shares; fills what the kernels take
 static int32_t attr_begin(gs_renderer* r, int32_t attr, const float* point, int32_t scope, AttrArgs& A) {
@@ -253,21 +247,19 @@ static int32_t attr_values_impl(gs_renderer* r, int32_t attr, const float* point
     if (count != (size_t)r->n) return fail(GS_ERR_INVALID_ARGUMENT, "attribute_values: count must be the renderer's splat count");
     hipStream_t st = r->ctx->stream;
     DevBuf<uint32_t> out;
-    const int32_t rc = [&]() -> int32_t {
+    return drain(st, [&]() -> int32_t {
         GS_HIP(out.alloc(((size_t)r->n + 16) * 4));
-        GS_HIP(attr_mark(probe, kAttrEvStart, kAttrEvStart, st));
+        GS_HIP(mark_events(events_of(probe), kAttrEvStart, kAttrEvStart, st));
         if (r->n) {
 #define GS_ATTR_LAUNCH(C) hipLaunchKernelGGL(attr_values_kernel<C>, dim3(attr_grid(r, 8u)), dim3(256), 0, st, asset_view(r), edit_view(r), A, attr_chunks(r), out.get())
             GS_ATTR_CLASS_SWITCH(gsm::AttributeClass(attr), GS_ATTR_LAUNCH)
 #undef GS_ATTR_LAUNCH
             GS_HIP(hipGetLastError());
         }
-        GS_HIP(attr_mark(probe, kAttrEvEnd, kAttrEvSortEnd, st));
+        GS_HIP(mark_events(events_of(probe), kAttrEvEnd, kAttrEvSortEnd, st));
         if (r->n) GS_HIP(hipMemcpyAsync(values_out, out.get(), (size_t)r->n * 4, hipMemcpyDeviceToHost, st));
         return GS_OK;
-    }();
-    const hipError_t hs = hipStreamSynchronize(st);                // whatever failed: nothing in flight outlives the buffer
-    return rc == GS_OK && hs != hipSuccess ? fail_hip(hs, "attribute_values", __FILE__, __LINE__) : rc;
+    }(), "attribute_values");
 }
 
 static int32_t attr_select_impl(gs_renderer* r, int32_t attr, const float* point, float lo, float hi, int32_t subtract, const AttrProbe* probe) {
@@ -277,7 +269,7 @@ static int32_t attr_select_impl(gs_renderer* r, int32_t attr, const float* point
     GS_TRY(edit_ensure(r));
     hist_mutated(r, true);
     hipStream_t st = r->ctx->stream;
-    GS_HIP(attr_mark(probe, kAttrEvStart, kAttrEvStart, st));
+    GS_HIP(mark_events(events_of(probe), kAttrEvStart, kAttrEvStart, st));
     if (r->n && lo <= hi) {                                        // lo > hi: nothing is in the range
 #define GS_ATTR_LAUNCH(C) hipLaunchKernelGGL(attr_select_kernel<C>, dim3(attr_grid(r, 8u)), dim3(256), 0, st, asset_view(r), edit_view(r), A, attr_chunks(r), lo, hi, \
                                              r->editSelected.get(), (uint32_t)bit_words(r->n), subtract ? 1u : 0u)
@@ -285,7 +277,7 @@ static int32_t attr_select_impl(gs_renderer* r, int32_t attr, const float* point
 #undef GS_ATTR_LAUNCH
         GS_HIP(hipGetLastError());
     }
-    GS_HIP(attr_mark(probe, kAttrEvEnd, kAttrEvSortEnd, st));
+    GS_HIP(mark_events(events_of(probe), kAttrEvEnd, kAttrEvSortEnd, st));
     return edit_selected_to_lanes(r);
 }
 
@@ -300,20 +292,18 @@ static int32_t attr_stats_impl(gs_renderer* r, int32_t attr, const float* point,
     const int32_t rc = [&]() -> int32_t {
         GS_HIP(acc.alloc(accBytes));
         GS_HIP(hipMemsetAsync(acc, 0, accBytes, st));
-        GS_HIP(attr_mark(probe, kAttrEvStart, kAttrEvStart, st));
+        GS_HIP(mark_events(events_of(probe), kAttrEvStart, kAttrEvStart, st));
         if (r->n) {
 #define GS_ATTR_LAUNCH(C) hipLaunchKernelGGL(attr_stats_kernel<C>, dim3(attr_grid(r, 8u)), dim3(256), 0, st, asset_view(r), edit_view(r), A, attr_chunks(r), acc.get())
             GS_ATTR_CLASS_SWITCH(gsm::AttributeClass(attr), GS_ATTR_LAUNCH)
 #undef GS_ATTR_LAUNCH
             GS_HIP(hipGetLastError());
         }
-        GS_HIP(attr_mark(probe, kAttrEvEnd, kAttrEvSortEnd, st));
+        GS_HIP(mark_events(events_of(probe), kAttrEvEnd, kAttrEvSortEnd, st));
         GS_HIP(hipMemcpyAsync(rows, acc.get(), accBytes, hipMemcpyDeviceToHost, st));
         return GS_OK;
     }();
-    const hipError_t hs = hipStreamSynchronize(st);
-    if (rc != GS_OK) return rc;
-    if (hs != hipSuccess) return fail_hip(hs, "attribute_stats", __FILE__, __LINE__);
+    GS_TRY(drain(st, rc, "attribute_stats"));
     uint32_t host[4] = { 0u, 0u, 0u, 0u };
     for (uint32_t k = 0; k < kAttrSlots; ++k) {                    // integer sums and maxima: any grouping gives the same words
         const uint32_t* row = rows + k * kAttrSlotWords;
@@ -351,10 +341,10 @@ static int32_t attr_histogram_impl(gs_renderer* r, int32_t attr, const float* po
     const int variant = attr_hist_variant(probe);
     const uint32_t copies = ((variant & 2) && words <= 1024u) ? 4u : 1u;
     DevBuf<uint32_t> hist;
-    const int32_t rc = [&]() -> int32_t {
+    return drain(st, [&]() -> int32_t {
         GS_HIP(hist.alloc((size_t)words * 4));
         GS_HIP(hipMemsetAsync(hist, 0, (size_t)words * 4, st));
-        GS_HIP(attr_mark(probe, kAttrEvStart, kAttrEvStart, st));
+        GS_HIP(mark_events(events_of(probe), kAttrEvStart, kAttrEvStart, st));
         if (r->n) {
             const size_t lds = (size_t)words * copies * 4;
 #define GS_ATTR_LAUNCH_V(C, G) hipLaunchKernelGGL((attr_hist_kernel<C, G>), dim3(attr_grid(r, 4u)), dim3(256), lds, st, asset_view(r), edit_view(r), A, attr_chunks(r), lo, hi, s, \
@@ -365,12 +355,10 @@ static int32_t attr_histogram_impl(gs_renderer* r, int32_t attr, const float* po
 #undef GS_ATTR_LAUNCH_V
             GS_HIP(hipGetLastError());
         }
-        GS_HIP(attr_mark(probe, kAttrEvEnd, kAttrEvSortEnd, st));
+        GS_HIP(mark_events(events_of(probe), kAttrEvEnd, kAttrEvSortEnd, st));
         GS_HIP(hipMemcpyAsync(hist_out, hist.get(), (size_t)words * 4, hipMemcpyDeviceToHost, st));
         return GS_OK;
-    }();
-    const hipError_t hs = hipStreamSynchronize(st);
-    return rc == GS_OK && hs != hipSuccess ? fail_hip(hs, "attribute_histogram", __FILE__, __LINE__) : rc;
+    }(), "attribute_histogram");
 }
 
 static int32_t attr_ranks_impl(gs_renderer* r, int32_t attr, const float* point, int32_t scope, const uint32_t* ranks, uint32_t rank_count, float* values_out,
@@ -392,7 +380,7 @@ static int32_t attr_ranks_impl(gs_renderer* r, int32_t attr, const float* point,
     const uint32_t n = r->n;
     std::vector<uint32_t> got(rank_count, kAttrNotAlive);
     const int32_t rc = [&]() -> int32_t {
-        GS_HIP(attr_mark(probe, kAttrEvStart, kAttrEvStart, st));
+        GS_HIP(mark_events(events_of(probe), kAttrEvStart, kAttrEvStart, st));
         if (n) {
             GS_HIP(keys.alloc(((size_t)n + 16) * 4));
             GS_HIP(vals.alloc(((size_t)n + 16) * 4));              // the sorter moves pairs: a payload nobody reads
@@ -406,12 +394,12 @@ static int32_t attr_ranks_impl(gs_renderer* r, int32_t attr, const float* point,
 #undef GS_ATTR_LAUNCH
             GS_HIP(hipGetLastError());
             GS_HIP(hipMemcpyAsync(rows, counter.get(), rowBytes, hipMemcpyDeviceToHost, st));
-            GS_HIP(attr_mark(probe, kAttrEvSortStart, kAttrEvSortStart, st));
+            GS_HIP(mark_events(events_of(probe), kAttrEvSortStart, kAttrEvSortStart, st));
             GS_TRY(enqueue_histogram(ctx, st, keys, n, nullptr, 4, 255u, control.get(), sort));
             GS_TRY(enqueue_sort_passes(ctx, st, sort, control.get(), keys, vals, n, nullptr, 4, 255u));
-            GS_HIP(attr_mark(probe, kAttrEvSortEnd, kAttrEvSortEnd, st));
+            GS_HIP(mark_events(events_of(probe), kAttrEvSortEnd, kAttrEvSortEnd, st));
         } else {
-            GS_HIP(attr_mark(probe, kAttrEvSortStart, kAttrEvSortEnd, st));
+            GS_HIP(mark_events(events_of(probe), kAttrEvSortStart, kAttrEvSortEnd, st));
         }
         if (rank_count && n) {
             // the population m is not known on the host yet: a rank at or beyond it reads a key of all ones, the word the gather writes for it anyway
@@ -423,13 +411,11 @@ static int32_t attr_ranks_impl(gs_renderer* r, int32_t attr, const float* point,
             GS_HIP(hipGetLastError());
             GS_HIP(hipMemcpyAsync(got.data(), outDev.get(), (size_t)rank_count * 4, hipMemcpyDeviceToHost, st));
         }
-        GS_HIP(attr_mark(probe, kAttrEvEnd, kAttrEvEnd, st));
+        GS_HIP(mark_events(events_of(probe), kAttrEvEnd, kAttrEvEnd, st));
         if (n) GS_HIP(hipMemcpyAsync(&err, &control.get()->error, 4, hipMemcpyDeviceToHost, st));
         return GS_OK;
     }();
-    const hipError_t hs = hipStreamSynchronize(st);                // whatever failed: nothing in flight outlives the buffers
-    if (rc != GS_OK) return rc;
-    if (hs != hipSuccess) return fail_hip(hs, "attribute_ranks", __FILE__, __LINE__);
+    GS_TRY(drain(st, rc, "attribute_ranks"));
     if (err) return fail(GS_ERR_SORT_TIMEOUT, "attribute_ranks: a bounded look-back spin expired");
     uint32_t m = 0;
     for (uint32_t k = 0; k < kAttrSlots; ++k) m += rows[k * kAttrSlotWords];
@@ -469,7 +455,7 @@ int32_t gs_renderer_edit_attribute_ranks(gs_renderer* r, int32_t attr, const flo
 // A measurement aid of scripts/attribute_timing.py, which binds it itself: not declared in gsplat_c.h, not part of the ABI.  One whole call with events
 // inside it -- op 0: gs_renderer_edit_select_range(attr, lo, hi, 0); 1: _attribute_stats; 2: _attribute_histogram at `bins` with contention variant
 // `variant` (-1: the library's; bit 0 the wave fold over four bins, bit 1 per-wave LDS copies, bit 2 the fold over one bin); 3: _attribute_ranks of rank 0; 4: _attribute_values; 5: the floor --
-// the alive count of the export (export_count_kernel and its scan over the chunks), which reads positions, deleted words and cutouts only.
+// the alive count of the export (enqueue_alive_counts: alive_count_kernel and its scan over the chunks), which reads positions, deleted words and cutouts only.
 // ms[0] = GPU milliseconds of the call's kernels, ms[1] = of the sort inside op 3 (else 0).
 __attribute__((visibility("default"))) int32_t gs_attribute_times_for_scripts(gs_renderer* r, int32_t op, int32_t attr, const float* point, int32_t scope, float lo, float hi,
                                                                                uint32_t bins, int32_t variant, float ms[2]) {
@@ -497,9 +483,9 @@ __attribute__((visibility("default"))) int32_t gs_attribute_times_for_scripts(gs
         DevBuf<uint32_t> counts, base;
         GS_HIP(counts.alloc((size_t)chunks * 4));
         GS_HIP(base.alloc(((size_t)chunks + 1) * 4));
-        GS_HIP(attr_mark(&probe, kAttrEvStart, kAttrEvStart, st));
-        const int32_t rc = enqueue_alive_counts(st, asset_view(r), edit_view(r), chunks, counts.get(), base.get());
-        GS_HIP(attr_mark(&probe, kAttrEvEnd, kAttrEvSortEnd, st));
+        GS_HIP(mark_events(probe.ev, kAttrEvStart, kAttrEvStart, st));
+        const int32_t rc = enqueue_alive_counts(st, asset_view(r), edit_view(r), false, chunks, counts.get(), base.get());
+        GS_HIP(mark_events(probe.ev, kAttrEvEnd, kAttrEvSortEnd, st));
         GS_HIP(hipStreamSynchronize(st));
         GS_TRY(rc);
     }

@@ -5,11 +5,12 @@
 // host and device from one text.  gs_asset_download_blobs reads any asset back.
 //
 // Plain launches on the context's stream; the only kernels that wait on other workgroups are the library's Onesweep passes.
-//   1. alive list + bounds   export_count / export_scan (gs_export.hip), then bake_alive: alive[j] = source index of the j-th alive splat in index order,
-//                            and per workgroup the min / max of its alive positions; bake_bounds folds the partials (min / max: exact in any order).
-//   2. order                 morton = 1: bake_codes writes the 63-bit code of every alive splat as two words; two stable Onesweep sorts -- the low word
-//                            with payload = rank, then the high word gathered through the payload, 31 bits -- leave the payload in (code, rank) order.
-//                            The sort state is the bake's own: the renderer's may be in use.
+//   1. alive list + bounds   enqueue_alive_counts, then enqueue_alive_list (gs_compact.hip): alive[j] = source index of the j-th alive splat in index order,
+//                            and per workgroup the min / max of its alive positions; bounds_fold folds the partials (min / max: exact in any order).
+//   2. order                 morton = 1: bake_codes writes the 63-bit code of every alive splat as two words; TwoWordSort (gs_compact.hip) -- two stable
+//                            Onesweep sorts, the low word with payload = rank, then the high word gathered through the payload, 31 bits -- leaves the
+//                            payload in (code, rank) order.  The sort state is the bake's own: the renderer's may be in use.  Each sort has an error
+//                            word of its own and bake_finish reads both.
 //   3. encode                one 256-thread workgroup per DESTINATION chunk, so that the chunk record is workgroup-uniform; lane k decodes source splat
 //                            alive[order[256 c + k]] (its own source chunk ci = src >> 8) with gsm::LoadSplatDataFull from the renderer's current view.  The
 //                            26 reductions run by cross-lane shuffles inside a wave and through LDS across the four.  Stores: pos / other per lane (2-16
@@ -36,24 +37,12 @@
 #include <new>
 
 #include "gs_common.h"
+#include "gs_block.h"
 #include "gs_splat_file.h"
 
 namespace gs {
 
-constexpr uint32_t kBakeReduceThreads = 1024;
-
 struct BakeDst { uint8_t* pos; uint8_t* other; uint8_t* color; uint8_t* sh; uint8_t* chunk; uint32_t n; gsm::BakeFormats f; const uint32_t* shIndex; };   // shIndex: Cluster* SH targets only
-
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = fminf(v, __shfl_xor(v, d));
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d));
-    return v;
-}
 
 // Where the kernels of steps 2 and 3 take splat j from (j: a place in the source's own order, before the Morton reorder).
 // BakeRendererSource: the j-th alive splat of a renderer, decoded from its current view.  BakeArraySource: splat j of six raw arrays in device
@@ -86,112 +75,18 @@ struct BakeSpzSource {
     __device__ __forceinline__ void record(uint32_t j, gsm::BakeRec& rec) const { gsm::SpzRecord(s, j, rec); }
 };
 
-// alive[base[chunk] + rank] = idx for the alive splats of source chunk blockIdx.x; partial[chunk][0..2 / 3..5] = min / max of their positions -- as
-// stored, or (X.through: the SPZ export's bounds) through the matrix a baked export moves them by
-__global__ __launch_bounds__(256) void bake_alive_kernel(gsm::AssetView a, gsm::EditView e, AliveXform X, const uint32_t* __restrict__ base,
-                                                         uint32_t* __restrict__ alive, float* __restrict__ partial) {
-    __shared__ uint32_t s_cnt[4];
-    __shared__ float s_red[4][6];
-    const uint32_t idx = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    gsm::V3 pos; bool cut;
-    const bool mine = export_alive(a, e, idx, blockIdx.x, pos, cut);
-    const unsigned long long bal = __ballot(mine);
-    const uint32_t slot = (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0u) s_cnt[wave] = (uint32_t)__popcll(bal);
-    const float inf = gsm::u2f(0x7f800000u);
-    float p[3] = { pos.x, pos.y, pos.z };
-    if (X.through != 0u) {                                         // BakeSplatTransform's position
-#pragma unroll
-        for (int c = 0; c < 3; ++c) p[c] = gsm::mrow(X.m, c, pos.x, pos.y, pos.z);
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float mn = wave_min(mine ? p[c] : inf), mx = wave_max(mine ? p[c] : -inf);
-        if (lane == 0u) { s_red[wave][c] = mn; s_red[wave][3 + c] = mx; }
-    }
-    __syncthreads();
-    uint32_t first = base[blockIdx.x];
-    for (uint32_t w = 0; w < wave; ++w) first += s_cnt[w];
-    if (mine) alive[first + slot] = idx;
-    if (threadIdx.x < 3u) partial[blockIdx.x * 6u + threadIdx.x] = fminf(fminf(s_red[0][threadIdx.x], s_red[1][threadIdx.x]), fminf(s_red[2][threadIdx.x], s_red[3][threadIdx.x]));
-    else if (threadIdx.x < 6u) partial[blockIdx.x * 6u + threadIdx.x] = fmaxf(fmaxf(s_red[0][threadIdx.x], s_red[1][threadIdx.x]), fmaxf(s_red[2][threadIdx.x], s_red[3][threadIdx.x]));
-}
-
-// the same partials for raw arrays: partial[block][0..2 / 3..5] = min / max of positions [256 block, 256 block + 256) below n
-__global__ __launch_bounds__(256) void bake_array_bounds_kernel(const float* __restrict__ pos, uint32_t n, float* __restrict__ partial) {
-    __shared__ float s_red[4][6];
-    const uint32_t idx = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const bool mine = idx < n;
-    const float inf = gsm::u2f(0x7f800000u);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float p = mine ? pos[(size_t)idx * 3u + c] : 0.0f;
-        const float mn = wave_min(mine ? p : inf), mx = wave_max(mine ? p : -inf);
-        if (lane == 0u) { s_red[wave][c] = mn; s_red[wave][3 + c] = mx; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 3u) partial[blockIdx.x * 6u + threadIdx.x] = fminf(fminf(s_red[0][threadIdx.x], s_red[1][threadIdx.x]), fminf(s_red[2][threadIdx.x], s_red[3][threadIdx.x]));
-    else if (threadIdx.x < 6u) partial[blockIdx.x * 6u + threadIdx.x] = fmaxf(fmaxf(s_red[0][threadIdx.x], s_red[1][threadIdx.x]), fmaxf(s_red[2][threadIdx.x], s_red[3][threadIdx.x]));
-}
-
-// the same partials for any source whose every splat is alive: the pre-pass as a template over Src::position
+// the alive list's partials (alive_list, gs_compact.hip) for a source whose every splat is alive: partial[block][0..2 / 3..5] = min / max of the
+// positions [256 block, 256 block + 256) below n
 template <class Src>
 __global__ __launch_bounds__(256) void bake_source_bounds_kernel(Src src, uint32_t n, float* __restrict__ partial) {
     __shared__ float s_red[4][6];
-    const uint32_t idx = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
     const bool mine = idx < n;
-    const float inf = gsm::u2f(0x7f800000u);
     const gsm::V3 pos = mine ? src.position(idx) : gsm::V3{ 0.0f, 0.0f, 0.0f };
     const float p[3] = { pos.x, pos.y, pos.z };
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float mn = wave_min(mine ? p[c] : inf), mx = wave_max(mine ? p[c] : -inf);
-        if (lane == 0u) { s_red[wave][c] = mn; s_red[wave][3 + c] = mx; }
-    }
+    block_bounds(mine, p, threadIdx.x & 63u, threadIdx.x >> 6, s_red);
     __syncthreads();
-    if (threadIdx.x < 3u) partial[blockIdx.x * 6u + threadIdx.x] = fminf(fminf(s_red[0][threadIdx.x], s_red[1][threadIdx.x]), fminf(s_red[2][threadIdx.x], s_red[3][threadIdx.x]));
-    else if (threadIdx.x < 6u) partial[blockIdx.x * 6u + threadIdx.x] = fmaxf(fmaxf(s_red[0][threadIdx.x], s_red[1][threadIdx.x]), fmaxf(s_red[2][threadIdx.x], s_red[3][threadIdx.x]));
-}
-// the pre-pass of a source: the six arrays keep the kernel over their positions array as it is
-static void bake_launch_source_bounds(hipStream_t st, const BakeArraySource& src, uint32_t n, float* partial) {
-    hipLaunchKernelGGL(bake_array_bounds_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, src.in.pos, n, partial);
-}
-template <class Src>
-static void bake_launch_source_bounds(hipStream_t st, const Src& src, uint32_t n, float* partial) {
-    hipLaunchKernelGGL(bake_source_bounds_kernel<Src>, dim3((n + 255u) / 256u), dim3(256), 0, st, src, n, partial);
-}
-
-// bounds[0..2 / 3..5] = min / max over the partials; one workgroup
-__global__ __launch_bounds__(kBakeReduceThreads) void bake_bounds_kernel(const float* __restrict__ partial, uint32_t chunks, float* __restrict__ bounds) {
-    __shared__ float s_red[kBakeReduceThreads / 64][6];
-    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
-    const float inf = gsm::u2f(0x7f800000u);
-    float v[6] = { inf, inf, inf, -inf, -inf, -inf };
-    for (uint32_t i = t; i < chunks; i += kBakeReduceThreads) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { v[c] = fminf(v[c], partial[i * 6u + c]); v[3 + c] = fmaxf(v[3 + c], partial[i * 6u + 3 + c]); }
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float mn = wave_min(v[c]), mx = wave_max(v[3 + c]);
-        if (lane == 0u) { s_red[wave][c] = mn; s_red[wave][3 + c] = mx; }
-    }
-    __syncthreads();
-    if (t < 6u) {
-        float r = s_red[0][t];
-        for (uint32_t w = 1; w < kBakeReduceThreads / 64; ++w) r = t < 3u ? fminf(r, s_red[w][t]) : fmaxf(r, s_red[w][t]);
-        bounds[t] = r;
-    }
-}
-
-// step 1's second half on st, after enqueue_alive_counts: the alive list, the per-chunk partials and their fold (the bake's, and the SPZ export's in
-// gs_export.hip)
-int32_t enqueue_alive_list(hipStream_t st, const gsm::AssetView& a, const gsm::EditView& e, const AliveXform& X, uint32_t chunks, const uint32_t* base,
-                           uint32_t* alive, float* partial, float* bounds) {
-    hipLaunchKernelGGL(bake_alive_kernel, dim3(chunks), dim3(256), 0, st, a, e, X, base, alive, partial);
-    hipLaunchKernelGGL(bake_bounds_kernel, dim3(1), dim3(kBakeReduceThreads), 0, st, (const float*)partial, chunks, bounds);
-    GS_HIP(hipGetLastError());
-    return GS_OK;
+    block_bounds_store(s_red, partial + blockIdx.x * 6u);
 }
 
 // the Morton code of the source's splat j as two sort keys, and the identity payload
@@ -202,11 +97,6 @@ __global__ __launch_bounds__(256) void bake_codes_kernel(Src src, const float* _
     if (j >= total) return;
     const unsigned long long code = gsm::BakeMortonCode(src.position(j), bounds, bounds + 3);
     lo[j] = (uint32_t)code; hi[j] = (uint32_t)(code >> 32); rank[j] = j;
-}
-
-__global__ __launch_bounds__(256) void bake_gather_kernel(const uint32_t* __restrict__ hi, const uint32_t* __restrict__ rank, uint32_t total, uint32_t* __restrict__ out) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i < total) out[i] = hi[rank[i]];
 }
 
 // bytes in { 2, 4, 6, 8, 10, 12, 16, 18 } of w (5 words) to p; p is `bytes`-strided from an aligned base: a multiple of 4 bytes = dword stores, else
@@ -376,31 +266,18 @@ __global__ __launch_bounds__(256) void bake_encode_kernel(Src src, const uint32_
 // ---- host -----------------------------------------------------------------------------------------------------------------------------
 // everything a bake holds besides the asset it makes: freed when the call returns
 struct BakeRun {
-    DevBuf<uint32_t> counts, base, alive, lo, hi, hi2, rank;
+    DevBuf<uint32_t> counts, base, alive;
     DevBuf<float> partial, bounds;
-    SortState sort;
-    DevBuf<SortControl> control;
+    TwoWordSort keys;                       // morton = 1: the Morton codes and their order
     DevBuf<float> shRows, shMeans;          // a Cluster* SH target: the n x 45 SH rows in destination order, the K x 45 means,
     DevBuf<uint32_t> shIndex;               // the n table indices
     ClusterRun cluster;                     // and the Lloyd loop's own state
 };
 
-
-static int32_t bake_sort(gs_context* ctx, BakeRun& run, uint32_t* keys, uint32_t total, uint32_t keyBits) {
-    const int passes = (int)((keyBits + 7u) / 8u);
-    const uint32_t lastMask = (1u << (keyBits - 8u * (uint32_t)(passes - 1))) - 1u;
-    GS_TRY(enqueue_histogram(ctx, ctx->stream, keys, total, nullptr, passes, lastMask, run.control, run.sort));
-    return enqueue_sort_passes(ctx, ctx->stream, run.sort, run.control, keys, run.rank, total, nullptr, passes, lastMask);
-}
-
 // what steps 2 and 3 need besides the source: the sort's buffers and state (morton = 1), the palette's (a Cluster* SH target)
 static int32_t bake_run_alloc(gs_context* ctx, const gs_import_formats* f, BakeRun& run, uint32_t total) {
     GS_HIP(run.bounds.alloc(6 * 4));
-    if (f->morton) {
-        for (DevBuf<uint32_t>* b : { &run.lo, &run.hi, &run.hi2, &run.rank }) GS_HIP(b->alloc(((size_t)total + 16) * 4));
-        GS_TRY(sort_state_create(ctx, run.sort, total, true));
-        GS_HIP(run.control.alloc(sizeof(SortControl)));
-    }
+    if (f->morton) GS_TRY(run.keys.alloc(ctx, total));
     const uint32_t K = gsm::shClusterCount(f->sh_format);
     if (K) {                                                       // n x 184 bytes + the subset and the sort state: freed with `run`
         GS_HIP(run.shRows.alloc((size_t)total * 180));
@@ -428,15 +305,13 @@ static int32_t bake_enqueue_from(gs_context* ctx, const Src& src, const gs_impor
     hipStream_t st = ctx->stream;
     const uint32_t blocks = (total + 255u) / 256u;
     if (f->morton) {
-        hipLaunchKernelGGL(bake_codes_kernel<Src>, dim3(blocks), dim3(256), 0, st, src, (const float*)run.bounds.get(), total, run.lo.get(), run.hi.get(), run.rank.get());
+        hipLaunchKernelGGL(bake_codes_kernel<Src>, dim3(blocks), dim3(256), 0, st, src, (const float*)run.bounds.get(), total, run.keys.lo.get(), run.keys.hi.get(),
+                           run.keys.rank.get());
         GS_HIP(hipGetLastError());
-        GS_TRY(bake_sort(ctx, run, run.lo, total, 32u));
-        hipLaunchKernelGGL(bake_gather_kernel, dim3(blocks), dim3(256), 0, st, (const uint32_t*)run.hi.get(), (const uint32_t*)run.rank.get(), total, run.hi2.get());
-        GS_HIP(hipGetLastError());
-        GS_TRY(bake_sort(ctx, run, run.hi2, total, 31u));
+        GS_TRY(run.keys.enqueue(ctx, total));
     }
     if (ev) GS_HIP(hipEventRecord(ev[4], st));
-    const uint32_t* order = f->morton ? (const uint32_t*)run.rank.get() : (const uint32_t*)nullptr;
+    const uint32_t* order = f->morton ? (const uint32_t*)run.keys.rank.get() : (const uint32_t*)nullptr;
     const uint32_t K = gsm::shClusterCount(f->sh_format);
     if (K) {
         if (cev) GS_HIP(hipEventRecord(cev[0], st));
@@ -464,7 +339,7 @@ static int32_t bake_enqueue(gs_renderer* r, const gs_import_formats* f, BakeRun&
     GS_TRY(bake_run_alloc(ctx, f, run, total));
     const BakeRendererSource src = { asset_view(r), run.alive.get() };
     if (ev) GS_HIP(hipEventRecord(ev[2], st));
-    GS_TRY(enqueue_alive_list(st, src.a, edit_view(r), AliveXform{}, chunks, run.base.get(), run.alive.get(), run.partial.get(), run.bounds.get()));
+    GS_TRY(enqueue_alive_list(st, src.a, edit_view(r), false, false, AliveXform{}, chunks, run.base.get(), run.alive.get(), run.partial.get(), run.bounds.get()));
     if (ev) GS_HIP(hipEventRecord(ev[3], st));
     return bake_enqueue_from(ctx, src, f, run, total, d, colorBytes, ev, cev);
 }
@@ -503,18 +378,15 @@ static BakeDst bake_dst_of(const gs_asset* a, uint32_t total, const gs_import_fo
 // flight outlives the transient buffers or the asset -- and the asset's view filled in, or the asset destroyed
 static int32_t bake_finish(gs_context* ctx, int32_t rc, BakeRun& run, const gs_import_formats* f, gs_asset* a, uint32_t total, float hostBounds[6]) {
     hipStream_t st = ctx->stream;
-    uint32_t sortError = 0, clusterSortError = 0;
+    uint32_t sortError[2] = { 0u, 0u }, clusterSortError = 0;
     if (rc == GS_OK) {
         hipError_t he = hipMemcpyAsync(hostBounds, run.bounds.get(), 6 * sizeof(float), hipMemcpyDeviceToHost, st);
-        if (he == hipSuccess && f->morton) he = hipMemcpyAsync(&sortError, &run.control.get()->error, 4, hipMemcpyDeviceToHost, st);
+        if (he == hipSuccess && f->morton) he = run.keys.enqueue_error_readback(st, sortError);
         if (he == hipSuccess && f->sh_format > GS_SH_NORM6) he = hipMemcpyAsync(&clusterSortError, run.cluster.error.get(), 4, hipMemcpyDeviceToHost, st);
         if (he != hipSuccess) rc = fail_hip(he, "bake: read back", __FILE__, __LINE__);
     }
-    {
-        const hipError_t hs = hipStreamSynchronize(st);
-        if (rc == GS_OK && hs != hipSuccess) rc = fail_hip(hs, "bake", __FILE__, __LINE__);
-    }
-    if (rc == GS_OK && (sortError | clusterSortError)) rc = fail(GS_ERR_SORT_TIMEOUT, "bake: a bounded look-back spin expired");
+    rc = drain(st, rc, "bake");
+    if (rc == GS_OK && (sortError[0] | sortError[1] | clusterSortError)) rc = fail(GS_ERR_SORT_TIMEOUT, "bake: a bounded look-back spin expired");
     if (rc != GS_OK) { (void)gs_asset_destroy(a); return rc; }
     gsm::AssetView& v = a->view;
     v.pos = (const uint8_t*)a->blobs[0]; v.other = (const uint8_t*)a->blobs[1]; v.color = (const uint8_t*)a->blobs[2]; v.sh = (const uint8_t*)a->blobs[3];
@@ -544,15 +416,10 @@ static int32_t bake_impl(gs_renderer* r, const gs_import_formats* f, gs_asset** 
     GS_HIP(run.counts.alloc((size_t)chunks * 4));
     GS_HIP(run.base.alloc(((size_t)chunks + 1) * 4));
     if (ev) GS_HIP(hipEventRecord(ev[0], st));
-    GS_TRY(enqueue_alive_counts(st, asset_view(r), edit_view(r), chunks, run.counts.get(), run.base.get()));
+    GS_TRY(enqueue_alive_counts(st, asset_view(r), edit_view(r), false, chunks, run.counts.get(), run.base.get()));
     if (ev) GS_HIP(hipEventRecord(ev[1], st));
     uint32_t total = 0;
-    {
-        const hipError_t he = hipMemcpyAsync(&total, run.base.get() + chunks, 4, hipMemcpyDeviceToHost, st);
-        const hipError_t hs = hipStreamSynchronize(st);            // nothing in flight outlives the buffers
-        GS_HIP(he);
-        GS_HIP(hs);
-    }
+    GS_TRY(drain(st, [&]() -> int32_t { GS_HIP(hipMemcpyAsync(&total, run.base.get() + chunks, 4, hipMemcpyDeviceToHost, st)); return GS_OK; }(), "bake: the alive count"));
     if (total == 0u) return fail(GS_ERR_INVALID_ARGUMENT, "bake: no alive splat");
     uint64_t need[5];
     GS_TRY(gs_import_blob_sizes(total, f, need));               // (a Cluster* SH target needs more alive splats than table entries: the importer's rule)
@@ -588,9 +455,8 @@ static int32_t import_from_source(gs_context* ctx, const Src& src, const gs_impo
         if (rcAsset != GS_OK) { (void)hipStreamSynchronize(st); return rcAsset; }
     }
     int32_t rc = [&]() -> int32_t {
-        bake_launch_source_bounds(st, src, total, run.partial.get());
-        hipLaunchKernelGGL(bake_bounds_kernel, dim3(1), dim3(kBakeReduceThreads), 0, st, (const float*)run.partial.get(), blocks, run.bounds.get());
-        GS_HIP(hipGetLastError());
+        hipLaunchKernelGGL(bake_source_bounds_kernel<Src>, dim3(blocks), dim3(256), 0, st, src, total, run.partial.get());
+        GS_TRY(enqueue_bounds_fold(st, run.partial.get(), blocks, run.bounds.get(), false));
         if (ev) GS_HIP(hipEventRecord(ev[3], st));
         return bake_enqueue_from(ctx, src, f, run, total, bake_dst_of(a, total, f), need[2], ev, cev);
     }();
@@ -758,14 +624,11 @@ int32_t gs_asset_download_blobs(const gs_asset* asset, void* const blobs[5], con
     hipError_t he = hipSuccess;
     for (int k = 0; k < 5 && he == hipSuccess; ++k)
         if (blobs[k] && sizes[k]) he = hipMemcpyAsync(blobs[k], asset->blobs[k], (size_t)sizes[k], hipMemcpyDeviceToHost, st);
-    const hipError_t hs = hipStreamSynchronize(st);
-    GS_HIP(he);
-    GS_HIP(hs);
-    return GS_OK;
+    return drain(st, he == hipSuccess ? GS_OK : fail_hip(he, "download_blobs", __FILE__, __LINE__), "download_blobs");
 }
 
 // A measurement aid of scripts/bake_timing.py, which binds it itself: not declared in gsplat_c.h, not part of the ABI.  One whole bake whose asset is
-// destroyed again; ms[0..3] = GPU milliseconds of export_count + export_scan, of the alive list + bounds, of the Morton codes + the two sorts, of the encode.
+// destroyed again; ms[0..3] = GPU milliseconds of alive_count + export_scan, of the alive list + bounds, of the Morton codes + the two sorts, of the encode.
 __attribute__((visibility("default"))) int32_t gs_bake_stage_times_for_scripts(gs_renderer* r, const gs_import_formats* formats, float ms[4], uint32_t* alive) {
     if (!r || !formats || !ms || !alive) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
     GS_HIP(hipSetDevice(r->ctx->device));

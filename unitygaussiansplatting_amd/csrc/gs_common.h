@@ -509,7 +509,7 @@ void hist_transform(gs_renderer* r);                 // ... a transform: hist_mu
 int32_t hist_clear(gs_renderer* r);                  // every entry released (waits for the stream first)
 void hist_forget(gs_renderer* r);                    // ... without waiting: every entry dropped now, its memory released at the next call of the history's that waits
 void hist_carry(gs_renderer* to, const gs_renderer* from);   // a resize: the switch, the budget and the counters move on to the new state, the entries do not
-// gs_export.hip: base[i] = counts[0] + .. + counts[i - 1] for i in [0, n] on st (export_scan_kernel, one workgroup)
+// gs_compact.hip: base[i] = counts[0] + .. + counts[i - 1] for i in [0, n] on st (export_scan_kernel, one workgroup)
 int32_t enqueue_scan(hipStream_t st, const uint32_t* counts, uint32_t* base, uint32_t n);
 // what brackets a kernel that rewrites positions (the transforms, the merge): ordering against sorts, GS_SORT_VISIBLE's history and the lanes
 int32_t edit_before_move(gs_renderer* r);
@@ -552,24 +552,43 @@ inline gsm::EditView edit_view(const gs_renderer* r) {
     return e;
 }
 inline size_t bit_words(uint32_t n) { return ((size_t)n + 31) / 32; }   // words of a 1-bit-per-splat buffer
-// export / bake (gs_export.hip): alive = idx < N, not deleted, not cut (ExportPlyFile's rule); also hands back the position and the cut flag
-__device__ __forceinline__ bool export_alive(const gsm::AssetView& a, const gsm::EditView& e, uint32_t idx, uint32_t ci, gsm::V3& pos, bool& cut) {
-    cut = false;
-    pos = { 0.0f, 0.0f, 0.0f };
-    if (idx >= a.n) return false;
-    pos = gsm::LoadSplatPosChunk(a, idx, ci);
-    cut = gsm::IsSplatCut(e, pos.x, pos.y, pos.z);
-    const bool deleted = e.deletedBits && ((e.deletedBits[idx >> 5] >> (idx & 31u)) & 1u);
-    return !cut && !deleted;
-}
-// export_count_kernel + export_scan_kernel on st: counts[c] = alive splats of chunk c, base[0 .. chunks] = their exclusive prefix and the total
-int32_t enqueue_alive_counts(hipStream_t st, const gsm::AssetView& a, const gsm::EditView& e, uint32_t chunks, uint32_t* counts, uint32_t* base);
-// bake_alive_kernel + bake_bounds_kernel on st (gs_bake.hip), after enqueue_alive_counts: alive[j] = source index of the j-th alive splat (total + 16
-// words), partial = chunks x 6 floats, bounds[0..2 / 3..5] = min / max of the alive positions -- as stored, or with X.through != 0 moved through the
-// rows 0..2 of X.m first (what a baked export does to them)
+// ---- the compaction of the alive splats and the sort of a two-word key (gs_compact.hip): what the export, the bake, the imports and the neighbour grid share ----
+// counts[c] = alive splats of chunk c (export_alive, gs_block.h; finiteOnly: and every component of the position finite -- the neighbour grid's list),
+// base[0 .. chunks] = their exclusive prefix and the total.  enqueue_alive_chunk_counts is its first launch alone (enqueue_scan, above, the second)
+int32_t enqueue_alive_counts(hipStream_t st, const gsm::AssetView& a, const gsm::EditView& e, bool finiteOnly, uint32_t chunks, uint32_t* counts, uint32_t* base);
+int32_t enqueue_alive_chunk_counts(hipStream_t st, const gsm::AssetView& a, const gsm::EditView& e, bool finiteOnly, uint32_t chunks, uint32_t* counts);
+// after enqueue_alive_counts with the same finiteOnly: alive[j] = source index of the j-th such splat (total + 16 words), partial = chunks x 6 floats,
+// bounds[0..2 / 3..5] = min / max of their positions -- as stored, or with X.through != 0 moved through the rows 0..2 of X.m first (what a baked export
+// does to them).  minOnly: the minima alone -- partial = chunks x 3 floats, bounds = 3 floats; nothing is reduced, stored or folded for the maxima
 struct AliveXform { uint32_t through = 0; float m[12] = {}; };
-int32_t enqueue_alive_list(hipStream_t st, const gsm::AssetView& a, const gsm::EditView& e, const AliveXform& X, uint32_t chunks, const uint32_t* base,
-                           uint32_t* alive, float* partial, float* bounds);
+int32_t enqueue_alive_list(hipStream_t st, const gsm::AssetView& a, const gsm::EditView& e, bool finiteOnly, bool minOnly, const AliveXform& X, uint32_t chunks,
+                           const uint32_t* base, uint32_t* alive, float* partial, float* bounds);
+// bounds[0..2 / 3..5] = min / max over `count` x 6 partials, or (minOnly) bounds[0..2] = min over `count` x 3 (one workgroup; min / max: exact in any order)
+int32_t enqueue_bounds_fold(hipStream_t st, const float* partial, uint32_t count, float* bounds, bool minOnly);
+// The stable sort of m 63-bit keys given as two words: the caller fills lo, hi and rank = identity; enqueue() sorts the low word over 32 bits with rank as
+// the payload, gathers the high word through it into hi2 and sorts that over 31 bits: rank is then the (key, index) order.  Each of the two sorts has a
+// control block, and so an error word, of its own: enqueue_histogram zeroes the block it is given
+struct TwoWordSort {
+    DevBuf<uint32_t> lo, hi, hi2, rank;
+    SortState sort;
+    DevBuf<SortControl> control;            // two blocks
+    int32_t alloc(gs_context* ctx, uint32_t m);
+    int32_t enqueue(gs_context* ctx, uint32_t m);                  // on ctx->stream
+    // err[0 .. 1] := the two sorts' error words (!= 0: a bounded look-back spin expired), valid after the caller's next synchronisation of st
+    hipError_t enqueue_error_readback(hipStream_t st, uint32_t err[2]) const;
+};
+// records ev[from .. to] on st; a null ev (no probe) does nothing.  events_of: the events of a timing script's probe, which may be null
+template <class Probe> inline const hipEvent_t* events_of(const Probe* probe) { return probe ? probe->ev : nullptr; }
+inline hipError_t mark_events(const hipEvent_t* ev, int from, int to, hipStream_t st) {
+    for (int k = from; ev && k <= to; ++k) { const hipError_t e = hipEventRecord(ev[k], st); if (e != hipSuccess) return e; }
+    return hipSuccess;
+}
+// how a call that enqueued on st ends, whatever rc it got so far: nothing in flight outlives the call's buffers, and the stream's own error is reported
+// only if nothing failed before -- with the caller's file and line, as GS_HIP reports its own
+inline int32_t drain(hipStream_t st, int32_t rc, const char* what, const char* file = __builtin_FILE(), int line = __builtin_LINE()) {
+    const hipError_t hs = hipStreamSynchronize(st);
+    return rc == GS_OK && hs != hipSuccess ? fail_hip(hs, what, file, line) : rc;
+}
 // the Cluster* SH palette on device pointers (gs_cluster.hip): what one run of the Lloyd loop holds besides the points, the means and the indices
 struct ClusterRun {
     DevBuf<float> sub;                      // the stride-sampled training subset (only when n > 200,000)

@@ -22,7 +22,8 @@
 //
 // Shape (wave64; not the reference's, which runs one thread per WORD with a 32-iteration position loop, neighbouring threads reading
 // positions 32 records apart): one thread per SPLAT, 256-thread workgroups aligned to the 256-splat chunk so that the chunk header is
-// workgroup-uniform.  The per-splat predicate (cut / hit) becomes a word through __ballot; a wave owns exactly two consecutive words, one
+// workgroup-uniform.  The per-splat predicate (cut / hit) becomes a word through __ballot (ballot_word, gs_block.h, which also holds the
+// read-modify-write the later selection tools share, selection_apply); a wave owns exactly two consecutive words, one
 // lane per word does a plain read-modify-write -- no other wave touches that word, so the reference's per-splat InterlockedOr / And is not
 // needed and the result is identical.  No word index >= ceil(N/32) is ever stored.  Counts are popcounts of the words, bounds reduce per
 // wave with __shfl_xor and across the four waves in LDS: at most nine global atomics per workgroup.
@@ -36,14 +37,12 @@
 #include <new>
 
 #include "gs_common.h"
+#include "gs_block.h"
 
 namespace gs {
 
 constexpr uint32_t kSortableMinInit = __builtin_bit_cast(uint32_t, 1.0e38f) ^ 0x80000000u;   // FloatToSortableUint(1.0e38)
 constexpr uint32_t kSortableMaxInit = ~__builtin_bit_cast(uint32_t, -1.0e38f);              // FloatToSortableUint(-1.0e38)
-
-// the word of a 64-bit ballot this lane's splat belongs to
-__device__ __forceinline__ uint32_t ballot_word(unsigned long long b, uint32_t lane) { return (uint32_t)(b >> (lane & 32u)); }
 
 // CSSelectAll (invert = 0) / CSInvertSelection (invert = 1)
 __global__ __launch_bounds__(256) void edit_select_all_kernel(gsm::AssetView a, gsm::EditView e, uint32_t* __restrict__ sel, uint32_t nWords, uint32_t invert) {
@@ -227,7 +226,7 @@ __device__ __forceinline__ void edit_select_record(const gsm::AssetView& a, cons
                                                    uint32_t* __restrict__ sel) {
     if (pr.tag != S.tag || pr.splat >= a.n) return;
     const uint32_t idx = pr.splat;
-    if (e.deletedBits && ((e.deletedBits[idx >> 5] >> (idx & 31u)) & 1u)) return;
+    if (e.deletedBits && bit_set(e.deletedBits, idx)) return;
     const gsm::V3 pos = gsm::LoadSplatPosChunk(a, idx, idx >> 8);
     if (gsm::IsSplatCut(e, pos.x, pos.y, pos.z)) return;
     if (S.subtract) atomicAnd(sel + (idx >> 5), ~(1u << (idx & 31u)));

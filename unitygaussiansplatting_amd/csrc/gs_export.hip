@@ -7,9 +7,10 @@
 // log / sqrt families the project fixes (LogDetFull, the band matrices' recurrence).
 //
 // Three plain launches, none waits on another workgroup (an offline path on shared machines: no look-back, no spinning):
-//   export_count    per 256-splat chunk, the number of splats that are alive (idx < N, not deleted, not cut): popcounts of ballots.  Reads positions,
-//                   the deleted words and the cutouts only.
-//   export_scan     exclusive prefix over the chunk counts, one workgroup looping over the array 1024 counts at a time; base[chunks] = the total.
+//   alive_count     (enqueue_alive_counts, gs_compact.hip) per 256-splat chunk, the number of splats that are alive (idx < N, not deleted, not cut):
+//                   popcounts of ballots.  Reads positions, the deleted words and the cutouts only.
+//   export_scan     (the same call) exclusive prefix over the chunk counts, one workgroup looping over the array 1024 counts at a time;
+//                   base[chunks] = the total.
 //   export_records  one 256-thread workgroup per chunk (so the chunk header is workgroup-uniform) of a range of whole chunks.  Reference-shaped mode
 //                   (base == null) writes all N records at index idx, nor = 1 for a cut splat; compacted mode writes the alive records only, in index
 //                   order, at base[chunk] + rank inside the chunk.
@@ -29,68 +30,13 @@
 #include <string>
 
 #include "gs_common.h"
+#include "gs_block.h"
 
 namespace gs {
 
 constexpr uint32_t kRecFloats = GS_EXPORT_RECORD_BYTES / 4;       // 62
-constexpr uint32_t kScanThreads = 1024;
 constexpr uint32_t kExportBatchDefault = 131072;                  // splats per batch: 31 MB of records in the device buffer and in each pinned buffer
 static_assert(kRecFloats * 4 == GS_EXPORT_RECORD_BYTES && kRecFloats % 2 == 0, "records are whole dwordx2s");
-
-__global__ __launch_bounds__(256) void export_count_kernel(gsm::AssetView a, gsm::EditView e, uint32_t* __restrict__ counts) {
-    __shared__ uint32_t s_cnt[4];
-    const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
-    gsm::V3 pos; bool cut;
-    const bool alive = export_alive(a, e, idx, blockIdx.x, pos, cut);
-    const uint32_t c = (uint32_t)__popcll(__ballot(alive));
-    if ((threadIdx.x & 63u) == 0u) s_cnt[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0u) counts[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-}
-
-// base[i] = counts[0] + .. + counts[i - 1] for i in [0, n]; one workgroup
-__global__ __launch_bounds__(kScanThreads) void export_scan_kernel(const uint32_t* __restrict__ counts, uint32_t* __restrict__ base, uint32_t n) {
-    __shared__ uint32_t s_wave[kScanThreads / 64];
-    __shared__ uint32_t s_carry;
-    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
-    if (t == 0u) s_carry = 0u;
-    __syncthreads();
-    for (uint32_t start = 0; start < n; start += kScanThreads) {
-        const uint32_t i = start + t;
-        const uint32_t v = i < n ? counts[i] : 0u;
-        uint32_t incl = v;                                         // inclusive scan inside the wave
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t up = (uint32_t)__shfl_up((int)incl, d);
-            if (lane >= (uint32_t)d) incl += up;
-        }
-        if (lane == 63u) s_wave[wave] = incl;
-        __syncthreads();
-        uint32_t before = s_carry;
-        for (uint32_t w = 0; w < wave; ++w) before += s_wave[w];
-        if (i < n) base[i] = before + incl - v;
-        __syncthreads();                                           // everyone has read s_carry and s_wave
-        if (t == kScanThreads - 1u) s_carry = before + incl;
-        __syncthreads();
-    }
-    if (t == 0u) base[n] = s_carry;
-}
-
-// counts[c] = alive splats of chunk c, base = their exclusive prefix (base[chunks] = the total), on st: the two launches every compaction starts with
-// (the export's, and the bake's in gs_bake.hip)
-int32_t enqueue_alive_counts(hipStream_t st, const gsm::AssetView& a, const gsm::EditView& e, uint32_t chunks, uint32_t* counts, uint32_t* base) {
-    hipLaunchKernelGGL(export_count_kernel, dim3(chunks), dim3(256), 0, st, a, e, counts);
-    hipLaunchKernelGGL(export_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, (const uint32_t*)counts, base, chunks);
-    GS_HIP(hipGetLastError());
-    return GS_OK;
-}
-
-// the scan alone, for counts made elsewhere (the edit history's compaction, gs_edit.hip)
-int32_t enqueue_scan(hipStream_t st, const uint32_t* counts, uint32_t* base, uint32_t n) {
-    hipLaunchKernelGGL(export_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, counts, base, n);
-    GS_HIP(hipGetLastError());
-    return GS_OK;
-}
 
 // out: the records of the chunks [firstChunk, firstChunk + gridDim.x).  base == null: record idx - firstChunk * 256 for every idx < N; else record
 // base[chunk] - base[firstChunk] + rank for the alive ones.
@@ -101,10 +47,7 @@ __global__ __launch_bounds__(256) void export_records_kernel(gsm::AssetView a, g
     gsm::V3 pos; bool cut;
     const bool alive = export_alive(a, e, idx, ci, pos, cut);
     const bool mine = base ? alive : (idx < a.n);                  // does this lane write a record?
-    const unsigned long long bal = __ballot(mine);
-    const uint32_t waveCount = (uint32_t)__popcll(bal);
-    const uint32_t slot = (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));      // rank inside the wave (reference-shaped: the lane itself, the tail is at the end)
-    if (lane == 0u) s_cnt[wave] = waveCount;
+    const uint32_t slot = block_rank(mine, lane, wave, s_cnt);    // rank inside the wave (reference-shaped: the lane itself, the tail is at the end)
     float rec[kRecFloats];
     if (mine) gsm::ExportSplat(a, X, idx, ci, pos, base ? false : cut, rec);
 #ifndef GS_EXPORT_DIRECT
@@ -115,9 +58,9 @@ __global__ __launch_bounds__(256) void export_records_kernel(gsm::AssetView a, g
     }
 #endif
     __syncthreads();
-    uint32_t first = base ? (base[ci] - base[firstChunk]) : blockIdx.x * 256u;      // first record of the workgroup, then of the wave
-    for (uint32_t w = 0; w < wave; ++w) first += s_cnt[w];
+    const uint32_t first = block_first(s_cnt, wave, base ? (base[ci] - base[firstChunk]) : blockIdx.x * 256u);      // first record of the workgroup, then of the wave
 #ifndef GS_EXPORT_DIRECT
+    const uint32_t waveCount = s_cnt[wave];
     // the wave's records are contiguous: waveCount * 31 dwordx2s from an 8-byte aligned address
     float2* dst = (float2*)(out + (size_t)first * kRecFloats);
     const float2* src = (const float2*)s_rec[wave];
@@ -159,7 +102,7 @@ struct ExportRun {
         hostBase.resize((size_t)chunks + 1);                       // (may throw: before anything is in flight)
         GS_HIP(counts.alloc((size_t)chunks * 4));
         GS_HIP(base.alloc(((size_t)chunks + 1) * 4));
-        GS_TRY(enqueue_alive_counts(st, asset_view(r), edit_view(r), chunks, counts.get(), base.get()));
+        GS_TRY(enqueue_alive_counts(st, asset_view(r), edit_view(r), false, chunks, counts.get(), base.get()));
         GS_HIP(hipMemcpyAsync(hostBase.data(), base.get(), hostBase.size() * 4, hipMemcpyDeviceToHost, st));
         GS_HIP(hipStreamSynchronize(st));
         return GS_OK;
@@ -229,7 +172,7 @@ static int32_t export_begin(gs_renderer* r, const gs_export_params* p, bool comp
 }
 
 // ---- SPZ: the alive splats as the six byte columns of an SPZ version 2 stream ----------------------------------------
-// After export_count / export_scan, the bake's alive list (enqueue_alive_list, gs_bake.hip: alive[j] = source index of the j-th alive splat) with its
+// After enqueue_alive_counts, the alive list the bake uses too (enqueue_alive_list, gs_compact.hip: alive[j] = source index of the j-th alive splat) with its
 // bounds taken of the positions AS EXPORTED (through the matrix when the transform is baked: the automatic fract_bits follows from them; the host
 // derives it from the six floats), then one plain launch that waits on no other workgroup:
 //   export_spz         256 threads per 256 destination ranks: lane j decodes alive[256 b + j] (LoadSplatDataFull + the ExportSplat body) and packs.
@@ -299,14 +242,9 @@ struct SpzRun {
         GS_HIP(counts.alloc((size_t)chunks * 4));
         GS_HIP(base.alloc(((size_t)chunks + 1) * 4));
         if (ev) GS_HIP(hipEventRecord(ev[0], st));
-        GS_TRY(enqueue_alive_counts(st, asset_view(r), edit_view(r), chunks, counts.get(), base.get()));
+        GS_TRY(enqueue_alive_counts(st, asset_view(r), edit_view(r), false, chunks, counts.get(), base.get()));
         if (ev) GS_HIP(hipEventRecord(ev[1], st));
-        {
-            const hipError_t he = hipMemcpyAsync(&total, base.get() + chunks, 4, hipMemcpyDeviceToHost, st);
-            const hipError_t hs = hipStreamSynchronize(st);        // nothing in flight outlives the buffers
-            GS_HIP(he);
-            GS_HIP(hs);
-        }
+        GS_TRY(drain(st, [&]() -> int32_t { GS_HIP(hipMemcpyAsync(&total, base.get() + chunks, 4, hipMemcpyDeviceToHost, st)); return GS_OK; }(), "export: the alive count"));
         if (const char* why = spz_alive_refusal(total)) return fail(GS_ERR_INVALID_ARGUMENT, why);
         GS_HIP(alive.alloc(((size_t)total + 16) * 4));
         GS_HIP(partial.alloc((size_t)chunks * 6 * 4));
@@ -316,14 +254,12 @@ struct SpzRun {
         memcpy(B.m, X.o2w, sizeof(B.m));
         float hostBounds[6] = { 0, 0, 0, 0, 0, 0 };
         if (ev) GS_HIP(hipEventRecord(ev[2], st));
-        const int32_t rc = enqueue_alive_list(st, asset_view(r), edit_view(r), B, chunks, base.get(), alive.get(), partial.get(), bounds.get());
-        hipError_t he = hipSuccess;
-        if (rc == GS_OK && ev) he = hipEventRecord(ev[3], st);
-        if (rc == GS_OK && he == hipSuccess) he = hipMemcpyAsync(hostBounds, bounds.get(), sizeof(hostBounds), hipMemcpyDeviceToHost, st);
-        const hipError_t hs = hipStreamSynchronize(st);            // whatever failed: nothing in flight outlives the buffers
-        GS_TRY(rc);
-        GS_HIP(he);
-        GS_HIP(hs);
+        GS_TRY(drain(st, [&]() -> int32_t {
+            GS_TRY(enqueue_alive_list(st, asset_view(r), edit_view(r), false, false, B, chunks, base.get(), alive.get(), partial.get(), bounds.get()));
+            if (ev) GS_HIP(hipEventRecord(ev[3], st));
+            GS_HIP(hipMemcpyAsync(hostBounds, bounds.get(), sizeof(hostBounds), hipMemcpyDeviceToHost, st));
+            return GS_OK;
+        }(), "export: the alive list"));
         fract = s.fract_bits == GS_SPZ_FRACT_AUTO ? gsm::SpzAutoFractBits(hostBounds) : s.fract_bits;
         return GS_OK;
     }
@@ -391,9 +327,7 @@ struct SpzRun {
             if (!have) break;
             pending = cur; pendingBytes = len; cur ^= 1;
         }
-        const hipError_t hs = hipStreamSynchronize(st);            // nothing in flight may outlive the buffers
-        if (rc == GS_OK && hs != hipSuccess) rc = fail_hip(hs, "export", __FILE__, __LINE__);
-        return rc;
+        return drain(st, rc, "export");
     }
 };
 
@@ -458,10 +392,7 @@ static int32_t export_data_impl(gs_renderer* r, const gs_export_params* p, void*
     if (run.chunks == 0u) return GS_OK;                            // no splats: nothing to launch
     if (memory_kind == 1) {
         run.launch(0, run.chunks, (float*)out);
-        const hipError_t he = hipGetLastError();
-        GS_HIP(hipStreamSynchronize(r->ctx->stream));
-        GS_HIP(he);
-        return GS_OK;
+        return drain(r->ctx->stream, [&]() -> int32_t { GS_HIP(hipGetLastError()); return GS_OK; }(), "export_data");
     }
     uint8_t* dst = (uint8_t*)out;
     return run.to_host([&](const uint8_t* data, size_t n) { memcpy(dst, data, n); dst += n; return 0; });
@@ -519,17 +450,17 @@ static int32_t export_kernel_times_impl(gs_renderer* r, const gs_export_params* 
     hipStream_t st = r->ctx->stream;
     Event ev[4];
     for (Event& e : ev) GS_HIP(e.create(hipEventDefault));         // (nothing is in flight yet)
-    hipError_t he = hipEventRecord(ev[0], st);
-    hipLaunchKernelGGL(export_count_kernel, dim3(run.chunks), dim3(256), 0, st, asset_view(r), edit_view(r), run.counts.get());
-    if (he == hipSuccess) he = hipEventRecord(ev[1], st);
-    hipLaunchKernelGGL(export_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, (const uint32_t*)run.counts.get(), run.base.get(), run.chunks);
-    if (he == hipSuccess) he = hipEventRecord(ev[2], st);
-    run.launch(0, run.chunks, (float*)device_out);
-    if (he == hipSuccess) he = hipEventRecord(ev[3], st);
-    if (he == hipSuccess) he = hipGetLastError();
-    const hipError_t hs = hipStreamSynchronize(st);                // whatever failed: nothing in flight outlives the events and the buffers
-    GS_HIP(he);
-    GS_HIP(hs);
+    GS_TRY(drain(st, [&]() -> int32_t {
+        GS_HIP(hipEventRecord(ev[0], st));
+        GS_TRY(enqueue_alive_chunk_counts(st, asset_view(r), edit_view(r), false, run.chunks, run.counts.get()));
+        GS_HIP(hipEventRecord(ev[1], st));
+        GS_TRY(enqueue_scan(st, run.counts.get(), run.base.get(), run.chunks));
+        GS_HIP(hipEventRecord(ev[2], st));
+        run.launch(0, run.chunks, (float*)device_out);
+        GS_HIP(hipGetLastError());
+        GS_HIP(hipEventRecord(ev[3], st));
+        return GS_OK;
+    }(), "export: kernel times"));
     for (int k = 0; k < 3; ++k) GS_HIP(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
     return GS_OK;
 }
@@ -572,17 +503,14 @@ static int32_t export_spz_impl(gs_renderer* r, const gs_export_params* p, const 
     return GS_OK;
 }
 
-// The SPZ export's kernels once, timed by events: ms[0] export_count + export_scan, ms[1] the alive list + the bounds, ms[2] export_spz
+// The SPZ export's kernels once, timed by events: ms[0] alive_count + export_scan, ms[1] the alive list + the bounds, ms[2] export_spz
 static int32_t export_spz_kernel_times_impl(gs_renderer* r, const gs_export_params* p, const gs_spz_params* s, float ms[3], uint32_t* alive, uint64_t* body_bytes) {
     if (!ms) return fail(GS_ERR_INVALID_ARGUMENT, "null argument");
     Event ev[6];
     for (Event& e : ev) GS_HIP(e.create(hipEventDefault));
     SpzRun run;
     GS_TRY(spz_begin(r, p, s, run, ev));
-    const int32_t rc = run.pack(ev);
-    const hipError_t hs = hipStreamSynchronize(r->ctx->stream);   // whatever failed: nothing in flight outlives the events and the buffers
-    GS_TRY(rc);
-    GS_HIP(hs);
+    GS_TRY(drain(r->ctx->stream, run.pack(ev), "export: kernel times"));
     for (int k = 0; k < 3; ++k) GS_HIP(hipEventElapsedTime(&ms[k], ev[2 * k], ev[2 * k + 1]));
     if (alive) *alive = run.total;
     if (body_bytes) *body_bytes = run.body_bytes();
@@ -619,7 +547,7 @@ int32_t gs_renderer_edit_export_ply(gs_renderer* r, const gs_export_params* p, c
 }
 
 // A measurement aid of scripts/export_timing.py, which binds it itself: not declared in gsplat_c.h, not part of the ABI.  ms[0..2] = GPU milliseconds of
-// export_count, export_scan and export_records; device_out: device memory, 8-byte aligned, bytes >= alive x 248.
+// alive_count, export_scan and export_records; device_out: device memory, 8-byte aligned, bytes >= alive x 248.
 __attribute__((visibility("default"))) int32_t gs_export_kernel_times_for_scripts(gs_renderer* r, const gs_export_params* p, void* device_out, size_t bytes,
                                                                                 float ms[3], uint32_t* alive) {
     return export_guarded([&] { return export_kernel_times_impl(r, p, device_out, bytes, ms, alive); });

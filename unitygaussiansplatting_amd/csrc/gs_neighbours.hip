@@ -4,16 +4,17 @@
 // runs on the host.
 //
 // One call, on the context's stream, everything transient and freed before it returns:
-//   1. nb_count + the scan + nb_list + nb_origin   the LIST: alive splats (index < N, not deleted, not cut -- export_alive, the test of every edit kernel)
-//                                                  whose position is finite, in index order, and the per-axis minimum of their positions, the grid's origin
-//   2. nb_keys + two stable Onesweep sorts         the 63-bit cell key of every listed splat, x lowest, sorted as the bake sorts its Morton codes: the low
-//                                                  word over 32 bits, then the gathered high word over 31
+//   1. enqueue_alive_counts + enqueue_alive_list   the LIST (gs_compact.hip, finiteOnly): alive splats (index < N, not deleted, not cut -- export_alive, the test
+//                                                  of every edit kernel) whose position is finite, in index order, and (minOnly) the per-axis
+//                                                  minimum of their positions, the grid's origin
+//   2. nb_keys + TwoWordSort                       the 63-bit cell key of every listed splat, x lowest, sorted as the bake sorts its Morton codes
+//                                                  (gs_compact.hip): the low word over 32 bits, then the gathered high word over 31
 //   3. nb_records                                  the sorted splats as 16-byte records (x, y, z, index) and their keys: what the walk streams
 //   4. nb_walk                                     one thread per listed splat in SORTED order -- the lanes of a wave then search for the same runs and walk
 //                                                  the same cache lines -- nine runs each (gsm::NeighbourCount: the start by bisection, the end by doubling
 //                                                  steps from it), stopping at the limit; one store per splat
-//   5. nb_counts_out / nb_apply                    by splat index, 256-thread workgroups like gs_edit.hip: the host's array, or the predicate as a word
-//                                                  through __ballot and a plain read-modify-write of the word a half-wave owns
+//   5. nb_counts_out / nb_apply                    by splat index, 256-thread workgroups like gs_edit.hip: the host's array, or the predicate into the
+//                                                  selection words (selection_apply, gs_block.h)
 // No atomics (but the optional statistic of the timing script), no workgroup waits on another outside the sorts, no scratch, no LDS beyond the reductions'.
 //
 // The island tools (gs_renderer_edit_components / _select_islands / _grow_selection) share steps 1 to 3 (nb_grid) and go on:
@@ -26,82 +27,11 @@
 #include <cmath>
 
 #include "gs_common.h"
+#include "gs_block.h"
 
 namespace gs {
 
-constexpr uint32_t kNbReduceThreads = 1024;
 constexpr uint32_t kNbNotAlive = 0xFFFFFFFFu;
-
-__device__ __forceinline__ float nb_wave_min(float v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = fminf(v, __shfl_xor(v, d));
-    return v;
-}
-
-// is splat idx listed?  (alive and every component of its position finite)
-__device__ __forceinline__ bool nb_listed(const gsm::AssetView& a, const gsm::EditView& e, uint32_t idx, uint32_t ci, gsm::V3& pos) {
-    bool cut;
-    return export_alive(a, e, idx, ci, pos, cut) && gsm::NeighbourFinite(pos);
-}
-
-// counts[c] = listed splats of chunk c
-__global__ __launch_bounds__(256) void nb_count_kernel(gsm::AssetView a, gsm::EditView e, uint32_t* __restrict__ counts) {
-    __shared__ uint32_t s_cnt[4];
-    const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
-    gsm::V3 pos;
-    const uint32_t c = (uint32_t)__popcll(__ballot(nb_listed(a, e, idx, blockIdx.x, pos)));
-    if ((threadIdx.x & 63u) == 0u) s_cnt[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0u) counts[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-}
-
-// list[base[chunk] + rank] = idx for the listed splats of chunk blockIdx.x; partial[chunk][0..2] = the minimum of their positions (+inf: none)
-__global__ __launch_bounds__(256) void nb_list_kernel(gsm::AssetView a, gsm::EditView e, const uint32_t* __restrict__ base, uint32_t* __restrict__ list,
-                                                      float* __restrict__ partial) {
-    __shared__ uint32_t s_cnt[4];
-    __shared__ float s_red[4][3];
-    const uint32_t idx = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    gsm::V3 pos;
-    const bool mine = nb_listed(a, e, idx, blockIdx.x, pos);
-    const unsigned long long bal = __ballot(mine);
-    const uint32_t slot = (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0u) s_cnt[wave] = (uint32_t)__popcll(bal);
-    const float inf = gsm::u2f(0x7f800000u);
-    const float p[3] = { pos.x, pos.y, pos.z };
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float mn = nb_wave_min(mine ? p[c] : inf);
-        if (lane == 0u) s_red[wave][c] = mn;
-    }
-    __syncthreads();
-    uint32_t first = base[blockIdx.x];
-    for (uint32_t w = 0; w < wave; ++w) first += s_cnt[w];
-    if (mine) list[first + slot] = idx;
-    if (threadIdx.x < 3u) partial[blockIdx.x * 3u + threadIdx.x] = fminf(fminf(s_red[0][threadIdx.x], s_red[1][threadIdx.x]), fminf(s_red[2][threadIdx.x], s_red[3][threadIdx.x]));
-}
-
-// origin[0..2] = the minimum over the partials; one workgroup
-__global__ __launch_bounds__(kNbReduceThreads) void nb_origin_kernel(const float* __restrict__ partial, uint32_t chunks, float* __restrict__ origin) {
-    __shared__ float s_red[kNbReduceThreads / 64][3];
-    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
-    const float inf = gsm::u2f(0x7f800000u);
-    float v[3] = { inf, inf, inf };
-    for (uint32_t i = t; i < chunks; i += kNbReduceThreads) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) v[c] = fminf(v[c], partial[i * 3u + c]);
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float mn = nb_wave_min(v[c]);
-        if (lane == 0u) s_red[wave][c] = mn;
-    }
-    __syncthreads();
-    if (t < 3u) {
-        float r = s_red[0][t];
-        for (uint32_t w = 1; w < kNbReduceThreads / 64; ++w) r = fminf(r, s_red[w][t]);
-        origin[t] = r;
-    }
-}
 
 // the cell key of listed splat j as two sort keys, and the identity payload
 __global__ __launch_bounds__(256) void nb_keys_kernel(gsm::AssetView a, const uint32_t* __restrict__ list, const float* __restrict__ origin, double h, uint32_t m,
@@ -111,11 +41,6 @@ __global__ __launch_bounds__(256) void nb_keys_kernel(gsm::AssetView a, const ui
     const uint32_t idx = list[j];
     const unsigned long long key = gsm::NeighbourKeyOf(gsm::LoadSplatPosChunk(a, idx, idx >> 8), origin, h);
     lo[j] = (uint32_t)key; hi[j] = (uint32_t)(key >> 32); rank[j] = j;
-}
-
-__global__ __launch_bounds__(256) void nb_gather_kernel(const uint32_t* __restrict__ hi, const uint32_t* __restrict__ rank, uint32_t m, uint32_t* __restrict__ out) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i < m) out[i] = hi[rank[i]];
 }
 
 // sorted position i: the record and the key of the splat the two sorts put there
@@ -157,10 +82,7 @@ __global__ __launch_bounds__(256) void nb_apply_kernel(gsm::AssetView a, gsm::Ed
                                                        uint32_t* __restrict__ sel, uint32_t nWords, uint32_t subtract) {
     const uint32_t idx = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u;
     gsm::V3 pos; bool cut;
-    const bool sparse = export_alive(a, e, idx, blockIdx.x, pos, cut) && counts[idx] < minNeighbours;
-    const uint32_t word = (uint32_t)(__ballot(sparse) >> (lane & 32u));
-    const uint32_t w = idx >> 5;
-    if ((lane & 31u) == 0u && w < nWords && word) sel[w] = subtract ? (sel[w] & ~word) : (sel[w] | word);
+    selection_apply(export_alive(a, e, idx, blockIdx.x, pos, cut) && counts[idx] < minNeighbours, idx, lane, sel, nWords, subtract);
 }
 
 // ---- connected components of the neighbour graph (gs_renderer_edit_components / _select_islands / _grow_selection) ----------
@@ -273,10 +195,7 @@ __global__ __launch_bounds__(256) void cc_out_kernel(gsm::AssetView a, gsm::Edit
 __global__ __launch_bounds__(256) void cc_islands_apply_kernel(gsm::AssetView a, const uint32_t* __restrict__ labels, const uint32_t* __restrict__ sizes, uint32_t minSize,
                                                                uint32_t* __restrict__ sel, uint32_t nWords, uint32_t subtract) {
     const uint32_t idx = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u;
-    const bool island = idx < a.n && labels[idx] != kNbNotAlive && sizes[idx] < minSize;
-    const uint32_t word = (uint32_t)(__ballot(island) >> (lane & 32u));
-    const uint32_t w = idx >> 5;
-    if ((lane & 31u) == 0u && w < nWords && word) sel[w] = subtract ? (sel[w] & ~word) : (sel[w] | word);
+    selection_apply(idx < a.n && labels[idx] != kNbNotAlive && sizes[idx] < minSize, idx, lane, sel, nWords, subtract);
 }
 
 // a seed is an alive splat (index < N) whose selected bit is set: hit[label] = 1 (every writer stores the same word)
@@ -284,7 +203,7 @@ __global__ __launch_bounds__(256) void cc_seed_kernel(uint32_t n, const uint32_t
     const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
     if (idx >= n) return;
     const uint32_t label = labels[idx];
-    if (label != kNbNotAlive && ((sel[idx >> 5] >> (idx & 31u)) & 1u)) hit[label] = 1u;
+    if (label != kNbNotAlive && bit_set(sel, idx)) hit[label] = 1u;
 }
 
 // after the kernel boundary: selected |= alive and hit[label]
@@ -293,20 +212,17 @@ __global__ __launch_bounds__(256) void cc_grow_apply_kernel(uint32_t n, const ui
     const uint32_t idx = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u;
     bool grow = false;
     if (idx < n) { const uint32_t label = labels[idx]; grow = label != kNbNotAlive && hit[label] != 0u; }
-    const uint32_t word = (uint32_t)(__ballot(grow) >> (lane & 32u));
-    const uint32_t w = idx >> 5;
-    if ((lane & 31u) == 0u && w < nWords && word) sel[w] |= word;
+    selection_apply(grow, idx, lane, sel, nWords, 0u);
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------------
 // everything a call holds: freed when it returns
 struct NeighbourRun {
-    DevBuf<uint32_t> chunkCounts, base, list, lo, hi, hi2, rank, counts;
-    DevBuf<float> partial, origin;
+    DevBuf<uint32_t> chunkCounts, base, list, counts;
+    DevBuf<float> partial, origin;          // the per-chunk minima of the listed positions and their fold, the grid's origin
     DevBuf<gsm::NeighbourRec> recs;
     DevBuf<unsigned long long> keys, tests;
-    SortState sort;
-    DevBuf<SortControl> control;            // two blocks, one per sort: each has an error word of its own
+    TwoWordSort sort;                       // the cell keys as two words, and their order
     uint32_t listed = 0;
 };
 
@@ -314,19 +230,6 @@ struct NeighbourRun {
 // predicates the walk evaluated, the listed splats
 enum { kNbEvCount = 0, kNbEvScan, kNbEvList, kNbEvOrigin, kNbEvSorted, kNbEvRecords, kNbEvWalk, kNbEvApply, kNbEvDone, kNbEvents };
 struct NeighbourProbe { hipEvent_t ev[kNbEvents]; unsigned long long tests; uint32_t listed; };
-static hipError_t nb_mark(const NeighbourProbe* probe, int from, int to, hipStream_t st) {
-    if (!probe) return hipSuccess;
-    for (int k = from; k <= to; ++k) { const hipError_t e = hipEventRecord(probe->ev[k], st); if (e != hipSuccess) return e; }
-    return hipSuccess;
-}
-
-static int32_t nb_sort(gs_context* ctx, NeighbourRun& run, SortControl* control, uint32_t* keys, uint32_t m, uint32_t keyBits) {
-    const int passes = (int)((keyBits + 7u) / 8u);
-    const uint32_t lastMask = (1u << (keyBits - 8u * (uint32_t)(passes - 1))) - 1u;
-    GS_TRY(enqueue_histogram(ctx, ctx->stream, keys, m, nullptr, passes, lastMask, control, run.sort));
-    return enqueue_sort_passes(ctx, ctx->stream, run.sort, control, keys, run.rank, m, nullptr, passes, lastMask);
-}
-
 static const char* nb_radius_refusal(float radius) {
     return (std::isfinite(radius) && radius >= 1.0e-15f && radius <= 1.0e15f) ? nullptr : "neighbours: radius must be finite and within [1e-15, 1e15]";
 }
@@ -335,8 +238,7 @@ static const char* nb_radius_refusal(float radius) {
 static int32_t nb_sort_errors(gs_renderer* r, NeighbourRun& run) {
     hipStream_t st = r->ctx->stream;
     uint32_t err[2] = { 0u, 0u };
-    GS_HIP(hipMemcpyAsync(&err[0], &run.control.get()[0].error, 4, hipMemcpyDeviceToHost, st));
-    GS_HIP(hipMemcpyAsync(&err[1], &run.control.get()[1].error, 4, hipMemcpyDeviceToHost, st));
+    GS_HIP(run.sort.enqueue_error_readback(st, err));
     GS_HIP(hipStreamSynchronize(st));
     if (err[0] | err[1]) return fail(GS_ERR_SORT_TIMEOUT, "neighbours: a bounded look-back spin expired");
     return GS_OK;
@@ -353,46 +255,38 @@ static int32_t nb_grid(gs_renderer* r, float radius, NeighbourRun& run, const Ne
     const uint32_t chunks = (r->n + 255u) / 256u;
     GS_HIP(run.chunkCounts.alloc((size_t)chunks * 4));
     GS_HIP(run.base.alloc(((size_t)chunks + 1) * 4));
-    GS_HIP(nb_mark(probe, kNbEvCount, kNbEvCount, st));
-    hipLaunchKernelGGL(nb_count_kernel, dim3(chunks), dim3(256), 0, st, a, e, run.chunkCounts.get());
-    GS_HIP(hipGetLastError());
-    GS_TRY(enqueue_scan(st, run.chunkCounts, run.base, chunks));
-    GS_HIP(nb_mark(probe, kNbEvScan, kNbEvScan, st));
+    GS_HIP(mark_events(events_of(probe), kNbEvCount, kNbEvCount, st));
+    GS_TRY(enqueue_alive_counts(st, a, e, true, chunks, run.chunkCounts, run.base));
+    GS_HIP(mark_events(events_of(probe), kNbEvScan, kNbEvScan, st));
     uint32_t m = 0;
     GS_HIP(hipMemcpyAsync(&m, run.base.get() + chunks, 4, hipMemcpyDeviceToHost, st));
     GS_HIP(hipStreamSynchronize(st));
     run.listed = m;
-    if (m == 0u) return nb_mark(probe, kNbEvList, kNbEvRecords, st) == hipSuccess ? GS_OK : fail(GS_ERR_HIP, "neighbours: an event failed");
+    if (m == 0u) return mark_events(events_of(probe), kNbEvList, kNbEvRecords, st) == hipSuccess ? GS_OK : fail(GS_ERR_HIP, "neighbours: an event failed");
     const uint32_t blocks = (m + 255u) / 256u;
     GS_HIP(run.list.alloc(((size_t)m + 16) * 4));
     GS_HIP(run.partial.alloc((size_t)chunks * 3 * 4));
     GS_HIP(run.origin.alloc(3 * 4));
-    for (DevBuf<uint32_t>* b : { &run.lo, &run.hi, &run.hi2, &run.rank }) GS_HIP(b->alloc(((size_t)m + 16) * 4));
     GS_HIP(run.recs.alloc((size_t)m * sizeof(gsm::NeighbourRec)));
     GS_HIP(run.keys.alloc((size_t)m * 8));
-    GS_TRY(sort_state_create(ctx, run.sort, m, true));
-    GS_HIP(run.control.alloc(2 * sizeof(SortControl)));
+    GS_TRY(run.sort.alloc(ctx, m));
     const double h = gsm::NeighbourCellEdge(radius);
+    const float* origin = run.origin.get();
     // 1. the list and the origin
-    GS_HIP(nb_mark(probe, kNbEvList, kNbEvList, st));
-    hipLaunchKernelGGL(nb_list_kernel, dim3(chunks), dim3(256), 0, st, a, e, (const uint32_t*)run.base.get(), run.list.get(), run.partial.get());
-    hipLaunchKernelGGL(nb_origin_kernel, dim3(1), dim3(kNbReduceThreads), 0, st, (const float*)run.partial.get(), chunks, run.origin.get());
-    GS_HIP(hipGetLastError());
-    GS_HIP(nb_mark(probe, kNbEvOrigin, kNbEvOrigin, st));
+    GS_HIP(mark_events(events_of(probe), kNbEvList, kNbEvList, st));
+    GS_TRY(enqueue_alive_list(st, a, e, true, true, AliveXform{}, chunks, run.base.get(), run.list.get(), run.partial.get(), run.origin.get()));
+    GS_HIP(mark_events(events_of(probe), kNbEvOrigin, kNbEvOrigin, st));
     // 2. keys and sorts
-    hipLaunchKernelGGL(nb_keys_kernel, dim3(blocks), dim3(256), 0, st, a, (const uint32_t*)run.list.get(), (const float*)run.origin.get(), h, m, run.lo.get(), run.hi.get(),
-                       run.rank.get());
+    hipLaunchKernelGGL(nb_keys_kernel, dim3(blocks), dim3(256), 0, st, a, (const uint32_t*)run.list.get(), origin, h, m, run.sort.lo.get(), run.sort.hi.get(),
+                       run.sort.rank.get());
     GS_HIP(hipGetLastError());
-    GS_TRY(nb_sort(ctx, run, run.control.get(), run.lo, m, 32u));
-    hipLaunchKernelGGL(nb_gather_kernel, dim3(blocks), dim3(256), 0, st, (const uint32_t*)run.hi.get(), (const uint32_t*)run.rank.get(), m, run.hi2.get());
-    GS_HIP(hipGetLastError());
-    GS_TRY(nb_sort(ctx, run, run.control.get() + 1, run.hi2, m, 31u));
-    GS_HIP(nb_mark(probe, kNbEvSorted, kNbEvSorted, st));
+    GS_TRY(run.sort.enqueue(ctx, m));
+    GS_HIP(mark_events(events_of(probe), kNbEvSorted, kNbEvSorted, st));
     // 3. the records
-    hipLaunchKernelGGL(nb_records_kernel, dim3(blocks), dim3(256), 0, st, a, (const uint32_t*)run.list.get(), (const uint32_t*)run.rank.get(), (const float*)run.origin.get(),
+    hipLaunchKernelGGL(nb_records_kernel, dim3(blocks), dim3(256), 0, st, a, (const uint32_t*)run.list.get(), (const uint32_t*)run.sort.rank.get(), origin,
                        h, m, run.recs.get(), run.keys.get());
     GS_HIP(hipGetLastError());
-    GS_HIP(nb_mark(probe, kNbEvRecords, kNbEvRecords, st));
+    GS_HIP(mark_events(events_of(probe), kNbEvRecords, kNbEvRecords, st));
     return GS_OK;
 }
 
@@ -408,20 +302,20 @@ static int32_t nb_enqueue(gs_renderer* r, float radius, uint32_t limit, Neighbou
         GS_HIP(hipMemsetAsync(run.tests, 0, 8, st));
     }
     if (r->n == 0u || limit == 0u) {
-        GS_HIP(nb_mark(probe, kNbEvCount, kNbEvWalk, st));
-        return hipStreamSynchronize(st) == hipSuccess ? GS_OK : fail(GS_ERR_HIP, "neighbours: the stream failed");
+        GS_HIP(mark_events(events_of(probe), kNbEvCount, kNbEvWalk, st));
+        return drain(st, GS_OK, "neighbours");
     }
     GS_TRY(nb_grid(r, radius, run, probe));
     const uint32_t m = run.listed;
     if (m == 0u) {
-        GS_HIP(nb_mark(probe, kNbEvWalk, kNbEvWalk, st));
+        GS_HIP(mark_events(events_of(probe), kNbEvWalk, kNbEvWalk, st));
         return GS_OK;
     }
     // 4. the walk
     hipLaunchKernelGGL(nb_walk_kernel, dim3((m + 255u) / 256u), dim3(256), 0, st, (const unsigned long long*)run.keys.get(), (const gsm::NeighbourRec*)run.recs.get(), m,
                        radius * radius, limit, run.counts.get(), stats ? run.tests.get() : (unsigned long long*)nullptr);
     GS_HIP(hipGetLastError());
-    GS_HIP(nb_mark(probe, kNbEvWalk, kNbEvWalk, st));
+    GS_HIP(mark_events(events_of(probe), kNbEvWalk, kNbEvWalk, st));
     // the sorts' error words, before anything of the renderer's is touched
     return nb_sort_errors(r, run);
 }
@@ -445,19 +339,17 @@ static int32_t nb_counts_impl(gs_renderer* r, float radius, uint32_t cap, uint32
     int32_t rc = nb_enqueue(r, radius, cap, run, probe);
     if (rc == GS_OK) {
         rc = [&]() -> int32_t {
-            GS_HIP(nb_mark(probe, kNbEvApply, kNbEvApply, st));
+            GS_HIP(mark_events(events_of(probe), kNbEvApply, kNbEvApply, st));
             if (r->n) hipLaunchKernelGGL(nb_counts_out_kernel, dim3((r->n + 255u) / 256u), dim3(256), 0, st, asset_view(r), edit_view(r), run.counts.get());
             GS_HIP(hipGetLastError());
-            GS_HIP(nb_mark(probe, kNbEvDone, kNbEvDone, st));
+            GS_HIP(mark_events(events_of(probe), kNbEvDone, kNbEvDone, st));
             if (r->n) GS_HIP(hipMemcpyAsync(counts_out, run.counts.get(), (size_t)r->n * 4, hipMemcpyDeviceToHost, st));
             if (probe) GS_HIP(hipMemcpyAsync(&probe->tests, run.tests.get(), 8, hipMemcpyDeviceToHost, st));
             return GS_OK;
         }();
     }
-    const hipError_t hs = hipStreamSynchronize(st);                // whatever failed: nothing in flight outlives the buffers
-    if (rc == GS_OK && hs != hipSuccess) rc = fail_hip(hs, "neighbour_counts", __FILE__, __LINE__);
     if (probe) probe->listed = run.listed;
-    return rc;
+    return drain(st, rc, "neighbour_counts");
 }
 
 static int32_t nb_select_impl(gs_renderer* r, float radius, uint32_t min_neighbours, int32_t subtract, NeighbourProbe* probe) {
@@ -470,21 +362,19 @@ static int32_t nb_select_impl(gs_renderer* r, float radius, uint32_t min_neighbo
     if (rc == GS_OK) {
         rc = [&]() -> int32_t {
             hist_mutated(r, true);
-            GS_HIP(nb_mark(probe, kNbEvApply, kNbEvApply, st));
+            GS_HIP(mark_events(events_of(probe), kNbEvApply, kNbEvApply, st));
             if (r->n && min_neighbours) {
                 hipLaunchKernelGGL(nb_apply_kernel, dim3((r->n + 255u) / 256u), dim3(256), 0, st, asset_view(r), edit_view(r), (const uint32_t*)run.counts.get(),
                                    min_neighbours, r->editSelected.get(), (uint32_t)bit_words(r->n), subtract ? 1u : 0u);
                 GS_HIP(hipGetLastError());
             }
-            GS_HIP(nb_mark(probe, kNbEvDone, kNbEvDone, st));
+            GS_HIP(mark_events(events_of(probe), kNbEvDone, kNbEvDone, st));
             if (probe) GS_HIP(hipMemcpyAsync(&probe->tests, run.tests.get(), 8, hipMemcpyDeviceToHost, st));
             return edit_selected_to_lanes(r);
         }();
     }
-    const hipError_t hs = hipStreamSynchronize(st);                // whatever failed: nothing in flight outlives the buffers
-    if (rc == GS_OK && hs != hipSuccess) rc = fail_hip(hs, "select_sparse", __FILE__, __LINE__);
     if (probe) probe->listed = run.listed;
-    return rc;
+    return drain(st, rc, "select_sparse");
 }
 
 // ---- components: the host side ----------------------------------------------------------------------------------------------------------------
@@ -497,12 +387,6 @@ struct ComponentRun {
 // what scripts/islands_timing.py asks of a call: the grid's events (nb: count .. records) and the ones around the stages that follow
 enum { kCcEvLinkStart = 0, kCcEvLink, kCcEvFlatten, kCcEvReduce, kCcEvApply, kCcEvDone, kCcEvents };
 struct ComponentProbe { NeighbourProbe nb; hipEvent_t ev[kCcEvents]; };
-static hipError_t cc_mark(const ComponentProbe* probe, int from, int to, hipStream_t st) {
-    if (!probe) return hipSuccess;
-    for (int k = from; k <= to; ++k) { const hipError_t e = hipEventRecord(probe->ev[k], st); if (e != hipSuccess) return e; }
-    return hipSuccess;
-}
-
 // run.labels[idx] / run.sizes[idx] for every index < N as gs_renderer_edit_components defines them.  The stream has drained when this returns GS_OK;
 // the caller drains it otherwise
 static int32_t cc_enqueue(gs_renderer* r, float radius, ComponentRun& run, const ComponentProbe* probe) {
@@ -513,9 +397,9 @@ static int32_t cc_enqueue(gs_renderer* r, float radius, ComponentRun& run, const
     GS_HIP(hipMemsetAsync(run.labels, 0, (size_t)r->n * 4, st));
     GS_HIP(hipMemsetAsync(run.sizes, 0, (size_t)r->n * 4, st));
     if (r->n == 0u) {
-        GS_HIP(nb_mark(grid, kNbEvCount, kNbEvRecords, st));
-        GS_HIP(cc_mark(probe, kCcEvLinkStart, kCcEvReduce, st));
-        return hipStreamSynchronize(st) == hipSuccess ? GS_OK : fail(GS_ERR_HIP, "components: the stream failed");
+        GS_HIP(mark_events(events_of(grid), kNbEvCount, kNbEvRecords, st));
+        GS_HIP(mark_events(events_of(probe), kCcEvLinkStart, kCcEvReduce, st));
+        return drain(st, GS_OK, "components");
     }
     GS_TRY(nb_grid(r, radius, run.nb, grid));
     const uint32_t m = run.nb.listed, blocks = (m + 255u) / 256u;
@@ -525,28 +409,28 @@ static int32_t cc_enqueue(gs_renderer* r, float radius, ComponentRun& run, const
         GS_HIP(hipMemsetAsync(run.size, 0, (size_t)m * 4, st));
         hipLaunchKernelGGL(cc_init_kernel, dim3(blocks), dim3(256), 0, st, run.parent.get(), m);
         GS_HIP(hipGetLastError());
-        GS_HIP(cc_mark(probe, kCcEvLinkStart, kCcEvLinkStart, st));
+        GS_HIP(mark_events(events_of(probe), kCcEvLinkStart, kCcEvLinkStart, st));
         hipLaunchKernelGGL(cc_link_kernel, dim3(blocks), dim3(256), 0, st, (const unsigned long long*)run.nb.keys.get(), (const gsm::NeighbourRec*)run.nb.recs.get(), m,
                            radius * radius, run.parent.get());
         GS_HIP(hipGetLastError());
-        GS_HIP(cc_mark(probe, kCcEvLink, kCcEvLink, st));
+        GS_HIP(mark_events(events_of(probe), kCcEvLink, kCcEvLink, st));
         hipLaunchKernelGGL(cc_flatten_kernel, dim3(blocks), dim3(256), 0, st, (const uint32_t*)run.parent.get(), m, run.root.get());
         GS_HIP(hipGetLastError());
-        GS_HIP(cc_mark(probe, kCcEvFlatten, kCcEvFlatten, st));
+        GS_HIP(mark_events(events_of(probe), kCcEvFlatten, kCcEvFlatten, st));
         hipLaunchKernelGGL(cc_reduce_kernel, dim3(blocks), dim3(256), 0, st, (const gsm::NeighbourRec*)run.nb.recs.get(), (const uint32_t*)run.root.get(), m,
                            run.minIdx.get(), run.size.get());
         hipLaunchKernelGGL(cc_labels_kernel, dim3(blocks), dim3(256), 0, st, (const gsm::NeighbourRec*)run.nb.recs.get(), (const uint32_t*)run.root.get(),
                            (const uint32_t*)run.minIdx.get(), (const uint32_t*)run.size.get(), m, run.labels.get(), run.sizes.get());
         GS_HIP(hipGetLastError());
     } else {
-        GS_HIP(cc_mark(probe, kCcEvLinkStart, kCcEvFlatten, st));
+        GS_HIP(mark_events(events_of(probe), kCcEvLinkStart, kCcEvFlatten, st));
     }
     hipLaunchKernelGGL(cc_out_kernel, dim3((r->n + 255u) / 256u), dim3(256), 0, st, asset_view(r), edit_view(r), run.labels.get(), run.sizes.get());
     GS_HIP(hipGetLastError());
-    GS_HIP(cc_mark(probe, kCcEvReduce, kCcEvReduce, st));
+    GS_HIP(mark_events(events_of(probe), kCcEvReduce, kCcEvReduce, st));
     // the sorts' error words, before anything of the renderer's is touched
     if (m) return nb_sort_errors(r, run.nb);
-    return hipStreamSynchronize(st) == hipSuccess ? GS_OK : fail(GS_ERR_HIP, "components: the stream failed");
+    return drain(st, GS_OK, "components");
 }
 
 static int32_t cc_components_impl(gs_renderer* r, float radius, uint32_t* labels_out, uint32_t* sizes_out, size_t count, ComponentProbe* probe) {
@@ -559,16 +443,14 @@ static int32_t cc_components_impl(gs_renderer* r, float radius, uint32_t* labels
     int32_t rc = cc_enqueue(r, radius, run, probe);
     if (rc == GS_OK) {
         rc = [&]() -> int32_t {
-            GS_HIP(cc_mark(probe, kCcEvApply, kCcEvDone, st));
+            GS_HIP(mark_events(events_of(probe), kCcEvApply, kCcEvDone, st));
             if (r->n && labels_out) GS_HIP(hipMemcpyAsync(labels_out, run.labels.get(), (size_t)r->n * 4, hipMemcpyDeviceToHost, st));
             if (r->n && sizes_out) GS_HIP(hipMemcpyAsync(sizes_out, run.sizes.get(), (size_t)r->n * 4, hipMemcpyDeviceToHost, st));
             return GS_OK;
         }();
     }
-    const hipError_t hs = hipStreamSynchronize(st);                // whatever failed: nothing in flight outlives the buffers
-    if (rc == GS_OK && hs != hipSuccess) rc = fail_hip(hs, "components", __FILE__, __LINE__);
     if (probe) probe->nb.listed = run.nb.listed;
-    return rc;
+    return drain(st, rc, "components");
 }
 
 // grow == false: gs_renderer_edit_select_islands(min_size, subtract); grow == true: gs_renderer_edit_grow_selection
@@ -583,7 +465,7 @@ static int32_t cc_select_impl(gs_renderer* r, float radius, bool grow, uint32_t 
     if (rc == GS_OK) {
         rc = [&]() -> int32_t {
             hist_mutated(r, true);
-            GS_HIP(cc_mark(probe, kCcEvApply, kCcEvApply, st));
+            GS_HIP(mark_events(events_of(probe), kCcEvApply, kCcEvApply, st));
             const uint32_t blocks = (r->n + 255u) / 256u, nWords = (uint32_t)bit_words(r->n);
             if (work && grow) {
                 GS_HIP(run.hit.alloc(((size_t)r->n + 16) * 4));
@@ -598,14 +480,12 @@ static int32_t cc_select_impl(gs_renderer* r, float radius, bool grow, uint32_t 
                                    (const uint32_t*)run.sizes.get(), min_size, r->editSelected.get(), nWords, subtract ? 1u : 0u);
                 GS_HIP(hipGetLastError());
             }
-            GS_HIP(cc_mark(probe, kCcEvDone, kCcEvDone, st));
+            GS_HIP(mark_events(events_of(probe), kCcEvDone, kCcEvDone, st));
             return edit_selected_to_lanes(r);
         }();
     }
-    const hipError_t hs = hipStreamSynchronize(st);                // whatever failed: nothing in flight outlives the buffers
-    if (rc == GS_OK && hs != hipSuccess) rc = fail_hip(hs, grow ? "grow_selection" : "select_islands", __FILE__, __LINE__);
     if (probe) probe->nb.listed = run.nb.listed;
-    return rc;
+    return drain(st, rc, grow ? "grow_selection" : "select_islands");
 }
 
 } // namespace gs
